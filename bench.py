@@ -46,6 +46,31 @@ def emit(out):
     print(json.dumps(out), flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 19      # rows kept of a larger output: 8 float64 per particle (index, 3 + 3 + 1 outputs) = 32 MiB
+DUMP_SEED = 20261015       # the sample's rows: the same in every run with the same particle number
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` ({name: device tensor, one row per particle}) as DIR/<name>.npy in float64, for every row or, above
+    DUMP_SAMPLE rows, for a sample of rows drawn with a fixed seed (DIR/index.npy: the row numbers, as float64)."""
+    import torch
+    first = next(iter(arrays.values()))
+    n = first.shape[0]
+    if n > DUMP_SAMPLE:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    else:
+        rows = np.arange(n)
+    sel = torch.from_numpy(rows).to(first.device)
+    out = {"index": rows.astype(np.float64)}
+    out.update({name: t.index_select(0, sel).to(torch.float64).cpu().numpy() for name, t in arrays.items()})
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(out)
+
+
 FP64_VALU_PEAK_TF = 78.6   # MI355X_MICROARCH.md: fp64 vector peak (256 CUs x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz)
 FLOP_PER_INTERACTION = 38  # SURVEY 8(d): flop-equivalents of one particle-particle or particle-node evaluation
 
@@ -823,6 +848,9 @@ def gravity_bench_single(pkg, torch, args, dev, local_rank):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     walk_ms, walk_launches, lists_ms, eval_ms, nsplit = eng.walk_events_collect_split()
+    if args.dump_outputs:       # (before the untimed passes below overwrite them)
+        dumped = dump_outputs(args.dump_outputs, {"GravPM": gravpm, "FullTreeGravAccel": acc, "Potential": pot})
+        print("bench.py: wrote %s.npy to %s" % (".npy, ".join(dumped), args.dump_outputs), file=sys.stderr, flush=True)
     if args.traffic_child:      # (a child of live_walk_traffic under rocprofv3: the walks above are what it wanted)
         eng.close()
         return None
@@ -984,12 +1012,20 @@ def main():
     ap.add_argument("--workload", default="gravity", choices=["gravity", "hydro", "integrate", "fof", "domain", "substep"],
                     help="gravity: BASELINE.json configs[1] (default, the headline metric; its line also carries the sub-steps and configs[2]); "
                          "hydro: configs[2] / [4] as their own line; substep: the short-range-only step; integrate / fof / domain: SURVEY 8(f) rows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one-GPU gravity workload: after the timed steps, write what the last timed step returned (GravPM, "
+                         "FullTreeGravAccel, Potential) as DIR/<name>.npy in float64, for every particle or a fixed, seeded sample of "
+                         "%d (DIR/index.npy: their indices), at most %d MiB in all" % (DUMP_SAMPLE, DUMP_MAX_BYTES >> 20))
     args = ap.parse_args()
     if args.traffic_child:
         args.steps, args.warmup, args.no_extras, args.no_cpu_baseline, args.gpus = 2, 1, True, True, 1
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.workload != "gravity" or args.gpus != 1 or os.environ.get("MPG_FORCE_MGPU")):
+        raise SystemExit("--dump-outputs is implemented for the one-GPU gravity workload (the headline line) only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as a plain process (`python bench.py --gpus N`, no launcher): the ranks are launched from here, one per GPU -
         # never a one-GPU line under an N-GPU command

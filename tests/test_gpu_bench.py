@@ -55,6 +55,33 @@ def test_default_workload_line():
     assert h["ms_per_step"] > 0 and h["roofline"]["bound"] == "fp64_valu" and 0 < h["roofline"]["frac"] <= 1 and 0 < h["roofline_hydro"]["frac"] <= 1
 
 
+def test_dump_outputs_are_the_last_timed_step(pkg, tmp_path):
+    """--dump-outputs DIR: what the last of the --steps timed steps returned, float64, one row per particle at this size - GravPM equal to
+    the CPU oracle's PM force on the same particles, FullTreeGravAccel and Potential; --steps sets the number of timed walks; a second run
+    with the same arguments has the same inputs and gives the same outputs (up to the deposit's atomic sums)."""
+    import numpy as np
+    from oracle import oracle as O
+    n = 32
+    N = n ** 3
+    args = ["--size", str(n), "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-live-traffic"]
+    j = run_bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    assert j["steps"] == 3 and j["roofline"]["launches_timed"] == 3
+    run_bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    names = ("index", "GravPM", "FullTreeGravAccel", "Potential")
+    a, b = ({k: np.load(str(tmp_path / d / (k + ".npy"))) for k in names} for d in ("a", "b"))
+    assert sorted(os.listdir(str(tmp_path / "a"))) == sorted(k + ".npy" for k in names)
+    assert all(a[k].dtype == np.float64 and np.isfinite(a[k]).all() for k in names)
+    assert np.array_equal(a["index"], np.arange(N, dtype=np.float64))
+    assert a["GravPM"].shape == a["FullTreeGravAccel"].shape == (N, 3) and a["Potential"].shape == (N,)
+    assert np.abs(a["FullTreeGravAccel"]).mean() > 0 and np.abs(a["Potential"]).mean() > 0
+    for k in ("GravPM", "FullTreeGravAccel", "Potential"):
+        d = np.abs(a[k] - b[k]).reshape(N, -1).max(1) / np.abs(b[k]).mean()
+        assert (d <= 1e-10).mean() >= 0.999 and d.max() <= 0.004, (k, d.max())
+    pos, mass, box = pkg.ics.s_zel(n)
+    gpm, _ = O.gravpm_force(pos, mass, box, 2 * n, 1.5, 43.0071)
+    assert np.abs(a["GravPM"] - gpm).max() <= 1e-10 * np.abs(gpm).mean()
+
+
 @pytest.mark.parametrize("overlap", [True, False])
 def test_multi_gpu_path_in_a_one_rank_group_checks_itself(overlap):
     """bench.py --gpus N runs the library's choreography and then checks its own forces: sampled particles recomputed on one GPU from

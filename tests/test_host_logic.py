@@ -204,3 +204,32 @@ def test_bench_gpus_n_refuses_without_n_gpus():
     assert not [x for x in r.stdout.splitlines() if x.startswith("{")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(env, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0"), cwd=ROOT)
     assert r.returncode != 0 and "WORLD_SIZE 4 != --gpus 2" in r.stderr
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs writes float64 .npy files: every row of a small output; of a larger one the same seeded sample of
+    DUMP_SAMPLE rows in every run (index.npy), within 64 MiB.  A workload without the dump, and --steps 0, are refused before any work."""
+    import subprocess
+    import bench
+    n = bench.DUMP_SAMPLE + 12345
+    g = torch.Generator().manual_seed(3)
+    arrays = {"A": torch.randn(n, 3, dtype=torch.float64, generator=g), "B": torch.randn(n, generator=g)}     # (B: float32)
+    for d in ("one", "two"):
+        assert bench.dump_outputs(str(tmp_path / d), arrays) == ["A", "B", "index"]
+    got = {d: {k: np.load(str(tmp_path / d / (k + ".npy"))) for k in ("A", "B", "index")} for d in ("one", "two")}
+    assert all(np.array_equal(got["one"][k], got["two"][k]) for k in ("A", "B", "index"))
+    idx = got["one"]["index"]
+    assert idx.dtype == np.float64 and len(idx) == bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    rows = idx.astype(np.int64)
+    assert got["one"]["A"].dtype == np.float64 and np.array_equal(got["one"]["A"], arrays["A"].numpy()[rows])
+    assert got["one"]["B"].dtype == np.float64 and np.array_equal(got["one"]["B"], arrays["B"].numpy()[rows].astype(np.float64))
+    assert sum(os.path.getsize(str(tmp_path / "one" / f)) for f in os.listdir(str(tmp_path / "one"))) <= 64 << 20
+    small = {k: v[:100] for k, v in arrays.items()}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert np.array_equal(np.load(str(tmp_path / "small" / "index.npy")), np.arange(100.0))
+    assert np.array_equal(np.load(str(tmp_path / "small" / "A.npy")), small["A"].numpy())
+    for extra, msg in ((["--workload", "fof", "--dump-outputs", str(tmp_path / "x")], "--dump-outputs is implemented"),
+                       (["--steps", "0"], "--steps must be >= 1")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode != 0 and msg in r.stderr, r.stderr[-1500:]
+    assert not os.path.exists(str(tmp_path / "x"))

@@ -5,9 +5,8 @@
  * libgadget/tests/test_gravity.c: PM + tree vs direct summation over 27 images (max < 3 ErrTol, mean < 0.8 ErrTol,
    :146-160) on the "close" and "random" sets, and the regular-grid net-force bounds (:259-260);
  * libgadget/tests/test_forcetree.c: structural invariants of the tree (:33-171, :208);
- * oracle/_ref (reference leaf files built in place): the window table values.
+ * oracle/_ref (reference leaf files built in place): the window table values, as recorded in tests/golden/reference_leaf.npz.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -16,6 +15,7 @@ import pytest
 from oracle import oracle as O
 
 G = 43.0071
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def two_walks(orc, pos, mass, box, n, nmesh, gravpm=None, rcut=6.0, bh_second=False):
@@ -128,14 +128,10 @@ def test_pair_vs_open_tree(pkg, orc):
 
 
 def test_window_table_matches_reference_leaf_build(orc):
-    """oracle/_ref/libref_leaf.so is the reference's own shortrange-kernel.c compiled in place: the carried data file
-    must be bit-identical to it."""
-    path = os.path.join(os.path.dirname(O.__file__), "_ref", "libref_leaf.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    L = C.CDLL(path, mode=os.RTLD_LAZY)   # densitykernel.c's error path references endrun(): bind lazily
-    tab = (C.c_double * (512 * 5)).in_dll(L, "shortrange_force_kernels")
-    ref = np.ctypeslib.as_array(tab).reshape(512, 5)
+    """The table of the reference's own shortrange-kernel.c, as its in-place build (oracle/_ref/libref_leaf.so) exports it, recorded in
+    tests/golden/reference_leaf.npz (make_reference_golden.py): the carried data file must be bit-identical to it."""
+    ref = np.load(os.path.join(ROOT, "tests", "golden", "reference_leaf.npz"))["window_table"]
+    assert ref.shape == (512, 5)
     assert np.array_equal(ref, orc.table)
     f, p = orc.get_ntab()
     assert np.array_equal(f, ref[:, 2].astype(np.float32)) and np.array_equal(p, ref[:, 1].astype(np.float32))

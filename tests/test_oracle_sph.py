@@ -3,7 +3,8 @@
  * libgadget/tests/test_density.c: mean Hsml 0.501747 +- 1e-4 on the 32^3 gas grid (:170) and 0.131726 +- 1e-4 on the
    'close' set with one black hole (:203); cubic spline, eta = 1, MaxNumNgbDeviation = 2, box 8; and the stability of
    Hsml when the tolerance is tightened to 0.5 (:126-147);
- * oracle/_ref/libref_leaf.so = the reference's densitykernel.c compiled in place: kernel values bit for bit.
+ * oracle/_ref/libref_leaf.so = the reference's densitykernel.c compiled in place: kernel values bit for bit, as recorded in
+   tests/golden/reference_leaf.npz.
 """
 import ctypes as C
 import os
@@ -13,39 +14,32 @@ import pytest
 
 from oracle import oracle as O
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 def test_density_kernels_match_reference_build(orc):
-    path = os.path.join(os.path.dirname(O.__file__), "_ref", "libref_leaf.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    R = C.CDLL(path, mode=os.RTLD_LAZY)
-
-    class RK(C.Structure):   # DensityKernel, densitykernel.h:23-33
-        _fields_ = [("H", C.c_double), ("HH", C.c_double), ("Hinv", C.c_double), ("type", C.c_int), ("support", C.c_double),
-                    ("name", C.c_char_p), ("Wknorm", C.c_double), ("dWknorm", C.c_double)]
+    """densitykernel.c as its in-place build (oracle/_ref/libref_leaf.so) computes it, recorded in tests/golden/reference_leaf.npz
+    (make_reference_golden.py): norms, support, W(u), dW(u) and the desired neighbour number of the oracle's kernels bit for bit."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "reference_leaf.npz"))
 
     class OK(C.Structure):   # okernel of sph_oracle.c
         _fields_ = [("H", C.c_double), ("HH", C.c_double), ("Hinv", C.c_double), ("type", C.c_int), ("support", C.c_double),
                     ("Wknorm", C.c_double), ("dWknorm", C.c_double)]
-    R.density_kernel_wk.restype = R.density_kernel_dwk.restype = C.c_double
-    R.density_kernel_wk.argtypes = R.density_kernel_dwk.argtypes = [C.POINTER(RK), C.c_double]
-    R.density_kernel_init.argtypes = [C.POINTER(RK), C.c_double, C.c_int]
-    R.density_kernel_desnumngb.restype = C.c_double
-    R.density_kernel_desnumngb.argtypes = [C.POINTER(RK), C.c_double]
     L = orc.lib
     O._sph_bind(L)
     L.os_kernel_wk.restype = L.os_kernel_dwk.restype = C.c_double
     L.os_kernel_wk.argtypes = L.os_kernel_dwk.argtypes = [C.POINTER(OK), C.c_double]
     L.os_kernel_init.argtypes = [C.POINTER(OK), C.c_double, C.c_int]
-    for enumtype in (1, 2, 4):
-        rk, ok = RK(), OK()
-        R.density_kernel_init(C.byref(rk), 0.37, enumtype)
-        L.os_kernel_init(C.byref(ok), 0.37, L.os_kernel_index(enumtype))
-        assert (rk.Wknorm, rk.dWknorm, rk.support) == (ok.Wknorm, ok.dWknorm, ok.support)
-        for u in np.linspace(0, 1.0, 41):
-            assert R.density_kernel_wk(C.byref(rk), u) == L.os_kernel_wk(C.byref(ok), u)
-            assert R.density_kernel_dwk(C.byref(rk), u) == L.os_kernel_dwk(C.byref(ok), u)
-        assert R.density_kernel_desnumngb(C.byref(rk), 1.0) == L.os_kernel_desnumngb(L.os_kernel_index(enumtype), 1.0)
+    u = g["kernel_u"]
+    assert g["kernel_types"].tolist() == [1, 2, 4] and len(u) == 41
+    for k, enumtype in enumerate(g["kernel_types"].tolist()):
+        ok = OK()
+        L.os_kernel_init(C.byref(ok), float(g["kernel_H"]), L.os_kernel_index(enumtype))
+        assert (g["kernel_Wknorm"][k], g["kernel_dWknorm"][k], g["kernel_support"][k]) == (ok.Wknorm, ok.dWknorm, ok.support)
+        for i, x in enumerate(u):
+            assert g["kernel_wk"][k, i] == L.os_kernel_wk(C.byref(ok), x)
+            assert g["kernel_dwk"][k, i] == L.os_kernel_dwk(C.byref(ok), x)
+        assert g["kernel_desnumngb"][k] == L.os_kernel_desnumngb(L.os_kernel_index(enumtype), 1.0)
 
 
 def density_test_set(kind):

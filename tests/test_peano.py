@@ -1,12 +1,10 @@
 """The Peano-Hilbert state machine generated for the device (mp-gadget_amd/csrc/peano_tables.h, made by tools/gen_peano_tables.py)
-against golden vectors taken from the reference function (tests/golden/peano_keys.npz, make_peano_golden.py) and, when
-oracle/_ref is present, against the reference function itself on fresh random input.  CPU only: the tables are parsed from the header."""
-import ctypes as C
+against golden vectors taken from the reference function (tests/golden/peano_keys.npz, make_peano_golden.py, and the random
+triplets of every bit count in tests/golden/reference_leaf.npz, make_reference_golden.py).  CPU only: the tables are parsed from the header."""
 import os
 import re
 
 import numpy as np
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -58,14 +56,11 @@ def test_golden_keys():
 
 
 def test_against_reference_function_when_built():
-    path = os.path.join(ROOT, "oracle", "_ref", "libref_leaf.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    lib = C.CDLL(path, mode=os.RTLD_LAZY)
-    lib.peano_hilbert_key.restype = C.c_uint64
-    lib.peano_hilbert_key.argtypes = [C.c_int] * 4
-    rng = np.random.RandomState(5)
-    for bits in (1, 2, 5, 13, 21):
-        xyz = rng.randint(0, 1 << bits, size=(3000, 3))
-        ref = np.array([lib.peano_hilbert_key(int(a), int(b), int(c), bits) for a, b, c in xyz], np.uint64)
+    """peano_hilbert_key of the reference's utils/peano.c, as its in-place build (oracle/_ref/libref_leaf.so) computes it on random
+    triplets of 1, 2, 5, 13 and 21 bits, recorded in tests/golden/reference_leaf.npz (make_reference_golden.py)."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "reference_leaf.npz"))
+    assert g["peano_bits"].tolist() == [1, 2, 5, 13, 21]
+    for bits in g["peano_bits"].tolist():
+        xyz, ref = g["peano_xyz_%d" % bits], g["peano_keys_%d" % bits]
+        assert xyz.shape == (3000, 3) and xyz.min() >= 0 and xyz.max() < (1 << bits)
         assert np.array_equal(keys_from_tables(xyz, bits), ref), bits

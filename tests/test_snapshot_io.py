@@ -1,6 +1,7 @@
 """Snapshot / IC wire format (csrc/snapshot_io.hip through the C-ABI; host IO, no GPU): round trips, the on-disk layout, and
-interoperability BOTH WAYS with the reference's own library (depends/bigfile/src/bigfile.c built in place into oracle/_ref)."""
-import ctypes as C
+interoperability BOTH WAYS with the reference's own library (depends/bigfile/src/bigfile.c built in place into oracle/_ref), as
+recorded in tests/golden/reference_bigfile.npz."""
+import hashlib
 import os
 
 import numpy as np
@@ -66,119 +67,78 @@ def test_mass_table_fills_missing_mass_block(snap, tmp_path):
     assert np.all(parts[1]["Mass"] == np.float32(0.5)) and len(parts[1]["Mass"]) == 10
 
 
-# ---- the reference's own library (built in place, oracle/Makefile) -------------------------------------------------------------
+# ---- the reference's own library (depends/bigfile/src/bigfile.c built in place, oracle/Makefile), as recorded --------------------
+# tests/golden/make_reference_golden.py runs the reference library on the two snapshots below and records in
+# tests/golden/reference_bigfile.npz what it wrote (text of its header / attr-v2 files, SHA-256 of its data files) and what it read.
 
-def ref_lib():
-    path = os.path.join(ROOT, "oracle", "_ref", "libref_bigfile.so")
-    if not os.path.exists(path):
-        pytest.skip("oracle/_ref/libref_bigfile.so not built (reference tree absent)")
-    L = C.CDLL(path)
-    L.big_file_get_error_message.restype = C.c_char_p
-    return L
+def golden():
+    return np.load(os.path.join(ROOT, "tests", "golden", "reference_bigfile.npz"))
 
 
-class Opaque(C.Structure):
-    _fields_ = [("raw", C.c_char * 4096)]      # BigFile / BigBlock / BigBlockPtr / BigArray: opaque, over-sized
+def sha256(path):
+    with open(path, "rb") as f:
+        return hashlib.sha256(f.read()).hexdigest()
 
 
-def ref_write_block(L, fpath, block, arr, dtype, nfile):
-    bf, bb, ptr, ba = Opaque(), Opaque(), Opaque(), Opaque()
-    assert L.big_file_create(C.byref(bf), fpath.encode()) == 0, L.big_file_get_error_message()
-    n = arr.shape[0]
-    nmemb = 1 if arr.ndim == 1 else arr.shape[1]
-    fsize = (C.c_size_t * nfile)(*[n * (i + 1) // nfile - n * i // nfile for i in range(nfile)])
-    assert L.big_file_create_block(C.byref(bf), C.byref(bb), block.encode(), dtype.encode(), nmemb, nfile, fsize) == 0, L.big_file_get_error_message()
-    dims = (C.c_size_t * 2)(n, nmemb)
-    src = {np.float64: b"f8", np.float32: b"f4", np.uint64: b"u8"}[arr.dtype.type]
-    assert L.big_array_init(C.byref(ba), arr.ctypes.data_as(C.c_void_p), src, 2, dims, None) == 0
-    assert L.big_block_seek(C.byref(bb), C.byref(ptr), C.c_ssize_t(0)) == 0
-    assert L.big_block_write(C.byref(bb), C.byref(ptr), C.byref(ba)) == 0, L.big_file_get_error_message()
-    assert L.big_block_close(C.byref(bb)) == 0
-    L.big_file_close(C.byref(bf))
-
-
-def ref_set_attr(L, fpath, block, name, arr, dtype):
-    bf, bb = Opaque(), Opaque()
-    assert L.big_file_create(C.byref(bf), fpath.encode()) == 0
-    if os.path.exists(os.path.join(fpath, block, "header")):
-        assert L.big_file_open_block(C.byref(bf), C.byref(bb), block.encode()) == 0
-    else:
-        assert L.big_file_create_block(C.byref(bf), C.byref(bb), block.encode(), None, 0, 0, None) == 0
-    a = np.ascontiguousarray(arr)
-    assert L.big_block_set_attr(C.byref(bb), name.encode(), a.ctypes.data_as(C.c_void_p), dtype.encode(), int(a.shape[0])) == 0
-    assert L.big_block_close(C.byref(bb)) == 0
-    L.big_file_close(C.byref(bf))
-
-
-def ref_read_block(L, fpath, block, n, nmemb, npdtype, dtype):
-    bf, bb, ptr, ba = Opaque(), Opaque(), Opaque(), Opaque()
-    assert L.big_file_open(C.byref(bf), fpath.encode()) == 0, L.big_file_get_error_message()
-    assert L.big_file_open_block(C.byref(bf), C.byref(bb), block.encode()) == 0, L.big_file_get_error_message()
-    out = np.zeros((n, nmemb), npdtype)
-    dims = (C.c_size_t * 2)(n, nmemb)
-    assert L.big_array_init(C.byref(ba), out.ctypes.data_as(C.c_void_p), dtype.encode(), 2, dims, None) == 0
-    assert L.big_block_seek(C.byref(bb), C.byref(ptr), C.c_ssize_t(0)) == 0
-    assert L.big_block_read(C.byref(bb), C.byref(ptr), C.byref(ba)) == 0, L.big_file_get_error_message()
-    L.big_block_close(C.byref(bb))
-    L.big_file_close(C.byref(bf))
-    return out
-
-
-def ref_get_attr(L, fpath, block, name, npdtype, dtype, nmemb):
-    bf, bb = Opaque(), Opaque()
-    assert L.big_file_open(C.byref(bf), fpath.encode()) == 0
-    assert L.big_file_open_block(C.byref(bf), C.byref(bb), block.encode()) == 0
-    out = np.zeros(nmemb, npdtype)
-    assert L.big_block_get_attr(C.byref(bb), name.encode(), out.ctypes.data_as(C.c_void_p), dtype.encode(), nmemb) == 0, L.big_file_get_error_message()
-    L.big_block_close(C.byref(bb))
-    L.big_file_close(C.byref(bf))
-    return out
+def tree_files(path):
+    out = []
+    for d, _, fs in os.walk(path):
+        out += [os.path.relpath(os.path.join(d, f), path) for f in fs]
+    return sorted(out)
 
 
 def test_files_of_the_reference_library_are_read(snap, tmp_path):
-    L = ref_lib()
-    path = str(tmp_path / "REF")
+    """The reference library wrote particles(5003, 3) as a snapshot (Position f8 over 4 files, Velocity f4 over 2, ID u8, the Header
+    attributes).  This library writes the same blocks to the same bytes; and it reads the reference's snapshot: the data files, whose
+    bytes are the reference's (SHA-256), under the reference's own header / attr-v2 files."""
+    g = golden()
     p = particles(5003, 3)
-    ref_write_block(L, path, "1/Position", p["Position"], "f8", 4)
-    ref_write_block(L, path, "1/Velocity", p["Velocity"], "f4", 2)
-    ref_write_block(L, path, "1/ID", p["ID"], "u8", 1)
-    ref_set_attr(L, path, "Header", "TotNumPart", np.array([0, 5003, 0, 0, 0, 0], np.uint64), "u8")
-    ref_set_attr(L, path, "Header", "MassTable", np.array([0, 0.25, 0, 0, 0, 0]), "f8")
-    ref_set_attr(L, path, "Header", "BoxSize", np.array([25000.0]), "f8")
-    ref_set_attr(L, path, "Header", "Time", np.array([0.05]), "f8")
+    path = str(tmp_path / "REF")
+    snap.write_block(path, "1/Position", p["Position"], "f8", nfile=4)
+    snap.write_block(path, "1/Velocity", p["Velocity"], "f4", nfile=2)
+    snap.write_block(path, "1/ID", p["ID"], "u8", nfile=1)
+    snap.set_attr(path, "Header", "TotNumPart", np.array([0, 5003, 0, 0, 0, 0], np.uint64), "u8")
+    snap.set_attr(path, "Header", "MassTable", np.array([0, 0.25, 0, 0, 0, 0]), "f8")
+    snap.set_attr(path, "Header", "BoxSize", 25000.0, "f8")
+    snap.set_attr(path, "Header", "Time", 0.05, "f8")
+    # the two writers produce the same bytes
+    ref_meta = dict(zip(g["ref_meta_files"].tolist(), g["ref_meta_text"].tolist()))
+    ref_data = dict(zip(g["ref_data_files"].tolist(), g["ref_data_sha256"].tolist()))
+    assert sorted(ref_data) == ["1/ID/000000"] + ["1/Position/%06X" % f for f in range(4)] + ["1/Velocity/%06X" % f for f in range(2)]
+    for f, h in ref_data.items():
+        assert sha256(os.path.join(path, f)) == h, f
+    for f in ("1/Position/header", "1/Velocity/header", "Header/attr-v2"):
+        assert open(os.path.join(path, f)).read() == ref_meta[f], f
+    # ... so that with the reference's header / attr-v2 files in place the directory holds what the reference wrote
+    for f, text in ref_meta.items():
+        with open(os.path.join(path, f), "w") as fh:
+            fh.write(text)
+    assert set(ref_meta) | set(ref_data) <= set(tree_files(path))
     h, parts = snap.read_snapshot(path)
     assert h["TotNumPart"][1] == 5003 and h["BoxSize"] == 25000.0 and h["Time"] == 0.05
     assert np.array_equal(parts[1]["Position"], p["Position"]) and np.array_equal(parts[1]["ID"], p["ID"])
     assert np.array_equal(parts[1]["Velocity"], p["Velocity"].astype(np.float32).astype(np.float64))
     assert np.all(parts[1]["Mass"] == np.float32(0.25))
     assert snap.block_info(path, "1/Position") == dict(dtype="<f8", nmemb=3, nfile=4, size=5003)
-    # ... and the two writers produce the same bytes
-    mine = str(tmp_path / "MINE")
-    snap.write_block(mine, "1/Position", p["Position"], "f8", nfile=4)
-    snap.write_block(mine, "1/Velocity", p["Velocity"], "f4", nfile=2)
-    for blk, nf in (("1/Position", 4), ("1/Velocity", 2)):
-        assert open(os.path.join(mine, blk, "header")).read() == open(os.path.join(path, blk, "header")).read()
-        for f in range(nf):
-            assert open(os.path.join(mine, blk, "%06X" % f), "rb").read() == open(os.path.join(path, blk, "%06X" % f), "rb").read()
-    snap.set_attr(mine, "Header", "TotNumPart", np.array([0, 5003, 0, 0, 0, 0], np.uint64), "u8")
-    snap.set_attr(mine, "Header", "MassTable", np.array([0, 0.25, 0, 0, 0, 0]), "f8")
-    snap.set_attr(mine, "Header", "BoxSize", 25000.0, "f8")
-    snap.set_attr(mine, "Header", "Time", 0.05, "f8")
-    assert open(os.path.join(mine, "Header", "attr-v2")).read() == open(os.path.join(path, "Header", "attr-v2")).read()
 
 
 def test_files_written_here_are_read_by_the_reference_library(snap, tmp_path):
-    L = ref_lib()
+    """The reference library read particles(4097, 4) as written here (write_snapshot over 5 files) and returned every block and attribute
+    unchanged.  This library still writes those files byte for byte, and what the reference returned is what was written."""
+    g = golden()
     path = str(tmp_path / "PART_001")
     p = particles(4097, 4)
     snap.write_snapshot(path, {1: p}, box=8000.0, time=0.25, nfile=5)
-    assert np.array_equal(ref_read_block(L, path, "1/Position", 4097, 3, np.float64, "f8"), p["Position"])
-    assert np.array_equal(ref_read_block(L, path, "1/Velocity", 4097, 3, np.float32, "f4"), p["Velocity"].astype(np.float32))
-    assert np.array_equal(ref_read_block(L, path, "1/ID", 4097, 1, np.uint64, "u8")[:, 0], p["ID"])
-    assert np.array_equal(ref_read_block(L, path, "1/Mass", 4097, 1, np.float64, "f8")[:, 0], p["Mass"].astype(np.float64))   # cast on read
-    assert ref_get_attr(L, path, "Header", "TotNumPart", np.uint64, "u8", 6).tolist() == [0, 4097, 0, 0, 0, 0]
-    assert ref_get_attr(L, path, "Header", "BoxSize", np.float64, "f8", 1)[0] == 8000.0
-    assert ref_get_attr(L, path, "Header", "Time", np.float64, "f8", 1)[0] == 0.25
+    assert tree_files(path) == g["here_files"].tolist()
+    for f, h in zip(g["here_files"].tolist(), g["here_sha256"].tolist()):
+        assert sha256(os.path.join(path, f)) == h, f
+    want = {"1/Position": p["Position"], "1/Velocity": p["Velocity"].astype(np.float32), "1/ID": p["ID"],
+            "1/Mass": p["Mass"].astype(np.float64)}                     # (Mass cast on read)
+    assert g["here_read_blocks"].tolist() == sorted(want)
+    for b, h in zip(g["here_read_blocks"].tolist(), g["here_read_sha256"].tolist()):
+        assert hashlib.sha256(np.ascontiguousarray(want[b]).tobytes()).hexdigest() == h, b
+    assert g["here_attr_TotNumPart"].tolist() == [0, 4097, 0, 0, 0, 0]
+    assert g["here_attr_BoxSize"][0] == 8000.0 and g["here_attr_Time"][0] == 0.25
 
 
 def test_zero_length_attribute_does_not_break_the_block(snap, tmp_path):
