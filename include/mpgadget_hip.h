@@ -159,7 +159,8 @@ int mpg_grav_short_tree(mpg_engine *eng, const mpg_particle_view *pv, const int 
  * FullTreeGravAccel, GravPM and Potential once; from then on mpg_gravpm_force, mpg_force_tree_full / _rebuild_mask and
  * mpg_grav_short_tree called with the same view run on the device copies and leave their results there (P[] on the host goes stale:
  * AccelStore, when given, still receives its copy).  mpg_resident_fetch writes the named columns back into P[] for the host modules
- * that read them, mpg_resident_push takes columns the host changed, mpg_resident_end fetches everything and leaves the mode.
+ * that read them, mpg_resident_push takes columns the host changed, mpg_resident_end fetches everything and leaves the mode (and writes
+ * a StoredGravAccel held for a split-gravity step back into the caller's array: mpg_resident_hierarchical_*, further down).
  * Anything that reorders or resizes P[] (domain_exchange, slots_gc) goes between _end and a new _begin. */
 #define MPG_FIELD_POS 1u
 #define MPG_FIELD_VEL 2u
@@ -373,6 +374,13 @@ int mpg_dev_apply_half_kick(mpg_engine *eng, int64_t n, const int *d_active, int
                             const unsigned char *d_type, const unsigned char *d_flags, const unsigned char *d_tb_grav,
                             const unsigned char *d_tb_hydro, const double *d_hydroaccel, double *d_entropy, const double *d_dtentropy,
                             const mpg_kick_factors *K);
+/* apply_hydro_half_kick (timestep.c:930-968): the hydro kick of do_hydro_kick (timestep.c:1004-1036) alone - Vel += HydroAccel *
+ * hydrokick[TimeBinHydro], the gas velocity limit MaxGasVel * atime, Entropy += DtEntropy * dt_entr[TimeBinHydro] - for the gas among the
+ * listed particles (d_active == NULL: all n), bit-identical to the reference; no gravity kick (K->gravkick is not read), other types
+ * unchanged.  d_tb_hydro NULL: bin 0.  A hydro bin above MPG_TIMEBINS is an error. */
+int mpg_dev_apply_hydro_half_kick(mpg_engine *eng, int64_t n, const int *d_active, int64_t nactive, double *d_vel, const unsigned char *d_type,
+                                  const unsigned char *d_flags, const unsigned char *d_tb_hydro, const double *d_hydroaccel, double *d_entropy,
+                                  const double *d_dtentropy, const mpg_kick_factors *K);
 
 /* get_timestep_gravity_dloga (timestep.c:1039-1074) for every particle: dloga = H * sqrt(2 ErrTolIntAccuracy a (FORCE_SOFTENING/2.8)
  * / |a_phys|), a_phys = (FullTreeGravAccel + GravPM) / a^2.  Uses the softening set by mpg_gravshort_set_softenings. */
@@ -486,6 +494,9 @@ int mpg_find_timesteps_finish(int mTimeBin_global, int maxTimeBin_global, int is
  *   mpg_resident_apply_pm_half_kick    apply_PM_half_kick (timestep.c:964-985)
  *   mpg_resident_apply_half_kick       apply_half_kick (timestep.c:873-929): gravity kick, hydro kick, gas velocity limit, entropy
  *   mpg_resident_find_timesteps        find_timesteps (timestep.c:739-849): the step assignment of run.c:756 (no SplitGravityTimestepsOn)
+ *   mpg_resident_apply_hydro_half_kick apply_hydro_half_kick (timestep.c:930-968): the hydro kick alone (SplitGravityTimestepsOn)
+ *   mpg_resident_hierarchical_gravity_accelerations / _and_timesteps
+ *                                      the level loop of SplitGravityTimestepsOn (timestep.c:293-599, run.c:536-540, 766-767)
  *   mpg_resident_find_hydro_timesteps  find_hydro_timesteps (timestep.c:617-733) on TimeBinHydro (both halves, one rank; several ranks:
  *                                      mpg_dev_find_hydro_timesteps + the caller's MPI_Allreduce + mpg_dev_hydro_timesteps_finish on
  *                                      mpg_resident_sph_arrays)
@@ -510,6 +521,31 @@ int mpg_resident_find_timesteps(mpg_engine *eng, const mpg_particle_view *pv, co
 int mpg_resident_find_hydro_timesteps(mpg_engine *eng, const mpg_particle_view *pv, const int *ActiveParticle, int64_t NumActiveParticle,
                                       mpg_drift_kick_times *times, const mpg_timeline *timeline, const mpg_timestep_params *par, double CourantFac,
                                       double atime, double hubble, int isFirstTimeStep, mpg_hydrostep_result *out);
+
+int mpg_resident_apply_hydro_half_kick(mpg_engine *eng, const mpg_particle_view *pv, const int *ActiveParticle, int64_t NumActiveParticle,
+                                       const mpg_kick_factors *K);
+/* The branch of run.c WITH SplitGravityTimestepsOn (the default) on a resident run, one rank: mpg_dev_hierarchical_gravity_accelerations /
+ * _and_timesteps on the resident table.  Vel, GravPM, FullTreeGravAccel and Potential are the table's columns, TimeBinGravity is the resident
+ * gas run's tb_grav (so, as for mpg_resident_find_timesteps, mpg_resident_sph_begin comes first), the flags are the table's; the host active
+ * list is uploaded (NULL: all n particles active, whatever NumActiveParticle says), the level trees are built from the resident positions.  rho0, the timeline, the PM step length on a PM step and the
+ * gravkick callback are as for the dev forms.
+ * StoredGravAccel (run.c:533-540: filled by the first call, read by the second) lives on the device for the caller's host array of
+ * [n][3] (the first n rows of struct grav_accel_store's GravAccel):
+ *   - a call naming a host array the engine does not hold yet uploads its first n rows and holds it from then on;
+ *   - mpg_resident_end writes the device copy back into the held array (n rows) and releases it, so the stretch may end and a new one begin
+ *     between the two calls (cooling, star formation, FOF, a snapshot) and the second call then takes the array up again;
+ *   - _and_timesteps releases the array once it has used it (the reference frees it there, timestep.c:417-418);
+ *   - NULL: no stored array, FullTreeGravAccel plays its part (timestep.c:352, 417).
+ * Not carried: several ranks (the dev forms on mpg_dist state are the multi-rank path), black holes (mpg_shim_resident_begin refuses
+ * them), and star particles created during the step (only n rows are kept).  The trees of the levels replace the engine's tree. */
+int mpg_resident_hierarchical_gravity_accelerations(mpg_engine *eng, const mpg_particle_view *pv, const int *ActiveParticle, int64_t NumActiveParticle,
+                                                    int64_t NumActiveGravity, mpg_drift_kick_times *times, double rho0, int HybridNuGrav,
+                                                    mpg_gravkick_fn gravkick, void *gravkick_ctx, double (*StoredGravAccel)[3]);
+int mpg_resident_hierarchical_gravity_and_timesteps(mpg_engine *eng, const mpg_particle_view *pv, const int *ActiveParticle, int64_t NumActiveParticle,
+                                                    int64_t NumActiveGravity, mpg_drift_kick_times *times, const mpg_timeline *timeline,
+                                                    const mpg_timestep_params *par, double atime, double hubble, int64_t dti_max_pm, double rho0,
+                                                    int HybridNuGrav, mpg_gravkick_fn gravkick, void *gravkick_ctx, double (*StoredGravAccel)[3],
+                                                    int64_t *badstepsizecount);
 
 /* build_active_sublist (timestep.c:1435-1478): the entries of d_active (NULL = all n) that are not garbage, whose gravity bin
  * is <= maxtimebin and active at Ti_Current, order preserved.  d_out must hold NumActiveParticle entries. */

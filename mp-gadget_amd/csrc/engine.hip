@@ -689,6 +689,21 @@ int mpg_dev_apply_half_kick(mpg_engine *eng, int64_t n, const int *d_active, int
     API_END
 }
 
+int mpg_dev_apply_hydro_half_kick(mpg_engine *eng, int64_t n, const int *d_active, int64_t nactive, double *d_vel, const unsigned char *d_type,
+                                  const unsigned char *d_flags, const unsigned char *d_tb_hydro, const double *d_hydroaccel, double *d_entropy,
+                                  const double *d_dtentropy, const mpg_kick_factors *K)
+{
+    API_BEGIN
+    MPG_CHECK(eng && d_vel && d_type && d_hydroaccel && d_entropy && d_dtentropy && K && n >= 0 && nactive >= 0, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    eng->ts_flag.reserve(4);
+    MPG_HIP(hipMemsetAsync(eng->ts_flag.p, 0, sizeof(unsigned), eng->stream));
+    launch_hydro_half_kick(n, d_active, nactive, d_vel, d_type, d_flags, d_tb_hydro, d_hydroaccel, d_entropy, d_dtentropy, *K, eng->ts_flag.p,
+                           eng->stream);
+    MPG_CHECK(read_flag(eng, eng->ts_flag.p) == 0, "hydro half kick: a particle has an unexpected hydro time bin (> TIMEBINS)");
+    API_END
+}
+
 int mpg_dev_timestep_gravity_dloga(mpg_engine *eng, int64_t n, const double *d_gravaccel, const double *d_gravpm, double atime, double hubble,
                                    double ErrTolIntAccuracy, double *d_dloga)
 {
@@ -2276,6 +2291,11 @@ int mpg_resident_end(mpg_engine *eng, const mpg_particle_view *P)
     if(mpg_resident_fetch(eng, P, MPG_FIELD_POS | MPG_FIELD_VEL | MPG_FIELD_ACCEL | MPG_FIELD_GRAVPM | MPG_FIELD_POTENTIAL))
         throw Error(g_err);
     MPG_CHECK(!eng->sph_resident, "mpg_resident_end: the gas arrays are still resident (mpg_resident_sph_end first)");
+    if(eng->r_stored_host) { // the StoredGravAccel of a split-gravity step left between its two halves goes back to the caller's array
+        MPG_HIP(hipMemcpyAsync(eng->r_stored_host, eng->r_stored.p, 3 * (size_t)P->n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+        MPG_HIP(hipStreamSynchronize(eng->stream));
+        eng->r_stored_host = nullptr;
+    }
     eng->resident = false;
     eng->res_has_vel = false;
     eng->res_base = nullptr;
@@ -2852,6 +2872,111 @@ int mpg_resident_find_timesteps(mpg_engine *eng, const mpg_particle_view *P, con
                               CourantFac, atime, hubble, dti_max_pm, out) ||
        mpg_find_timesteps_finish(out->mTimeBin, out->maxTimeBin, out->isPM, times))
         throw Error(g_err);
+    API_END
+}
+
+int mpg_resident_apply_hydro_half_kick(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
+                                       const mpg_kick_factors *K)
+{
+    API_BEGIN
+    MPG_CHECK(eng && P && K, "null argument");
+    resident_sph_check(eng, P);
+    const mpg_sph_arrays &d = eng->res_sph_dev;
+    const int *d_act = nullptr;
+    if(ActiveParticle) {
+        eng->s_active.reserve((size_t)NumActiveParticle + 1);
+        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
+        d_act = eng->s_active.p;
+    }
+    if(mpg_dev_apply_hydro_half_kick(eng, P->n, d_act, NumActiveParticle, eng->r_vel.p, eng->s_type.p, eng->r_flags.p, d.tb_hydro, d.hydroacc_out,
+                                     (double *)d.entropy, d.dtentropy_out, K))
+        throw Error(g_err);
+    API_END
+}
+
+/* The branch of run.c WITH SplitGravityTimestepsOn (run.c:497-499, 536-540, 766-775) on a resident run: the level loop of
+ * mpg_dev_hierarchical_* on the resident table - Vel, GravPM, FullTreeGravAccel and Potential are its columns, TimeBinGravity the resident gas
+ * run's tb_grav (mpg_resident_sph_begin, as for mpg_resident_find_timesteps), the flags those of the resident table.  The trees of the levels
+ * are built from the resident positions.  StoredGravAccel: the device copy r_stored stands for the caller's host array (include/mpgadget_hip.h).
+ * Carried: one rank, dark matter and gas.  Not carried: several ranks (the level loop's trees are local), black holes, and star particles
+ * created during the step (the reference's extra StoredGravAccel rows, run.c:537-538: only the first n rows exist here). */
+namespace {
+void resident_hier_arrays(mpg_engine *eng, const mpg_particle_view *P, double (*StoredGravAccel)[3], mpg_hiergrav_arrays *A)
+{
+    resident_sph_check(eng, P);
+    MPG_CHECK(eng->res_has_vel, "resident hierarchical gravity: the resident table has no Vel column");
+    const mpg_sph_arrays &d = eng->res_sph_dev;
+    MPG_CHECK(d.tb_grav, "resident hierarchical gravity: the gas arrays have no TimeBinGravity");
+    stage_particles(eng, P, eng->box); // (resident: checks that the device binding is still the table's)
+    const int64_t n = P->n;
+    A->d_vel = eng->r_vel.p;
+    A->d_gravpm = eng->r_gravpm.p;
+    A->d_fulltree_accel = eng->r_accel.p;
+    A->d_potential = eng->r_pot.p;
+    A->d_tb_grav = (unsigned char *)d.tb_grav;
+    A->d_flags = eng->r_flags.p;
+    A->d_stored_accel = nullptr;
+    if(!StoredGravAccel)
+        return; // FullTreeGravAccel plays the part of the stored array
+    if(StoredGravAccel != eng->r_stored_host) {
+        MPG_CHECK(!eng->r_stored_host, "resident hierarchical gravity: another StoredGravAccel array is still held (hierarchical_gravity_and_timesteps "
+                                       "or mpg_resident_end releases it)");
+        eng->r_stored.reserve(3 * (size_t)n + 3);
+        if(n > 0) { // (a host array the engine does not hold yet: its first n rows)
+            MPG_HIP(hipMemcpyAsync(eng->r_stored.p, StoredGravAccel, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+            MPG_HIP(hipStreamSynchronize(eng->stream));
+        }
+        eng->r_stored_host = StoredGravAccel;
+    }
+    A->d_stored_accel = eng->r_stored.p;
+}
+const int *resident_active(mpg_engine *eng, const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    if(!ActiveParticle)
+        return nullptr;
+    eng->s_active.reserve((size_t)NumActiveParticle + 1);
+    MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
+    return eng->s_active.p;
+}
+} // namespace
+
+int mpg_resident_hierarchical_gravity_accelerations(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
+                                                    int64_t NumActiveGravity, mpg_drift_kick_times *times, double rho0, int HybridNuGrav,
+                                                    mpg_gravkick_fn gravkick, void *gravkick_ctx, double (*StoredGravAccel)[3])
+{
+    API_BEGIN
+    MPG_CHECK(eng && P && times && gravkick && NumActiveParticle >= 0 && NumActiveGravity >= 0, "null argument");
+    MPG_CHECK(!ActiveParticle || NumActiveParticle <= P->n, "resident hierarchical gravity: more active particles than particles");
+    mpg_hiergrav_arrays A;
+    resident_hier_arrays(eng, P, StoredGravAccel, &A);
+    const int *d_act = resident_active(eng, ActiveParticle, NumActiveParticle);
+    if(!ActiveParticle) // every particle is active (build_active_particles on a PM step: NumActiveParticle = NumPart)
+        NumActiveParticle = P->n;
+    if(mpg_dev_hierarchical_gravity_accelerations(eng, &A, d_act, NumActiveParticle, NumActiveGravity, times, rho0, HybridNuGrav, gravkick, gravkick_ctx))
+        throw Error(g_err);
+    API_END
+}
+
+int mpg_resident_hierarchical_gravity_and_timesteps(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
+                                                    int64_t NumActiveGravity, mpg_drift_kick_times *times, const mpg_timeline *timeline,
+                                                    const mpg_timestep_params *par, double atime, double hubble, int64_t dti_max_pm, double rho0,
+                                                    int HybridNuGrav, mpg_gravkick_fn gravkick, void *gravkick_ctx, double (*StoredGravAccel)[3],
+                                                    int64_t *badstepsizecount)
+{
+    API_BEGIN
+    MPG_CHECK(eng && P && times && timeline && par && gravkick && badstepsizecount && NumActiveParticle >= 0 && NumActiveGravity >= 0, "null argument");
+    MPG_CHECK(!ActiveParticle || NumActiveParticle <= P->n, "resident hierarchical gravity: more active particles than particles");
+    mpg_hiergrav_arrays A;
+    resident_hier_arrays(eng, P, StoredGravAccel, &A);
+    const int *d_act = resident_active(eng, ActiveParticle, NumActiveParticle);
+    if(!ActiveParticle)
+        NumActiveParticle = P->n;
+    if(mpg_dev_hierarchical_gravity_and_timesteps(eng, &A, d_act, NumActiveParticle, NumActiveGravity, times, timeline, par, atime, hubble, dti_max_pm,
+                                                  rho0, HybridNuGrav, gravkick, gravkick_ctx, badstepsizecount))
+        throw Error(g_err);
+    // the step has consumed the stored accelerations: the reference frees the array here (timestep.c:417-418)
+    if(StoredGravAccel)
+        eng->r_stored_host = nullptr;
     API_END
 }
 

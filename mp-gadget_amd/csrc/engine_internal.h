@@ -249,6 +249,10 @@ struct mpg_engine {
     bool sph_resident = false;
     mpg_sph_arrays res_sph_host{}, res_sph_dev{};
     DevBuf<uint8_t> r_flags;
+    // ... and the device copy of the caller's StoredGravAccel of a resident split-gravity step (mpg_resident_hierarchical_*): the host array it
+    // stands for (nullptr: none held), written back into it by mpg_resident_end
+    DevBuf<double> r_stored;
+    double (*r_stored_host)[3] = nullptr;
     double staged_box = 0;
     hipEvent_t chunk_ev[8] = {};
     // Host path with overlap (mpg_set_host_overlap): within one particle-table epoch Pos / Mass / Type, Potential AND the

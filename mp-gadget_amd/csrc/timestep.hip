@@ -5,12 +5,14 @@
 //   k_drift          drift_all_particles / real_drift_particle   libgadget/drift.c:18-102
 //   k_pm_half_kick   apply_PM_half_kick                          libgadget/timestep.c:964-985
 //   k_half_kick      apply_half_kick + do_grav_short_range_kick + do_hydro_kick (gas part)   timestep.c:873-929, 988-1036
+//   k_hydro_half_kick  apply_hydro_half_kick + do_hydro_kick (gas part), no gravity kick        timestep.c:930-968, 1004-1036
 //   k_assign_gravity_bins, k_level_gravity_bins, k_push_down_bins, k_kick_list, k_sublist_flags
 //                    the per-particle loops of the hierarchical gravity level loop             timestep.c:239-599, 1435-1478
 // The per-bin factors (get_exact_drift/gravkick/hydrokick_factor, dloga_from_dti) are computed by the caller with the
 // reference's own functions and passed in (mpg_kick_factors), as for the SPH loops.  Not carried: black-hole repositioning
 // and the dynamic-friction / drag kicks of type-5 particles (sub-grid physics, out of scope).
-// Pure HBM streaming: per particle 73 B read + 32 B written (drift), 48 + 24 B (PM kick), up to 98 + 32 B (half kick).
+// Pure HBM streaming: per particle 73 B read + 32 B written (drift), 48 + 24 B (PM kick), up to 98 + 32 B (half kick), about 90 + 32 B
+// per gas particle (hydro half kick).
 // Floating-point contraction is off in this file: the reference's loops are compiled without FMA, and these results are
 // required to be bit-identical to it (tests/test_gpu_timestep.py).
 #include "mpg_common.h"
@@ -119,6 +121,47 @@ __global__ void __launch_bounds__(256) k_half_kick(int64_t n, const int *__restr
         }
         entropy[i] += dtentropy[i] * K.dt_entr[bh];
     }
+#pragma unroll
+    for(int j = 0; j < 3; j++)
+        vel[3 * i + j] = v[j];
+}
+
+// apply_hydro_half_kick (timestep.c:930-968): the hydro part of do_hydro_kick (timestep.c:1004-1036) for the gas among the listed
+// particles, in the reference's order - velocity kick, gas velocity limit, entropy - and applied whatever the factor (0 for a bin that is
+// not active or lies below mintimebin), as the reference does.  No gravity kick: FullTreeGravAccel is not read.  Other types are left
+// alone; black holes (the dynamic-friction / drag kicks of type 5) never get here, mpg_shim_resident_begin refuses them.
+__global__ void __launch_bounds__(256) k_hydro_half_kick(int64_t n, const int *__restrict__ active, int64_t nactive, double *__restrict__ vel,
+                                                         const uint8_t *__restrict__ type, const uint8_t *__restrict__ flags,
+                                                         const uint8_t *__restrict__ tbh, const double *__restrict__ hacc,
+                                                         double *__restrict__ entropy, const double *__restrict__ dtentropy, const mpg_kick_factors K,
+                                                         unsigned *__restrict__ err)
+{
+    const int64_t pa = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(pa >= (active ? nactive : n))
+        return;
+    const int64_t i = active ? active[pa] : pa;
+    if((flags && (flags[i] & 3)) || type[i] != 0)
+        return;
+    const int bh = tbh ? tbh[i] : 0;
+    if(bh > MPG_TIMEBINS) {
+        atomicExch(err, 4u);
+        return;
+    }
+    double v[3] = {vel[3 * i], vel[3 * i + 1], vel[3 * i + 2]};
+#pragma unroll
+    for(int j = 0; j < 3; j++)
+        v[j] += hacc[3 * i + j] * K.hydrokick[bh];
+    double vv = 0;
+#pragma unroll
+    for(int j = 0; j < 3; j++)
+        vv += v[j] * v[j];
+    vv = sqrt(vv);
+    if(vv > 0 && vv / K.atime > K.MaxGasVel) {
+#pragma unroll
+        for(int j = 0; j < 3; j++)
+            v[j] *= K.MaxGasVel * K.atime / vv;
+    }
+    entropy[i] += dtentropy[i] * K.dt_entr[bh];
 #pragma unroll
     for(int j = 0; j < 3; j++)
         vel[3 * i + j] = v[j];
@@ -622,6 +665,16 @@ void launch_half_kick(int64_t n, const int *active, int64_t nactive, double *vel
     if(na > 0)
         hipLaunchKernelGGL(k_half_kick, dim3(nblk(na)), dim3(256), 0, st, n, active, nactive, vel, gacc, type, flags, tbg, tbh, hacc, entropy,
                            dtentropy, K, err);
+    MPG_HIP(hipGetLastError());
+}
+
+void launch_hydro_half_kick(int64_t n, const int *active, int64_t nactive, double *vel, const uint8_t *type, const uint8_t *flags, const uint8_t *tbh,
+                            const double *hacc, double *entropy, const double *dtentropy, const mpg_kick_factors &K, unsigned *err, hipStream_t st)
+{
+    const int64_t na = active ? nactive : n;
+    if(na > 0)
+        hipLaunchKernelGGL(k_hydro_half_kick, dim3(nblk(na)), dim3(256), 0, st, n, active, nactive, vel, type, flags, tbh, hacc, entropy, dtentropy,
+                           K, err);
     MPG_HIP(hipGetLastError());
 }
 

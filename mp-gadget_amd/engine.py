@@ -443,6 +443,60 @@ class Engine:
         return dict(mTimeBin=res.mTimeBin, maxTimeBin=res.maxTimeBin, isPM=res.isPM, ntitype=list(res.ntitype),
                     badstepsizecount=res.badstepsizecount, badtimebins=res.badtimebins)
 
+    def resident_apply_hydro_half_kick(self, P, K, ActiveParticle=None):
+        """apply_hydro_half_kick (timestep.c:930-968) on a resident gas run: the hydro kick of the gas alone (SplitGravityTimestepsOn)"""
+        v = self._view(P)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_resident_apply_hydro_half_kick(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
+                                                             C.c_int64(0 if act is None else len(act)), C.byref(K)))
+
+    def _stored_accel(self, P, StoredGravAccel):
+        """the host StoredGravAccel of a resident split-gravity step: the engine keeps its pointer until _and_timesteps or resident_end"""
+        if StoredGravAccel is None:
+            return None
+        a = StoredGravAccel
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < len(P) or \
+                not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+            raise EngineError("StoredGravAccel must be a writeable contiguous float64 array of (n, 3) with n >= len(P)")
+        self._keep["stored_accel"] = a
+        return a.ctypes.data_as(C.c_void_p)
+
+    def resident_hierarchical_gravity_accelerations(self, P, times, rho0, gravkick, ActiveParticle=None, NumActiveGravity=None,
+                                                    StoredGravAccel=None, HybridNuGrav=0):
+        """hierarchical_gravity_accelerations (timestep.c:495-599) on a resident run (after resident_sph_begin): the accelerations of every
+        active level and their kicks on the resident table.  StoredGravAccel: None or a NumPy (n, 3) array (include/mpgadget_hip.h: the
+        engine holds a device copy for it, written back by resident_end).  gravkick(ti0, ti1) -> get_exact_gravkick_factor."""
+        v = self._view(P)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        na = len(P) if act is None else len(act)
+        nag = na if NumActiveGravity is None else int(NumActiveGravity)
+        sga = self._stored_accel(P, StoredGravAccel)
+        fn = GRAVKICK_FN(lambda ctx, a, b: float(gravkick(a, b)))
+        self._ck(self.lib.mpg_resident_hierarchical_gravity_accelerations(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
+                                                                          C.c_int64(na), C.c_int64(nag), C.byref(times), C.c_double(rho0),
+                                                                          int(HybridNuGrav), fn, None, sga))
+
+    def resident_hierarchical_gravity_and_timesteps(self, P, times, sync_loga, ErrTolIntAccuracy, MinSizeTimestep, atime, hubble, dti_max_pm, rho0,
+                                                    gravkick, ActiveParticle=None, NumActiveGravity=None, StoredGravAccel=None, HybridNuGrav=0):
+        """hierarchical_gravity_and_timesteps (timestep.c:293-490) on a resident run: new gravity bins, the accelerations of the lower
+        levels and the kicks; times updated in place (dti_max_pm = the caller's get_PM_timestep_ti on a PM step).  Returns
+        badstepsizecount.  The engine releases StoredGravAccel afterwards (the reference frees it there)."""
+        v = self._view(P)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        na = len(P) if act is None else len(act)
+        nag = na if NumActiveGravity is None else int(NumActiveGravity)
+        sga = self._stored_accel(P, StoredGravAccel)
+        loga = (C.c_double * len(sync_loga))(*[float(x) for x in sync_loga])
+        tl = Timeline(len(sync_loga), C.cast(loga, C.POINTER(C.c_double)))
+        par = TimestepParams(ErrTolIntAccuracy, MinSizeTimestep)
+        fn = GRAVKICK_FN(lambda ctx, a, b: float(gravkick(a, b)))
+        bad = C.c_int64(0)
+        self._ck(self.lib.mpg_resident_hierarchical_gravity_and_timesteps(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
+                                                                          C.c_int64(na), C.c_int64(nag), C.byref(times), C.byref(tl), C.byref(par),
+                                                                          C.c_double(atime), C.c_double(hubble), C.c_int64(dti_max_pm),
+                                                                          C.c_double(rho0), int(HybridNuGrav), fn, None, sga, C.byref(bad)))
+        return bad.value
+
     def host_prefetch(self, P, box):
         """mpg_host_prefetch: start this epoch's packing pass + uploads of P[] on a host thread (after set_particle_epoch; needs
         set_host_overlap)"""
@@ -538,6 +592,12 @@ class Engine:
         self._ck(self.lib.mpg_dev_apply_half_kick(self.h, C.c_int64(vel.shape[0]), _ptr(active), C.c_int64(0 if active is None else active.shape[0]),
                                                   _ptr(vel), _ptr(gravaccel), _ptr(type), _ptr(flags), _ptr(tb_grav), _ptr(tb_hydro),
                                                   _ptr(hydroaccel), _ptr(entropy), _ptr(dtentropy), C.byref(K)))
+
+    def dev_apply_hydro_half_kick(self, vel, K, type, hydroaccel, entropy, dtentropy, active=None, flags=None, tb_hydro=None):
+        """apply_hydro_half_kick (timestep.c:930-968): the hydro kick of the gas alone, no gravity kick (K.gravkick is not read)"""
+        self._ck(self.lib.mpg_dev_apply_hydro_half_kick(self.h, C.c_int64(vel.shape[0]), _ptr(active),
+                                                        C.c_int64(0 if active is None else active.shape[0]), _ptr(vel), _ptr(type), _ptr(flags),
+                                                        _ptr(tb_hydro), _ptr(hydroaccel), _ptr(entropy), _ptr(dtentropy), C.byref(K)))
 
     def dev_timestep_gravity_dloga(self, gravaccel, gravpm, atime, hubble, ErrTolIntAccuracy, dloga):
         self._ck(self.lib.mpg_dev_timestep_gravity_dloga(self.h, C.c_int64(gravaccel.shape[0]), _ptr(gravaccel), _ptr(gravpm), C.c_double(atime),

@@ -61,8 +61,8 @@ mpg_particle_view mpg_shim_view(void);
 /* ---- a run whose table stays in HBM between two domain decompositions (timestep-hip.c) ----
  * mpg_shim_resident_begin after the step's domain_decompose_full / domain_maintain, mpg_shim_resident_end before the next one and before
  * any host module that reads P[] / SphP[]; in between density(), hydro_force(), gravpm_force(), force_tree_full(), grav_short_tree(),
- * find_timesteps(), find_hydro_timesteps(), apply_half_kick(), apply_PM_half_kick() and drift_all_particles() run on the device copies;
- * the hierarchical-gravity functions (apply_hydro_half_kick, hierarchical_gravity_*) stop the run there. */
+ * find_timesteps(), find_hydro_timesteps(), apply_half_kick(), apply_PM_half_kick(), drift_all_particles() and - the branch with
+ * SplitGravityTimestepsOn - apply_hydro_half_kick() and hierarchical_gravity_accelerations() / _and_timesteps() run on the device copies. */
 void mpg_shim_resident_begin(double BoxSize);
 void mpg_shim_resident_end(void);
 int mpg_shim_resident(void);

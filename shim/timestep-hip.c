@@ -19,17 +19,20 @@
  *     drift.o:    CFLAGS += -Ddrift_all_particles=cpu_drift_all_particles
  * These are ALL the functions of run.c's step that read or write the integrated columns (run.c:420, 498-499, 536-565, 754-794): a function of
  * that set that stayed on the host inside a resident stretch would integrate the stale host copies and its work would be discarded by the
- * fetch at the end.  The resident stretch carries the branch WITHOUT SplitGravityTimestepsOn (run.c:553-565, 754-759:
- * find_timesteps + apply_half_kick); with All.HierarchicalGravity the three functions of that branch stop the run with a message instead
- * of kicking host copies (its level loop has a device form of its own, mpg_dev_hierarchical_*, which takes device arrays the resident
- * table does not hand out yet).
+ * fetch at the end.  The resident stretch carries BOTH branches of run.c:
+ *   - without SplitGravityTimestepsOn (run.c:553-565, 754-759): find_timesteps + apply_half_kick;
+ *   - with it (the default, run.c:497-499, 536-540, 766-775): apply_hydro_half_kick, hierarchical_gravity_accelerations and
+ *     hierarchical_gravity_and_timesteps, the level loop on the resident table (mpg_resident_hierarchical_*).  The StoredGravAccel of the step
+ *     lives on the device between the two halves; if the stretch ends in between (cooling / star formation, FOF, a snapshot), the engine
+ *     writes it back into the caller's array and takes it up again in the second half.
  * Outside a resident stretch the definitions here call those cpu_ originals, so a run that never calls mpg_shim_resident_begin behaves as
  * before.  Inside one, the factors come from the reference's own get_exact_*_factor / dloga_from_dti (host arithmetic on the integer
  * timeline) and the per-particle loops run as mpg_resident_* on the device (include/mpgadget_hip.h).  One rank per GPU; NTask > 1 keeps the
  * host path (the resident calls are one-rank forms: mpg_dist_* owns the multi-rank choreography).
  * Not covered (the shim stops with a message): black-hole particles inside a resident stretch (drift.c:33-55 repositioning, the
- * dynamic-friction kicks, timestep.c:1003-1010), hierarchical gravity (apply_hydro_half_kick, hierarchical_gravity_and_timesteps and
- * hierarchical_gravity_accelerations below call endrun inside a resident stretch), ForceEqualTimesteps. */
+ * dynamic-friction kicks, timestep.c:1003-1010), ForceEqualTimesteps; star particles created inside a stretch get no stored acceleration
+ * (only NumPart rows of StoredGravAccel are kept).  With NTask > 1 mpg_shim_resident_begin returns at once and both branches keep the
+ * host path. */
 #include <mpi.h>
 #include <math.h>
 #include <string.h>
@@ -193,6 +196,25 @@ static void fetch_timebins(void)
 
 /* ---- the reference's entry points ---- */
 
+/* the kick factors per bin of apply_half_kick and apply_hydro_half_kick (the same loop, timestep.c:878-890 and 936-945): the factors of
+ * the active bins from mintimebin on, dt_entr (timestep.c:915-917) for every bin */
+static void kick_factors(mpg_kick_factors *K, Cosmology *CP, const DriftKickTimes *times, const double atime)
+{
+    int bin;
+    memset(K, 0, sizeof(*K));
+    for(bin = 0; bin <= TIMEBINS; bin++) {
+        K->bin_active[bin] = (unsigned char)is_timebin_active(bin, times->Ti_Current);
+        K->dt_entr[bin] = dloga_from_dti(dti_from_timebin(bin) / 2, times->Ti_Current);
+        if(bin < times->mintimebin || !K->bin_active[bin])
+            continue;
+        const inttime_t newkick = times->Ti_kick[bin] + dti_from_timebin(bin) / 2;
+        K->gravkick[bin] = get_exact_gravkick_factor(CP, times->Ti_kick[bin], newkick);
+        K->hydrokick[bin] = get_exact_hydrokick_factor(CP, times->Ti_kick[bin], newkick);
+    }
+    K->atime = atime;
+    K->MaxGasVel = mpg_shim_max_gas_vel(); /* TimestepParams.MaxGasVel is static in timestep.c: one accessor added there */
+}
+
 /* apply_half_kick, timestep.c:873-929: the kick factors per bin on the host as there, the particle loop on the device */
 void apply_half_kick(const ActiveParticles *act, Cosmology *CP, DriftKickTimes *times, const double atime)
 {
@@ -200,21 +222,9 @@ void apply_half_kick(const ActiveParticles *act, Cosmology *CP, DriftKickTimes *
         cpu_apply_half_kick(act, CP, times, atime);
         return;
     }
-    int bin;
     mpg_kick_factors K;
     walltime_measure("/Misc");
-    memset(&K, 0, sizeof(K));
-    for(bin = 0; bin <= TIMEBINS; bin++) {
-        K.bin_active[bin] = (unsigned char)is_timebin_active(bin, times->Ti_Current);
-        K.dt_entr[bin] = dloga_from_dti(dti_from_timebin(bin) / 2, times->Ti_Current); /* timestep.c:915-917 */
-        if(bin < times->mintimebin || !K.bin_active[bin])
-            continue;
-        const inttime_t newkick = times->Ti_kick[bin] + dti_from_timebin(bin) / 2;
-        K.gravkick[bin] = get_exact_gravkick_factor(CP, times->Ti_kick[bin], newkick);
-        K.hydrokick[bin] = get_exact_hydrokick_factor(CP, times->Ti_kick[bin], newkick);
-    }
-    K.atime = atime;
-    K.MaxGasVel = mpg_shim_max_gas_vel(); /* TimestepParams.MaxGasVel is static in timestep.c: one accessor added there */
+    kick_factors(&K, CP, times, atime);
     mpg_particle_view v = view();
     ck(mpg_resident_apply_half_kick(mpg_shim_engine(), &v, act->ActiveParticle, act->NumActiveParticle, &K));
     walltime_measure("/Timeline/HalfKick/Short");
@@ -318,33 +328,84 @@ int find_timesteps(const ActiveParticles *act, DriftKickTimes *times, const doub
 }
 
 /* The branch of run.c with All.HierarchicalGravity (run.c:498-499, 536-541, 766-775).  Outside a resident stretch: the originals.  Inside
- * one they must not run - they would kick and re-bin the stale host copies, and mpg_shim_resident_end would then overwrite their work. */
-static void no_hierarchical_gravity(const char *fn)
-{
-    endrun(5, "%s inside mpg_shim_resident_begin / _end: hierarchical gravity (SplitGravityTimestepsOn) is not carried by the resident "
-              "integrator - set SplitGravityTimestepsOn = 0 or leave the resident stretch (mpg_shim_resident_end) first\n", fn);
-}
+ * one: the hydro-only half kick and the level loop on the device copies (mpg_resident_apply_hydro_half_kick,
+ * mpg_resident_hierarchical_gravity_*).  StoredGravAccel.GravAccel is handed to the engine as the host array its device copy stands for:
+ * mpg_shim_resident_end writes the copy back into it when the stretch ends between the two halves of the step. */
 
+/* apply_hydro_half_kick, timestep.c:930-968: the factors as for apply_half_kick, the hydro kick of the gas on the device */
 void apply_hydro_half_kick(const ActiveParticles *act, Cosmology *CP, DriftKickTimes *times, const double atime)
 {
-    if(R.on)
-        no_hierarchical_gravity("apply_hydro_half_kick");
-    cpu_apply_hydro_half_kick(act, CP, times, atime);
+    if(!R.on) {
+        cpu_apply_hydro_half_kick(act, CP, times, atime);
+        return;
+    }
+    mpg_kick_factors K;
+    kick_factors(&K, CP, times, atime);
+    mpg_particle_view v = view();
+    ck(mpg_resident_apply_hydro_half_kick(mpg_shim_engine(), &v, act->ActiveParticle, act->NumActiveParticle, &K));
+    walltime_measure("/Timeline/HalfKick/Short");
 }
 
+/* get_exact_gravkick_factor (timefac.c:65-68) for the level loop's kicks */
+static double shim_gravkick(void *CP, int64_t ti0, int64_t ti1) { return get_exact_gravkick_factor((Cosmology *)CP, ti0, ti1); }
+/* the mean density of grav_short_tree (run.c:545, timestep.c:323) */
+static double shim_rho0(const Cosmology *CP) { return CP->Omega0 * 3 * CP->Hubble * CP->Hubble / (8 * M_PI * CP->GravInternal); }
+
+/* hierarchical_gravity_and_timesteps, timestep.c:293-490: the new gravity bins, the accelerations of the lower levels and the kicks on the
+ * device copies.  On a PM step the new PM length comes from the reference's own get_PM_timestep_ti on the fetched velocities, as in
+ * find_timesteps.  The stored accelerations are consumed here, as in the reference, which frees the array (timestep.c:417-418). */
 int hierarchical_gravity_and_timesteps(const ActiveParticles *act, PetaPM *pm, DomainDecomp *ddecomp, struct grav_accel_store StoredGravAccel,
                                        DriftKickTimes *times, const double atime, int HybridNuGrav, int FastParticleType, Cosmology *CP,
                                        const char *EmergencyOutputDir)
 {
-    if(R.on)
-        no_hierarchical_gravity("hierarchical_gravity_and_timesteps");
-    return cpu_hierarchical_gravity_and_timesteps(act, pm, ddecomp, StoredGravAccel, times, atime, HybridNuGrav, FastParticleType, CP, EmergencyOutputDir);
+    if(!R.on)
+        return cpu_hierarchical_gravity_and_timesteps(act, pm, ddecomp, StoredGravAccel, times, atime, HybridNuGrav, FastParticleType, CP, EmergencyOutputDir);
+    /* (ddecomp and EmergencyOutputDir: one rank, the level trees are the device's) */
+    mpg_particle_view v = view();
+    inttime_t dti_max_pm = 0, PM_length = times->PM_length;
+    if(is_PM_timestep(times)) {
+        const double asmth = pm->Asmth * PartManager->BoxSize / pm->Nmesh;
+        ck(mpg_resident_fetch(mpg_shim_engine(), &v, MPG_FIELD_VEL)); /* P[].Vel current for the rms velocities */
+        dti_max_pm = PM_length = mpg_shim_get_PM_timestep_ti(times, atime, CP, FastParticleType, asmth);
+        message(0, "PM timebin: %lx (dloga: %g).\n", PM_length, dloga_from_dti(PM_length, times->Ti_Current));
+    }
+    int ti, largest_active = TIMEBINS;
+    for(ti = TIMEBINS; ti >= 0; ti--)
+        if(is_timebin_active(ti, times->Ti_Current) && dti_from_timebin(ti) <= PM_length) {
+            largest_active = ti;
+            break;
+        }
+    message(0, "Finding short-range gravity timesteps. Largest %d time %ld PM %ld dti %ld\n", largest_active, times->Ti_Current, PM_length,
+            dti_from_timebin(largest_active));
+    const double hubble = hubble_function(CP, atime);
+    mpg_timeline tl;
+    mpg_timestep_params par;
+    int64_t bad = 0;
+    mpg_shim_timeline(&tl);
+    par.ErrTolIntAccuracy = mpg_shim_err_tol_int_accuracy();
+    par.MinSizeTimestep = mpg_shim_min_size_timestep();
+    ck(mpg_resident_hierarchical_gravity_and_timesteps(mpg_shim_engine(), &v, act->ActiveParticle, act->NumActiveParticle, act->NumActiveGravity,
+                                                       (mpg_drift_kick_times *)times, &tl, &par, atime, hubble, dti_max_pm, shim_rho0(CP), HybridNuGrav,
+                                                       shim_gravkick, CP, StoredGravAccel.GravAccel, &bad));
+    if(StoredGravAccel.GravAccel)
+        myfree(StoredGravAccel.GravAccel);
+    fetch_timebins(); /* build_active_particles reads the gravity bins on the host */
+    walltime_measure("/Timeline/HierGrav/Init");
+    return (int)bad;
 }
 
+/* hierarchical_gravity_accelerations, timestep.c:495-599: the accelerations of every active level and their kicks on the device copies;
+ * the longest level's into the device copy of StoredGravAccel */
 int hierarchical_gravity_accelerations(const ActiveParticles *act, PetaPM *pm, DomainDecomp *ddecomp, struct grav_accel_store StoredGravAccel,
                                        DriftKickTimes *times, int HybridNuGrav, Cosmology *CP, const char *EmergencyOutputDir)
 {
-    if(R.on)
-        no_hierarchical_gravity("hierarchical_gravity_accelerations");
-    return cpu_hierarchical_gravity_accelerations(act, pm, ddecomp, StoredGravAccel, times, HybridNuGrav, CP, EmergencyOutputDir);
+    if(!R.on)
+        return cpu_hierarchical_gravity_accelerations(act, pm, ddecomp, StoredGravAccel, times, HybridNuGrav, CP, EmergencyOutputDir);
+    /* (pm, ddecomp and EmergencyOutputDir: unused on one rank) */
+    mpg_particle_view v = view();
+    ck(mpg_resident_hierarchical_gravity_accelerations(mpg_shim_engine(), &v, act->ActiveParticle, act->NumActiveParticle, act->NumActiveGravity,
+                                                       (mpg_drift_kick_times *)times, shim_rho0(CP), HybridNuGrav, shim_gravkick, CP,
+                                                       StoredGravAccel.GravAccel));
+    walltime_measure("/Timeline/HierGrav/Init2");
+    return 0;
 }
