@@ -650,8 +650,8 @@ int mpg_bigfile_set_attr(const char *file, const char *block, const char *name, 
 /* ---- matter power spectrum of the PM density field: gravpm_force measures it on every PM step (measure_power_spectrum /
  * powerspectrum_add_mode, gravpm.c:331-382: |delta_k|^2 with the CIC window removed once, weight 2 off the kz = 0 / Nyquist planes,
  * Nmesh logarithmic bins) and writes powerspectrum-<a>.txt (powerspectrum_sum / powerspectrum_save, powerspectrum.c:55-122).
- * The engine accumulates the raw sums during mpg_(dev_)gravpm_force and mpg_dev_pm_slab_forward_b; the neutrino linear-response
- * correction (gravpm.c:307-327, 415-436) is not carried. */
+ * The engine accumulates the raw sums during mpg_(dev_)gravpm_force and mpg_dev_pm_slab_forward_b.  With the neutrino linear response
+ * on (mpg_gravpm_set_nu_response below) the spectrum is the total-matter one of gravpm.c:436-446. */
 int mpg_gravpm_measure_power(mpg_engine *eng, int on);   /* default on, as in the reference */
 /* raw sums of the last PM step into caller device arrays: d_acc[2 Nmesh + 1] = Power[Nmesh], kk[Nmesh], Norm; d_modes[Nmesh].
  * One process per GPU: sum them over the ranks (the MPI_Allreduce of powerspectrum_sum) before mpg_powerspectrum_sum. */
@@ -662,6 +662,29 @@ int mpg_powerspectrum_sum(int nbins, const double *acc, const int64_t *modes, do
                           int64_t *Nmodes, int *nonzero);
 /* both steps for one GPU */
 int mpg_gravpm_get_powerspectrum(mpg_engine *eng, double BoxSize_in_MPC, double *kk, double *Power, int64_t *Nmodes, int *nonzero);
+/* ---- massive-neutrino linear response (MassiveNuLinRespOn: gravpm.c:72-79, 303-326, 418-446; petapm.c:311-315).
+ * The reference measures P(k) of the CDM field after the r2c transform (measure_power_spectrum, gravpm.c:365-382), then
+ * compute_neutrino_power (gravpm.c:308-326) runs delta_nu_from_power (neutrinos_lra.c:134-232) on delta_cdm = sqrt(Power), and
+ * potential_transfer (gravpm.c:418-446) multiplies every k2 > 0 mode by nufac = 1 + nu_prefac * delta_nu_ratio(log k) (linear
+ * interpolation in logknu; a log k within log 2 below logknu[0] is clamped to it, one above logknu[nonzero-1] to that), measures it
+ * again (the total-matter spectrum) and multiplies Norm by MtotbyMcdm^2.  The LRA integral stays on the host: the engine calls `fn`
+ * at that point of every PM step, with the normalised Mpc/h bins mpg_powerspectrum_sum gives (kk, delta_cdm = sqrt(Power), Nmodes;
+ * `nonzero` entries each).  fn fills logknu[nonzero], delta_nu_ratio[nonzero], *nu_prefac, *MtotbyMcdm and returns 0; a non-zero
+ * return fails the PM call ("neutrino response callback ...").  The table must have nonzero >= 2, logknu strictly increasing and every
+ * value finite, else the call fails.  The measurement is made while the response is on even with mpg_gravpm_measure_power(eng, 0);
+ * mpg_(dist_)gravpm_get_powerspectrum then return the total-matter spectrum.  The callback runs on the calling thread, once per PM
+ * step and rank (in the several-GPU form after the bins are summed over the ranks, as powerspectrum_sum's MPI_Allreduce does: every
+ * rank gets the same inputs and must return the same table).  Honoured by mpg_gravpm_force, mpg_dev_gravpm_force,
+ * mpg_dist_gravpm_force, mpg_dist_dev_gravpm_force and mpg_dist_gravity_step; mpg_dev_pm_slab_forward_b refuses while it is on.
+ * fn = NULL (the default) turns it off: the one-pass transfer, no host wait. */
+typedef int (*mpg_nu_response_fn)(void *ctx, int nonzero, const double *kk, const double *delta_cdm, const int64_t *Nmodes, double *logknu,
+                                  double *delta_nu_ratio, double *nu_prefac, double *MtotbyMcdm);
+int mpg_gravpm_set_nu_response(mpg_engine *eng, mpg_nu_response_fn fn, void *ctx, double BoxSize_in_MPC);
+/* hybrid neutrinos as passive tracers (hybrid_nu_tracer, gravpm.c:84-85, 469-474; petapm.c:1138-1143): while on, particles of type 2
+ * are left out of the mass deposit and still receive GravPM / Potential.  mpg_gravpm_force reads the type from the particle view,
+ * mpg_dev_gravpm_force from the d_type of mpg_dev_bind_particles (an error if it is NULL); for the mpg_dist forms see
+ * mpg_dist_dev_set_types.  Default off. */
+int mpg_gravpm_set_hybrid_nu_tracer(mpg_engine *eng, int on);
 /* powerspectrum_save (powerspectrum.c:93-122): OutputDir/filename-<Time>.txt with the reference's columns "k P N P(z=0)" */
 int mpg_powerspectrum_save(const char *OutputDir, const char *filename, double Time, double D1, int nonzero, const double *kk,
                            const double *Power, const int64_t *Nmodes);
@@ -804,6 +827,11 @@ int mpg_dist_gravity_step(mpg_dist *d, int64_t n_own, const double *d_pos, const
  *   force_tree_full (forcetree.h:115)    -> ghost import, local tree with the global top
  *   grav_short_tree (gravity.h:40)       -> accelerations of all own particles (and the tree potential, assigned) */
 int mpg_dist_dev_gravpm_force(mpg_dist *d, int64_t n_own, const double *d_pos, const float *d_mass, double *d_gravpm, double *d_potential);
+/* The types of the own rows (n_own device bytes, caller order) for the hybrid-neutrino deposit mask (mpg_gravpm_set_hybrid_nu_tracer on
+ * the rank's engine): the typed form of mpg_dist_dev_gravpm_force and mpg_dist_gravity_step.  While the mask is on, those two calls fail
+ * unless types for the same n_own were set; stays in force until the next call (NULL clears it).  The host forms read the type of the
+ * particle view themselves. */
+int mpg_dist_dev_set_types(mpg_dist *d, int64_t n_own, const uint8_t *d_type);
 /* Garbage and swallowed particles among the own rows (P[].IsGarbage, P[].Swallowed: star formation and black-hole mergers leave them in
  * the table until the next domain_decompose_full collects them).  The reference skips them in place in every loop of this path
  * (treewalk.c:234, forcetree.c:806, gravpm.c:176-179); so do the mpg_dist_dev_* calls that follow on a table of n_own rows: such rows are

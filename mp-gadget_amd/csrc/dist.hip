@@ -669,6 +669,10 @@ struct mpg_dist {
     int64_t n_skip = 0, n_skip_rows = -1;
     DevBuf<uint8_t> ltype, o_skip;
     const unsigned char *skip_for(int64_t n) const { return (n_skip > 0 && n == n_skip_rows) ? d_skip : nullptr; }
+    // the types of the own rows for the hybrid-neutrino deposit mask (mpg_dist_dev_set_types): a copy, over n_type_rows rows
+    DevBuf<uint8_t> type_own;
+    int64_t n_type_rows = -1;
+    const uint8_t *types_for(int64_t n) const { return n == n_type_rows ? type_own.p : nullptr; }
     HostBuf<unsigned long long> chk; // [0] own particles found in the local tree, [1] the two flags of the global top (pinned: read back without a wait)
     bool chk_pending = false;
     bool grav_tree_valid = false; // the engine's tree is the gravity tree of mpg_dist_dev_force_tree_build (the SPH loops and FOF replace it)
@@ -778,6 +782,7 @@ void a2a_uniform(mpg_dist *d, const void *dsend, void *drecv, int64_t bytes_per_
     d->stats[5] += bytes_per_peer * d->nt;
 }
 
+void allreduce_i64(mpg_dist *d, int64_t *v, int64_t n, int op);
 void allreduce_host_f64(mpg_dist *d, double *h, int64_t n, int op)
 {
     if(d->nt == 1 && !d->comm.allreduce)
@@ -918,6 +923,10 @@ void pm_step(mpg_dist *d, int64_t n, const double *pos, const float *mass, doubl
     if(!d->slab_ready || pm.slab.rank != d->me || pm.slab.world != d->nt || !pm.slab.ready)
         pm_slab_setup(d);
     const int nmesh = pm.nmesh, P = nmesh / d->nt;
+    // hybrid neutrinos as tracers: type-2 rows travel with mass 0 (they are still read out)
+    MPG_CHECK(!pm.hybrid_tracer || n == 0 || d->types_for(n),
+              "mpg_dist: the hybrid-neutrino deposit mask needs the types of the own rows (mpg_dist_dev_set_types with this n_own)");
+    mass = pm.tracer_mass(n, mass, d->types_for(n), st);
     d->mask.reserve((size_t)n + 1);
     if(n > 0)
         hipLaunchKernelGGL(k_pm_mask, dim3(nblk(n)), dim3(256), 0, st, n, pos, pm.cellsize, nmesh, P, d->skip_for(n), d->mask.p);
@@ -941,7 +950,21 @@ void pm_step(mpg_dist *d, int64_t n, const double *pos, const float *mass, doubl
     // local stages of the slab solver with the two transposes and the neighbour planes in between (pm.hip, "slab-decomposed form")
     pm.slab_forward_a(nr, d->spos.p, d->smass.p, d->sendA.p, st);
     a2a_uniform(d, d->sendA.p, d->recvA.p, 16 * d->per_peer);
-    pm.slab_forward_b(d->recvA.p, d->sendB.p, st);
+    if(pm.nu_fn) { // neutrino response: the bins of every rank summed (powerspectrum_sum's MPI_Allreduce), then the same callback everywhere
+        pm.slab_forward_b1(d->recvA.p, st);
+        const size_t nb = (size_t)nmesh;
+        double *acc;
+        unsigned long long *modes;
+        pm.nu_fetch(st, &acc, &modes);
+        std::vector<double> a(acc, acc + 2 * nb + 1);
+        std::vector<int64_t> m((const int64_t *)modes, (const int64_t *)modes + nb);
+        allreduce_host_f64(d, a.data(), (int64_t)a.size(), 0);
+        allreduce_i64(d, m.data(), (int64_t)nb, 0);
+        pm.nu_table(a.data(), (const unsigned long long *)m.data(), st);
+        pm.slab_forward_b2(d->sendB.p, st);
+    }
+    else
+        pm.slab_forward_b(d->recvA.p, d->sendB.p, st);
     a2a_uniform(d, d->sendB.p, d->recvB.p, 16 * d->per_peer);
     pm.slab_inverse_c(d->recvB.p, d->gsend.p, st);
     {
@@ -1226,6 +1249,21 @@ int mpg_dist_dev_set_garbage(mpg_dist *d, int64_t n_own, const unsigned char *d_
             d->n_skip = (int64_t)c;
             d->n_skip_rows = n_own;
         }
+    }
+    API_END
+}
+
+int mpg_dist_dev_set_types(mpg_dist *d, int64_t n_own, const uint8_t *d_type)
+{
+    API_BEGIN
+    MPG_CHECK(d && n_own >= 0, "null argument");
+    MPG_HIP(hipSetDevice(d->eng->device));
+    d->n_type_rows = -1;
+    if(d_type) {
+        d->type_own.reserve((size_t)n_own + 1);
+        if(n_own > 0)
+            MPG_HIP(hipMemcpyAsync(d->type_own.p, d_type, (size_t)n_own, hipMemcpyDeviceToDevice, d->eng->stream));
+        d->n_type_rows = n_own;
     }
     API_END
 }
@@ -1596,6 +1634,22 @@ int mpg_dist_gravpm_force(mpg_dist *d, const mpg_particle_view *P)
     MPG_HIP(hipSetDevice(d->eng->device));
     stage_own(d, P);
     const int64_t n = P->n;
+    if(d->eng->pm.hybrid_tracer) { // the types for the deposit mask (hybrid_nu_gravpm_is_active, gravpm.c:469-474)
+        MPG_CHECK(P->off_type >= 0, "gravpm_force: the hybrid-neutrino deposit mask needs the particle type in the view");
+        std::vector<uint8_t> ht((size_t)n + 1); // (not hbuf_b: it keeps the garbage flags of stage_own for the walk)
+        uint8_t *hb = ht.data();
+        const mpg_particle_view V = *P;
+        const char *b = (const char *)P->base;
+        parallel_for(n, [=](int64_t lo, int64_t hi) {
+            for(int64_t i = lo; i < hi; i++)
+                hb[i] = *(const uint8_t *)(b + i * V.stride + V.off_type) & 7;
+        });
+        d->o_u8[0].reserve((size_t)n + 1);
+        if(n > 0)
+            MPG_HIP(hipMemcpyAsync(d->o_u8[0].p, hb, (size_t)n, hipMemcpyHostToDevice, d->eng->stream));
+        MPG_CHECK(mpg_dist_dev_set_types(d, n, d->o_u8[0].p) == 0, mpg_last_error());
+        sync(d);
+    }
     if(n > 0)
         MPG_HIP(hipMemsetAsync(d->o_pot.p, 0, (size_t)n * sizeof(double), d->eng->stream));
     MPG_CHECK(mpg_dist_dev_gravpm_force(d, n, d->o_pos.p, d->o_mass.p, d->o_gravpm.p, d->o_pot.p) == 0, mpg_last_error());

@@ -255,7 +255,9 @@ int mpg_dev_gravpm_force(mpg_engine *eng, double *d_gravpm, double *d_potential)
         MPG_HIP(hipEventRecord(eng->ev_inputs, eng->stream)); // everything queued so far: the particle arrays are final, the last walk is done
         eng->pm_queued = true;
     }
-    eng->pm.force(eng->n, eng->d_pos, eng->d_mass, nullptr, d_gravpm, d_potential, eng->stream, &eng->timer);
+    MPG_CHECK(!eng->pm.hybrid_tracer || eng->d_type || eng->n == 0, "gravpm_force: the hybrid-neutrino deposit mask needs d_type in mpg_dev_bind_particles");
+    const float *dep_mass = eng->pm.tracer_mass(eng->n, eng->d_mass, eng->d_type, eng->stream);
+    eng->pm.force(eng->n, eng->d_pos, dep_mass, nullptr, d_gravpm, d_potential, eng->stream, &eng->timer);
     API_END
 }
 
@@ -307,6 +309,7 @@ int mpg_dev_pm_slab_forward_b(mpg_engine *eng, double *recvA, double *sendB)
     API_BEGIN
     MPG_CHECK(eng && recvA && sendB, "null argument");
     MPG_HIP(hipSetDevice(eng->device));
+    MPG_CHECK(!eng->pm.nu_fn, "mpg_dev_pm_slab_forward_b: the neutrino response needs the bins of all ranks between the two halves (use mpg_dist)");
     eng->pm.slab_forward_b(recvA, sendB, eng->stream);
     API_END
 }
@@ -906,6 +909,25 @@ int mpg_gravpm_measure_power(mpg_engine *eng, int on)
     API_BEGIN
     MPG_CHECK(eng, "null engine");
     eng->pm.measure_power = on != 0;
+    API_END
+}
+
+int mpg_gravpm_set_nu_response(mpg_engine *eng, mpg_nu_response_fn fn, void *ctx, double BoxSize_in_MPC)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null engine");
+    MPG_CHECK(!fn || (BoxSize_in_MPC > 0 && std::isfinite(BoxSize_in_MPC)), "mpg_gravpm_set_nu_response: BoxSize_in_MPC must be positive");
+    eng->pm.nu_fn = fn;
+    eng->pm.nu_ctx = fn ? ctx : nullptr;
+    eng->pm.nu_box_mpc = fn ? BoxSize_in_MPC : 0;
+    API_END
+}
+
+int mpg_gravpm_set_hybrid_nu_tracer(mpg_engine *eng, int on)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null engine");
+    eng->pm.hybrid_tracer = on != 0;
     API_END
 }
 
@@ -1700,6 +1722,7 @@ int mpg_gravpm_force(mpg_engine *eng, const mpg_particle_view *P)
     MPG_HIP(hipSetDevice(eng->device));
     MPG_CHECK(eng->pm.nmesh > 0, "gravpm_force called before gravpm_init_periodic");
     MPG_CHECK(P->off_gravpm >= 0, "particle view needs GravPM");
+    MPG_CHECK(!eng->pm.hybrid_tracer || P->off_type >= 0, "gravpm_force: the hybrid-neutrino deposit mask needs the particle type in the view");
     HostClock hc("gravpm_force");
     eng->host_join(); // (the write-back of an earlier call)
     MPG_CHECK(eng->unpack_error.empty(), "host path: the write-back of GravPM failed: " + eng->unpack_error);
@@ -1709,7 +1732,8 @@ int mpg_gravpm_force(mpg_engine *eng, const mpg_particle_view *P)
     if(eng->resident && eng->res_base == P->base) { // results stay in HBM: GravPM assigned, Potential accumulated (gravpm.c:499-501)
         if(eng->pm_live) // (gravpm.c:88-92 zeroes GravPM of every particle; the readout reaches the live ones)
             MPG_HIP(hipMemsetAsync(eng->r_gravpm.p, 0, 3 * (size_t)n * sizeof(double), eng->stream));
-        eng->pm.force(n, eng->d_pos, eng->d_mass, eng->pm_live, eng->r_gravpm.p, eng->r_pot.p, eng->stream, &eng->timer);
+        eng->pm.force(n, eng->d_pos, eng->pm.tracer_mass(n, eng->d_mass, eng->d_type, eng->stream), eng->pm_live, eng->r_gravpm.p, eng->r_pot.p,
+                      eng->stream, &eng->timer);
         mpg_err_slot().clear();
         return 0;
     }
@@ -1732,7 +1756,8 @@ int mpg_gravpm_force(mpg_engine *eng, const mpg_particle_view *P)
     }
     if(eng->pm_live)
         MPG_HIP(hipMemsetAsync(eng->s_gravpm.p, 0, 3 * (size_t)n * sizeof(double), eng->stream));
-    eng->pm.force(n, eng->d_pos, eng->d_mass, eng->pm_live, eng->s_gravpm.p, wantpot ? eng->s_pot.p : nullptr, eng->stream, &eng->timer);
+    eng->pm.force(n, eng->d_pos, eng->pm.tracer_mass(n, eng->d_mass, eng->d_type, eng->stream), eng->pm_live, eng->s_gravpm.p,
+                  wantpot ? eng->s_pot.p : nullptr, eng->stream, &eng->timer);
     eng->gravpm_epoch = eng->host_epoch;
     const double *dg = eng->s_gravpm.p, *dp = eng->s_pot.p;
     if(overlap) {

@@ -1,5 +1,6 @@
 // pm.h -- single-GPU particle-mesh solver (see pm.hip)
 #pragma once
+#include "../../include/mpgadget_hip.h"
 #include "mpg_common.h"
 #include "tree_build.h"
 #include <rocfft/rocfft.h>
@@ -48,6 +49,31 @@ struct PMesh {
     void ps_zero(hipStream_t st);
     size_t ps_lds_bytes() const { return (size_t)nmesh * 3 * sizeof(double); }
 
+    // massive-neutrino linear response (MassiveNuLinRespOn, gravpm.c:72-79, 303-326, 418-446).  With nu_fn set the transfer becomes
+    // two passes over rho_k: the measurement of the CDM field, a host step (nu_fetch + nu_table: powerspectrum_sum, delta_cdm =
+    // sqrt(Power), the callback, the table uploaded), then k_power_spectrum<..., NU>: every k2 > 0 mode times nufac(k), measured again
+    // (the total-matter spectrum, Norm times MtotbyMcdm^2), then the potential transfer.  nu_fn == null: the one-pass path, unchanged.
+    mpg_nu_response_fn nu_fn = nullptr;
+    void *nu_ctx = nullptr;
+    double nu_box_mpc = 0;
+    int nu_nonzero = 0;
+    double nu_prefac = 0, nu_normfac = 1;
+    DevBuf<double> nu_tab;              // logknu[nmesh], delta_nu_ratio[nmesh]
+    DevBuf<int> nu_guess;               // per log-k bin: the table interval its modes start the search from
+    double *nu_host = nullptr;          // pinned: the raw sums of pass 1 (2 nmesh + 1 doubles, nmesh u64), then the table going up
+    size_t nu_host_cap = 0;
+    size_t ps_lds_bytes_nu() const { return ps_lds_bytes() + (size_t)nmesh * (2 * sizeof(double) + sizeof(int)); }
+    // pass 1's raw sums -> the pinned buffer, then wait for the stream (the one host wait of the response); returns {acc, modes}
+    void nu_fetch(hipStream_t st, double **acc, unsigned long long **modes);
+    // acc / modes: the raw sums over the whole mesh (all-reduced over the ranks in the slab form).  Runs the callback, checks its
+    // table, uploads it and zeroes the accumulators for the second measurement
+    void nu_table(const double *acc, const unsigned long long *modes, hipStream_t st);
+    // hybrid neutrinos as passive tracers (HybridNeutrinosOn, gravpm.c:84-85, 469-474): type-2 particles are not deposited but are read
+    // out.  tracer_mass() gives the mass array with those masses zeroed (a zero adds nothing to a cell), or d_mass when off
+    bool hybrid_tracer = false;
+    DevBuf<float> tracer_mass_buf;
+    const float *tracer_mass(int64_t n, const float *d_mass, const uint8_t *d_type, hipStream_t st);
+
     // gravpm_init_periodic -> petapm_init (gravpm.c:51-54, petapm.c:105-223)
     void init(double BoxSize, double Asmth, int Nmesh, double G, hipStream_t st);
     void ensure_single(); // meshes + 3-D plans of the single-GPU form, made on first use
@@ -80,6 +106,10 @@ struct PMesh {
     void slab_forward_a(int64_t n, const double *d_pos, const float *d_mass, double *sendA, hipStream_t st);
     // recvA[Nmesh][Py][Nz] (x slowest): 1-D transform along x, potential transfer, inverse 1-D transform -> sendB[Nmesh][Py][Nz]
     void slab_forward_b(double *recvA, double *sendB, hipStream_t st);
+    // the same in two halves around the measurement, for the neutrino response: b1 = transform along x + this rank's bins of
+    // P(k); the caller sums the bins over the ranks and runs nu_table; b2 = nufac, measurement, potential transfer, inverse transform
+    void slab_forward_b1(double *recvA, hipStream_t st);
+    void slab_forward_b2(double *sendB, hipStream_t st);
     // recvB[world][P][Py][Nz] -> the potential slab (2-D c2r); ghost_send[5][Nmesh^2] = its first 3 and last 2 planes
     void slab_inverse_c(const double *recvB, double *ghost_send, hipStream_t st);
     // ghost_recv[5][Nmesh^2] = the next rank's first 3 planes, then the previous rank's last 2; forces by differencing the

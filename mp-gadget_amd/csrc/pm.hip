@@ -9,6 +9,7 @@
 // PFFT (third-party, not vendored) is an unnormalised DFT; the real-to-complex / complex-to-real transforms of rocFFT are the same transform.
 // All kernels are HBM-streaming: per PM step ~ N*(28+128) + 5*3*2*R + 5*2*R + N*(24+256+32) bytes, R = 8*Nmesh^3.
 #include "pm.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -216,19 +217,61 @@ __global__ void __launch_bounds__(256) k_potential_transfer(int nmesh, int ny, i
 // kk[nbins], Norm], modes[nbins]; the reference's per-thread copies are per-block LDS histograms here.
 // FUSE (round 6): the potential transfer of the same cell in the same pass (k_potential_transfer's arithmetic, after the mode has been
 // measured: gravpm.c measures before it multiplies) - one read of the 1.07 GB of rho_k instead of two
-template <bool XLAST, bool FUSE = false>
+// NU (the massive-neutrino linear response, gravpm.c:418-446): first each k2 > 0 mode is multiplied by
+// nufac = 1 + prefac * delta_nu_ratio(log k) and written back, then measured (the total-matter spectrum), then - FUSE - transferred;
+// Norm is |rho_0|^2 * normfac (MtotbyMcdm^2).  The table (logknu, delta_nu_ratio: nonzero entries; guess: per log-k bin the interval
+// to start from) is copied to LDS: 2.5 Nmesh more words beside the 3 Nmesh of the histograms (44 KB at Nmesh 1024).
+struct NuArgs {
+    const double *tab;   // logknu[nbins], delta_nu_ratio[nbins]
+    const int *guess;    // [nbins]
+    int nonzero;
+    double prefac, normfac;
+    double kscale;       // 2 pi / BoxSize_in_MPC: log k in the table's units = log(sqrt(k2) kscale)
+};
+
+// gsl_interp_linear on the LDS table after the two clamps of gravpm.c:423-428.  The interval j with logknu[j] <= x < logknu[j+1]
+// (j = nonzero - 2 for x = logknu[nonzero-1], as gsl_interp_bsearch) is found by stepping from the guess of the mode's log-k bin: the
+// table is the bins' own log kk, so a mode lies in the interval of its bin or the one before (one or two steps, no binary search).
+__device__ __forceinline__ double nu_factor(double x, int kint, const double *s_lk, const double *s_rt, const int *s_gs, int nonzero,
+                                            double prefac)
+{
+    const double x0 = s_lk[0], x1 = s_lk[nonzero - 1];
+    if(x < x0 && x > x0 - log(2.0))
+        x = x0;
+    else if(x > x1)
+        x = x1;
+    // (further below, where gsl_interp_eval fails with a domain error, the first value is used as well)
+    x = x < x0 ? x0 : x;
+    int j = s_gs[kint];
+    while(j > 0 && x < s_lk[j])
+        j--;
+    while(j < nonzero - 2 && x >= s_lk[j + 1])
+        j++;
+    const double x_lo = s_lk[j], x_hi = s_lk[j + 1], y_lo = s_rt[j], y_hi = s_rt[j + 1];
+    return 1 + prefac * (y_lo + (x - x_lo) / (x_hi - x_lo) * (y_hi - y_lo));
+}
+
+template <bool XLAST, bool FUSE = false, bool NU = false>
 __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y0, const double *__restrict__ invsinc2,
                                                         double2 *__restrict__ cplx, double *__restrict__ acc,
-                                                        unsigned long long *__restrict__ modes, double asmth2 = 0, double pot_factor = 0)
+                                                        unsigned long long *__restrict__ modes, double asmth2 = 0, double pot_factor = 0,
+                                                        NuArgs nu = NuArgs{})
 {
-    extern __shared__ double s_ps[]; // Power[nbins], kk[nbins], then modes[nbins] (u64)
+    extern __shared__ double s_ps[]; // Power[nbins], kk[nbins], then modes[nbins] (u64); NU: logknu[nbins], ratio[nbins], guess[nbins] (int)
     const int nbins = nmesh;
     double *s_pow = s_ps, *s_kk = s_ps + nbins;
     unsigned long long *s_n = (unsigned long long *)(s_ps + 2 * nbins);
+    double *s_lk = s_ps + 3 * nbins, *s_rt = s_ps + 4 * nbins;
+    int *s_gs = (int *)(s_ps + 5 * nbins);
     for(int b = threadIdx.x; b < nbins; b += blockDim.x) {
         s_pow[b] = 0;
         s_kk[b] = 0;
         s_n[b] = 0;
+        if(NU) {
+            s_lk[b] = nu.tab[b];
+            s_rt[b] = nu.tab[nbins + b];
+            s_gs[b] = nu.guess[b];
+        }
     }
     __syncthreads();
     const int nz = nmesh / 2 + 1;
@@ -252,14 +295,25 @@ __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y
         const int ky = iy <= nmesh / 2 ? iy : iy - nmesh;
         const int kz = iz;
         const long long k2 = (long long)kx * kx + (long long)ky * ky + (long long)kz * kz;
-        const double2 v = cplx[ip];
-        const double m = v.x * v.x + v.y * v.y;
+        double2 v = cplx[ip];
         if(k2 == 0) {
-            acc[2 * nbins] = m; // Norm
+            const double m0 = v.x * v.x + v.y * v.y;
+            acc[2 * nbins] = NU ? m0 * nu.normfac : m0; // Norm (gravpm.c:437-441: Norm *= MtotbyMcdm^2 with the response)
             if(FUSE)
                 cplx[ip] = make_double2(0.0, 0.0);
             continue;
         }
+        int kint = 0;
+        if(NU) { // the mode times nufac before it is measured (gravpm.c:418-436)
+            kint = (int)floor(binsperunit * log((double)k2) / 2.);
+            const double nufac = nu_factor(log(sqrt((double)k2) * nu.kscale), kint < nbins ? kint : nbins - 1, s_lk, s_rt, s_gs, nu.nonzero,
+                                           nu.prefac);
+            v.x *= nufac;
+            v.y *= nufac;
+            if(!FUSE)
+                cplx[ip] = v;
+        }
+        const double m = v.x * v.x + v.y * v.y;
         const double f = invsinc2[ix] * invsinc2[iy] * invsinc2[iz];
         if(FUSE) { // (k_potential_transfer, same expressions in the same order.  exp(-k2 asmth2) / k2 and the bin from tables indexed by k2 -
                    // 2.4 MB of them at Nmesh 512 - measured SLOWER than the exp and the log: 1.06 against 0.64 ms, the gathers miss)
@@ -267,7 +321,8 @@ __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y
             const double fac = pot_factor * smth * f * f;
             cplx[ip] = make_double2(v.x * fac, v.y * fac);
         }
-        const int kint = (int)floor(binsperunit * log((double)k2) / 2.);
+        if(!NU)
+            kint = (int)floor(binsperunit * log((double)k2) / 2.);
         if(kint >= nbins)
             continue;
         const int w = (kz == 0 || kz == nmesh / 2) ? 1 : 2;
@@ -601,6 +656,88 @@ void PMesh::ps_zero(hipStream_t st)
     ps_valid = true;
 }
 
+void PMesh::nu_fetch(hipStream_t st, double **acc, unsigned long long **modes)
+{
+    const size_t nb = (size_t)nmesh, want = 3 * nb + 1;
+    if(nu_host_cap < want) {
+        if(nu_host)
+            (void)hipHostFree(nu_host);
+        nu_host = nullptr;
+        nu_host_cap = 0;
+        MPG_HIP(hipHostMalloc((void **)&nu_host, want * sizeof(double), hipHostMallocDefault));
+        nu_host_cap = want;
+    }
+    MPG_HIP(hipMemcpyAsync(nu_host, ps_acc.p, (2 * nb + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipMemcpyAsync(nu_host + 2 * nb + 1, ps_modes.p, nb * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipStreamSynchronize(st));
+    *acc = nu_host;
+    *modes = (unsigned long long *)(nu_host + 2 * nb + 1);
+}
+
+void PMesh::nu_table(const double *acc, const unsigned long long *modes, hipStream_t st)
+{
+    // compute_neutrino_power, gravpm.c:308-326: powerspectrum_sum, Power -> sqrt(Power) = delta_cdm, delta_nu_from_power, zero
+    const int nb = nmesh;
+    MPG_CHECK(ps_lds_bytes_nu() <= 65536, "gravpm_force: the neutrino response keeps its table in LDS: Nmesh " + std::to_string(nmesh) + " is too large");
+    std::vector<double> kk(nb), dcdm(nb), tab(2 * (size_t)nb, 0.0);
+    std::vector<int64_t> nm(nb);
+    int nonzero = 0;
+    if(mpg_powerspectrum_sum(nb, acc, (const int64_t *)modes, nu_box_mpc, kk.data(), dcdm.data(), nm.data(), &nonzero) != 0)
+        throw Error(mpg_last_error());
+    for(int i = 0; i < nonzero; i++)
+        dcdm[i] = sqrt(dcdm[i]);
+    double prefac = NAN, mtot = NAN;
+    double *lk = tab.data(), *rt = tab.data() + nb;
+    for(int i = 0; i < nonzero; i++)
+        lk[i] = rt[i] = NAN;
+    const int rc = nu_fn(nu_ctx, nonzero, kk.data(), dcdm.data(), nm.data(), lk, rt, &prefac, &mtot);
+    MPG_CHECK(rc == 0, "gravpm_force: the neutrino response callback failed (returned " + std::to_string(rc) + ")");
+    MPG_CHECK(nonzero >= 2, "gravpm_force: neutrino response table: " + std::to_string(nonzero) + " power spectrum bins, at least 2 needed");
+    MPG_CHECK(std::isfinite(prefac) && std::isfinite(mtot), "gravpm_force: neutrino response callback: nu_prefac / MtotbyMcdm not finite");
+    for(int i = 0; i < nonzero; i++) {
+        MPG_CHECK(std::isfinite(lk[i]) && std::isfinite(rt[i]),
+                  "gravpm_force: neutrino response table: entry " + std::to_string(i) + " is not finite");
+        MPG_CHECK(i == 0 || lk[i] > lk[i - 1], "gravpm_force: neutrino response table: logknu is not strictly increasing at entry " + std::to_string(i));
+    }
+    // per log-k bin the table interval to start from: the bin's position among the non-empty bins (the table is their log kk)
+    std::vector<int> guess(nb);
+    int c = 0;
+    for(int b = 0; b < nb; b++) {
+        guess[b] = std::min(std::max(c - 1, 0), nonzero - 2);
+        if(modes[b])
+            c++;
+    }
+    nu_tab.reserve(2 * (size_t)nb);
+    nu_guess.reserve((size_t)nb);
+    // (through the pinned buffer: the raw sums in it have been read)
+    memcpy(nu_host, tab.data(), 2 * (size_t)nb * sizeof(double));
+    memcpy(nu_host + 2 * (size_t)nb, guess.data(), (size_t)nb * sizeof(int));
+    MPG_HIP(hipMemcpyAsync(nu_tab.p, nu_host, 2 * (size_t)nb * sizeof(double), hipMemcpyHostToDevice, st));
+    MPG_HIP(hipMemcpyAsync(nu_guess.p, nu_host + 2 * (size_t)nb, (size_t)nb * sizeof(int), hipMemcpyHostToDevice, st));
+    nu_nonzero = nonzero;
+    nu_prefac = prefac;
+    nu_normfac = mtot * mtot;
+    ps_zero(st); // the second measurement: total matter (powerspectrum_zero, gravpm.c:325)
+}
+
+__global__ void __launch_bounds__(256) k_tracer_mass(int64_t n, const float *__restrict__ mass, const uint8_t *__restrict__ type,
+                                                     float *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i < n)
+        out[i] = type[i] == 2 ? 0.0f : mass[i]; // hybrid_nu_gravpm_is_active, gravpm.c:469-474
+}
+
+const float *PMesh::tracer_mass(int64_t n, const float *d_mass, const uint8_t *d_type, hipStream_t st)
+{
+    if(!hybrid_tracer || n <= 0)
+        return d_mass;
+    MPG_CHECK(d_type != nullptr, "gravpm_force: the hybrid-neutrino deposit mask needs the particle types");
+    tracer_mass_buf.reserve((size_t)n);
+    hipLaunchKernelGGL(k_tracer_mass, dim3(nblk(n)), dim3(256), 0, st, n, d_mass, d_type, tracer_mass_buf.p);
+    return tracer_mass_buf.p;
+}
+
 void PMesh::destroy()
 {
     if(have_plans) {
@@ -613,6 +750,10 @@ void PMesh::destroy()
     rho_k.release();
     work_k.release();
     grad_z.release();
+    if(nu_host)
+        (void)hipHostFree(nu_host);
+    nu_host = nullptr;
+    nu_host_cap = 0;
     nmesh = 0;
 }
 
@@ -707,7 +848,26 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
     const double asmth2 = pow((2 * M_PI) * Asmth / nmesh, 2);
     const double pot_factor = -G / (M_PI * box);
     static const bool fuse_ps = !(getenv("MPG_PM_FUSE_PS") && getenv("MPG_PM_FUSE_PS")[0] == '0');
-    if(measure_power && fuse_ps) { // P(k) and the potential transfer in one pass over rho_k (round 6)
+    if(nu_fn) { // neutrino linear response: measure, host step, then nufac + measurement + transfer (see pm.h)
+        ps_zero(st);
+        hipLaunchKernelGGL((k_power_spectrum<false, false>), dim3(2048), dim3(256), ps_lds_bytes(), st, nmesh, nmesh, 0, invsinc2.p,
+                           (double2 *)rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0, NuArgs{});
+        double *acc;
+        unsigned long long *modes;
+        nu_fetch(st, &acc, &modes);
+        nu_table(acc, modes, st);
+        const NuArgs na{nu_tab.p, nu_guess.p, nu_nonzero, nu_prefac, nu_normfac, 2 * M_PI / nu_box_mpc};
+        if(fuse_ps)
+            hipLaunchKernelGGL((k_power_spectrum<false, true, true>), dim3(2048), dim3(256), ps_lds_bytes_nu(), st, nmesh, nmesh, 0, invsinc2.p,
+                               (double2 *)rho_k.p, ps_acc.p, ps_modes.p, asmth2, pot_factor, na);
+        else {
+            hipLaunchKernelGGL((k_power_spectrum<false, false, true>), dim3(2048), dim3(256), ps_lds_bytes_nu(), st, nmesh, nmesh, 0, invsinc2.p,
+                               (double2 *)rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0, na);
+            hipLaunchKernelGGL(k_potential_transfer<false>, dim3(nblk(ncplx)), dim3(256), 0, st, nmesh, nmesh, 0, asmth2, pot_factor, invsinc2.p,
+                               (double2 *)rho_k.p);
+        }
+    }
+    else if(measure_power && fuse_ps) { // P(k) and the potential transfer in one pass over rho_k (round 6)
         ps_zero(st);
         hipLaunchKernelGGL((k_power_spectrum<false, true>), dim3(2048), dim3(256), ps_lds_bytes(), st, nmesh, nmesh, 0, invsinc2.p, (double2 *)rho_k.p,
                            ps_acc.p, ps_modes.p, asmth2, pot_factor);
@@ -1056,25 +1216,45 @@ void PMesh::slab_forward_a(int64_t n, const double *d_pos, const float *d_mass, 
 
 void PMesh::slab_forward_b(double *recvA, double *sendB, hipStream_t st)
 {
+    slab_forward_b1(recvA, st);
+    slab_forward_b2(sendB, st);
+}
+
+void PMesh::slab_forward_b1(double *recvA, hipStream_t st)
+{
     MPG_CHECK(slab.ready, "pm_slab: not initialised");
     const int nz = nmesh / 2 + 1;
-    const size_t ncplx = (size_t)nmesh * slab.Py * nz;
     const int y0 = slab.rank * slab.Py;
     const size_t S = (size_t)slab.Py * nz;
     // [x][j] -> [j][x], j = (ky local, kz): the transforms along x run on contiguous rows
-    const dim3 tgrid_f((unsigned)((S + 31) / 32), (unsigned)((nmesh + 31) / 32)), tgrid_b((unsigned)((nmesh + 31) / 32), (unsigned)((S + 31) / 32));
+    const dim3 tgrid_f((unsigned)((S + 31) / 32), (unsigned)((nmesh + 31) / 32));
     if(slab.strided)
         slab.p1d_fwd_t.exec(recvA, slab.rho_k.p, st);
     else {
         hipLaunchKernelGGL(k_transpose, tgrid_f, dim3(256), 0, st, nmesh, (int)S, (const double2 *)recvA, S, (double2 *)slab.rho_k.p, (size_t)nmesh);
         slab.p1d_fwd.exec(slab.rho_k.p, slab.rho_k.p, st);
     }
-    const double asmth2 = pow((2 * M_PI) * Asmth / nmesh, 2);
-    const double pot_factor = -G / (M_PI * box);
-    if(measure_power) { // this rank's ky rows: the caller sums the raw accumulators over the ranks (powerspectrum_sum's Allreduce)
+    if(measure_power || nu_fn) { // this rank's ky rows: the caller sums the raw accumulators over the ranks (powerspectrum_sum's Allreduce)
         ps_zero(st);
         hipLaunchKernelGGL((k_power_spectrum<true, false>), dim3(1024), dim3(256), ps_lds_bytes(), st, nmesh, slab.Py, y0, invsinc2.p,
-                           (double2 *)slab.rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0);
+                           (double2 *)slab.rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0, NuArgs{});
+    }
+}
+
+void PMesh::slab_forward_b2(double *sendB, hipStream_t st)
+{
+    MPG_CHECK(slab.ready, "pm_slab: not initialised");
+    const int nz = nmesh / 2 + 1;
+    const size_t ncplx = (size_t)nmesh * slab.Py * nz;
+    const int y0 = slab.rank * slab.Py;
+    const size_t S = (size_t)slab.Py * nz;
+    const dim3 tgrid_b((unsigned)((nmesh + 31) / 32), (unsigned)((S + 31) / 32));
+    const double asmth2 = pow((2 * M_PI) * Asmth / nmesh, 2);
+    const double pot_factor = -G / (M_PI * box);
+    if(nu_fn) { // the table is up (nu_table, after the bins were summed over the ranks): nufac + this rank's bins of the total matter
+        const NuArgs na{nu_tab.p, nu_guess.p, nu_nonzero, nu_prefac, nu_normfac, 2 * M_PI / nu_box_mpc};
+        hipLaunchKernelGGL((k_power_spectrum<true, false, true>), dim3(1024), dim3(256), ps_lds_bytes_nu(), st, nmesh, slab.Py, y0, invsinc2.p,
+                           (double2 *)slab.rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0, na);
     }
     hipLaunchKernelGGL(k_potential_transfer<true>, dim3(nblk(ncplx)), dim3(256), 0, st, nmesh, slab.Py, y0, asmth2, pot_factor, invsinc2.p,
                        (double2 *)slab.rho_k.p);

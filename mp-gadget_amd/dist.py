@@ -256,6 +256,32 @@ class DistForce:
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         self._ck(self.lib.mpg_dist_dev_gravpm_force(self.h, C.c_int64(pos.shape[0]), p(pos), p(mass), p(gravpm), p(potential)))
 
+    def host_gravpm_force(self, P):
+        """mpg_dist_gravpm_force: the drop-in form on this rank's particle table (a make_particles array)"""
+        v = self.eng._view(P)
+        self._ck(self.lib.mpg_dist_gravpm_force(self.h, C.byref(v)))
+
+    def gravpm_get_powerspectrum(self, nmesh, BoxSize_in_MPC):
+        """(kk, Power, Nmodes) of the last PM step summed over the ranks (collective), empty bins dropped"""
+        kk, P, N = np.zeros(nmesh), np.zeros(nmesh), np.zeros(nmesh, np.int64)
+        nz = C.c_int(0)
+        self._ck(self.lib.mpg_dist_gravpm_get_powerspectrum(self.h, C.c_double(BoxSize_in_MPC), kk.ctypes.data_as(C.c_void_p),
+                                                            P.ctypes.data_as(C.c_void_p), N.ctypes.data_as(C.c_void_p), C.byref(nz)))
+        return kk[:nz.value], P[:nz.value], N[:nz.value]
+
+    # massive-neutrino linear response and hybrid-neutrino tracers: engine state (Engine.gravpm_set_nu_response), honoured by every
+    # mpg_dist PM entry; the callback runs on every rank with the bins summed over the ranks
+    def gravpm_set_nu_response(self, fn, BoxSize_in_MPC=1.0):
+        self.eng.gravpm_set_nu_response(fn, BoxSize_in_MPC)
+
+    def gravpm_set_hybrid_nu_tracer(self, on):
+        self.eng.gravpm_set_hybrid_nu_tracer(on)
+
+    def set_types(self, type):
+        """mpg_dist_dev_set_types: uint8 device tensor of the own rows' types (the deposit mask of the hybrid tracers), or None"""
+        n = 0 if type is None else type.shape[0]
+        self._ck(self.lib.mpg_dist_dev_set_types(self.h, C.c_int64(n), None if type is None else C.c_void_p(type.data_ptr())))
+
     def grav_short_tree(self, accel, oldacc=None, prev_accel=None, gravpm=None, potential=None, rho0=0.0, active=None):
         """the walk on the tree of the last force_tree_build; active: int32 device tensor of own-particle indices (a sub-step's
         ActiveParticle) or None for all"""

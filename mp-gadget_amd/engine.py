@@ -200,6 +200,37 @@ class FofGroupsC(C.Structure):
 
 
 GRAVKICK_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_int64, C.c_int64)
+# mpg_nu_response_fn (include/mpgadget_hip.h): (ctx, nonzero, kk, delta_cdm, Nmodes, logknu, delta_nu_ratio, nu_prefac, MtotbyMcdm) -> int
+NU_RESPONSE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                             C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+
+def _nu_response_thunk(fn):
+    """ctypes thunk around fn(kk, delta_cdm, Nmodes) -> (logknu, delta_nu_ratio, nu_prefac, MtotbyMcdm).  An exception in fn (or a table
+    of the wrong length) becomes the non-zero return the engine reports as an error; it is kept in thunk.error."""
+    def call(ctx, nonzero, kk, dcdm, nmodes, logknu, ratio, prefac, mtot):
+        try:
+            nz = int(nonzero)
+            k = np.ctypeslib.as_array(kk, (nz,)).copy() if nz else np.zeros(0)
+            d = np.ctypeslib.as_array(dcdm, (nz,)).copy() if nz else np.zeros(0)
+            m = np.ctypeslib.as_array(nmodes, (nz,)).copy() if nz else np.zeros(0, np.int64)
+            lk, rt, pf, mt = fn(k, d, m)
+            lk = np.asarray(lk, np.float64).reshape(-1)
+            rt = np.asarray(rt, np.float64).reshape(-1)
+            if lk.size != nz or rt.size != nz:
+                raise ValueError("neutrino response: logknu / delta_nu_ratio must have %d entries, not %d / %d" % (nz, lk.size, rt.size))
+            if nz:
+                np.ctypeslib.as_array(logknu, (nz,))[:] = lk
+                np.ctypeslib.as_array(ratio, (nz,))[:] = rt
+            prefac[0] = float(pf)
+            mtot[0] = float(mt)
+            return 0
+        except BaseException as e:  # (nothing may propagate through the C frames)
+            thunk.error = e
+            return 1
+    thunk = NU_RESPONSE_FN(call)
+    thunk.error = None
+    return thunk
 
 
 class Engine:
@@ -323,6 +354,26 @@ class Engine:
         self._ck(self.lib.mpg_gravpm_get_powerspectrum(self.h, C.c_double(BoxSize_in_MPC), kk.ctypes.data_as(C.c_void_p),
                                                        P.ctypes.data_as(C.c_void_p), N.ctypes.data_as(C.c_void_p), C.byref(nz)))
         return kk[:nz.value], P[:nz.value], N[:nz.value]
+
+    # massive-neutrino linear response (gravpm.c:72-79, 303-326, 418-446) and hybrid-neutrino tracers (gravpm.c:84-85, 469-474)
+    def gravpm_set_nu_response(self, fn, BoxSize_in_MPC=1.0):
+        """fn(kk, delta_cdm, Nmodes) -> (logknu, delta_nu_ratio, nu_prefac, MtotbyMcdm), called once per PM step with the Mpc/h bins of
+        the CDM spectrum (delta_cdm = sqrt(Power)); None turns the response off.  See mpg_gravpm_set_nu_response."""
+        if fn is None:
+            self._ck(self.lib.mpg_gravpm_set_nu_response(self.h, None, None, C.c_double(0.0)))
+            self._keep.pop("nu_response", None)
+            return
+        thunk = _nu_response_thunk(fn)
+        self._ck(self.lib.mpg_gravpm_set_nu_response(self.h, thunk, None, C.c_double(BoxSize_in_MPC)))
+        self._keep["nu_response"] = thunk  # alive while installed
+
+    def gravpm_nu_response_error(self):
+        """the exception the installed response callback raised last, or None"""
+        t = self._keep.get("nu_response")
+        return None if t is None else t.error
+
+    def gravpm_set_hybrid_nu_tracer(self, on):
+        self._ck(self.lib.mpg_gravpm_set_hybrid_nu_tracer(self.h, int(bool(on))))
 
     def dev_gravpm_powerspectrum_raw(self, acc, modes):
         self._ck(self.lib.mpg_dev_gravpm_powerspectrum_raw(self.h, _ptr(acc), _ptr(modes)))

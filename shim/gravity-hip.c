@@ -19,6 +19,10 @@
 #include "walltime.h"
 #include "utils/endrun.h"
 #include "utils/mymalloc.h"
+#include "cosmology.h"       /* Cosmology, hybrid_nu_tracer */
+#include "powerspectrum.h"   /* Power, powerspectrum_alloc / _free */
+#include "omega_nu_single.h" /* get_omega_nu_nopart */
+#include <math.h>
 #include <mpgadget_hip.h>
 #include "mpg_mpi_comm.h"
 #include "mpg_shim.h"
@@ -258,12 +262,68 @@ void gravpm_init_periodic(PetaPM *pm, double BoxSize, double Asmth, int Nmesh, d
     ck(mpg_gravpm_init_periodic(eng(), BoxSize, Asmth, Nmesh, G));
 }
 
+/* ---- the massive-neutrino linear response (MassiveNuLinRespOn, gravpm.c:72-79, 303-326): the engine calls this between its two passes
+ * over rho_k, with the CDM bins summed over the ranks (delta_cdm = sqrt(Power)), as compute_neutrino_power does; the LRA integral and
+ * its delta_tot_table stay the reference's (neutrinos_lra.c).  The Power it fills lives until gravpm_force has saved powerspectrum-nu. */
+/* neutrinos_lra.h:59, :68 (the header itself pulls in bigfile-mpi.h, which nothing else of this file needs) */
+void delta_nu_from_power(struct _powerspectrum *PowerSpectrum, Cosmology *CP, const double Time, const double TimeIC);
+void powerspectrum_nu_save(struct _powerspectrum *PowerSpectrum, const char *OutputDir, const char *filename, const double Time);
+
+struct nu_response_ctx {
+    Cosmology *CP;
+    double Time, TimeIC, BoxSize_in_cm;
+    int Nmesh;
+    int have_ps;
+    Power ps;
+};
+static struct nu_response_ctx NuCtx;
+static int NuResponseInstalled, HybridTracerSet;
+
+static int nu_response(void *ctx, int nonzero, const double *kk, const double *delta_cdm, const int64_t *Nmodes, double *logknu,
+                       double *delta_nu_ratio, double *nu_prefac, double *MtotbyMcdm)
+{
+    struct nu_response_ctx *c = (struct nu_response_ctx *)ctx;
+    if(nonzero < 1 || nonzero > c->Nmesh || c->have_ps)
+        return 1;
+    powerspectrum_alloc(&c->ps, c->Nmesh, 1, 1, c->BoxSize_in_cm);
+    c->have_ps = 1;
+    c->ps.nu_spline = NULL; /* powerspectrum_nu_save frees both: gsl_interp_free(NULL) / gsl_interp_accel_free(NULL) are no-ops */
+    c->ps.nu_acc = NULL;
+    memcpy(c->ps.kk, kk, nonzero * sizeof(double));
+    memcpy(c->ps.Power, delta_cdm, nonzero * sizeof(double));
+    memcpy(c->ps.Nmodes, Nmodes, nonzero * sizeof(int64_t));
+    c->ps.nonzero = nonzero;
+    delta_nu_from_power(&c->ps, c->CP, c->Time, c->TimeIC);
+    memcpy(logknu, c->ps.logknu, nonzero * sizeof(double));
+    memcpy(delta_nu_ratio, c->ps.delta_nu_ratio, nonzero * sizeof(double));
+    *nu_prefac = c->ps.nu_prefac;
+    /* gravpm.c:437-441 */
+    *MtotbyMcdm = c->CP->Omega0 / (c->CP->Omega0 - pow(c->Time, 3) * get_omega_nu_nopart(&c->CP->ONu, c->Time));
+    return 0;
+}
+
 void gravpm_force(PetaPM *pm, DomainDecomp *ddecomp, Cosmology *CP, double Time, double UnitLength_in_cm, const char *PowerOutputDir,
                   double TimeIC)
 {
-    (void)CP;
-    (void)TimeIC;
     walltime_measure("/Misc");
+    /* engine state, told only when it changes: with MassiveNuLinRespOn = 0 and no hybrid tracers nothing here is called */
+    if(CP->MassiveNuLinRespOn || NuResponseInstalled) {
+        NuCtx.CP = CP;
+        NuCtx.Time = Time;
+        NuCtx.TimeIC = TimeIC;
+        NuCtx.BoxSize_in_cm = pm->BoxSize * UnitLength_in_cm;
+        NuCtx.Nmesh = pm->Nmesh;
+        NuCtx.have_ps = 0;
+        ck(mpg_gravpm_set_nu_response(eng(), CP->MassiveNuLinRespOn ? nu_response : NULL, &NuCtx,
+                                      pm->BoxSize * UnitLength_in_cm / 3.085678e24));
+        NuResponseInstalled = CP->MassiveNuLinRespOn;
+    }
+    /* hybrid neutrinos as passive tracers: type 2 out of the deposit (gravpm.c:84-85, 469-474) */
+    const int tracer = hybrid_nu_tracer(CP, Time);
+    if(tracer != HybridTracerSet) {
+        ck(mpg_gravpm_set_hybrid_nu_tracer(eng(), tracer));
+        HybridTracerSet = tracer;
+    }
     mpg_shim_set_domain(ddecomp);
     const struct gravshort_tree_params tp = get_gravshort_treepar();
     /* one upload of Pos / Mass serves the calls of this step (run.c:472-548); Ti_Current is not an argument here: matched through Time */
@@ -289,6 +349,13 @@ void gravpm_force(PetaPM *pm, DomainDecomp *ddecomp, Cosmology *CP, double Time,
             ck(mpg_powerspectrum_save(PowerOutputDir, "powerspectrum", Time, 1.0, nonzero, kk, pw, nm));
         myfree(nm);
         myfree(kk);
+    }
+    /* powerspectrum-nu-<a>.txt (gravpm.c:115-116; powerspectrum_nu_save writes on rank 0 only), then the Power of the callback goes */
+    if(NuCtx.have_ps) {
+        if(PowerOutputDir)
+            powerspectrum_nu_save(&NuCtx.ps, PowerOutputDir, "powerspectrum-nu", Time);
+        powerspectrum_free(&NuCtx.ps);
+        NuCtx.have_ps = 0;
     }
     walltime_measure("/PMgrav/PowerSpec");
 }
