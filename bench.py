@@ -12,9 +12,12 @@ N > 1 : weak scaling, ~256^3 particles per GPU (n = 320 / 400 / 512 per dimensio
         (the library's choreography, csrc/dist.hip); the line carries `parity_check`, the forces of sampled
         particles against the one-GPU path.
 
-One JSON line is printed by rank 0 (contract of the task statement), with `roofline` for the dominant kernel
-(the short-range walk; HIP events on the engine stream inside the timed region) and `cpu_baseline` (the oracle
-built with the reference's compiler flags, timed on the host cores of this box on a bounded sample).
+One JSON line is printed by rank 0 (contract of the task statement).  On one GPU a plain run sets up, warms up, times the
+steps, writes --dump-outputs and prints the headline figure, nothing more.  --full adds the untimed legs after the timed
+steps: `roofline` for the dominant kernel (the short-range walk; HIP events on the engine stream inside the timed region,
+interaction counters and HBM traffic from passes of their own), `phases_ms`, `cpu_baseline` (the oracle built with the
+reference's compiler flags, timed on the host's cores on a bounded sample) and the sub-steps, drop-in paths, other input
+sets and the gas configuration.  The multi-rank lines and the other workloads carry their legs and self-checks either way.
 """
 import argparse
 import importlib
@@ -847,13 +850,29 @@ def gravity_bench_single(pkg, torch, args, dev, local_rank):
         step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    walk_ms, walk_launches, lists_ms, eval_ms, nsplit = eng.walk_events_collect_split()
     if args.dump_outputs:       # (before the untimed passes below overwrite them)
         dumped = dump_outputs(args.dump_outputs, {"GravPM": gravpm, "FullTreeGravAccel": acc, "Potential": pot})
         print("bench.py: wrote %s.npy to %s" % (".npy, ".join(dumped), args.dump_outputs), file=sys.stderr, flush=True)
     if args.traffic_child:      # (a child of live_walk_traffic under rocprofv3: the walks above are what it wanted)
         eng.close()
         return None
+    out = {
+        "metric": "particle-updates/sec (gravity force step: PM + tree build + short-range walk)",
+        "value": N * args.steps / elapsed, "unit": "particles/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "%d^3 DM-only TreePM force step, Nmesh=%d, %s ICs, all particles active, relative opening "
+                               "criterion (ErrTolForceAcc 0.002), TreeRcut 6, Asmth 1.5" % (n, nmesh, args.ic),
+                   "particles": N, "nmesh": nmesh, "parallelism": "1 GPU"},
+    }
+    if os.environ.get("MPG_BENCH_TREEUSEBH") or os.environ.get("MPG_BENCH_BHANGLE"):   # (a diagnostic run: not BASELINE's configuration)
+        out["config"]["workload"] += " -- DIAGNOSTIC: TreeUseBH=%s BHOpeningAngle=%s from the environment" % (
+            os.environ.get("MPG_BENCH_TREEUSEBH", "2"), os.environ.get("MPG_BENCH_BHANGLE", "0.175"))
+    if not args.full:           # a plain run: the headline figure alone
+        eng.close()
+        emit(out)
+        return out
+    walk_ms, walk_launches, lists_ms, eval_ms, nsplit = eng.walk_events_collect_split()     # (the walks of the timed steps)
     # ---- untimed diagnostic passes: phase times of one more step, interaction counters of another (the counting builds of the
     # walk kernels are slower: kept out of the phase times)
     eng.set_instrumentation(True, False)
@@ -878,23 +897,11 @@ def gravity_bench_single(pkg, torch, args, dev, local_rank):
             traffic, traffic_note = live, live_note + " (%.0f s)" % (time.perf_counter() - t0)
         else:
             traffic_note += "; live measurement not available: " + live_note
-    out = {
-        "metric": "particle-updates/sec (gravity force step: PM + tree build + short-range walk)",
-        "value": N * args.steps / elapsed, "unit": "particles/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "%d^3 DM-only TreePM force step, Nmesh=%d, %s ICs, all particles active, relative opening "
-                               "criterion (ErrTolForceAcc 0.002), TreeRcut 6, Asmth 1.5" % (n, nmesh, args.ic),
-                   "particles": N, "nmesh": nmesh, "parallelism": "1 GPU"},
-        "roofline": walk_roofline(eng, cnt, walk_ms, walk_launches, traffic, traffic_note),
-        "phases_ms": {k: round(v, 3) for k, v in ph.items()},
-    }
+    out["roofline"] = walk_roofline(eng, cnt, walk_ms, walk_launches, traffic, traffic_note)
+    out["phases_ms"] = {k: round(v, 3) for k, v in ph.items()}
     if nsplit:      # the walk's two kernels one by one (an event between them on the engine stream, inside the timed region)
         out["roofline"]["kernels_ms"] = {"k_walk_lists8": round(lists_ms / nsplit, 3), "k_walk_eval": round(eval_ms / nsplit, 3), "launches_timed": nsplit,
                                          "frac_of_k_walk_eval_alone": round(out["roofline"]["frac"] * (walk_ms / walk_launches) / (eval_ms / nsplit), 4)}
-    if os.environ.get("MPG_BENCH_TREEUSEBH") or os.environ.get("MPG_BENCH_BHANGLE"):   # (a diagnostic run: not BASELINE's configuration)
-        out["config"]["workload"] += " -- DIAGNOSTIC: TreeUseBH=%s BHOpeningAngle=%s from the environment" % (
-            os.environ.get("MPG_BENCH_TREEUSEBH", "2"), os.environ.get("MPG_BENCH_BHANGLE", "0.175"))
     if not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(pkg, d_pos.cpu().numpy(), mass, box, n, nmesh, prev.cpu().numpy() + gravpm.cpu().numpy(), args.cpu_sample)
     if not args.no_extras:
@@ -989,14 +996,18 @@ def main():
                     help="particles per dimension (default: 256 per GPU, weak scaling)")
     ap.add_argument("--ic", default="s_zel", choices=["s_grid", "s_zel", "s_clust"],
                     help="synthetic input set (SURVEY 8(d)); s_zel, the Zel'dovich-displaced grid, is the headline set")
+    ap.add_argument("--full", action="store_true",
+                    help="one-GPU gravity workload: after the timed steps also run the untimed legs - phase times and interaction counters "
+                         "(roofline, phases_ms), the walk's HBM traffic, cpu_baseline, substeps, host_path, resident_path, other_inputs, "
+                         "hydro; without it the line carries the headline figure alone.  The other lines carry theirs either way")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1: skip the untimed legs (substeps, host_path, resident_path, other_inputs, hydro)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-traffic", action="store_true", help="N = 1: take roofline.traffic from profiles/walk_traffic.json instead of two "
-                                                                   "rocprofv3 --pmc child runs of this command")
+                    help="with --full: skip the untimed legs after roofline and cpu_baseline (substeps, host_path, resident_path, other_inputs, hydro)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-live-traffic", action="store_true", help="take roofline.traffic from profiles/walk_traffic.json instead of two "
+                                                                   "rocprofv3 --pmc child runs of this command (the one-GPU gravity line runs them with --full only)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--no-parity-check", action="store_true", help="N > 1: skip the untimed self-check of the forces against the one-GPU path")
-    ap.add_argument("--cpu-sample", type=int, default=1 << 22, help="targets walked by the CPU baseline")
+    ap.add_argument("--cpu-sample", type=int, default=1 << 22, help="targets walked by the CPU baseline (--full)")
     ap.add_argument("--thresh", type=int, default=16)
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--mgpu", default="peano", choices=["peano"], help="(kept for the command lines of round 2; the x-slab / replicated forms were retired)")
@@ -1010,7 +1021,7 @@ def main():
                     help="hydro workload: density-entropy (BASELINE configs[2]) or pressure-entropy SPH (configs[4]); auto: de on one GPU, pe on several")
     ap.add_argument("--active-frac", type=float, default=1. / 64, help="substep workload: fraction of the particles that is active")
     ap.add_argument("--workload", default="gravity", choices=["gravity", "hydro", "integrate", "fof", "domain", "substep"],
-                    help="gravity: BASELINE.json configs[1] (default, the headline metric; its line also carries the sub-steps and configs[2]); "
+                    help="gravity: BASELINE.json configs[1] (default, the headline metric; with --full its line also carries the sub-steps and configs[2]); "
                          "hydro: configs[2] / [4] as their own line; substep: the short-range-only step; integrate / fof / domain: SURVEY 8(f) rows")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="one-GPU gravity workload: after the timed steps, write what the last timed step returned (GravPM, "

@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
         "config", "roofline"}
+PLAIN_KEYS = KEYS - {"roofline"}      # the one-GPU gravity line without --full: the headline figure alone
 
 
 def run_bench(args, env=None):
@@ -21,8 +22,18 @@ def run_bench(args, env=None):
     return json.loads(last)
 
 
+def test_plain_line_is_the_headline_alone():
+    """Without --full the one-GPU gravity line is set-up, warm-up, the timed steps and the headline figure: no untimed leg runs."""
+    j = run_bench(["--size", "64", "--steps", "2", "--warmup", "1"])
+    assert set(j) == PLAIN_KEYS, sorted(set(j) ^ PLAIN_KEYS)
+    assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["higher_is_better"] is True and j["dtype"] == "f64"
+    assert j["unit"] == "particles/s" and j["metric"].startswith("particle-updates/sec (gravity force step")
+    assert j["value"] > 1e6 and abs(j["value"] - 64 ** 3 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert "s_zel" in j["config"]["workload"] and j["config"]["particles"] == 64 ** 3 and j["config"]["nmesh"] == 128
+
+
 def test_default_workload_line():
-    j = run_bench(["--size", "64", "--steps", "2", "--warmup", "1", "--cpu-sample", "65536"])
+    j = run_bench(["--size", "64", "--steps", "2", "--warmup", "1", "--cpu-sample", "65536", "--full"])
     assert KEYS <= set(j) and "cpu_baseline" in j
     assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1 and j["higher_is_better"] is True and j["dtype"] == "f64"
     assert j["value"] > 1e6 and abs(j["value"] - 64 ** 3 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
@@ -58,15 +69,16 @@ def test_default_workload_line():
 def test_dump_outputs_are_the_last_timed_step(pkg, tmp_path):
     """--dump-outputs DIR: what the last of the --steps timed steps returned, float64, one row per particle at this size - GravPM equal to
     the CPU oracle's PM force on the same particles, FullTreeGravAccel and Potential; --steps sets the number of timed walks; a second run
-    with the same arguments has the same inputs and gives the same outputs (up to the deposit's atomic sums)."""
+    without --full has the same inputs and gives the same outputs (up to the deposit's atomic sums)."""
     import numpy as np
     from oracle import oracle as O
     n = 32
     N = n ** 3
     args = ["--size", str(n), "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-live-traffic"]
-    j = run_bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    j = run_bench(args + ["--full", "--dump-outputs", str(tmp_path / "a")])
     assert j["steps"] == 3 and j["roofline"]["launches_timed"] == 3
-    run_bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    jb = run_bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    assert jb["steps"] == 3 and set(jb) == PLAIN_KEYS
     names = ("index", "GravPM", "FullTreeGravAccel", "Potential")
     a, b = ({k: np.load(str(tmp_path / d / (k + ".npy"))) for k in names} for d in ("a", "b"))
     assert sorted(os.listdir(str(tmp_path / "a"))) == sorted(k + ".npy" for k in names)
@@ -194,7 +206,7 @@ def test_c4_whole_particle_set_on_one_gpu():
     the walk lists; the walk runs its 64-bit-offset kernels (source and node arrays beyond 4 GiB) and slices its list area.  One timed
     step; the line's counters must be those of a 512^3 Zel'dovich walk (about 700 pair interactions and 200 nodes used per target)
     and the rate that of the 256^3 run.  (this run was the builder's, not part of -m gpu.)"""
-    j = run_bench(["--size", "512", "--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline"])   # (the warm-up step sizes the walk's lists)
+    j = run_bench(["--size", "512", "--steps", "1", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"])   # (the warm-up step sizes the walk's lists)
     assert KEYS <= set(j) and j["config"]["particles"] == 512 ** 3 and j["config"]["nmesh"] == 1024
     r = j["roofline"]
     assert j["value"] > 1.2e8 and 0.08 < r["frac"] <= 1

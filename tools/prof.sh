@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-live-traffic $*"   # (bench.py would start rocprofv3 children of its own: not under a profiler)
+ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-live-traffic $*"   # (bench.py would start rocprofv3 children of its own: not under a profiler)
 # (the counter passes run the headline workload alone: the traffic per walk is summed over all walks of the run, and the sub-step /
 # other-input legs of the default line are walks of other sizes)
 PARGS="$ARGS --no-extras"

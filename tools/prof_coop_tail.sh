@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 export TMPDIR=/tmp PYTHONPATH=$ROOT
 OUT=/tmp/prof_coop_$$
 cd $ROOT
-rocprofv3 --output-format csv --kernel-trace -d $OUT -o t -- python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1 | grep -o "ms_per_step[^,]*"
+rocprofv3 --output-format csv --kernel-trace -d $OUT -o t -- python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 | grep -o "ms_per_step[^,]*"
 python - <<PY
 import csv, glob
 f = glob.glob("$OUT/**/*kernel_trace.csv", recursive=True)[0]

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-PARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-extras"
+PARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
 HARGS="--workload hydro --steps 2 --warmup 1"
 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace -o trace -- python $ROOT/bench.py $PARGS > $OUT/bench_trace.json 2> $OUT/trace.err
 rocprofv3 --output-format csv --pmc FETCH_SIZE -d $OUT/pmc_fetch -o pmc -- python $ROOT/bench.py $PARGS > /dev/null 2> $OUT/pmc_fetch.err
