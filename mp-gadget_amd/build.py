@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libmpgadget_hip.so")
 SOURCES = ["tree_build.hip", "grav_walk.hip", "grav_walk_coop.hip", "grav_walk_split.hip", "grav_pair_walk.hip", "pm.hip", "sph.hip", "timestep.hip", "peano.hip", "domain.hip", "fof.hip", "snapshot_io.hip", "engine.hip", "dist.hip", "rccl_comm.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
-# experiments (-DMPG_EXP_...): MPG_EXTRA_FLAGS="file.hip:-Dx -Dy" applies to one source, MPG_EXTRA_FLAGS="-Dx" to all; part of the
+# experiments (-D...): MPG_EXTRA_FLAGS="file.hip:-Dx -Dy" applies to one source, MPG_EXTRA_FLAGS="-Dx" to all; part of the
 # build stamp like every flag
 _EXTRA = os.environ.get("MPG_EXTRA_FLAGS", "")
 _EXTRA_FILE, _EXTRA = (_EXTRA.split(":", 1) if ".hip:" in _EXTRA else ("", _EXTRA))

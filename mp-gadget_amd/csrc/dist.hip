@@ -225,18 +225,6 @@ __global__ void __launch_bounds__(256) k_unpack_particles(int64_t nr, const PRow
     mass[k] = r.m;
 }
 
-// the particles a slab rank received whose BASE cell lies in its planes: the ones it reads the mesh out for
-__global__ void __launch_bounds__(256) k_flag_slab_targets(int64_t n, const double *__restrict__ pos, double cellsize, int nmesh, int P, int me,
-                                                           unsigned char *__restrict__ flag)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= n)
-        return;
-    int o0, o1;
-    pm_owners(pos[3 * i], cellsize, nmesh, P, o0, o1);
-    flag[i] = o0 == me;
-}
-
 __global__ void __launch_bounds__(256) k_pack_results(int64_t n, const double *__restrict__ gravpm, const double *__restrict__ pot,
                                                       RRow *__restrict__ rows)
 {
@@ -648,8 +636,6 @@ struct mpg_dist {
     // PM side
     DevBuf<double> spos, sgrav, spot;
     DevBuf<float> smass;
-    DevBuf<unsigned char> sflag;
-    DevBuf<int> starg;
     DevBuf<unsigned long long> scount;
     DevBuf<double> sendA, recvA, sendB, recvB, gsend, grecv;
     int64_t per_peer = 0, plane = 0;
@@ -942,9 +928,6 @@ void pm_step(mpg_dist *d, int64_t n, const double *pos, const float *mass, doubl
     d->smass.reserve((size_t)nr + 1);
     d->sgrav.reserve((size_t)3 * nr + 3);
     d->spot.reserve((size_t)nr + 1);
-    d->sflag.reserve((size_t)nr + 1);
-    d->starg.reserve((size_t)nr + 1);
-    d->scount.reserve(4);
     if(nr > 0)
         hipLaunchKernelGGL(k_unpack_particles, dim3(nblk(nr)), dim3(256), 0, st, nr, (const PRow *)d->recvbuf.p, d->spos.p, d->smass.p);
     // local stages of the slab solver with the two transposes and the neighbour planes in between (pm.hip, "slab-decomposed form")
@@ -995,25 +978,7 @@ void pm_step(mpg_dist *d, int64_t n, const double *pos, const float *mass, doubl
         MPG_HIP(hipMemsetAsync(d->sgrav.p, 0, (size_t)3 * nr * sizeof(double), st));
         MPG_HIP(hipMemsetAsync(d->spot.p, 0, (size_t)nr * sizeof(double), st));
     }
-    static const bool stencil_rows = !(getenv("MPG_PM_STENCIL") && getenv("MPG_PM_STENCIL")[0] == '0');
-    if(stencil_rows)
-        pm.slab_readout_rows(d->grecv.p, nr, d->spos.p, d->sgrav.p, d->spot.p, st);
-    else {
-        int64_t ntarg = 0;
-        if(nr > 0) {
-            hipLaunchKernelGGL(k_flag_slab_targets, dim3(nblk(nr)), dim3(256), 0, st, nr, d->spos.p, pm.cellsize, nmesh, P, d->me, d->sflag.p);
-            rocprim::counting_iterator<int> iota(0);
-            size_t tb = 0;
-            MPG_HIP(rocprim::select(nullptr, tb, iota, d->sflag.p, d->starg.p, d->scount.p, (size_t)nr, st));
-            d->tmp.reserve(tb + 16);
-            MPG_HIP(rocprim::select((void *)d->tmp.p, tb, iota, d->sflag.p, d->starg.p, d->scount.p, (size_t)nr, st));
-            unsigned long long c = 0;
-            MPG_HIP(hipMemcpyAsync(&c, d->scount.p, sizeof(c), hipMemcpyDeviceToHost, st));
-            sync(d);
-            ntarg = (int64_t)c;
-        }
-        pm.slab_readout(d->grecv.p, d->starg.p, ntarg, d->spos.p, d->sgrav.p, d->spot.p, st);
-    }
+    pm.slab_readout_rows(d->grecv.p, nr, d->spos.p, d->sgrav.p, d->spot.p, st);
     // results back along the same lists
     if(nr > 0)
         hipLaunchKernelGGL(k_pack_results, dim3(nblk(nr)), dim3(256), 0, st, nr, d->sgrav.p, d->spot.p, (RRow *)d->recvbuf.p);

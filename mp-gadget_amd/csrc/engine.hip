@@ -561,7 +561,7 @@ int mpg_dev_grav_short_tree(mpg_engine *eng, const double *d_oldacc, const doubl
         if(v == 1)
             launch_grav_walk(eng->tree.view(), gp, w, w.potential != nullptr, eng->count, fastwrap, eng->walk_thresh, eng->stream);
         else if(v == 6)
-            launch_grav_walk_split(eng->tree.view(), gp, w, w.potential != nullptr, eng->count, fastwrap, eng->walk_thresh, eng->w3, eng->stream);
+            launch_grav_walk_split(eng->tree.view(), gp, w, w.potential != nullptr, eng->count, fastwrap, eng->w3, eng->stream);
         else
             launch_grav_walk_coop(eng->tree.view(), gp, w, w.potential != nullptr, eng->count, fastwrap, eng->w3, eng->stream);
     };

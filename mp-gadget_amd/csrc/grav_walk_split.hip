@@ -33,29 +33,13 @@ namespace mpg {
 
 namespace {
 
-#ifndef MPG_EVAL_BLOCKS
 // resident 256-thread blocks per CU the evaluation kernel is compiled for.  4 (128 VGPRs) since round 4: the instantiation with the
 // potential spills 8 registers there (50 at 6 blocks / 80 VGPRs: 15 GB of scratch writes per walk at 256^3) and the walk is 1.5 ms faster
-// (69.2 -> 67.7 ms); round 3 had measured 4, 5 and 6 blocks as equal before the list kernel changed
-#define MPG_EVAL_BLOCKS 4
-#endif
-#ifndef MPG_LISTS_PREFETCH_MIN
-#define MPG_LISTS_PREFETCH_MIN 64
-#endif
-#ifndef MPG_LIST_BLOCKS
-#define MPG_LIST_BLOCKS 6 // resident 256-thread blocks per CU the list kernel is compiled for
-#endif
-#ifndef MPG_EVAL_BLOCKS_LONG
-// ... and where the lists are long (capacity >= 4096: a clustered set).  6 (80 registers) until round 5, when "it waits for memory and the
-// waves count" held; with every source record requested two evaluations ahead the 4-block build wins there too (256^3 clustered set:
-// 125.0 -> 118.7 ms per step; 5 blocks 121.9)
-#define MPG_EVAL_BLOCKS_LONG 4
-#endif
-
-
-#ifdef MPG_LEAF_HIST
-__device__ unsigned long long g_leaf_hist[16];
-#endif
+// (69.2 -> 67.7 ms); round 3 had measured 4, 5 and 6 blocks as equal before the list kernel changed.  Long lists (capacity >= 4096: a
+// clustered set) took 6 blocks until round 5; with every source record requested two evaluations ahead 4 wins there too (256^3 clustered
+// set: 125.0 -> 118.7 ms per step; 5 blocks 121.9)
+constexpr int EVAL_BLOCKS = 4;
+constexpr int LIST_BLOCKS = 6; // resident 256-thread blocks per CU the list kernel is compiled for
 
 __device__ __forceinline__ double rsqrt_nr(double x)
 {
@@ -71,13 +55,8 @@ __device__ __forceinline__ double rsqrt_nr(double x)
 // hipcc turned into flat_load + s_waitcnt vmcnt(0): two (inner spline branch) to five (outer) serialised memory round trips per
 // softened pair step, each wait also draining the prefetched source records - a softened step cost ~10 ordinary ones, and a clustered
 // set has them.  Now every constant is two s_mov_b32 of literals into a scalar register pair, emitted by a volatile asm at the point
-// of use (volatile: not hoisted out of the branch): no memory access, no wait.  (MPG_SPLINE_CONSTMEM restores the loads.)
+// of use (volatile: not hoisted out of the branch): no memory access, no wait.
 // The divisions are v_rcp_f64 + Newton steps (<= 1 ulp from the quotient) instead of the 40-instruction IEEE expansion.
-#ifdef MPG_SPLINE_CONSTMEM
-__constant__ double SPLINE_C[13] = {10.666666666667, 32.0, 38.4,  -2.8, 5.333333333333, 6.4, 9.6,
-                                    21.333333333333, 48.0, 0.066666666667, -3.2, -16.0, 2.133333333333};
-#endif
-
 template <unsigned long long BITS>
 __device__ __forceinline__ double scalar_literal()
 {
@@ -98,19 +77,6 @@ __device__ __forceinline__ void softened_pair(const double r, const double m, co
 {
     const double u = r * hinv;
     double wpk;
-#ifdef MPG_SPLINE_CONSTMEM
-    const double *c = SPLINE_C;
-    asm volatile("" : "+s"(c));
-    if(u < 0.5) {
-        fac = m * h3inv * (c[0] + u * u * (c[1] * u - c[2]));
-        wpk = c[3] + u * u * (c[4] + u * u * (c[5] * u - c[6]));
-    }
-    else {
-        const double iu = rcp_nr(u);
-        fac = m * h3inv * (c[7] - c[8] * u + c[2] * u * u - c[0] * u * u * u - c[9] * (iu * iu * iu));
-        wpk = c[10] + c[9] * iu + u * u * (c[0] + u * (c[11] + u * (c[6] - c[12] * u)));
-    }
-#else
     if(u < 0.5) {
         fac = m * h3inv * (MPG_K(10.666666666667) + u * u * (MPG_K(32.0) * u - MPG_K(38.4)));
         wpk = MPG_K(-2.8) + u * u * (MPG_K(5.333333333333) + u * u * (MPG_K(6.4) * u - MPG_K(9.6)));
@@ -122,14 +88,12 @@ __device__ __forceinline__ void softened_pair(const double r, const double m, co
         wpk = MPG_K(-3.2) + MPG_K(0.066666666667) * iu +
               u * u * (MPG_K(10.666666666667) + u * (MPG_K(-16.0) + u * (MPG_K(9.6) - MPG_K(2.133333333333) * u)));
     }
-#endif
     facpot = m * hinv * wpk;
 }
 
-// apply_accn_to_output, gravshort-tree.c:158-193, in three stages so that the evaluation loop can run TWO pairs side by side (their chains
-// of dependent fp64 operations are what the kernel waits for: with 2 / 3 / 4 resident waves per SIMD it takes 52.8 / 41.3 / 36.1 ms at 256^3,
-// i.e. 18 ms of issue + 69 ms / waves of exposed latency): the common arithmetic up to the softening test, the rare softened branch (taken
-// once for both pairs), the window table and the sums.
+// apply_accn_to_output, gravshort-tree.c:158-193, in three stages: the common arithmetic up to the softening test, the rare softened branch,
+// the window table and the sums.  (Round 5 ran two pairs side by side through them, one softened branch for both: 38.2 against 35.9 ms per
+// evaluation at 256^3 - the waves hide the latency of the source loads, not of the dependent arithmetic; that loop is removed.)
 struct PairTmp {
     double dx, dy, dz, r2, rinv, r, fac, facpot, m;
 };
@@ -153,15 +117,12 @@ __device__ __forceinline__ void pair_pre(const Src4 s, const double dx, const do
 // rare (the self interaction, close encounters): kept out of line so that its divisions and constants do not occupy registers in the pair loop
 __device__ __forceinline__ void pair_soft(const GravParams &gp, PairTmp &t)
 {
-#ifndef MPG_NO_SELF_FAST
     if(t.r2 == 0.0) { // the self interaction, once per target and so in ~6 % of a wave's pair steps: the spline's inner branch at u = 0
         t.r = 0.0;    // (bit for bit: c0 + 0 and c3 + 0), from literals - softened_pair's constant fetches are dependent vector loads whose
         t.fac = t.m * gp.h3inv * 10.666666666667; // waits also drain the prefetched source records
         t.facpot = t.m * gp.hinv * -2.8;
     }
-    else
-#endif
-    {
+    else {
         if(!(t.rinv < 1e150))
             t.r = 0.0;
         softened_pair(t.r, t.m, gp.hinv, gp.h3inv, t.fac, t.facpot);
@@ -331,10 +292,7 @@ __device__ __forceinline__ void node_test_masks(const GravParams &gp, const Node
 // go back to the frontier (one entry per child: a prefix sum over the lanes by four ballots).
 // Per target the set of nodes tested and the outcome of every test are exactly those of its own walk (a node reaches the frontier
 // with bit t set iff target t opened its parent); the ORDER of a target's list entries depends on its 7 wave-mates.
-#ifndef MPG_QCAP
-#define MPG_QCAP 1024
-#endif
-constexpr int QCAP = MPG_QCAP; // frontier entries per wave (node index 4 B + target mask 1 B); a wave that would exceed it hands its targets to the fallback
+constexpr int QCAP = 1024; // frontier entries per wave (node index 4 B + target mask 1 B); a wave that would exceed it hands its targets to the fallback
 
 __device__ __forceinline__ unsigned mbcnt64(const unsigned long long b)
 {
@@ -509,52 +467,6 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
             }
         }
     }
-#ifdef MPG_LISTS_PREFETCH
-    // Round 5 experiment, measured and left off (29.6 ms at 5 resident blocks, 34 at 6 with 37 spilled registers, against 25.3 ms without it;
-    // 20 more registers for the second batch cost a resident wave, which is worth what the prefetch hides; 7 blocks of the plain form: 25.7).
-    // Two batches of nodes in flight: the batch BELOW the one being tested is taken off the frontier and its 80 bytes per lane
-    // requested before the 8 passes over the current batch, which then hide that gather (the kernel is latency-bound: with 2 / 4 / 6 resident
-    // waves per SIMD it takes 55.5 / 33.1 / 25.7 ms at 256^3, i.e. 11 ms of issue + 89 ms / waves).  The batch below does not depend on
-    // what the current batch pushes, so the set of (node, target) tests is unchanged; the frontier is a batch deeper at most, and the order
-    // of a target's list entries changes (it already depended on its wave-mates).  When nothing waits below, the next batch is what the
-    // current one pushed, as before.
-    struct Batch {
-        unsigned my, qmask;
-        int n;
-        NodeGeo g;
-        Src4 mom;
-        NodeLinkB lk;
-    };
-    auto pop = [&](Batch &b) {
-        __builtin_amdgcn_wave_barrier();
-        b.n = sp < 64 ? sp : 64;
-        // (idle lanes read entry 0, which always holds a node index: no exec-mask regions around the two reads)
-        const int qi = lane < b.n ? sp - 1 - lane : 0;
-        b.my = q_node[qi];
-        b.qmask = lane < b.n ? (unsigned)q_mask[qi] : 0u;
-        sp -= b.n;
-        b.g = ld<O32>(tv.geoB, b.my);
-        b.mom = ld<O32>(tv.momB, b.my);
-        b.lk = ld<O32>(tv.linkB, b.my);
-    };
-    Batch cur, nxt;
-    pop(cur);
-    while(cur.n > 0 && live) {
-        if(++guard > guard_max) {
-            if(lane == 0)
-                atomicExch(&ctl[1], 1u);
-            return false;
-        }
-        nxt.n = 0;
-        if(sp >= MPG_LISTS_PREFETCH_MIN) // (a FULL batch waits below: a part of one would be tested with idle lanes, where the pure LIFO tops it up
-            pop(nxt);                    // with what the current batch pushes)
-        const int n = cur.n;
-        const unsigned my = cur.my;
-        const unsigned mask = cur.qmask & live;
-        const NodeGeo g = cur.g;
-        const Src4 mom = cur.mom;
-        const NodeLinkB lk = cur.lk;
-#else
     while(sp > 0 && live) {
         if(++guard > guard_max) {
             if(lane == 0)
@@ -572,7 +484,6 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
         const NodeGeo g = ld<O32>(tv.geoB, my);
         const Src4 mom = ld<O32>(tv.momB, my);
         const NodeLinkB lk = ld<O32>(tv.linkB, my);
-#endif
         // fp64 operands of the tests (F32: only the fall-back and the COUNT builds' cross-check use them, from a second read of the node)
         double eff = 0, l2 = 0, inside = 0, ml2 = 0;
         // F32: the node relative to the wave's origin and the normalising factors of its slacks (see F32Wave)
@@ -618,37 +529,15 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
         // appends CHECKED one by one.
         const unsigned long long m_leafnode = __builtin_amdgcn_ballot_w64(lk.pcount > 0);
         const unsigned long long m_intnode = ~m_leafnode & __builtin_amdgcn_ballot_w64(lk.nchild > 0);
-#ifndef MPG_NO_SINGLES_AS_NODES
         // An OPENED leaf of one particle is listed with the nodes (round 4): its moment record is that particle (centre of mass = its position
         // to a rounding, the same softening: apply_accn_to_output treats both alike), and there it shares an evaluation step with 7 other
         // sources instead of taking one alone - 201 M of the 1916 M opened leaves per walk at 256^3 (a cell split at its 9th particle leaves
         // children of one or two).  The decision stays the reference's and is counted as such (a pair interaction, not a node used).
         const unsigned long long m_single = __builtin_amdgcn_ballot_w64(lk.pcount == 1);
-#else
-        const unsigned long long m_single = 0ull;
-#endif
         auto pass = [&](auto checked_tag) {
             constexpr bool CHECKED = decltype(checked_tag)::value;
-#ifdef MPG_LISTS_TGT_PREFETCH
-            // experiment: target t + 1's record is requested before target t's pass (the LDS read's latency under the pass before it)
-            float4 tf_pre[9];
-            if constexpr(F32) {
-                unsigned o0 = 0u;
-                asm volatile("" : "+v"(o0));
-                tf_pre[0] = *(const float4 *)(W.s_tgtf + o0);
-            }
-#endif
 #pragma unroll
             for(int t = 0; t < 8; t++) {
-#ifdef MPG_LISTS_TGT_PREFETCH
-                if constexpr(F32) {
-                    if(t < 7) {
-                        unsigned on = 4u * (t + 1);
-                        asm volatile("" : "+v"(on));
-                        tf_pre[t + 1] = *(const float4 *)(W.s_tgtf + on);
-                    }
-                }
-#endif
                 // (no lane for a target that overflowed, is absent or did not open the parent; measured: 28 % of the passes over a
                 // target find no lane with its bit - the entries popped late in a walk belong to few of the 8 targets)
                 const unsigned long long m_act = __builtin_amdgcn_ballot_w64((mask & (1u << t)) != 0u);
@@ -660,11 +549,7 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
                 asm volatile("" : "+v"(ot));
                 unsigned long long m_discard, m_open, m_wrap;
                 if constexpr(F32) {
-#ifdef MPG_LISTS_TGT_PREFETCH
-                    const float4 tf = tf_pre[t];
-#else
                     const float4 tf = *(const float4 *)(W.s_tgtf + ot);
-#endif
                     const float cdx = Cx - tf.x, cdy = Cy - tf.y, cdz = Cz - tf.z;
                     const float dx = Sx - tf.x, dy = Sy - tf.y, dz = Sz - tf.z;
                     const float cmax = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(cdx), __builtin_fabsf(cdy)), __builtin_fabsf(cdz));
@@ -679,11 +564,7 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
                     m_wrap = 0ull;
                     const unsigned long long m_amb = (__builtin_amdgcn_ballot_w64(!(amb > 1.0f)) | m_nweird) & m_act;
                     const bool redo = m_amb != 0ull || ((W.tweird >> t) & 1u);
-#ifdef MPG_F32_NOEXPECT
-                    if(COUNT || redo) { // (rare: the node again, and the reference's arithmetic)
-#else
                     if(COUNT || __builtin_expect(redo, 0)) { // (rare - out of line: the node again, and the reference's arithmetic)
-#endif
                         unsigned my2 = my;
                         asm volatile("" : "+v"(my2));
                         const NodeGeo g2 = ld<O32>(tv.geoB, my2);
@@ -736,10 +617,6 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
                     T.c_vis[t] += (unsigned)__builtin_popcountll(m_act);
                     T.c_used[t] += (unsigned)__builtin_popcountll(bn0);
                     c_pp[t] += __builtin_amdgcn_inverse_ballot_w64(bl0) ? (unsigned)lk.pcount : 0u;
-#ifdef MPG_LEAF_HIST // experiment: opened leaves by particle count
-                    if(__builtin_amdgcn_inverse_ballot_w64(bl))
-                        atomicAdd(&g_leaf_hist[lk.pcount], 1ull);
-#endif
                 }
                 // (the 8 targets' tests are independent: left alone, hipcc interleaves them and runs out of registers)
                 __builtin_amdgcn_sched_barrier(0);
@@ -751,11 +628,6 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
             pass(std::false_type{});
         if(!push_children(openmask != 0u, lk, openmask))
             break;
-#ifdef MPG_LISTS_PREFETCH
-        if(nxt.n == 0 && sp > 0)
-            pop(nxt); // nothing waited below: on with what this batch pushed
-        cur = nxt;
-#endif
     }
     wrapped = wmask != 0ull;
     return true;
@@ -763,7 +635,7 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
 
 // one wave = one chunk of k_walk_eval (8 consecutive targets)
 template <bool COUNT, bool FASTWRAP, bool O32, bool F32>
-__global__ void __launch_bounds__(256, MPG_LIST_BLOCKS) k_walk_lists8(const TreeView tv, const GravParams gp, const WalkIO io, unsigned *__restrict__ lists,
+__global__ void __launch_bounds__(256, LIST_BLOCKS) k_walk_lists8(const TreeView tv, const GravParams gp, const WalkIO io, unsigned *__restrict__ lists,
                                                       int2 *__restrict__ counts, const int cap, const int64_t slot0, const int64_t nslots,
                                                       unsigned *__restrict__ ctl, int *__restrict__ ovf)
 {
@@ -771,11 +643,6 @@ __global__ void __launch_bounds__(256, MPG_LIST_BLOCKS) k_walk_lists8(const Tree
     __shared__ unsigned char s_qmask[4 * QCAP];
     __shared__ __attribute__((aligned(32))) double s_tgt4[4 * 8 * 4];
     __shared__ __attribute__((aligned(16))) float s_tgtf4[F32 ? 4 * 8 * 4 : 4];
-#ifdef MPG_EXP_LDSPAD_LISTS // timing experiment: fewer resident blocks per CU with the same code (bytes of unused LDS)
-    __shared__ unsigned s_pad[MPG_EXP_LDSPAD_LISTS / 4];
-    if(gp.box < 0)
-        s_pad[threadIdx.x] = 1u, s_qnode[0] = s_pad[(threadIdx.x + 1) & 255];
-#endif
     set_wave_prio(io.list_prio);
     const int lane = threadIdx.x & 63;
     unsigned *q_node = s_qnode + (threadIdx.x >> 6) * QCAP;
@@ -964,7 +831,7 @@ __device__ __forceinline__ void eval_lists(const TreeView &tv, const GravParams 
     // the leaf's count nor a select for the lanes beyond it is needed (rounds 3-5 read tv.src[first + s] with the count in the entry's low
     // bits: v_and, v_and, v_lshl_add, v_cmp, v_cndmask per pair step where this form is one v_lshl_add)
     const unsigned s32 = (unsigned)s * 32u;
-#define MPG_LOAD_REAL(EJ, SV)                                                                   \
+#define MPG_LOAD(EJ, SV)                                                                        \
     {                                                                                           \
         const unsigned ej_ = (EJ);                                                              \
         if(O32)                                                                                 \
@@ -972,11 +839,6 @@ __device__ __forceinline__ void eval_lists(const TreeView &tv, const GravParams 
         else                                                                                    \
             SV = tv.srcL[(size_t)ej_ * 8 + (size_t)s];                                          \
     }
-#ifdef MPG_EXP_NOLOAD // timing experiment (wrong results): the leaf loop keeps the records it started with - no load, no other instruction
-#define MPG_LOAD(EJ, SV) asm volatile("" : "+v"(SV.x), "+v"(SV.y), "+v"(SV.z), "+v"(SV.m) : "v"(EJ))
-#else
-#define MPG_LOAD(EJ, SV) MPG_LOAD_REAL(EJ, SV)
-#endif
 #define MPG_EVAL(SV)                                                              \
     {                                                                             \
         __builtin_amdgcn_sched_barrier(0);                                        \
@@ -991,7 +853,7 @@ __device__ __forceinline__ void eval_lists(const TreeView &tv, const GravParams 
         __builtin_amdgcn_sched_barrier(0);                                        \
     }
     {
-        // two source buffers (A, B) used alternately: while one pair is evaluated the other buffer's load is in flight.  The
+        // three source buffers (A, B, Cq) in rotation: while one pair is evaluated the other two buffers' loads are in flight.  The
         // stage loop is deliberately not unrolled beyond that: every unrolled stage carries its own copy of the (rare)
         // softened branch, and those copies are what drives register pressure and code size.
         // index of leaf entry e0 + s (e0 a multiple of 8)
@@ -1005,10 +867,7 @@ __device__ __forceinline__ void eval_lists(const TreeView &tv, const GravParams 
         __builtin_amdgcn_wave_barrier();
         unsigned eb = ring_g[1];
         Src4 A, B;
-        MPG_LOAD_REAL(ring_g[0], A);
-#if defined(MPG_EXP_NOLOAD) || !defined(MPG_EVAL_PF2)
-        B = A;
-#endif
+        MPG_LOAD(ring_g[0], A);
         // ONE loop over pairs of entries up to the longest leaf list of the wave's 8 targets (a loop over batches around a loop over
         // the pairs of a batch made hipcc copy the four accumulators out and back at every batch: 8 v_mov_b64 per 8 pair steps; and
         // whole batches ran up to 6 pair steps beyond the longest list)
@@ -1016,58 +875,10 @@ __device__ __forceinline__ void eval_lists(const TreeView &tv, const GravParams 
         for(int off = 8; off < 64; off <<= 1)
             wmax = max(wmax, __shfl_xor(wmax, off));
         wmax = __builtin_amdgcn_readfirstlane(wmax);
-#ifdef MPG_EVAL_ILP2
-        // Round 5 experiment (measured: 38.2 against 35.9 ms per evaluation at 256^3, removed from the default): the two pairs of a trip
-        // side by side up to the softening test, one branch for both, then their table parts side by side.  The kernel's time falls with
-        // the resident waves (2 / 3 / 4 per SIMD: 52.8 / 41.3 / 36.1 ms), but what the waves hide is the latency of the source loads, not of
-        // the dependent arithmetic: here both records of a trip are needed at its start and are requested only after the previous
-        // trip's first half, i.e. closer to their use than in the alternating form below.
-        MPG_LOAD(eb, B);
-        const double h2 = gp.h2;
-#pragma unroll 1
-        for(int e = 0; e < wmax; e += 2) {
-            if((e & 7) == 0) {
-                ring_g[((e + 8) & 8) + s] = ent_n;
-                ent_n = (e + 16 + s < nleaf) ? ld<true>(L, MPG_LEAF_AT(e + 16)) : empty;
-                __builtin_amdgcn_wave_barrier();
-            }
-            const unsigned *__restrict__ rr = ring_g + ((e + 2) & 15);
-            const unsigned ea = rr[0];
-            eb = rr[1];
-            __builtin_amdgcn_sched_barrier(0);
-            PairTmp ta, tb;
-            {
-                double dx_ = A.x - px, dy_ = A.y - py, dz_ = A.z - pz;
-                double ex_ = B.x - px, ey_ = B.y - py, ez_ = B.z - pz;
-                if(WRAP) {
-                    dx_ = nearest_img(dx_, gp.box, gp.invbox);
-                    dy_ = nearest_img(dy_, gp.box, gp.invbox);
-                    dz_ = nearest_img(dz_, gp.box, gp.invbox);
-                    ex_ = nearest_img(ex_, gp.box, gp.invbox);
-                    ey_ = nearest_img(ey_, gp.box, gp.invbox);
-                    ez_ = nearest_img(ez_, gp.box, gp.invbox);
-                }
-                pair_pre(A, dx_, dy_, dz_, ta);
-                pair_pre(B, ex_, ey_, ez_, tb);
-            }
-            MPG_LOAD(ea, A);
-            MPG_LOAD(eb, B);
-            if((ta.r2 < h2) | (tb.r2 < h2)) { // rare: one branch for both pairs
-                if(ta.r2 < h2)
-                    pair_soft(gp, ta);
-                if(tb.r2 < h2)
-                    pair_soft(gp, tb);
-            }
-            pair_post<POT>(ta, gp, s_wtab, ax, ay, az, pot);
-            pair_post<POT>(tb, gp, s_wtab, ax, ay, az, pot);
-            asm volatile("" : "+v"(ax), "+v"(ay), "+v"(az), "+v"(pot));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#elif !defined(MPG_EVAL_PF2)
         // three source buffers: every record is requested TWO pair evaluations ahead of its use (rounds 1-5 alternated two buffers, one
-        // evaluation ahead - kept under MPG_EVAL_PF2: 36.1 - 36.4 against 34.6 ms per evaluation at 256^3 on one box; the kernel's time falls
-        // with the resident waves - 2 / 3 / 4 per SIMD: 52.8 / 41.3 / 36.1 ms - and what the waves hide is the latency of these loads:
-        // without them, MPG_EXP_NOLOAD, the evaluation of a fixed set of lists takes 20.3 instead of 24.5 ms)
+        // evaluation ahead: 36.1 - 36.4 against 34.6 ms per evaluation at 256^3 on one box; the kernel's time falls with the resident waves
+        // - 2 / 3 / 4 per SIMD: 52.8 / 41.3 / 36.1 ms - and what the waves hide is the latency of these loads: without them the evaluation of
+        // a fixed set of lists takes 20.3 instead of 24.5 ms)
         Src4 Cq = A;
         MPG_LOAD(eb, B);
         int staged = 1; // batches of 8 entries written to the ring so far (batch `staged` is in flight in ent_n)
@@ -1087,25 +898,6 @@ __device__ __forceinline__ void eval_lists(const TreeView &tv, const GravParams 
             MPG_LOAD(e4, B);
             MPG_EVAL(Cq);
         }
-#else
-#pragma unroll 1
-        for(int e = 0; e < wmax; e += 2) {
-            if((e & 7) == 0) { // (wave-uniform) the next batch into the other half of the ring - its first entry is read in the
-                               // last stage of this batch -, the one after that requested
-                ring_g[((e + 8) & 8) + s] = ent_n;
-                ent_n = (e + 16 + s < nleaf) ? ld<true>(L, MPG_LEAF_AT(e + 16)) : empty;
-                __builtin_amdgcn_wave_barrier();
-            }
-            MPG_LOAD(eb, B);
-            // entries e + 2 (the next A) and e + 3 (the next B): one ds_read2_b32, back before the evaluation of A ends
-            const unsigned *__restrict__ rr = ring_g + ((e + 2) & 15);
-            const unsigned ea = rr[0];
-            eb = rr[1];
-            MPG_EVAL(A);
-            MPG_LOAD(ea, A);
-            MPG_EVAL(B);
-        }
-#endif
     }
     // ---- node entries (level-order indices): lane s takes entry r0 + s; entries two batches ahead, moments one
     if(any_lane(nnode > 0)) {
@@ -1113,20 +905,6 @@ __device__ __forceinline__ void eval_lists(const TreeView &tv, const GravParams 
         // index of node entry r0 + s counted from the top of the list (r0 a multiple of 8)
         const unsigned top = (unsigned)((gshift >> 3) * cap + cap - 1 - s);
 #define MPG_NODE_AT(R0) (top - (unsigned)(R0))
-#ifdef MPG_EVAL_PF2
-        unsigned ne = (s < nnode) ? ld<true>(L, MPG_NODE_AT(0)) : NONE;
-        unsigned ne_n = (8 + s < nnode) ? ld<true>(L, MPG_NODE_AT(8)) : NONE;
-        Src4 sc = ld<O32>(tv.momB, ne);
-        for(int r0 = 0;; r0 += 8) {
-            if(!any_lane(r0 < nnode))
-                break;
-            ne = ne_n;
-            ne_n = (r0 + 16 + s < nnode) ? ld<true>(L, MPG_NODE_AT(r0 + 16)) : NONE;
-            const Src4 sc_n = ld<O32>(tv.momB, ne);
-            MPG_EVAL(sc);
-            sc = sc_n;
-        }
-#else
         // three moment buffers in rotation (no register copies): the moments of a batch are requested two evaluations ahead of their use,
         // its entries three evaluations before that
 #define MPG_NODE_ENT(R0) (((R0) + s < nnode) ? ld<true>(L, MPG_NODE_AT(R0)) : NONE)
@@ -1153,10 +931,8 @@ __device__ __forceinline__ void eval_lists(const TreeView &tv, const GravParams 
             MPG_EVAL(Sc);
         }
 #undef MPG_NODE_ENT
-#endif
     }
 #undef MPG_LOAD
-#undef MPG_LOAD_REAL
 #undef MPG_EVAL
 #undef MPG_LEAF_AT
 #undef MPG_NODE_AT
@@ -1171,18 +947,13 @@ __device__ __attribute__((noinline)) double potential_postprocess(double pot, co
     return pot * G;
 }
 
-template <bool POT, bool FASTWRAP, bool O32, int BLK>
-__global__ void __launch_bounds__(256, BLK) k_walk_eval(const TreeView tv, const GravParams gp, const WalkIO io, const unsigned *__restrict__ lists,
+template <bool POT, bool FASTWRAP, bool O32>
+__global__ void __launch_bounds__(256, EVAL_BLOCKS) k_walk_eval(const TreeView tv, const GravParams gp, const WalkIO io, const unsigned *__restrict__ lists,
                                                     const int2 *__restrict__ counts, const int cap, const int64_t slot0, const int64_t nslots)
 {
     constexpr int ROW = POT ? 4 : 2;
     __shared__ __attribute__((aligned(16))) double s_wtab[NTAB * ROW];
     __shared__ unsigned s_ring[4 * 8 * RING_STRIDE]; // per wave and group: two batches of leaf entries (eval_lists)
-#ifdef MPG_EXP_LDSPAD // timing experiment: fewer resident blocks per CU with the same code (bytes of unused LDS)
-    __shared__ unsigned s_pad[MPG_EXP_LDSPAD / 4];
-    if(gp.box < 0)
-        s_pad[threadIdx.x] = 1u, s_ring[0] = s_pad[(threadIdx.x + 1) & 255];
-#endif
     set_wave_prio(io.eval_prio);
     for(int i = threadIdx.x; i < NTAB; i += blockDim.x) {
         const bool last = i == NTAB - 1; // the row the clamp lands on: zeros
@@ -1192,11 +963,6 @@ __global__ void __launch_bounds__(256, BLK) k_walk_eval(const TreeView tv, const
             s_wtab[2 * NTAB + i * 2 + 0] = last ? 0.0 : (double)io.tab_pot[i];
             s_wtab[2 * NTAB + i * 2 + 1] = last ? 0.0 : (double)io.tab_pot[i + 1] - (double)io.tab_pot[i];
         }
-#ifdef MPG_TAB_AFFINE
-        s_wtab[i * 2 + 0] -= (double)i * s_wtab[i * 2 + 1];
-        if(POT)
-            s_wtab[2 * NTAB + i * 2 + 0] -= (double)i * s_wtab[2 * NTAB + i * 2 + 1];
-#endif
     }
     __syncthreads();
 
@@ -1294,10 +1060,7 @@ void launch_split_t(const TreeView &tv, const GravParams &gp, const WalkIO &io, 
     const bool f32_env = f32_e && f32_e[0] == '1';
     const bool f32 = FASTWRAP && f32_env && gp.bhangle2 > 1e-6 && gp.bhangle2 < 1e6 && gp.rcut > 1e-12 && gp.rcut < 1e12 && gp.box < 1e12;
     auto kl = (FASTWRAP && f32) ? k_walk_lists8<COUNT, FASTWRAP, O32, FASTWRAP> : k_walk_lists8<COUNT, FASTWRAP, O32, false>;
-    // 4 resident blocks per CU (128 registers, hardly a spill) where the lists are short - the evaluation is then bound by instruction issue -
-    // and 6 (80 registers) where they are long (a clustered set: the list capacity has grown to >= 4096 entries), where it waits for memory and
-    // the waves count: 256^3 clustered 148 -> 127 ms per walk with 6, Zel'dovich 69.2 -> 67.7 with 4
-    auto ke = ws.split_cap >= 4096 ? k_walk_eval<POT, FASTWRAP, O32, MPG_EVAL_BLOCKS_LONG> : k_walk_eval<POT, FASTWRAP, O32, MPG_EVAL_BLOCKS>;
+    auto ke = k_walk_eval<POT, FASTWRAP, O32>;
     if(const char *e = getenv("MPG_LIST_CAP")) // experiment knob
         ws.split_cap = atoi(e) / 8 * 8;
     const int cap = ws.split_cap;
@@ -1391,8 +1154,8 @@ void launch_split_t(const TreeView &tv, const GravParams &gp, const WalkIO &io, 
 
 } // namespace
 
-void launch_grav_walk_split(const TreeView &tv, const GravParams &gp, const WalkIO &io, bool want_pot, bool count, bool fastwrap, int thresh,
-                            WalkScratch &ws, hipStream_t st)
+void launch_grav_walk_split(const TreeView &tv, const GravParams &gp, const WalkIO &io, bool want_pot, bool count, bool fastwrap, WalkScratch &ws,
+                            hipStream_t st)
 {
     if(io.ntargets == 0)
         return;
@@ -1430,18 +1193,6 @@ void launch_grav_walk_split(const TreeView &tv, const GravParams &gp, const Walk
         MPG_HIP(hipMemcpyAsync(ctl, ws.ctr.p, sizeof(ctl), hipMemcpyDeviceToHost, st));
         MPG_HIP(hipStreamSynchronize(st));
         MPG_CHECK(ctl[1] == 0, "short-range walk (list construction) aborted by its loop guard (corrupt tree?)");
-#ifdef MPG_LEAF_HIST
-        if(count) {
-            unsigned long long h[16];
-            MPG_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_leaf_hist), sizeof(h)));
-            fprintf(stderr, "LEAF_HIST targets %lld opened leaves by count 1..8:", (long long)io.ntargets);
-            for(int k = 1; k <= 8; k++)
-                fprintf(stderr, " %llu", h[k]);
-            fprintf(stderr, "\n");
-            memset(h, 0, sizeof(h));
-            MPG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_leaf_hist), h, sizeof(h)));
-        }
-#endif
         // More than a fifth of the targets did not fit their lists (the first walk of a clustered set with the initial capacity):
         // walking them all with the fallback kernel costs seconds (256^3 clustered set: 3.3 s), a second pass of this kernel with
         // four times the capacity a fraction of one.  (Not when the interaction counters are on: they would count twice.)
@@ -1465,12 +1216,8 @@ void launch_grav_walk_split(const TreeView &tv, const GravParams &gp, const Walk
         // The targets that overflow are the heaviest ones (a dense clump's core: tens of thousands of entries each).  The
         // cooperative kernel drains its lists in place and keeps 8 lanes busy per target; the lane-per-target kernel took
         // 115 ms for the 20 000 such targets of the 128^3 clustered test set, this takes a fraction of that.
-        if(getenv("MPG_SPLIT_FALLBACK_LANE"))
-            launch_grav_walk(tv, gp, io2, want_pot, count, fastwrap, thresh, st);
-        else {
-            launch_grav_walk_coop(tv, gp, io2, want_pot, count, fastwrap, ws, st);
-            MPG_CHECK(walk_coop_error(ws, st) == 0, "short-range walk (fallback for long lists) aborted by its loop guard");
-        }
+        launch_grav_walk_coop(tv, gp, io2, want_pot, count, fastwrap, ws, st);
+        MPG_CHECK(walk_coop_error(ws, st) == 0, "short-range walk (fallback for long lists) aborted by its loop guard");
         if((int64_t)ctl[0] * 50 > io.ntargets && ws.split_cap < 8192) {
             ws.split_cap *= 2; // more than 2 % of the targets overflowed: give the next walk longer lists
             if((int64_t)ctl[0] * 5 > io.ntargets && ws.split_cap < 8192)

@@ -116,7 +116,7 @@ struct TreeView {
     // around the PARTICLES it holds instead of its cell, and the largest smoothing length among them
     const NodeGeo *geoS = nullptr;
     const double *hsmaxS = nullptr;
-    // search links of the SPH loops (TreeBuilder::calc_search_links), or null: linkB with the small internal nodes as leaves
+    // always null: the SPH searches' own links are removed; the member keeps the argument layout of every kernel that takes a TreeView
     const NodeLinkB *linkS = nullptr;
     // the leaves' particles in blocks of 8 records by level-order node number, zero-mass filled (TreeBuilder::ensure_leaf_pad), or null
     const Src4 *srcL = nullptr;

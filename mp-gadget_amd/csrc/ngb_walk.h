@@ -27,40 +27,11 @@ __device__ __forceinline__ bool interior_wave(const bool valid, const double px,
     return ballot64(out) == 0ull;
 }
 
-// cull_node, treewalk.c:1015-1042 (hm = 0: asymmetric search radius Hsml; symmetric: max(node hmax, Hsml))
-template <bool WRAP = true>
-__device__ __forceinline__ bool cull_node(const NodeGeo &g, double hm, double hsml, double px, double py, double pz, double box, double invbox)
-{
-#ifdef NGB_CULL_BRANCHY // (the reference's form, with its early returns: experiment switch)
-    double dist = fmax(hm, hsml) + 0.5 * g.len;
-    const double dx = near_img<WRAP>(g.cx - px, box, invbox);
-    if(dx > dist || dx < -dist)
-        return true;
-    const double dy = near_img<WRAP>(g.cy - py, box, invbox);
-    if(dy > dist || dy < -dist)
-        return true;
-    const double dz = near_img<WRAP>(g.cz - pz, box, invbox);
-    if(dz > dist || dz < -dist)
-        return true;
-    const double r2 = dx * dx + dy * dy + dz * dz;
-    dist += FACT1 * g.len;
-    return r2 > dist * dist;
-#else
-    // (without the early returns of the reference: |d| > dist on any axis is max |d| > dist, and the wave's lanes never agree on an exit)
-    const double dist = fmax(hm, hsml) + 0.5 * g.len;
-    const double dx = near_img<WRAP>(g.cx - px, box, invbox);
-    const double dy = near_img<WRAP>(g.cy - py, box, invbox);
-    const double dz = near_img<WRAP>(g.cz - pz, box, invbox);
-    const double cmax = fmax(fmax(fabs(dx), fabs(dy)), fabs(dz));
-    const double r2 = dx * dx + dy * dy + dz * dz;
-    const double d2 = dist + FACT1 * g.len;
-    return (cmax > dist) | (r2 > d2 * d2);
-#endif
-}
-
-// The same test with its two comparisons taken as lane masks (walk_stepk): the ballot of a bare comparison is the comparison's own result
-// register, and the boolean algebra of the step runs once per wave on the scalar unit (as in k_walk_lists8).  Written with per-lane
-// booleans, hipcc materialised every `a && b` that went into a ballot as v_cndmask 0/1 + v_cmp again.
+// cull_node, treewalk.c:1015-1042 (hm = 0: asymmetric search radius Hsml; symmetric: max(node hmax, Hsml)), without the reference's early
+// returns (|d| > dist on any axis is max |d| > dist, and the wave's lanes never agree on an exit) and with its two comparisons taken as lane
+// masks (walk_stepk): the ballot of a bare comparison is the comparison's own result register, and the boolean algebra of the step runs once
+// per wave on the scalar unit (as in k_walk_lists8).  Written with per-lane booleans, hipcc materialised every `a && b` that went into a ballot
+// as v_cndmask 0/1 + v_cmp again.
 template <bool WRAP>
 __device__ __forceinline__ unsigned long long cull_mask(const NodeGeo &g, double hm, double hsml, double px, double py, double pz, double box, double invbox)
 {
@@ -113,16 +84,11 @@ __device__ __forceinline__ double group_sum(double v)
 // sgeo / shm: the geometry the cull tests and, for SYM, the radius per node - the nodes' cells and `hmax` as in the reference (tv.geoB,
 // tv.hmaxB: FOF, the pair-wise gravity check), or the cubes around the nodes' particles and their largest Hsml (tv.geoS, tv.hsmaxS: the
 // SPH loops; TreeBuilder::calc_search_boxes).
-// slink / NE (round 5): the links the search follows - tv.linkB, or the SEARCH links (tv.linkS, TreeBuilder::calc_search_links) in which an
-// internal node of <= 8 NE particles is a leaf of its whole particle range; such a leaf goes to the list as up to NE runs of <= 8.
-template <bool SYM, int K, bool MERGE = false, bool WRAP = true, int NE = 1>
+template <bool SYM, int K, bool MERGE = false, bool WRAP = true>
 __device__ __forceinline__ int walk_stepk(const TreeView &tv, const NodeGeo *__restrict__ sgeo, const double *__restrict__ shm, unsigned *stack, int &sp,
                                           const bool valid_more, const int s, const int gshift, const double hsml, const double px, const double py,
-                                          const double pz, unsigned *llist, int nl, bool &overflow, const NodeLinkB *__restrict__ slink = nullptr)
+                                          const double pz, unsigned *llist, int nl, bool &overflow)
 {
-    static_assert(NE == 1 || NE == 2 || NE == 4, "runs per search leaf");
-    if(NE == 1 || slink == nullptr)
-        slink = tv.linkB;
     const bool can = valid_more;
     const double invbox = 1.0 / tv.box;
     const unsigned below = (1u << s) - 1u;
@@ -144,68 +110,32 @@ __device__ __forceinline__ int walk_stepk(const TreeView &tv, const NodeGeo *__r
 #pragma unroll
     for(int k = 0; k < K; k++) {
         g[k] = sgeo[my[k]];
-        lk[k] = slink[my[k]];
+        lk[k] = tv.linkB[my[k]];
         hm[k] = SYM ? shm[my[k]] : 0.0;
     }
     unsigned gl[K], gp[K], ent[K];
-    unsigned pcn[K], gx[K][NE > 1 ? NE - 1 : 1]; // NE > 1: particles this lane lists; the group's lanes that list >= 2, >= 3, >= 4 runs
-    unsigned long long m_x[K][NE > 1 ? NE - 1 : 1];
     unsigned long long m_leaf[K], m_push[K]; // lane masks: the children opened as leaves / whose own children are pushed
 #pragma unroll
     for(int k = 0; k < K; k++) {
-#ifndef NGB_NO_MASKS
         const unsigned long long m_in = __builtin_amdgcn_ballot_w64(tst[k]) & ~cull_mask<WRAP>(g[k], hm[k], hsml, px, py, pz, tv.box, invbox);
         const unsigned long long m_pc = __builtin_amdgcn_ballot_w64(lk[k].pcount > 0);
         m_leaf[k] = m_in & m_pc;
         m_push[k] = m_in & ~m_pc & __builtin_amdgcn_ballot_w64(lk[k].nchild > 0);
-#else // (experiment switch: per-lane booleans, as until round 4)
-        const bool in = tst[k] && !cull_node<WRAP>(g[k], hm[k], hsml, px, py, pz, tv.box, invbox);
-        m_leaf[k] = ballot64(in && lk[k].pcount > 0);
-        m_push[k] = ballot64(in && lk[k].pcount <= 0 && lk[k].nchild > 0);
-#endif
         ent[k] = ((unsigned)lk[k].pstart << 4) | (unsigned)lk[k].pcount;
         if(MERGE) {
             const bool lf = __builtin_amdgcn_inverse_ballot_w64(m_leaf[k]);
             unsigned pcm = lf ? (unsigned)lk[k].pcount : 0u;
-#ifdef NGB_MERGE_ANY_OPENED
-            // Round 5 experiment (measured, no gain - profiles/r05a_experiments): a set is joined as soon as the target opened ANY leaf of it, its first lane emitting the whole run - whether or not
-            // that lane's own leaf was opened.  One list entry is one test iteration of 8 lanes whatever it holds, so the particles of the
-            // set's other leaves ride along on lanes that would idle (they fail the distance test: their leaf was culled), while a set
-            // opened in part is one entry instead of one per opened leaf.  (The default joins a set only when ALL its existing leaves were
-            // opened, which the tighter cull on the particles' cubes makes rarer.)
-            const bool isleaf = tst[k] && lk[k].pcount > 0;
-            const unsigned h = isleaf ? (unsigned)lk[k].firstchild : 0u;              // (a leaf's merge hints: NodeLinkB)
-            const unsigned m = (unsigned)((m_leaf[k] >> gshift) & 0xffull);           // the children this target opened as leaves
-            const unsigned sq = (h >> 4) & 15u, sp = h & 15u;
-            pcm = (sp != 0u && (m & (3u << (s & 6))) != 0u) ? ((s & 1) == 0 ? sp : 0u) : pcm;
-            pcm = (sq != 0u && (m & (15u << (s & 4))) != 0u) ? ((s & 3) == 0 ? sq : 0u) : pcm;
-#else
             const unsigned h = lf ? (unsigned)lk[k].firstchild : 0u;                  // (a leaf's merge hints: NodeLinkB)
             const unsigned m = (unsigned)((m_leaf[k] >> gshift) & 0xffull);           // the children this target opened as leaves
             const unsigned x = m ^ ((1u << (r[k] & 15u)) - 1u);                       // existing children that are not among them
             const unsigned sq = (h >> 4) & 15u, sp = h & 15u;
             pcm = (sp != 0u && (x & (3u << (s & 6))) == 0u) ? ((s & 1) == 0 ? sp : 0u) : pcm;
             pcm = (sq != 0u && (x & (15u << (s & 4))) == 0u) ? ((s & 3) == 0 ? sq : 0u) : pcm;
-#ifdef NGB_MERGE_OCT // (all children as one run: cannot occur in a tree whose cells are split at their 9th particle)
-            pcm = (((h >> 8) & 15u) != 0u && x == 0u) ? (s == 0 ? ((h >> 8) & 15u) : 0u) : pcm;
-#endif
-#endif
-            ent[k] = ((unsigned)lk[k].pstart << 4) | (NE > 1 ? min(pcm, 8u) : pcm);
+            ent[k] = ((unsigned)lk[k].pstart << 4) | pcm;
             m_leaf[k] = __builtin_amdgcn_ballot_w64(pcm != 0u);
-            pcn[k] = pcm;
         }
-        else
-            pcn[k] = (unsigned)lk[k].pcount;
         gl[k] = (unsigned)((m_leaf[k] >> gshift) & 0xffull);
         gp[k] = (unsigned)((m_push[k] >> gshift) & 0xffull);
-        if(NE > 1) {
-            static_assert(NE == 1 || MERGE, "runs per search leaf: the merging form only");
-#pragma unroll
-            for(int e = 1; e < NE; e++) { // (pcn is 0 on the lanes that list nothing)
-                m_x[k][e - 1] = __builtin_amdgcn_ballot_w64(pcn[k] > 8u * (unsigned)e);
-                gx[k][e - 1] = (unsigned)((m_x[k][e - 1] >> gshift) & 0xffull);
-            }
-        }
     }
     const int taken = can ? (sp < take ? sp : take) : 0;
     const int base = sp - taken;
@@ -229,27 +159,9 @@ __device__ __forceinline__ int walk_stepk(const TreeView &tv, const NodeGeo *__r
         sp = base + npush;
 #pragma unroll
     for(int k = 0; k < K; k++) {
-        if(NE == 1) {
-            if(__builtin_amdgcn_inverse_ballot_w64(m_leaf[k]))
-                llist[nl + __popc(gl[k] & below)] = ent[k];
-            nl += can ? __popc(gl[k]) : 0;
-        }
-        else {
-            // a lane's runs are consecutive list entries; its first one sits behind all runs of the lanes below it
-            int pos = nl + __popc(gl[k] & below), tot = __popc(gl[k]);
-#pragma unroll
-            for(int e = 1; e < NE; e++) {
-                pos += __popc(gx[k][e - 1] & below);
-                tot += __popc(gx[k][e - 1]);
-            }
-            if(__builtin_amdgcn_inverse_ballot_w64(m_leaf[k]))
-                llist[pos] = ent[k];
-#pragma unroll
-            for(int e = 1; e < NE; e++)
-                if(__builtin_amdgcn_inverse_ballot_w64(m_x[k][e - 1]))
-                    llist[pos + e] = (((unsigned)lk[k].pstart + 8u * (unsigned)e) << 4) | min(pcn[k] - 8u * (unsigned)e, 8u);
-            nl += can ? tot : 0;
-        }
+        if(__builtin_amdgcn_inverse_ballot_w64(m_leaf[k]))
+            llist[nl + __popc(gl[k] & below)] = ent[k];
+        nl += can ? __popc(gl[k]) : 0;
     }
     return nl;
 }

@@ -419,95 +419,21 @@ __global__ void __launch_bounds__(256) k_cic_readout(int64_t n, const double *__
         out[i] += acc;
 }
 
-// Force component along `axis` from the potential mesh by the 4-point central difference
+// Forces from the potential mesh by the 4-point central difference
 //     F = -[ 2/3 (phi[+1] - phi[-1]) - 1/12 (phi[+2] - phi[-2]) ] N / Box          (periodic)
 // This IS the reference's force_transfer (gravpm.c:456-489): its Fourier-space factor i * (-diff_kernel(w)) N/Box,
 // diff_kernel(w) = (8 sin w - sin 2w) / 6 ("the same as GADGET-2 but in fourier space: c1 = 2/3, c2 = 1/12"), is the symbol of
 // exactly this stencil, so differencing the potential in real space replaces three of the four inverse transforms (and their
-// transfer sweeps) by three streaming passes; the results differ from the Fourier-space form by rounding only.
-// nplanes / plane0: the x-planes held (all of them on one GPU); for axis 0 in the slab form, planes -2..-1 and P..P+1 are the
-// ghost planes stored around the slab (see slab_gradient).
-__global__ void __launch_bounds__(256) k_gradient_axis(int nmesh, int nplanes, int axis, double scale, const double *__restrict__ phi,
-                                                       double *__restrict__ out, int xghost)
-{
-    const size_t total = (size_t)nplanes * nmesh * nmesh;
-    const size_t ip = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(ip >= total)
-        return;
-    const int iz = (int)(ip % nmesh);
-    const size_t t = ip / nmesh;
-    const int iy = (int)(t % nmesh);
-    const int ix = (int)(t / nmesh);
-    const size_t plane = (size_t)nmesh * nmesh;
-    // phi is stored with `xghost` ghost planes below plane 0 (0 on one GPU, where x wraps periodically instead)
-    const double *c = phi + ((size_t)(ix + xghost) * nmesh + iy) * nmesh + iz;
-    double p1, m1, p2, m2;
-    if(axis == 0) {
-        if(xghost) {
-            p1 = c[plane];
-            m1 = c[-(ptrdiff_t)plane];
-            p2 = c[2 * plane];
-            m2 = c[-2 * (ptrdiff_t)plane];
-        }
-        else {
-            const size_t row = (size_t)iy * nmesh + iz;
-            p1 = phi[(size_t)wrap(ix + 1, nmesh) * plane + row];
-            m1 = phi[(size_t)wrap(ix - 1, nmesh) * plane + row];
-            p2 = phi[(size_t)wrap(ix + 2, nmesh) * plane + row];
-            m2 = phi[(size_t)wrap(ix - 2, nmesh) * plane + row];
-        }
-    }
-    else if(axis == 1) {
-        const double *r = c - (size_t)iy * nmesh;
-        p1 = r[(size_t)wrap(iy + 1, nmesh) * nmesh];
-        m1 = r[(size_t)wrap(iy - 1, nmesh) * nmesh];
-        p2 = r[(size_t)wrap(iy + 2, nmesh) * nmesh];
-        m2 = r[(size_t)wrap(iy - 2, nmesh) * nmesh];
-    }
-    else {
-        const double *r = c - iz;
-        p1 = r[wrap(iz + 1, nmesh)];
-        m1 = r[wrap(iz - 1, nmesh)];
-        p2 = r[wrap(iz + 2, nmesh)];
-        m2 = r[wrap(iz - 2, nmesh)];
-    }
-    out[ip] = -((2.0 / 3.0) * (p1 - m1) - (1.0 / 12.0) * (p2 - m2)) * scale;
-}
-
-// The three force components in ONE pass over the potential (single-GPU form: x wraps periodically): the twelve neighbours of a
-// cell are read once (the z row from registers of neighbouring lanes' cache lines, the y and x neighbours from L2), three meshes
-// are written - 4.3 GB at Nmesh = 512 instead of the 6.4 GB of three k_gradient_axis passes.  Same arithmetic per component.
-__global__ void __launch_bounds__(256) k_gradient3(int nmesh, double scale, const double *__restrict__ phi, double *__restrict__ gx,
-                                                   double *__restrict__ gy, double *__restrict__ gz)
-{
-    const size_t total = (size_t)nmesh * nmesh * nmesh;
-    const size_t ip = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(ip >= total)
-        return;
-    const int iz = (int)(ip % nmesh);
-    const size_t t = ip / nmesh;
-    const int iy = (int)(t % nmesh);
-    const int ix = (int)(t / nmesh);
-    const size_t plane = (size_t)nmesh * nmesh;
-    const size_t row = (size_t)iy * nmesh + iz;
-    const double *px = phi + row;
-    const double *py = phi + (size_t)ix * plane + iz;
-    const double *pz = phi + (size_t)ix * plane + (size_t)iy * nmesh;
-    const double c1 = 2.0 / 3.0, c2 = 1.0 / 12.0;
-    gx[ip] = -(c1 * (px[(size_t)wrap(ix + 1, nmesh) * plane] - px[(size_t)wrap(ix - 1, nmesh) * plane]) -
-               c2 * (px[(size_t)wrap(ix + 2, nmesh) * plane] - px[(size_t)wrap(ix - 2, nmesh) * plane])) * scale;
-    gy[ip] = -(c1 * (py[(size_t)wrap(iy + 1, nmesh) * nmesh] - py[(size_t)wrap(iy - 1, nmesh) * nmesh]) -
-               c2 * (py[(size_t)wrap(iy + 2, nmesh) * nmesh] - py[(size_t)wrap(iy - 2, nmesh) * nmesh])) * scale;
-    gz[ip] = -(c1 * (pz[wrap(iz + 1, nmesh)] - pz[wrap(iz - 1, nmesh)]) - c2 * (pz[wrap(iz + 2, nmesh)] - pz[wrap(iz - 2, nmesh)])) * scale;
-}
-
+// transfer sweeps); the results differ from the Fourier-space form by rounding only.
+//
 // readout_potential + readout_force_x/y/z (gravpm.c:491-510, petapm.c:1106-1144) in ONE pass without force meshes (round 4): the force at
-// a CIC corner is the 4-point difference of the potential there (k_gradient_axis above: the reference's force_transfer in real space), so
+// a CIC corner is the 4-point difference of the potential there (above: the reference's force_transfer in real space), so
 // a particle gathers, per corner, the potential and its 12 stencil neighbours straight from the potential mesh and differences on the
 // fly.  104 gathers per particle instead of 32 - but from ONE mesh, with the z neighbours in the same cache line and the lanes of a wave
 // (particles come in some spatial order: Peano-Hilbert after a domain decomposition, lattice order in initial conditions) sharing lines -
 // and the gradient pass with its 3 x Nmesh^3 stores (4.3 GB moved at Nmesh = 512) is gone: gradient 1.5 ms + four read-outs 1.6 ms ->
-// 1.2 ms at 256^3 / 512^3, PM 9.9 -> 7.9 ms.  Same stencil expression, weights and corner order as k_gradient3 + k_cic_readout.
+// 1.2 ms at 256^3 / 512^3, PM 9.9 -> 7.9 ms.  Same weights and corner order as k_cic_readout.  (The force meshes and four read-out passes
+// of rounds 2-3 are removed: DESIGN.md 3.3.)
 // (Measured against it and not kept, profiles/r04a_experiments: the potential staged in LDS tiles of 16^3 cells + halo, 74 KB per block,
 // with the particles grouped by tile first - 2.0 ms + 0.5 ms for the grouping; the same gathers in tile order - 1.6 + 0.5 ms.)
 __global__ void __launch_bounds__(256) k_cic_readout_stencil(int64_t n, const double *__restrict__ pos, const uint8_t *__restrict__ active,
@@ -586,24 +512,12 @@ void PMesh::init(double BoxSize, double Asmth_, int Nmesh_, double G_, hipStream
 }
 
 // ---- rocFFT plans (petapm.c:284-357 builds its PFFT plans here) ------------------------------------------------------------------
-void FftPlan::create(rocfft_result_placement placement, rocfft_transform_type type, int dims, const size_t *lengths, size_t batch,
-                     const size_t *in_strides, size_t in_dist, const size_t *out_strides, size_t out_dist)
+void FftPlan::create(rocfft_result_placement placement, rocfft_transform_type type, int dims, const size_t *lengths, size_t batch)
 {
     static const bool once = (rocfft_setup(), true);
     (void)once;
     destroy();
-    rocfft_plan_description desc = nullptr;
-    if(in_strides || out_strides) {
-        MPG_FFT(rocfft_plan_description_create(&desc));
-        const bool real_fwd = type == rocfft_transform_type_real_forward, real_inv = type == rocfft_transform_type_real_inverse;
-        const rocfft_array_type in_t = real_fwd ? rocfft_array_type_real : (real_inv ? rocfft_array_type_hermitian_interleaved : rocfft_array_type_complex_interleaved);
-        const rocfft_array_type out_t = real_fwd ? rocfft_array_type_hermitian_interleaved : (real_inv ? rocfft_array_type_real : rocfft_array_type_complex_interleaved);
-        MPG_FFT(rocfft_plan_description_set_data_layout(desc, in_t, out_t, nullptr, nullptr, in_strides ? (size_t)dims : 0, in_strides, in_dist,
-                                                        out_strides ? (size_t)dims : 0, out_strides, out_dist));
-    }
-    MPG_FFT(rocfft_plan_create(&plan, placement, type, rocfft_precision_double, (size_t)dims, lengths, batch, desc));
-    if(desc)
-        MPG_FFT(rocfft_plan_description_destroy(desc));
+    MPG_FFT(rocfft_plan_create(&plan, placement, type, rocfft_precision_double, (size_t)dims, lengths, batch, nullptr));
     MPG_FFT(rocfft_execution_info_create(&info));
     size_t wb = 0;
     MPG_FFT(rocfft_plan_get_work_buffer_size(plan, &wb));
@@ -749,7 +663,6 @@ void PMesh::destroy()
     real.release();
     rho_k.release();
     work_k.release();
-    grad_z.release();
     if(nu_host)
         (void)hipHostFree(nu_host);
     nu_host = nullptr;
@@ -886,7 +799,7 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
         t_tr += t;
     }
     // functions[] = Potential, ForceX, ForceY, ForceZ (gravpm.c:32-39).  Default: one inverse transform (the potential), the
-    // forces by differencing it in real space (k_gradient_axis: the same operator as force_transfer); kspace_force restores
+    // forces by differencing it in real space (k_cic_readout_stencil: the same operator as force_transfer); kspace_force restores
     // the reference's four inverse transforms.
     if(!kspace_force) {
         plan_c2r.exec(rho_k.p, real.p, st); // rho_k is consumed: it is not needed again
@@ -894,53 +807,13 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
             tm->lap(st, &t);
             t_fft += t;
         }
-        static const bool one_pass = !(getenv("MPG_PM_GRADIENT_PASSES") && getenv("MPG_PM_GRADIENT_PASSES")[0] == '3');
-        static const bool stencil = one_pass && !(getenv("MPG_PM_STENCIL") && getenv("MPG_PM_STENCIL")[0] == '0');
-        if(stencil) { // potential and forces in one read-out pass straight from the potential mesh (k_cic_readout_stencil)
-            if(n > 0)
-                hipLaunchKernelGGL(k_cic_readout_stencil, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_active, cellsize, nmesh, (double)nmesh / box,
-                                   (const double *)real.p, d_gravpm, d_potential);
-            if(tm) {
-                tm->lap(st, &t);
-                t_ro += t;
-            }
-        }
-        else {
-        if(n > 0 && d_potential)
-            hipLaunchKernelGGL(k_cic_readout, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_active, cellsize, nmesh, real.p, 3, d_potential);
+        // potential and forces in one read-out pass straight from the potential mesh (k_cic_readout_stencil)
+        if(n > 0)
+            hipLaunchKernelGGL(k_cic_readout_stencil, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_active, cellsize, nmesh, (double)nmesh / box,
+                               (const double *)real.p, d_gravpm, d_potential);
         if(tm) {
             tm->lap(st, &t);
             t_ro += t;
-        }
-        if(one_pass) { // the Fourier buffers are free now (Z2D consumed rho_k): they hold two of the three force meshes
-            grad_z.reserve(nreal);
-            double *g[3] = {work_k.p, rho_k.p, grad_z.p};
-            hipLaunchKernelGGL(k_gradient3, dim3(nblk(nreal)), dim3(256), 0, st, nmesh, (double)nmesh / box, real.p, g[0], g[1], g[2]);
-            if(tm) {
-                tm->lap(st, &t);
-                t_tr += t;
-            }
-            for(int axis = 0; axis < 3 && n > 0; axis++)
-                hipLaunchKernelGGL(k_cic_readout, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_active, cellsize, nmesh, g[axis], axis, d_gravpm);
-            if(tm) {
-                tm->lap(st, &t);
-                t_ro += t;
-            }
-        }
-        else
-            for(int axis = 0; axis < 3; axis++) {
-                hipLaunchKernelGGL(k_gradient_axis, dim3(nblk(nreal)), dim3(256), 0, st, nmesh, nmesh, axis, (double)nmesh / box, real.p, work_k.p, 0);
-                if(tm) {
-                    tm->lap(st, &t);
-                    t_tr += t;
-                }
-                if(n > 0)
-                    hipLaunchKernelGGL(k_cic_readout, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_active, cellsize, nmesh, work_k.p, axis, d_gravpm);
-                if(tm) {
-                    tm->lap(st, &t);
-                    t_ro += t;
-                }
-            }
         }
     }
     else
@@ -993,7 +866,7 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
 //               c2c -> tiled transpose back to [x][ky local][kz] (the block for rank d, its x-planes, is contiguous)  [sendB]
 //   all-to-all (caller)                                                                               [recvB]
 //   inverse_c : unpack to [x local][ky][kz] -> 2-D c2r -> the potential slab; its first 3 / last 2 planes out as ghosts [ghost_send]
-//   neighbour exchange (caller) -> readout: forces by differencing the potential (k_gradient_axis), CIC readout.
+//   neighbour exchange (caller) -> readout: forces by differencing the potential during the CIC readout (k_cic_readout_slab_stencil).
 // rocFFT transforms are unnormalised like PFFT's; the three 1-D stages compose to the same 3-D DFT.
 
 __global__ void __launch_bounds__(256) k_cic_deposit_slab(int64_t n, const double *__restrict__ pos, const float *__restrict__ mass,
@@ -1069,52 +942,6 @@ __global__ void __launch_bounds__(256) k_slab_unpack_b(int nmesh, int P, int Py,
     C[ip] = recvB[(((size_t)s * P + xl) * Py + yl) * nz + iz];
 }
 
-// readout for a list of targets whose base cell lies in the slab; plane P of the slab is the ghost (first plane of the next rank)
-__global__ void __launch_bounds__(256) k_cic_readout_slab(int64_t nt, const int *__restrict__ targets, const double *__restrict__ pos,
-                                                          double cellsize, int nmesh, int x0, int P, const double *__restrict__ slab, int comp,
-                                                          double *__restrict__ out, unsigned *__restrict__ err)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(t >= nt)
-        return;
-    const int64_t i = targets[t];
-    const double tx = pos[3 * i + 0] / cellsize;
-    const double fx = floor(tx);
-    const int px = wrap((int)fx, nmesh) - x0;
-    if(px < 0 || px >= P) { // the caller's target list is not this rank's slab
-        atomicExch(err, 1u);
-        return;
-    }
-    const double rx = tx - fx;
-    int ic[2];
-    double res[2];
-#pragma unroll
-    for(int k = 0; k < 2; k++) {
-        const double tmp = pos[3 * i + 1 + k] / cellsize;
-        const double fl = floor(tmp);
-        ic[k] = (int)fl;
-        res[k] = tmp - fl;
-    }
-    double acc = 0;
-#pragma unroll
-    for(int c = 0; c < 8; c++) {
-        const int offx = c & 1;
-        double w = offx ? rx : (1 - rx);
-        size_t lin = (size_t)(px + offx);
-#pragma unroll
-        for(int k = 0; k < 2; k++) {
-            const int off = (c >> (k + 1)) & 1;
-            lin = lin * (size_t)nmesh + (size_t)wrap(ic[k] + off, nmesh);
-            w *= off ? res[k] : (1 - res[k]);
-        }
-        acc += w * slab[lin];
-    }
-    if(comp < 3)
-        out[3 * i + comp] = acc;
-    else
-        out[i] += acc;
-}
-
 // out[c * out_ld + r] = in[r * in_ld + c] for r < rows, c < cols (complex doubles), through a 32 x 32 LDS tile so that both the
 // reads and the writes are coalesced.  The 1-D transforms along x then run on contiguous rows: rocFFT's strided plan for the
 // same transform (stride Py*Nz, batch Py*Nz) measured 2.06 ms against 0.4 ms + 0.5 ms for transpose + contiguous transform.
@@ -1146,8 +973,6 @@ void PMesh::slab_destroy()
         slab.p2d_c2r.destroy();
         slab.p1d_fwd.destroy();
         slab.p1d_inv.destroy();
-        slab.p1d_fwd_t.destroy();
-        slab.p1d_inv_t.destroy();
         slab.ready = false;
     }
     slab.phi.release();
@@ -1187,15 +1012,6 @@ void PMesh::slab_init(int rank, int world)
     slab.p2d_c2r.create(rocfft_placement_notinplace, rocfft_transform_type_real_inverse, 2, len2, (size_t)slab.P);
     slab.p1d_fwd.create(rocfft_placement_inplace, rocfft_transform_type_complex_forward, 1, len1, S); // contiguous rows of kx
     slab.p1d_inv.create(rocfft_placement_inplace, rocfft_transform_type_complex_inverse, 1, len1, S);
-    // the same transforms straight on the exchange buffers' [x][j] layout (element stride S along x, consecutive j one element apart):
-    // transform and transpose in one rocFFT plan each way, instead of k_transpose + a contiguous transform (MPG_PM_STRIDED_FFT=1; an
-    // experiment of round 5: profiles/r05a_experiments)
-    slab.strided = getenv("MPG_PM_STRIDED_FFT") != nullptr;
-    if(slab.strided) {
-        const size_t sS[1] = {S}, s1[1] = {1};
-        slab.p1d_fwd_t.create(rocfft_placement_notinplace, rocfft_transform_type_complex_forward, 1, len1, S, sS, 1, s1, (size_t)nmesh);
-        slab.p1d_inv_t.create(rocfft_placement_notinplace, rocfft_transform_type_complex_inverse, 1, len1, S, s1, (size_t)nmesh, sS, 1);
-    }
     slab.work.reserve(2 * (size_t)nmesh * S);
     slab.ready = true;
 }
@@ -1228,12 +1044,8 @@ void PMesh::slab_forward_b1(double *recvA, hipStream_t st)
     const size_t S = (size_t)slab.Py * nz;
     // [x][j] -> [j][x], j = (ky local, kz): the transforms along x run on contiguous rows
     const dim3 tgrid_f((unsigned)((S + 31) / 32), (unsigned)((nmesh + 31) / 32));
-    if(slab.strided)
-        slab.p1d_fwd_t.exec(recvA, slab.rho_k.p, st);
-    else {
-        hipLaunchKernelGGL(k_transpose, tgrid_f, dim3(256), 0, st, nmesh, (int)S, (const double2 *)recvA, S, (double2 *)slab.rho_k.p, (size_t)nmesh);
-        slab.p1d_fwd.exec(slab.rho_k.p, slab.rho_k.p, st);
-    }
+    hipLaunchKernelGGL(k_transpose, tgrid_f, dim3(256), 0, st, nmesh, (int)S, (const double2 *)recvA, S, (double2 *)slab.rho_k.p, (size_t)nmesh);
+    slab.p1d_fwd.exec(slab.rho_k.p, slab.rho_k.p, st);
     if(measure_power || nu_fn) { // this rank's ky rows: the caller sums the raw accumulators over the ranks (powerspectrum_sum's Allreduce)
         ps_zero(st);
         hipLaunchKernelGGL((k_power_spectrum<true, false>), dim3(1024), dim3(256), ps_lds_bytes(), st, nmesh, slab.Py, y0, invsinc2.p,
@@ -1258,15 +1070,11 @@ void PMesh::slab_forward_b2(double *sendB, hipStream_t st)
     }
     hipLaunchKernelGGL(k_potential_transfer<true>, dim3(nblk(ncplx)), dim3(256), 0, st, nmesh, slab.Py, y0, asmth2, pot_factor, invsinc2.p,
                        (double2 *)slab.rho_k.p);
-    // only the potential is transformed back: the forces are its real-space differences (k_gradient_axis), which also cuts
+    // only the potential is transformed back: the forces are its real-space differences (k_cic_readout_slab_stencil), which also cuts
     // the inverse all-to-all to a quarter
-    if(slab.strided)
-        slab.p1d_inv_t.exec(slab.rho_k.p, sendB, st);
-    else {
-        slab.p1d_inv.exec(slab.rho_k.p, slab.rho_k.p, st);
-        // [j][x] -> sendB[x][j]: the block for rank d (its x-planes) is contiguous
-        hipLaunchKernelGGL(k_transpose, tgrid_b, dim3(256), 0, st, (int)S, nmesh, (const double2 *)slab.rho_k.p, (size_t)nmesh, (double2 *)sendB, S);
-    }
+    slab.p1d_inv.exec(slab.rho_k.p, slab.rho_k.p, st);
+    // [j][x] -> sendB[x][j]: the block for rank d (its x-planes) is contiguous
+    hipLaunchKernelGGL(k_transpose, tgrid_b, dim3(256), 0, st, (int)S, nmesh, (const double2 *)slab.rho_k.p, (size_t)nmesh, (double2 *)sendB, S);
     MPG_HIP(hipGetLastError());
 }
 
@@ -1371,25 +1179,9 @@ void PMesh::slab_readout(const double *ghost_recv, const int *targets, int64_t n
     // ghost_recv: planes P, P+1, P+2 (the next rank's first three), then planes -2, -1 (the previous rank's last two)
     MPG_HIP(hipMemcpyAsync(phi0 + (size_t)slab.P * plane, ghost_recv, 3 * plane * sizeof(double), hipMemcpyDeviceToDevice, st));
     MPG_HIP(hipMemcpyAsync(slab.phi.p, ghost_recv + 3 * plane, 2 * plane * sizeof(double), hipMemcpyDeviceToDevice, st));
-    const int x0 = slab.rank * slab.P;
-    static const bool stencil = !(getenv("MPG_PM_STENCIL") && getenv("MPG_PM_STENCIL")[0] == '0');
-    if(stencil) {
-        if(nt > 0)
-            hipLaunchKernelGGL(k_cic_readout_slab_stencil, dim3(nblk(nt)), dim3(256), 0, st, nt, targets, d_pos, cellsize, nmesh, x0, slab.P,
-                               (double)nmesh / box, (const double *)slab.phi.p, d_gravpm, d_potential, flag.p);
-    }
-    else {
-    if(nt > 0 && d_potential)
-        hipLaunchKernelGGL(k_cic_readout_slab, dim3(nblk(nt)), dim3(256), 0, st, nt, targets, d_pos, cellsize, nmesh, x0, slab.P, phi0, 3, d_potential,
-                           flag.p);
-    }
-    const size_t ncell = (size_t)(slab.P + 1) * plane; // planes 0 .. P: the CIC readout reaches one plane beyond the slab
-    for(int axis = 0; axis < 3 && nt > 0 && !stencil; axis++) {
-        hipLaunchKernelGGL(k_gradient_axis, dim3(nblk(ncell)), dim3(256), 0, st, nmesh, slab.P + 1, axis, (double)nmesh / box, slab.phi.p,
-                           slab.force.p, 2);
-        hipLaunchKernelGGL(k_cic_readout_slab, dim3(nblk(nt)), dim3(256), 0, st, nt, targets, d_pos, cellsize, nmesh, x0, slab.P, slab.force.p, axis,
-                           d_gravpm, flag.p);
-    }
+    if(nt > 0)
+        hipLaunchKernelGGL(k_cic_readout_slab_stencil, dim3(nblk(nt)), dim3(256), 0, st, nt, targets, d_pos, cellsize, nmesh, slab.rank * slab.P,
+                           slab.P, (double)nmesh / box, (const double *)slab.phi.p, d_gravpm, d_potential, flag.p);
     MPG_HIP(hipGetLastError());
     unsigned e = 0;
     MPG_HIP(hipMemcpyAsync(&e, flag.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));

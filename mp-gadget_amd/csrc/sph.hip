@@ -85,11 +85,9 @@ __device__ __forceinline__ double kernel_dwk(const DKernel &k, int type, double 
     return k.dWknorm * (type == 0 ? dwk_q<0>(q) : (type == 1 ? dwk_q<1>(q) : dwk_q<2>(q)));
 }
 
-#ifndef SPH_EXACT_DIV
-#define SPH_FAST_DIV // round 4: the quotients and the square root of the pair evaluations by reciprocals (k_hydro 10.1 -> 9.6 ms)
-#endif
 // 1 / x and 1 / sqrt(x) to within an ulp: v_rcp_f64 / v_rsq_f64 and Newton steps instead of the ~30-instruction IEEE division and
-// square-root expansions (the reference itself is built with -ffast-math).  x > 0 and finite.
+// square-root expansions (the reference itself is built with -ffast-math).  x > 0 and finite.  Round 4 took the quotients and the square
+// root of the pair evaluations this way (k_hydro 10.1 -> 9.6 ms).
 __device__ __forceinline__ double rcp_fast(const double x)
 {
     double y = __builtin_amdgcn_rcp(x);
@@ -141,21 +139,8 @@ __global__ void __launch_bounds__(256) k_sph_predict(int64_t npart, const int *_
 
 
 
-#ifndef SPH_WALK_K
-#define SPH_WALK_K 2 // child ranges per search step (walk_stepk, ngb_walk.h)
-#endif
-
-#ifndef SPH_MERGE
-#define SPH_MERGE true // contiguous opened leaves of a child range joined into one list entry (walk_stepk, ngb_walk.h)
-#endif
-
-#ifndef SPH_NE
-// runs of <= 8 particles per search leaf: with -DSPH_NE=2 (or 4) the searches stop at nodes of <= 16 (32) particles and list their whole
-// particle range (TreeBuilder::calc_search_links; MPG_SPH_LEAF_CAP picks a smaller capacity at run time).  Measured at 2 x 128^3 on the
-// Zel'dovich set (profiles/r05a_experiments): fewer search steps, but 20 - 34 % more candidates and as many test iterations - density
-// 7.27 -> 7.32 ms, hydro 7.51 -> 7.41 ms - so the default stays 1 (the reference's leaves).
-#define SPH_NE 1
-#endif
+constexpr int SPH_WALK_K = 2;     // child ranges per search step (walk_stepk, ngb_walk.h)
+constexpr bool SPH_MERGE = true;  // contiguous opened leaves of a child range joined into one list entry (walk_stepk, ngb_walk.h)
 
 struct DensAcc {
     double EgyRho = 0, DhsmlEgy = 0, Rho = 0, DhsmlDensity = 0, Ngb = 0, Div = 0, Rot0 = 0, Rot1 = 0, Rot2 = 0, G0 = 0, G1 = 0, G2 = 0;
@@ -164,11 +149,9 @@ struct DensAcc {
 // Candidate handling is split in two so that the expensive part runs with full lanes: every candidate of an opened leaf
 // gets the distance test (treewalk.c:1218-1232; cheap, ~1/3 pass), the survivors are compacted into a small per-group
 // buffer in LDS, and the kernel evaluation (density_ngbiter / hydro_ngbiter) is run 8 survivors at a time.
-#ifndef SPH_TRIG
 // survivors in some group of the wave that trigger an evaluation (<= SPH_CBUF - 8: the next append must fit).  24 since round 4 (16 before): the
 // later the trigger, the more of the wave's 8 groups hold a full 8 survivors when it comes (k_hydro 8.4 -> 7.9 ms; k_density unchanged; 8: 10.2)
-#define SPH_TRIG 24
-#endif
+constexpr int SPH_TRIG = 24;
 constexpr int SPH_CBUF = 32; // survivor slots per group (a ring: a power of two)
 
 // distance test of density: returns whether the kernel evaluation is needed; counts the reference's "ninteractions"
@@ -196,12 +179,8 @@ __device__ __forceinline__ void density_eval(const Src4 s, const Aux4 o, const d
     const double d1 = near_img<WRAP>(py - s.y, box, 1.0 / box);
     const double d2 = near_img<WRAP>(pz - s.z, box, 1.0 / box);
     const double r2 = d0 * d0 + d1 * d1 + d2 * d2;
-#ifdef SPH_FAST_DIV
     const double rinv_d = r2 > 0 ? rsqrt_fast(r2) : 0.0;
     const double r = r2 * rinv_d;
-#else
-    const double r = sqrt(r2);
-#endif
     const double u = r * kern.Hinv;
     const double wk = kernel_wk(kern, C.ktype, u);
     a.Ngb += wk * kvol;
@@ -215,11 +194,7 @@ __device__ __forceinline__ void density_eval(const Src4 s, const Aux4 o, const d
         a.DhsmlEgy += mass_j * o.w * density_dW;
     }
     if(r > 0) {
-#ifdef SPH_FAST_DIV
         const double fac = mass_j * dwk * rinv_d;
-#else
-        const double fac = mass_j * dwk / r;
-#endif
         const double dv0 = ivel[0] - o.x, dv1 = ivel[1] - o.y, dv2 = ivel[2] - o.z;
         a.Div += -fac * (d0 * dv0 + d1 * dv1 + d2 * dv2);
         a.Rot0 += fac * (dv1 * d2 - d1 * dv2); // crossproduct(dv, dist), densitykernel.h:63-76
@@ -391,11 +366,6 @@ __global__ void __launch_bounds__(256, 4) k_density(const TreeView tv, const Sph
     __shared__ unsigned s_stack[4 * 8 * SPH_STK];
     __shared__ int s_cbuf[4 * 8 * SPH_CBUF];
     __shared__ unsigned s_llist[4 * 8 * SPH_LCAP];
-#ifdef MPG_EXP_LDSPAD_SPH // timing experiment: fewer resident blocks per CU with the same code (bytes of unused LDS)
-    __shared__ unsigned s_pad[MPG_EXP_LDSPAD_SPH / 4];
-    if(tv.box < 0)
-        s_pad[threadIdx.x] = 1u, s_llist[0] = s_pad[(threadIdx.x + 1) & 255];
-#endif
     const int lane = threadIdx.x & 63;
     const int grp = lane >> 3, s = lane & 7, gshift = grp * 8;
     unsigned *stack = s_stack + ((threadIdx.x >> 6) * 8 + grp) * SPH_STK;
@@ -423,7 +393,8 @@ __global__ void __launch_bounds__(256, 4) k_density(const TreeView tv, const Sph
             vel_pred(A, T, i, ivel);
         hsml = A.hsml[i];
     }
-    // the search's geometry: the cubes around the nodes' particles when the tree carries them (TreeBuilder::calc_search_boxes), else the cells
+    // the search's geometry: the cubes around the nodes' particles when the view carries them (TreeBuilder::calc_search_boxes), else the
+    // cells - SphEngine::density passes the cells
     const NodeGeo *__restrict__ sgeo = tv.geoS ? tv.geoS : tv.geoB;
     const DKernel kern = kernel_init(valid ? hsml : 1.0, C.ktype);
     const double kvol = NORM_COEFF * p3(kern.H);
@@ -443,10 +414,10 @@ __global__ void __launch_bounds__(256, 4) k_density(const TreeView tv, const Sph
         // ---- phase A: walk; opened leaves go to the group's list
         int nl = 0;
         for(;;) {
-            const bool go = sp > 0 && nl + 8 * SPH_WALK_K * SPH_NE <= SPH_LCAP;
+            const bool go = sp > 0 && nl + 8 * SPH_WALK_K <= SPH_LCAP;
             if(ballot64(go) == 0)
                 break;
-            nl = walk_stepk<false, SPH_WALK_K, SPH_MERGE, WRAP, SPH_NE>(tv, sgeo, nullptr, stack, sp, go, s, gshift, hsml, px, py, pz, llist, nl, overflow, tv.linkS);
+            nl = walk_stepk<false, SPH_WALK_K, SPH_MERGE, WRAP>(tv, sgeo, nullptr, stack, sp, go, s, gshift, hsml, px, py, pz, llist, nl, overflow);
             if(ballot64(overflow) != 0)
                 break;
         }
@@ -705,7 +676,6 @@ __device__ __forceinline__ void hydro_eval(const Src4 s, const HydroSrc &o, cons
     const double d1 = near_img<WRAP>(t.py - s.y, box, 1.0 / box);
     const double d2 = near_img<WRAP>(t.pz - s.z, box, 1.0 / box);
     const double rsq = d0 * d0 + d1 * d1 + d2 * d2;
-#ifdef SPH_FAST_DIV
     // (rsq > 0: hydro_test; the quotients of this function by reciprocals - see rcp_fast)
     const double rinv = rsqrt_fast(rsq);
     const double r = rsq * rinv;
@@ -723,13 +693,6 @@ __device__ __forceinline__ void hydro_eval(const Src4 s, const HydroSrc &o, cons
     const double p_over_rho2_j = o.pressure * inv_eom_j * inv_eom_j;
 #define SPH_DIV_R(x) ((x) * rinv)
 #define SPH_DIV(x, y) ((x) * rcp_fast(y))
-#else
-    const DKernel kernel_j = kernel_init(o.hsml, C.ktype);
-    const double r = sqrt(rsq);
-    const double p_over_rho2_j = o.pressure / (o.eomdensity * o.eomdensity);
-#define SPH_DIV_R(x) ((x) / r)
-#define SPH_DIV(x, y) ((x) / (y))
-#endif
     const double soundspeed_j = o.soundspeed;
     const double vsig = t.soundspeed_i + soundspeed_j;
     if(vsig > a.MaxSignalVel)
@@ -816,11 +779,6 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
     __shared__ unsigned s_stack[4 * 8 * SPH_STK];
     __shared__ int s_cbuf[4 * 8 * SPH_CBUF];
     __shared__ unsigned s_llist[4 * 8 * SPH_LCAP];
-#ifdef MPG_EXP_LDSPAD_SPH // timing experiment: fewer resident blocks per CU with the same code (bytes of unused LDS)
-    __shared__ unsigned s_pad[MPG_EXP_LDSPAD_SPH / 4];
-    if(tv.box < 0)
-        s_pad[threadIdx.x] = 1u, s_llist[0] = s_pad[(threadIdx.x + 1) & 255];
-#endif
     const int lane = threadIdx.x & 63;
     const int grp = lane >> 3, s = lane & 7, gshift = grp * 8;
     unsigned *stack = s_stack + ((threadIdx.x >> 6) * 8 + grp) * SPH_STK;
@@ -878,14 +836,10 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
         // ---- phase A: walk; opened leaves go to the group's list
         int nl = 0;
         for(;;) {
-            const bool go = sp > 0 && nl + 8 * SPH_WALK_K * SPH_NE <= SPH_LCAP;
+            const bool go = sp > 0 && nl + 8 * SPH_WALK_K <= SPH_LCAP;
             if(ballot64(go) == 0)
                 break;
-            nl = walk_stepk<true, SPH_WALK_K, SPH_MERGE, WRAP, SPH_NE>(tv, sgeo, shm, stack, sp, go, s, gshift, t.me.hsml, t.px, t.py, t.pz, llist, nl, overflow, tv.linkS);
-#ifdef SPH_HIST
-            if(lane == 0)
-                atomicAdd(&stats[7], 1ull);
-#endif
+            nl = walk_stepk<true, SPH_WALK_K, SPH_MERGE, WRAP>(tv, sgeo, shm, stack, sp, go, s, gshift, t.me.hsml, t.px, t.py, t.pz, llist, nl, overflow);
             if(ballot64(overflow) != 0)
                 break;
         }
@@ -906,12 +860,6 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
             const Src4 cand_n = tv.src[ps_n + (s < pc_n ? s : 0)];
             const double cand_hn = hsml_t[ps_n + (s < pc_n ? s : 0)];
             bool keep = false;
-#ifdef SPH_HIST // experiment: list entries by particle count (1-2, 3-4, 5-6, 7-8), phase-B iterations and walk steps per wave
-            if(s == 0 && has)
-                atomicAdd(&stats[2 + (pc - 1) / 2], 1ull);
-            if(lane == 0)
-                atomicAdd(&stats[6], 1ull);
-#endif
             if(s < pc) {
                 n_cand++;
                 keep = hydro_test<WRAP>(cand, cand_h, t, kernel_i, C, tv.box);
@@ -974,20 +922,6 @@ static int kernel_index(int enumtype)
     return enumtype == 1 ? 0 : (enumtype == 2 ? 1 : 2);
 }
 
-// The SPH searches stop at nodes of <= this many particles and list their whole range (TreeBuilder::calc_search_links): 8 = the
-// reference's leaves only (also under MPG_SPH_CELL_CULL=1, where the candidates are the reference's one for one).
-static int search_leaf_cap()
-{
-    static const int cap = [] {
-        if(getenv("MPG_SPH_CELL_CULL"))
-            return 8;
-        const char *e = getenv("MPG_SPH_LEAF_CAP");
-        const int c = e ? atoi(e) : 8 * SPH_NE;
-        return c < 8 ? 8 : (c > 8 * SPH_NE ? 8 * SPH_NE : c);
-    }();
-    return cap;
-}
-
 double sph_desnumngb(const mpg_density_params &P)
 {
     const int t = kernel_index(P.DensityKernelType);
@@ -1003,18 +937,9 @@ void SphEngine::density(TreeBuilder &tree, const SphView &A, const mpg_sph_times
     // The asymmetric search of the density loop keeps the reference's CELL test (cull_node): on the cubes around the nodes' particles it
     // tests 29 % fewer candidates (2 x 128^3: 686 M -> 487 M for 231 M neighbours) but runs 3 % longer - a candidate is a lane of a test
     // iteration that runs anyway, and leaves dropped from a set of siblings break the join of the rest (profiles/r05a_experiments).  The
-    // hydro loop's symmetric search gains from the cubes (hydro_force below).  MPG_SPH_DENSITY_CUBES=1 switches them on here too.
-    static const bool density_cubes = getenv("MPG_SPH_DENSITY_CUBES") != nullptr && getenv("MPG_SPH_CELL_CULL") == nullptr;
-    if(density_cubes && !tree.has_boxes)
-        tree.calc_search_boxes(st);
-    const int leaf_cap = search_leaf_cap();
-    if(leaf_cap > 8 && !(tree.has_slinks && tree.slink_cap == leaf_cap))
-        tree.calc_search_links(leaf_cap, st);
+    // hydro loop's symmetric search gains from the cubes (hydro_force below).
     TreeView tv = tree.view();
-    if(!density_cubes)
-        tv.geoS = nullptr;
-    if(leaf_cap <= 8)
-        tv.linkS = nullptr;
+    tv.geoS = nullptr;
     MPG_CHECK(tv.npart > 0 || n == 0, "density: the tree holds no gas particles");
     const int64_t nact = d_active ? nactive : n;
     left.reserve(n + 1);
@@ -1152,15 +1077,8 @@ void SphEngine::hydro_force(TreeBuilder &tree, const SphView &A, const mpg_sph_t
             if(!tree.has_boxes)
                 tree.calc_search_boxes(st);
             tree.calc_search_hsmax(hsml_t.p, st);
-            const int leaf_cap = search_leaf_cap();
-            if(leaf_cap > 8 && !(tree.has_slinks && tree.slink_cap == leaf_cap))
-                tree.calc_search_links(leaf_cap, st);
             tv = tree.view();
-            if(leaf_cap <= 8)
-                tv.linkS = nullptr;
         }
-        else
-            tv.linkS = nullptr;
     }
     // work queue: the active gas particles in tree order
     queue_a.reserve(tv.npart + 1);
@@ -1183,14 +1101,6 @@ void SphEngine::hydro_force(TreeBuilder &tree, const SphView &A, const mpg_sph_t
     MPG_HIP(hipMemcpyAsync(hs, stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
     MPG_HIP(hipMemcpyAsync(&e, ctr.p + 7, sizeof(e), hipMemcpyDeviceToHost, st));
     MPG_HIP(hipStreamSynchronize(st));
-#ifdef SPH_HIST
-    {
-        unsigned long long h8[8];
-        MPG_HIP(hipMemcpy(h8, stats.p, sizeof(h8), hipMemcpyDeviceToHost));
-        fprintf(stderr, "SPH_HIST hydro: targets %lld cand %llu pairs %llu entries[1-2,3-4,5-6,7-8] %llu %llu %llu %llu waveiters %llu wavesteps %llu\n", (long long)nt,
-                h8[0], h8[1], h8[2], h8[3], h8[4], h8[5], h8[6], h8[7]);
-    }
-#endif
     MPG_CHECK(e == 0, "hydro_force: neighbour-search stack overflow (tree deeper than the walk supports)");
     last_candidates = (int64_t)hs[0];
     last_interactions = (int64_t)hs[1];

@@ -14,7 +14,7 @@
 //                   particles, from the common-prefix lengths with its +-8 neighbours;
 //   4. scan         depth-first pre-order node numbering: a leaf head emits the internal nodes that start
 //                   at it (levels common+1 .. leaf-1) followed by the leaf;
-//   5. k_fill_nodes geometry, particle ranges and `sibling` (= first node after the sub-tree);
+//   5. k_node_heads + k_fill_nodes_n: geometry, particle ranges and `sibling` (= first node after the sub-tree);
 //   6. k_leaf_moments / k_internal_moments (bottom-up by level): mass, centre of mass, hmax
 //                   (forcetree.c:947-966, :985-1104).
 // Node numbering and in-leaf particle order differ from the reference (they also differ between two
@@ -183,84 +183,8 @@ __global__ void __launch_bounds__(256) k_level_extrema(int64_t nwaves, const int
     }
 }
 
-__global__ void __launch_bounds__(256) k_fill_nodes(int64_t n, const uint64_t *__restrict__ keys, const uint8_t *__restrict__ leaflevel,
-                                                    const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ base, double box,
-                                                    NodeGeo *__restrict__ geo, NodeLink *__restrict__ link)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= n || cnt[i] == 0)
-        return;
-    const uint64_t ki = keys[i];
-    const int L = leaflevel[i];
-    const int first = L - (int)cnt[i] + 1; // shallowest new level
-    // size of the leaf: particles up to the next head
-    int pc = 1;
-    while(i + pc < n && cnt[i + pc] == 0)
-        pc++;
-    double cx = box / 2., cy = box / 2., cz = box / 2.;
-    double len = box * 1.001;
-    for(int l = 0; l <= L; l++) {
-        if(l >= first) {
-            const int64_t j = (int64_t)base[i] + (l - first);
-            geo[j] = NodeGeo{cx, cy, cz, len};
-            NodeLink lk;
-            lk.level = l;
-            lk.pstart = (int)i;
-            int64_t e;
-            if(l == L) {
-                lk.pcount = pc;
-                e = i + pc;
-            }
-            else {
-                lk.pcount = 0;
-                // first particle after i that leaves this level-l cell: keys are sorted.  Nine internal nodes in ten are parents of leaves and
-                // hold 9 .. 64 particles, so the end is looked for by doubling steps from the leaf's end first (probes within a few hundred
-                // bytes of keys[i]) and by bisection inside the bracket that finds (round 6: a bisection over [i, n) from the start took
-                // ~24 dependent loads, the first dozen of them megabytes apart - 0.90 ms of the 3.5 ms tree build at 256^3)
-                const int shift = 3 * (MAXLEVEL - l);
-                const uint64_t pref = (l == 0) ? 0 : (ki >> shift);
-                int64_t lo = i + pc, hi = n; // everything in the leaf shares the prefix
-                if(l > 0)
-                    for(int64_t step = 8;; step <<= 1) {
-                        const int64_t p = lo - 1 + step;
-                        if(p >= n)
-                            break;
-                        if((keys[p] >> shift) == pref)
-                            lo = p + 1;
-                        else {
-                            hi = p;
-                            break;
-                        }
-                    }
-                else
-                    lo = n; // (the root holds everything)
-                while(lo < hi) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    const uint64_t km = keys[mid];
-                    const bool same = (l == 0) ? true : ((km >> shift) == pref);
-                    if(same)
-                        lo = mid + 1;
-                    else
-                        hi = mid;
-                }
-                e = lo;
-            }
-            lk.sibling = (e < n) ? (int)base[e] : -1;
-            link[j] = lk;
-        }
-        if(l < L) {
-            const int d = (int)((ki >> (3 * (MAXLEVEL - 1 - l))) & 7);
-            const double q = 0.25 * len;
-            cx += (d & 1) ? q : -q;
-            cy += (d & 2) ? q : -q;
-            cz += (d & 4) ? q : -q;
-            len *= 0.5;
-        }
-    }
-}
-
-// Round 6: the same records, one thread per NODE.  k_fill_nodes above runs one thread per particle of which only the leaf heads (one in
-// eight) have work, and of those one in eight a bracket search: 0.55 ms at 256^3 after the doubling steps.  k_node_heads scatters every
+// Geometry, particle range and `sibling` of every node, one thread per NODE (round 6; rounds 1-5 ran one thread per particle, of which only
+// the leaf heads - one in eight - had work, and of those one in eight a bracket search: 0.55 ms at 256^3).  k_node_heads scatters every
 // head's index to the nodes it starts; k_fill_nodes_n then lets node j descend from the root to its own level along its head's key - the
 // reference's arithmetic (centre +- len / 4, len / 2) in the same order, so the geometry is bit-identical - and finds its end.
 __global__ void __launch_bounds__(256) k_node_heads(int64_t n, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ base,
@@ -679,39 +603,6 @@ void TreeBuilder::calc_search_hsmax(const double *d_hsml_treeorder, hipStream_t 
     has_hsmax = true;
 }
 
-// linkB with the internal nodes of <= cap particles as leaves of their whole particle range (tree order is depth-first: the particles
-// below node j end where those of the node after its subtree begin)
-__global__ void __launch_bounds__(256) k_search_links(int64_t nnodes, int64_t npart, int cap, const uint32_t *__restrict__ dfs_of_bfs,
-                                                      const NodeLink *__restrict__ link, const NodeLinkB *__restrict__ linkB, NodeLinkB *__restrict__ linkS)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= nnodes)
-        return;
-    NodeLinkB o = linkB[i];
-    if(o.pcount == 0 && o.nchild > 0) {
-        const NodeLink lk = link[dfs_of_bfs[i]];
-        const int64_t end = lk.sibling >= 0 ? (int64_t)link[lk.sibling].pstart : npart;
-        const int64_t total = end - (int64_t)lk.pstart;
-        if(total <= cap) {
-            o.pstart = lk.pstart;
-            o.pcount = (int)total;
-            o.nchild = 0;
-            o.firstchild = 0; // (no merge hints: its parent's children are not all leaves of <= 8)
-        }
-    }
-    linkS[i] = o;
-}
-
-void TreeBuilder::calc_search_links(int cap, hipStream_t st)
-{
-    ensure_level_order(st);
-    linkS.reserve(nnodes + 16);
-    hipLaunchKernelGGL(k_search_links, dim3(nblk(nnodes)), dim3(256), 0, st, nnodes, npart, cap, nid_b.p, link.p, linkB.p, linkS.p);
-    MPG_HIP(hipGetLastError());
-    has_slinks = true;
-    slink_cap = cap;
-}
-
 // the particles of leaf i (level order) as the 8 records srcL[8 i ..]: one thread per record; a slot beyond the leaf's count holds a
 // zero-mass record at the leaf's first particle (any finite position will do: its pair evaluates to exactly zero)
 __global__ void __launch_bounds__(256) k_pad_leaves(int64_t nnodes, const NodeLinkB *__restrict__ linkB, const Src4 *__restrict__ src, Src4 *__restrict__ srcL)
@@ -788,7 +679,6 @@ void TreeBuilder::build(int64_t n, const double *d_pos, const float *d_mass, con
     has_bfs = false;
     has_boxes = false;
     has_hsmax = false;
-    has_slinks = false;
     has_leaf_pad = false;
     if(tm)
         tm->start(st);
@@ -904,15 +794,10 @@ void TreeBuilder::build(int64_t n, const double *d_pos, const float *d_mass, con
     MPG_HIP(hipMemsetAsync(src.p + npart + nnodes, 0, 16 * sizeof(Src4), st));
     if(npart > 0) {
         hipLaunchKernelGGL(k_gather_src, dim3(nblk(npart)), dim3(256), 0, st, npart, idx_b.p, d_pos, d_mass, src.p);
-        static const bool per_particle = getenv("MPG_TREE_FILL_PER_PARTICLE") != nullptr; // (rounds 1-5: one thread per particle)
-        if(per_particle)
-            hipLaunchKernelGGL(k_fill_nodes, dim3(nblk(npart)), dim3(256), 0, st, npart, keys_b.p, leaflevel.p, cnt.p, base.p, box, geo.p, link.p);
-        else {
-            node_head.reserve((size_t)nnodes + 1);
-            hipLaunchKernelGGL(k_node_heads, dim3(nblk(npart)), dim3(256), 0, st, npart, cnt.p, base.p, node_head.p);
-            hipLaunchKernelGGL(k_fill_nodes_n, dim3(nblk(nnodes)), dim3(256), 0, st, nnodes, npart, node_head.p, keys_b.p, leaflevel.p, cnt.p, base.p,
-                               box, geo.p, link.p);
-        }
+        node_head.reserve((size_t)nnodes + 1);
+        hipLaunchKernelGGL(k_node_heads, dim3(nblk(npart)), dim3(256), 0, st, npart, cnt.p, base.p, node_head.p);
+        hipLaunchKernelGGL(k_fill_nodes_n, dim3(nblk(nnodes)), dim3(256), 0, st, nnodes, npart, node_head.p, keys_b.p, leaflevel.p, cnt.p, base.p,
+                           box, geo.p, link.p);
     }
     else {
         NodeGeo g{box / 2., box / 2., box / 2., box * 1.001};
@@ -1082,7 +967,6 @@ TreeView TreeBuilder::view() const
         v.hmaxB = has_hmax ? hmaxB.p : nullptr;
         v.geoS = has_boxes ? geoS.p : nullptr;
         v.hsmaxS = (has_boxes && has_hsmax) ? hsmaxS.p : nullptr;
-        v.linkS = has_slinks ? linkS.p : nullptr;
         v.srcL = has_leaf_pad ? srcL.p : nullptr;
     }
     v.box = box;
