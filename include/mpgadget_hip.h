@@ -689,6 +689,63 @@ int mpg_gravpm_set_hybrid_nu_tracer(mpg_engine *eng, int on);
 int mpg_powerspectrum_save(const char *OutputDir, const char *filename, double Time, double D1, int nonzero, const double *kk,
                            const double *Power, const int64_t *Nmodes);
 
+/* ---- lensing potential planes (write_plane, libgadget/plane.c:572-683, called from run.c:727 at the sync points that ask for it).
+ * For every cut point and every normal, in the loop order of plane.c:633-634: the active particles of the slab
+ * [cut - Thickness/2, cut + Thickness/2) along the normal are COUNTED (nearest grid point, not mass) on a Resolution^2 image
+ * (cutPlaneGaussianGrid / grid3d_ngb / find_bin, lenstools.c:68-124, 233-319), the counts are normalised to the density contrast and the
+ * 2-D Poisson equation is solved for the lensing potential (calculate_lensing_potential, lenstools.c:168-231).  The image axes are
+ * projectDensity's (lenstools.c:126-166): normal 0 -> (y, z), normal 1 -> (x, z), normal 2 -> (x, y), the first one is the row.
+ * Active is lenstools_particle_is_active (lenstools.c:18-26): not Swallowed, and not type 2 while the hybrid-neutrino tracer switch
+ * (mpg_gravpm_set_hybrid_nu_tracer) is on; rows with IsGarbage are skipped as well, as in every other loop of the engine (the reference
+ * does not test that bit here because write_plane runs after the table has been collected).  The counters are 32-bit integers: a call
+ * with 2^32 or more active rows on one rank is refused.  The pixel index is the reference's arithmetic operation for operation, so the
+ * counts equal the reference's exactly.
+ * With fn != NULL the massive-neutrino correction of PlaneMassiveNuCorrection (plane_pm_grid_init_neutrino_correction,
+ * cutPlanePMNeutrinoCorrection, plane_add_periodic_bilinear, plane.c:313-478) is added: the active particles' mass on the engine's PM
+ * mesh, its spectrum, the callback (called once per planes call with the inputs documented at mpg_nu_response_fn; its MtotbyMcdm is
+ * ignored; this is NOT the callback registered with mpg_gravpm_set_nu_response: the reference runs delta_nu_from_power a second time
+ * here and its state is the caller's business), every mode times nufac - 1, the mesh projected onto an Nmesh^2 image whose axes are
+ * plane_directions[] = (normal + 1) % 3, (normal + 2) % 3 (plane.c:399, 421-425) - for normal 1 that is (z, x), the TRANSPOSE of the
+ * particle plane's (x, z); restated as the reference has it - solved, and resampled bilinearly onto the plane.  The PM meshes are scratch
+ * during the call; the spectrum of the last PM step, the registered response and the deposit tuner come out unchanged. */
+typedef struct mpg_plane_params {
+    int Resolution;                  /* PlaneResolution >= 1 (>= 2 with a correction, plane.c:618) */
+    double Thickness;                /* PlaneThickness in internal length units; <= 0: BoxSize (plane.c:581-584) */
+    int ncuts;                       /* <= 1024; 0: CutPoints[i] = (i + 1/2) Thickness, i < (int64) (BoxSize / Thickness) (plane.c:587-591) */
+    const double *CutPoints;
+    int nnormals;                    /* <= 3 */
+    const int *Normals;              /* each 0, 1 or 2 */
+    double left_corner[3];           /* the reference passes zeros (plane.c:637) */
+    double atime;
+    double comoving_distance;        /* compute_comoving_distance(CP, atime, 1., UnitVelocity_in_cm_per_s), internal length units */
+    double HubbleParam;
+    double omega_source;             /* plane_particle_omega_source (plane.c:65-74); <= 0 is an error */
+    double CurrentParticleOffset[3]; /* PartManager->CurrentParticleOffset */
+    mpg_nu_response_fn fn;           /* NULL: no correction */
+    void *ctx;
+    double BoxSize_in_MPC;           /* BoxSize * UnitLength_in_cm / CM_PER_MPC (plane.c:337), for the correction */
+} mpg_plane_params;
+/* the number of cut points a call with these parameters makes (the first dimension of its outputs).  BoxSize <= 0: the box of the
+ * particles bound to eng (mpg_dev_bind_particles, the resident table), which is what the device and resident calls use. */
+int mpg_plane_count(mpg_engine *eng, const mpg_plane_params *params, double BoxSize, int64_t *ncuts);
+/* Counter memory of a planes call: ncuts x nnormals x R^2 x 4 bytes (12 with the 64-bit copy of the several-rank form).  When that
+ * exceeds the budget the counting pass runs once per batch of planes.  bytes = 0 (the default): a quarter of the device memory free at
+ * the call; one plane is always held. */
+int mpg_set_plane_counter_budget(mpg_engine *eng, int64_t bytes);
+/* On the particles of mpg_dev_bind_particles; d_flags: device bytes with bit 0 IsGarbage, bit 1 Swallowed (as mpg_dev_fof_fof takes
+ * them), or NULL.  d_planes[ncuts][nnormals][R][R] doubles on the device, npart[ncuts][nnormals] on the host (num_particles_plane). */
+int mpg_dev_potential_planes(mpg_engine *eng, const mpg_plane_params *params, const unsigned char *d_flags, double *d_planes, int64_t *npart);
+/* the counting pass alone (grid3d_ngb + projectDensity): d_counts[ncuts][nnormals][R][R] 32-bit counters on the device, *n_active =
+ * plane_count_active_particles of the bound rows (may be NULL).  For tests and measurements. */
+int mpg_dev_plane_counts(mpg_engine *eng, const mpg_plane_params *params, const unsigned char *d_flags, uint32_t *d_counts, int64_t *n_active);
+/* On the records of a particle view (host pointers in and out; joins a running prefetch like the other host-path calls, reuses the
+ * upload of a declared epoch; on the resident table it runs on the device copies). */
+int mpg_potential_planes(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_plane_params *params, double *planes,
+                         int64_t *npart);
+/* On the resident table (mpg_resident_begin): positions, masses and types are the device's; IsGarbage / Swallowed are read from the
+ * host records, which nothing on the device changes.  planes / npart are host arrays. */
+int mpg_resident_potential_planes(mpg_engine *eng, const mpg_particle_view *pv, const mpg_plane_params *params, double *planes, int64_t *npart);
+
 /* ---- long-range PM over several GPUs, one process per GPU (petapm.c:584-885 exchanges region meshes with 2-D pencils and lets
  * PFFT transpose; here: x-slabs of Nmesh/world planes, two all-to-all transposes per PM step and one neighbour plane).  The
  * engine does the local stages; the caller (one rank per GPU) does the collectives between them on the engine's stream:
@@ -910,6 +967,17 @@ int mpg_dist_domain_set_maxpart(mpg_dist *d, int64_t MaxPart);
 /* the matter power spectrum of the last mpg_dist_(dev_)gravpm_force over all ranks (gravpm.c:110-118; powerspectrum_sum's
  * MPI_Allreduce, powerspectrum.c:55-91).  Collective; arrays of Nmesh entries, *nonzero of which are filled on every rank. */
 int mpg_dist_gravpm_get_powerspectrum(mpg_dist *d, double BoxSize_in_MPC, double *kk, double *Power, int64_t *Nmodes, int *nonzero);
+/* write_plane over the ranks (plane.c:572-683), collective: every rank passes its OWN rows (device arrays; d_mass / d_type / d_flags may
+ * be NULL) and the parameters of mpg_dev_potential_planes, and receives the planes and npart of the whole box.  Each rank counts its rows;
+ * the counters are widened to 64-bit integers and summed with the communicator's allreduce, as are the active-particle number and
+ * npart.  (The reference reduces the finished potentials, plane.c:654; the solve is linear, so summing the integer counts first is the
+ * same plane with one solve instead of one per rank.)  The call leaves the rows bound to the engine.  With params->fn != NULL and more
+ * than one rank it fails with "the massive-neutrino correction on several ranks is not implemented" on every rank, before any collective.
+ * The number of planes per batch is agreed on over the ranks (the smallest any rank's budget holds), and a refusal of one rank's counting
+ * pass (a position that cannot be wrapped, 2^32 active rows) is all-reduced, so every rank returns that error together.  Errors of the
+ * parameters are the same on every rank by construction.  NOT collective-safe: a failed device allocation or a HIP error on one rank. */
+int mpg_dist_potential_planes(mpg_dist *d, int64_t n_own, const double *d_pos, const float *d_mass, const uint8_t *d_type,
+                              const unsigned char *d_flags, double BoxSize, const mpg_plane_params *params, double *d_planes, int64_t *npart);
 int mpg_dist_density(mpg_dist *d, const mpg_particle_view *pv, const mpg_sph_arrays *A, const mpg_sph_times *T, const int *ActiveParticle,
                      int64_t NumActiveParticle, int update_hsml, int DoEgyDensity);
 int mpg_dist_hydro_force(mpg_dist *d, const mpg_particle_view *pv, const mpg_sph_arrays *A, const mpg_sph_times *T, const int *ActiveParticle,

@@ -3020,3 +3020,58 @@ extern "C" int mpg_dist_grav_short_tree_active_tree(mpg_dist *d, const mpg_parti
     });
     API_END
 }
+
+/* ---- potential planes over the ranks (write_plane, plane.c:572-683; the kernels are planes.hip's).  Every rank counts its own rows; the
+ * counters are widened to 64-bit integers and summed with the communicator's allreduce, as are the active-particle number and the
+ * particles per plane.  The reference reduces the finished potentials (plane.c:654); the solve is linear, so summing the integer counts
+ * first gives the same plane with one solve instead of one per rank, and every rank holds the result.  The neutrino correction would need
+ * the slab form of the mesh pass and is refused - before any collective, so that every rank returns.  The planes of a batch (what the
+ * counter budget holds) are agreed on as the smallest number any rank can hold, and a rank-local refusal of the counting pass (a
+ * position that cannot be wrapped, 2^32 active rows) travels with a MAX all-reduce, so every rank makes the same collectives and
+ * returns the same error. */
+namespace {
+void planes_sum_device(void *ctx, int64_t *d_v, int64_t count)
+{
+    mpg_dist *d = (mpg_dist *)ctx;
+    MPG_CHECK(d->comm.allreduce, "mpg_comm: allreduce callback missing");
+    hipStream_t st = d->eng->stream;
+    if(d->comm.device_buffers) {
+        follow_stream(d);
+        if(!d->stream_ordered)
+            sync(d);
+        cb(d->comm.allreduce(d->comm.ctx, d_v, count, 1, 0, 1), "allreduce");
+        return;
+    }
+    std::vector<int64_t> h((size_t)count);
+    MPG_HIP(hipMemcpyAsync(h.data(), d_v, (size_t)count * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    sync(d);
+    cb(d->comm.allreduce(d->comm.ctx, h.data(), count, 1, 0, 0), "allreduce");
+    MPG_HIP(hipMemcpyAsync(d_v, h.data(), (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    sync(d);
+}
+void planes_sum_host(void *ctx, int64_t *v, int64_t count) { allreduce_i64((mpg_dist *)ctx, v, count, 0); }
+void planes_max_host(void *ctx, int64_t *v, int64_t count) { allreduce_i64((mpg_dist *)ctx, v, count, 1); }
+} // namespace
+
+extern "C" int mpg_dist_potential_planes(mpg_dist *d, int64_t n_own, const double *d_pos, const float *d_mass, const uint8_t *d_type,
+                                         const unsigned char *d_flags, double BoxSize, const mpg_plane_params *params, double *d_planes,
+                                         int64_t *npart)
+{
+    API_BEGIN
+    MPG_CHECK(d && params, "null argument");
+    MPG_CHECK(n_own >= 0 && (n_own == 0 || d_pos), "mpg_dist_potential_planes: null positions");
+    MPG_CHECK(BoxSize > 0, "mpg_dist_potential_planes: BoxSize must be positive");
+    MPG_CHECK(!(params->fn && d->nt > 1), "potential planes: the massive-neutrino correction on several ranks is not implemented");
+    mpg_engine *e = d->eng;
+    MPG_HIP(hipSetDevice(e->device));
+    e->host_join();
+    e->n = n_own;
+    e->d_pos = d_pos;
+    e->d_mass = d_mass;
+    e->d_type = d_type;
+    e->box = BoxSize;
+    e->pm_queued = false;
+    const PlaneReduce red{d, d->nt, planes_sum_device, planes_sum_host, planes_max_host};
+    planes_run(e, params, d_flags, d_planes, npart, d->nt > 1 ? &red : nullptr);
+    API_END
+}

@@ -2329,6 +2329,70 @@ int mpg_resident_end(mpg_engine *eng, const mpg_particle_view *P)
     API_END
 }
 
+/* ---- potential planes on a host table (write_plane, plane.c:572-683; the kernels are planes.hip's) ----------------------------------- */
+namespace {
+// IsGarbage / Swallowed of the records -> device bytes (null when the view has no flags).  In resident mode the host records are stale in
+// every column the engine integrates, but nothing on the device sets or clears these two bits, so they are read from the host table.
+const uint8_t *stage_plane_flags(mpg_engine *eng, const mpg_particle_view *P)
+{
+    if(P->off_flags < 0 || P->n == 0)
+        return nullptr;
+    const int64_t n = P->n;
+    // (not h_b: inside a declared epoch it holds the live flags the write-back of mpg_grav_short_tree reads)
+    eng->h_plane_flags.reserve((size_t)n + 1);
+    eng->plane_flags.reserve((size_t)n + 1);
+    uint8_t *hb = eng->h_plane_flags.p;
+    const char *b = (const char *)P->base;
+    const mpg_particle_view V = *P;
+    parallel_for(n, [=](int64_t lo, int64_t hi) {
+        for(int64_t i = lo; i < hi; i++)
+            hb[i] = *(const uint8_t *)(b + i * V.stride + V.off_flags) & 3;
+    });
+    MPG_HIP(hipMemcpyAsync(eng->plane_flags.p, hb, (size_t)n, hipMemcpyHostToDevice, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    return eng->plane_flags.p;
+}
+
+void host_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *par, double *planes, int64_t *npart)
+{
+    int64_t ncuts = 0;
+    MPG_CHECK(mpg_plane_count(eng, par, 0.0, &ncuts) == 0, mpg_last_error());
+    MPG_CHECK(par->Resolution >= 1, "potential planes: Resolution must be at least 1");
+    MPG_CHECK(par->Resolution <= 32768, "potential planes: Resolution above 32768");
+    const size_t tot = (size_t)ncuts * (size_t)(par->nnormals > 0 ? par->nnormals : 0) * (size_t)par->Resolution * par->Resolution;
+    MPG_CHECK(tot == 0 || (planes && npart), "potential planes: null output");
+    eng->plane_out.reserve(tot + 1);
+    const uint8_t *fl = stage_plane_flags(eng, P);
+    planes_run(eng, par, fl, eng->plane_out.p, npart, nullptr);
+    if(tot)
+        MPG_HIP(hipMemcpyAsync(planes, eng->plane_out.p, tot * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+}
+} // namespace
+
+int mpg_potential_planes(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, const mpg_plane_params *params, double *planes, int64_t *npart)
+{
+    API_BEGIN
+    MPG_CHECK(eng && P && params, "null argument");
+    MPG_CHECK(BoxSize > 0, "potential planes: BoxSize must be positive");
+    MPG_HIP(hipSetDevice(eng->device));
+    eng->host_join(); // (a running prefetch is joined, a write-back of the last PM step finished)
+    MPG_CHECK(eng->unpack_error.empty(), "host path: the write-back of GravPM failed: " + eng->unpack_error);
+    stage_particles(eng, P, BoxSize);
+    host_planes(eng, P, params, planes, npart);
+    API_END
+}
+
+int mpg_resident_potential_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *params, double *planes, int64_t *npart)
+{
+    API_BEGIN
+    resident_check(eng, P);
+    MPG_CHECK(params, "null argument");
+    MPG_CHECK(eng->d_pos == eng->s_pos.p && eng->n == P->n, "resident mode: the binding changed (mpg_resident_end / _begin)");
+    host_planes(eng, P, params, planes, npart);
+    API_END
+}
+
 int mpg_grav_short_pair(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle, double Rcut, double rho0)
 {
     API_BEGIN

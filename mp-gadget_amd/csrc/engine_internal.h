@@ -7,6 +7,7 @@
 #include "sph.h"
 #include "timestep.h"
 #include "peano.h"
+#include "planes.h"
 #include "domain.h"
 #include "fof.h"
 #include "snapshot_io.h"
@@ -232,6 +233,10 @@ struct mpg_engine {
     PeanoScratch peano;
     DomainScratch domain;
     FofEngine fof;
+    PlaneEngine planes;
+    DevBuf<uint8_t> plane_flags; // host forms of the potential planes: IsGarbage / Swallowed of the table ...
+    HostBuf<uint8_t> h_plane_flags; // ... staged through a pinned buffer of their own (h_b holds the live flags of the staged epoch)
+    DevBuf<double> plane_out;
     HostBuf<double> h_d, h_d2, h_d3; // pinned staging: positions / 3-vectors, scalars
     HostBuf<float> h_f;
     HostBuf<uint8_t> h_b;
@@ -291,6 +296,17 @@ struct mpg_engine {
 };
 
 extern "C" void engine_tree_build_on(mpg_engine *eng, int mask, hipStream_t st); // engine.hip
+
+// potential planes (planes.hip).  red: the sums over the ranks of the several-GPU form (dist.hip), or null; sum_device returns with the
+// device array summed and usable on the engine's stream
+struct PlaneReduce {
+    void *ctx;
+    int nt;
+    void (*sum_device)(void *ctx, int64_t *d_v, int64_t count);
+    void (*sum_host)(void *ctx, int64_t *v, int64_t count);
+    void (*max_host)(void *ctx, int64_t *v, int64_t count);
+};
+void planes_run(mpg_engine *eng, const mpg_plane_params *par, const uint8_t *d_flags, double *d_planes, int64_t *npart, const PlaneReduce *red);
 
 #define API_BEGIN try {
 #define API_END_NORETURN             \

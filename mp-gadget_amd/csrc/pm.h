@@ -42,6 +42,7 @@ struct PMesh {
     DevBuf<char> dep_tmp;
     // matter power spectrum of the PM density field (gravpm.c:331-382): raw sums of the last PM step
     bool measure_power = true, ps_valid = false;
+    int ps_nmesh = 0;                    // the Nmesh the accumulators were last zeroed for (ps_valid survives gravpm_init_periodic)
     DevBuf<double> ps_acc;               // Power[Nmesh], kk[Nmesh], Norm
     DevBuf<unsigned long long> ps_modes; // Nmodes[Nmesh]
     void ps_zero(hipStream_t st);
@@ -55,6 +56,7 @@ struct PMesh {
     void *nu_ctx = nullptr;
     double nu_box_mpc = 0;
     int nu_nonzero = 0;
+    const char *nu_who = "gravpm_force"; // the call nu_table names in its refusals (the potential planes borrow the host step)
     double nu_prefac = 0, nu_normfac = 1;
     DevBuf<double> nu_tab;              // logknu[nmesh], delta_nu_ratio[nmesh]
     DevBuf<int> nu_guess;               // per log-k bin: the table interval its modes start the search from
@@ -66,6 +68,16 @@ struct PMesh {
     // acc / modes: the raw sums over the whole mesh (all-reduced over the ranks in the slab form).  Runs the callback, checks its
     // table, uploads it and zeroes the accumulators for the second measurement
     void nu_table(const double *acc, const unsigned long long *modes, hipStream_t st);
+    // the neutrino correction of the lensing planes (plane_pm_grid_init_neutrino_correction, plane.c:313-351; used by planes.hip): the active
+    // particles' mass on the mesh, r2c, the CDM spectrum measured as in pass 1 above, the host step with the CALLER's callback of this call
+    // (not the registered nu_fn), then every mode times nufac - 1 = nu_prefac * interp(delta_nu_ratio, log k), the k = 0 mode zeroed - no
+    // potential transfer, no second measurement - and c2r.  Leaves the unnormalised result in `real` and returns the deposited mass (the
+    // k = 0 mode of the transform).  The meshes are scratch here: the raw spectrum of the last PM step, ps_valid, the registered callback
+    // and the deposit tuner of gravpm_force (a tuner of its own is used) come out as they went in.
+    DepositState dep_plane;
+    DevBuf<double> ps_keep;
+    double plane_nu_correction(int64_t n, const double *d_pos, const float *d_mass, const uint8_t *d_active, mpg_nu_response_fn fn, void *ctx,
+                               double box_mpc, hipStream_t st);
     // hybrid neutrinos as passive tracers (HybridNeutrinosOn, gravpm.c:84-85, 469-474): type-2 particles are not deposited but are read
     // out.  tracer_mass() gives the mass array with those masses zeroed (a zero adds nothing to a cell), or d_mass when off
     bool hybrid_tracer = false;

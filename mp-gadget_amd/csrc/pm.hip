@@ -339,6 +339,43 @@ __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y
         }
 }
 
+// plane_neutrino_correction_transfer, plane.c:291-311: every mode times nufac - 1 (the same table, clamps and interpolation as NU above,
+// without the 1), the k = 0 mode zeroed.  Single-GPU layout only.
+__global__ void __launch_bounds__(256) k_nu_correction(int nmesh, double2 *__restrict__ cplx, NuArgs nu)
+{
+    extern __shared__ double s_ps[]; // logknu[nbins], ratio[nbins], guess[nbins] (int)
+    const int nbins = nmesh;
+    double *s_lk = s_ps, *s_rt = s_ps + nbins;
+    int *s_gs = (int *)(s_ps + 2 * nbins);
+    for(int b = threadIdx.x; b < nbins; b += blockDim.x) {
+        s_lk[b] = nu.tab[b];
+        s_rt[b] = nu.tab[nbins + b];
+        s_gs[b] = nu.guess[b];
+    }
+    __syncthreads();
+    const int nz = nmesh / 2 + 1;
+    const size_t total = (size_t)nmesh * nmesh * nz;
+    const double binsperunit = (nbins - 1) / log(sqrt(3.0) * nmesh / 2.0);
+    for(size_t ip = (size_t)blockIdx.x * blockDim.x + threadIdx.x; ip < total; ip += (size_t)gridDim.x * blockDim.x) {
+        const int iz = (int)(ip % nz);
+        const size_t t = ip / nz;
+        const int iy = (int)(t % nmesh), ix = (int)(t / nmesh);
+        const int kx = ix <= nmesh / 2 ? ix : ix - nmesh;
+        const int ky = iy <= nmesh / 2 ? iy : iy - nmesh;
+        const long long k2 = (long long)kx * kx + (long long)ky * ky + (long long)iz * iz;
+        if(k2 == 0) {
+            cplx[ip] = make_double2(0.0, 0.0);
+            continue;
+        }
+        const int kint = (int)floor(binsperunit * log((double)k2) / 2.);
+        const double f = nu_factor(log(sqrt((double)k2) * nu.kscale), kint < nbins ? kint : nbins - 1, s_lk, s_rt, s_gs, nu.nonzero, nu.prefac) - 1;
+        double2 v = cplx[ip];
+        v.x *= f;
+        v.y *= f;
+        cplx[ip] = v;
+    }
+}
+
 // force_transfer for one axis, gravpm.c:476-498: (re, im) <- (-im*fac, re*fac), fac = -diff_kernel(k 2pi/N) N/Box.
 // axis < 0: plain copy (the Potential pass has no transfer function, gravpm.c:32-39).
 // The destination element of source (ix, row, iz) is dst[(ix * xmul + xoff) * ny * nz + row * nz + iz]: xmul = 1, xoff = 0 on one
@@ -568,6 +605,7 @@ void PMesh::ps_zero(hipStream_t st)
     MPG_HIP(hipMemsetAsync(ps_acc.p, 0, (2 * (size_t)nmesh + 1) * sizeof(double), st));
     MPG_HIP(hipMemsetAsync(ps_modes.p, 0, (size_t)nmesh * sizeof(unsigned long long), st));
     ps_valid = true;
+    ps_nmesh = nmesh;
 }
 
 void PMesh::nu_fetch(hipStream_t st, double **acc, unsigned long long **modes)
@@ -592,7 +630,7 @@ void PMesh::nu_table(const double *acc, const unsigned long long *modes, hipStre
 {
     // compute_neutrino_power, gravpm.c:308-326: powerspectrum_sum, Power -> sqrt(Power) = delta_cdm, delta_nu_from_power, zero
     const int nb = nmesh;
-    MPG_CHECK(ps_lds_bytes_nu() <= 65536, "gravpm_force: the neutrino response keeps its table in LDS: Nmesh " + std::to_string(nmesh) + " is too large");
+    MPG_CHECK(ps_lds_bytes_nu() <= 65536, std::string(nu_who) + ": the neutrino response keeps its table in LDS: Nmesh " + std::to_string(nmesh) + " is too large");
     std::vector<double> kk(nb), dcdm(nb), tab(2 * (size_t)nb, 0.0);
     std::vector<int64_t> nm(nb);
     int nonzero = 0;
@@ -605,13 +643,13 @@ void PMesh::nu_table(const double *acc, const unsigned long long *modes, hipStre
     for(int i = 0; i < nonzero; i++)
         lk[i] = rt[i] = NAN;
     const int rc = nu_fn(nu_ctx, nonzero, kk.data(), dcdm.data(), nm.data(), lk, rt, &prefac, &mtot);
-    MPG_CHECK(rc == 0, "gravpm_force: the neutrino response callback failed (returned " + std::to_string(rc) + ")");
-    MPG_CHECK(nonzero >= 2, "gravpm_force: neutrino response table: " + std::to_string(nonzero) + " power spectrum bins, at least 2 needed");
-    MPG_CHECK(std::isfinite(prefac) && std::isfinite(mtot), "gravpm_force: neutrino response callback: nu_prefac / MtotbyMcdm not finite");
+    MPG_CHECK(rc == 0, std::string(nu_who) + ": the neutrino response callback failed (returned " + std::to_string(rc) + ")");
+    MPG_CHECK(nonzero >= 2, std::string(nu_who) + ": neutrino response table: " + std::to_string(nonzero) + " power spectrum bins, at least 2 needed");
+    MPG_CHECK(std::isfinite(prefac) && std::isfinite(mtot), std::string(nu_who) + ": neutrino response callback: nu_prefac / MtotbyMcdm not finite");
     for(int i = 0; i < nonzero; i++) {
         MPG_CHECK(std::isfinite(lk[i]) && std::isfinite(rt[i]),
-                  "gravpm_force: neutrino response table: entry " + std::to_string(i) + " is not finite");
-        MPG_CHECK(i == 0 || lk[i] > lk[i - 1], "gravpm_force: neutrino response table: logknu is not strictly increasing at entry " + std::to_string(i));
+                  std::string(nu_who) + ": neutrino response table: entry " + std::to_string(i) + " is not finite");
+        MPG_CHECK(i == 0 || lk[i] > lk[i - 1], std::string(nu_who) + ": neutrino response table: logknu is not strictly increasing at entry " + std::to_string(i));
     }
     // per log-k bin the table interval to start from: the bin's position among the non-empty bins (the table is their log kk)
     std::vector<int> guess(nb);
@@ -734,6 +772,73 @@ void PMesh::deposit(int64_t n, const double *d_pos, const float *d_mass, const u
         sorted();
     else
         plain();
+}
+
+double PMesh::plane_nu_correction(int64_t n, const double *d_pos, const float *d_mass, const uint8_t *d_active, mpg_nu_response_fn fn, void *ctx,
+                                  double box_mpc, hipStream_t st)
+{
+    MPG_CHECK(nmesh > 0, "potential planes: the massive-neutrino correction needs the PM mesh (gravpm_init_periodic first)"); // plane.c:620
+    MPG_CHECK(!slab.ready, "potential planes: the massive-neutrino correction is not available while the mesh is in its slab-decomposed form");
+    MPG_CHECK(fn && box_mpc > 0, "potential planes: the massive-neutrino correction needs a callback and BoxSize_in_MPC > 0");
+    ensure_single();
+    const size_t nreal = (size_t)nmesh * nmesh * nmesh, nb = (size_t)nmesh;
+    // what the last PM step left for mpg_gravpm_get_powerspectrum is set aside
+    // (ps_valid survives gravpm_init_periodic: after a change of Nmesh without a PM step the accumulators are still the old mesh's and
+    // hold nothing a caller could ask for; ps_valid then comes out false, whatever capacity the buffers happen to have)
+    const bool had_ps = ps_valid && ps_nmesh == nmesh;
+    if(had_ps) {
+        ps_keep.reserve(3 * nb + 1);
+        MPG_HIP(hipMemcpyAsync(ps_keep.p, ps_acc.p, (2 * nb + 1) * sizeof(double), hipMemcpyDeviceToDevice, st));
+        MPG_HIP(hipMemcpyAsync(ps_keep.p + 2 * nb + 1, ps_modes.p, nb * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    }
+    struct Restore { // (also when the callback's table is refused)
+        PMesh *pm;
+        mpg_nu_response_fn fn;
+        void *ctx;
+        double box_mpc, prefac, normfac;
+        int nonzero;
+        bool had_ps;
+        hipStream_t st;
+        ~Restore()
+        {
+            pm->nu_who = "gravpm_force";
+            pm->nu_fn = fn;
+            pm->nu_ctx = ctx;
+            pm->nu_box_mpc = box_mpc;
+            pm->nu_prefac = prefac;
+            pm->nu_normfac = normfac;
+            pm->nu_nonzero = nonzero;
+            pm->ps_valid = had_ps;
+            if(had_ps) {
+                const size_t nb = (size_t)pm->nmesh;
+                (void)hipMemcpyAsync(pm->ps_acc.p, pm->ps_keep.p, (2 * nb + 1) * sizeof(double), hipMemcpyDeviceToDevice, st);
+                (void)hipMemcpyAsync(pm->ps_modes.p, pm->ps_keep.p + 2 * nb + 1, nb * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st);
+            }
+        }
+    } restore{this, nu_fn, nu_ctx, nu_box_mpc, nu_prefac, nu_normfac, nu_nonzero, had_ps, st};
+    MPG_HIP(hipMemsetAsync(real.p, 0, nreal * sizeof(double), st));
+    if(n > 0)
+        deposit(n, d_pos, d_mass, d_active, real.p, 0, nmesh, dep_plane, st, nullptr);
+    plan_r2c.exec(real.p, rho_k.p, st);
+    ps_zero(st);
+    hipLaunchKernelGGL((k_power_spectrum<false, false>), dim3(2048), dim3(256), ps_lds_bytes(), st, nmesh, nmesh, 0, invsinc2.p, (double2 *)rho_k.p,
+                       ps_acc.p, ps_modes.p, 0.0, 0.0, NuArgs{});
+    double total_mass = 0;
+    MPG_HIP(hipMemcpyAsync(&total_mass, rho_k.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    double *acc;
+    unsigned long long *modes;
+    nu_fetch(st, &acc, &modes); // (waits for the stream)
+    MPG_CHECK(total_mass > 0, "potential planes: cannot build a potential plane from zero active particle mass"); // plane.c:161
+    nu_who = "potential planes";
+    nu_fn = fn;
+    nu_ctx = ctx;
+    nu_box_mpc = box_mpc;
+    nu_table(acc, modes, st);
+    const NuArgs na{nu_tab.p, nu_guess.p, nu_nonzero, nu_prefac, nu_normfac, 2 * M_PI / nu_box_mpc};
+    hipLaunchKernelGGL(k_nu_correction, dim3(2048), dim3(256), (size_t)nmesh * (2 * sizeof(double) + sizeof(int)), st, nmesh, (double2 *)rho_k.p, na);
+    MPG_HIP(hipGetLastError());
+    plan_c2r.exec(rho_k.p, real.p, st);
+    return total_mass;
 }
 
 void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uint8_t *d_active, double *d_gravpm, double *d_potential,

@@ -371,6 +371,21 @@ class DistForce:
         self._ck(self.lib.mpg_dist_fof_groups(self.h, C.byref(out)))
         return grnr, tot.value, g
 
+    def potential_planes(self, pos, BoxSize, Resolution, Normals, mass=None, type=None, flags=None, **kw):
+        """mpg_dist_potential_planes (write_plane over the ranks; collective): every rank passes its own rows and gets the summed planes.
+        Keywords as Engine._plane_params.  Returns (planes [ncuts, nnormals, R, R] float64 device tensor, npart int64), the same on
+        every rank.  With nu_response and more than one rank the call fails on every rank before any collective."""
+        pp, keep, nc, nn, thunk = self.eng._plane_params(BoxSize, Resolution, Normals, **kw)
+        planes = torch.empty((nc, nn, max(pp.Resolution, 0), max(pp.Resolution, 0)), dtype=torch.float64, device=pos.device)
+        npart = np.zeros((nc, nn), np.int64)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self.lib.mpg_dist_potential_planes.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                                       C.POINTER(E.PlaneParams), C.c_void_p, C.c_void_p]
+        self.eng._keep["bind"] = (pos, mass, type)
+        self._ck(self.lib.mpg_dist_potential_planes(self.h, C.c_int64(pos.shape[0]), p(pos), p(mass), p(type), p(flags), C.c_double(BoxSize),
+                                                    C.byref(pp), p(planes), npart.ctypes.data_as(C.c_void_p)))
+        return planes, npart
+
     def force_tree_build(self, pos, mass):
         """mpg_dist_dev_force_tree_build alone: ghost import, local tree, global top (what the SPH loops need when no gravity step
         ran on this particle set)"""

@@ -205,6 +205,14 @@ NU_RESPONSE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double)
                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
 
 
+class PlaneParams(C.Structure):
+    """mpg_plane_params (include/mpgadget_hip.h)"""
+    _fields_ = [("Resolution", C.c_int), ("Thickness", C.c_double), ("ncuts", C.c_int), ("CutPoints", C.POINTER(C.c_double)),
+                ("nnormals", C.c_int), ("Normals", C.POINTER(C.c_int)), ("left_corner", C.c_double * 3), ("atime", C.c_double),
+                ("comoving_distance", C.c_double), ("HubbleParam", C.c_double), ("omega_source", C.c_double),
+                ("CurrentParticleOffset", C.c_double * 3), ("fn", NU_RESPONSE_FN), ("ctx", C.c_void_p), ("BoxSize_in_MPC", C.c_double)]
+
+
 def _nu_response_thunk(fn):
     """ctypes thunk around fn(kk, delta_cdm, Nmodes) -> (logknu, delta_nu_ratio, nu_prefac, MtotbyMcdm).  An exception in fn (or a table
     of the wrong length) becomes the non-zero return the engine reports as an error; it is kept in thunk.error."""
@@ -614,6 +622,92 @@ class Engine:
         n = pos.shape[0]
         self._keep["bind"] = (pos, mass, type)
         self._ck(self.lib.mpg_dev_bind_particles(self.h, C.c_int64(n), _ptr(pos), _ptr(mass), _ptr(type), C.c_double(BoxSize)))
+
+    # ------------------------------------------------------------------ lensing potential planes (write_plane, plane.c:572-683)
+    def _plane_params(self, BoxSize, Resolution, Normals, atime, comoving_distance, HubbleParam, omega_source, Thickness=0.0, CutPoints=None,
+                      left_corner=(0.0, 0.0, 0.0), CurrentParticleOffset=(0.0, 0.0, 0.0), nu_response=None, BoxSize_in_MPC=0.0):
+        """mpg_plane_params from keywords; returns (struct, objects to keep alive, ncuts, nnormals, the callback thunk or None).
+        BoxSize None: the box of the particles bound to the engine (the device and resident calls).  The parameters are checked by the
+        C entry the struct goes to, not here.
+        nu_response: fn(kk, delta_cdm, Nmodes) -> (logknu, delta_nu_ratio, nu_prefac, MtotbyMcdm) as for gravpm_set_nu_response, called
+        once by the planes call (PlaneMassiveNuCorrection); None: no correction."""
+        cuts = np.zeros(0) if CutPoints is None else np.ascontiguousarray(CutPoints, np.float64).reshape(-1)
+        nrm = np.ascontiguousarray(Normals, np.int32).reshape(-1)
+        thunk = None if nu_response is None else _nu_response_thunk(nu_response)
+        pp = PlaneParams(int(Resolution), float(Thickness), len(cuts), cuts.ctypes.data_as(C.POINTER(C.c_double)), len(nrm),
+                         nrm.ctypes.data_as(C.POINTER(C.c_int)), (C.c_double * 3)(*[float(x) for x in left_corner]), float(atime),
+                         float(comoving_distance), float(HubbleParam), float(omega_source),
+                         (C.c_double * 3)(*[float(x) for x in CurrentParticleOffset]), thunk if thunk is not None else NU_RESPONSE_FN(), None,
+                         float(BoxSize_in_MPC))
+        nc = C.c_int64(0)
+        self.lib.mpg_plane_count.argtypes = [C.c_void_p, C.POINTER(PlaneParams), C.c_double, C.POINTER(C.c_int64)]
+        self._ck(self.lib.mpg_plane_count(self.h, C.byref(pp), C.c_double(0.0 if BoxSize is None else BoxSize), C.byref(nc)))
+        return pp, (cuts, nrm, thunk), int(nc.value), len(nrm), thunk
+
+    def _plane_ck(self, rc, thunk):
+        if rc:
+            msg = self.lib.mpg_last_error().decode()
+            if thunk is not None and thunk.error is not None:
+                msg += " | callback: %r" % (thunk.error,)
+            raise EngineError(msg)
+
+    def set_plane_counter_budget(self, nbytes):
+        """mpg_set_plane_counter_budget: the counter memory a planes call may hold (0: a quarter of the free device memory)"""
+        self.lib.mpg_set_plane_counter_budget.argtypes = [C.c_void_p, C.c_int64]
+        self._ck(self.lib.mpg_set_plane_counter_budget(self.h, C.c_int64(nbytes)))
+
+    def dev_potential_planes(self, Resolution, Normals, flags=None, out=None, **kw):
+        """mpg_dev_potential_planes on the bound particles; flags: uint8 device tensor (bit 0 IsGarbage, bit 1 Swallowed) or None.
+        Keywords as _plane_params; out: a tensor of the result's shape to write into.  Returns (planes [ncuts, nnormals, R, R] float64
+        device tensor, npart [ncuts, nnormals] int64)."""
+        import torch
+        pos = self._keep["bind"][0]
+        pp, keep, nc, nn, thunk = self._plane_params(None, Resolution, Normals, **kw)
+        shape = (nc, nn, max(pp.Resolution, 0), max(pp.Resolution, 0))
+        planes = torch.empty(shape, dtype=torch.float64, device=pos.device) if out is None else out
+        if tuple(planes.shape) != shape or planes.dtype != torch.float64 or not planes.is_contiguous():
+            raise EngineError("dev_potential_planes: out must be a contiguous float64 tensor of shape %s" % (shape,))
+        npart = np.zeros((nc, nn), np.int64)
+        self.lib.mpg_dev_potential_planes.argtypes = [C.c_void_p, C.POINTER(PlaneParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        self._plane_ck(self.lib.mpg_dev_potential_planes(self.h, C.byref(pp), _ptr(flags), _ptr(planes), npart.ctypes.data_as(C.c_void_p)), thunk)
+        return planes, npart
+
+    def dev_plane_counts(self, Resolution, Normals, flags=None, out=None, **kw):
+        """mpg_dev_plane_counts: the counting pass alone.  Returns (counts [ncuts, nnormals, R, R] device tensor holding the 32-bit
+        counters (as int32), the number of active particles among the bound rows)."""
+        import torch
+        pos = self._keep["bind"][0]
+        pp, keep, nc, nn, thunk = self._plane_params(None, Resolution, Normals, **kw)
+        shape = (nc, nn, max(pp.Resolution, 0), max(pp.Resolution, 0))
+        counts = torch.empty(shape, dtype=torch.int32, device=pos.device) if out is None else out
+        if tuple(counts.shape) != shape or counts.dtype != torch.int32 or not counts.is_contiguous():
+            raise EngineError("dev_plane_counts: out must be a contiguous int32 tensor of shape %s" % (shape,))
+        nact = C.c_int64(0)
+        self.lib.mpg_dev_plane_counts.argtypes = [C.c_void_p, C.POINTER(PlaneParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        self._plane_ck(self.lib.mpg_dev_plane_counts(self.h, C.byref(pp), _ptr(flags), _ptr(counts), C.byref(nact)), thunk)
+        return counts, int(nact.value)
+
+    def potential_planes(self, P, BoxSize, Resolution, Normals, **kw):
+        """mpg_potential_planes on a host particle table (PARTICLE_DTYPE).  Returns (planes [ncuts, nnormals, R, R] float64, npart)."""
+        v = self._view(P)
+        pp, keep, nc, nn, thunk = self._plane_params(BoxSize, Resolution, Normals, **kw)
+        planes = np.zeros((nc, nn, max(pp.Resolution, 0), max(pp.Resolution, 0)))
+        npart = np.zeros((nc, nn), np.int64)
+        self.lib.mpg_potential_planes.argtypes = [C.c_void_p, C.POINTER(ParticleView), C.c_double, C.POINTER(PlaneParams), C.c_void_p, C.c_void_p]
+        self._plane_ck(self.lib.mpg_potential_planes(self.h, C.byref(v), C.c_double(BoxSize), C.byref(pp), planes.ctypes.data_as(C.c_void_p),
+                                                     npart.ctypes.data_as(C.c_void_p)), thunk)
+        return planes, npart
+
+    def resident_potential_planes(self, P, Resolution, Normals, **kw):
+        """mpg_resident_potential_planes on the resident table (resident_begin).  Returns host arrays as potential_planes."""
+        v = self._view(P)
+        pp, keep, nc, nn, thunk = self._plane_params(None, Resolution, Normals, **kw)
+        planes = np.zeros((nc, nn, max(pp.Resolution, 0), max(pp.Resolution, 0)))
+        npart = np.zeros((nc, nn), np.int64)
+        self.lib.mpg_resident_potential_planes.argtypes = [C.c_void_p, C.POINTER(ParticleView), C.POINTER(PlaneParams), C.c_void_p, C.c_void_p]
+        self._plane_ck(self.lib.mpg_resident_potential_planes(self.h, C.byref(v), C.byref(pp), planes.ctypes.data_as(C.c_void_p),
+                                                              npart.ctypes.data_as(C.c_void_p)), thunk)
+        return planes, npart
 
     def dev_gravpm_force(self, gravpm, potential=None):
         self._ck(self.lib.mpg_dev_gravpm_force(self.h, _ptr(gravpm), _ptr(potential)))
