@@ -50,8 +50,12 @@ __device__ __forceinline__ int wrapi(int i, int n) { return i < 0 ? i + n : (i >
 // slab owner(s) of a particle's CIC cloud: the planes floor(x / cellsize) and that + 1 (periodic), P planes per rank
 __device__ __forceinline__ void pm_owners(double x, double cellsize, int nmesh, int P, int &o0, int &o1)
 {
-    const int ix = (int)floor(x / cellsize);
-    o0 = wrapi(ix, nmesh) / P;
+    int ix = (int)floor(x / cellsize);
+    if((unsigned)ix >= (unsigned)nmesh) { // the base cell folds by any number of boxes, as fold() of pm.hip: the owner is a rank that exists
+        ix %= nmesh;
+        ix = ix < 0 ? ix + nmesh : ix;
+    }
+    o0 = ix / P;
     o1 = wrapi(ix + 1, nmesh) / P;
 }
 

@@ -26,10 +26,32 @@ namespace mpg {
 
 __device__ __forceinline__ int wrap(int i, int n)
 {
-    // periodic wrap of petapm.c:903-918 (cells -1 .. Nmesh+1 can occur)
+    // periodic wrap of petapm.c:903-918 by one box: for a folded base cell plus the CIC corner or a stencil offset (-2 .. n + 2)
     i = (i >= n) ? i - n : i;
     i = (i < 0) ? i + n : i;
     return i;
+}
+
+__device__ __forceinline__ int fold(int i, int n)
+{
+    // the same wrap for a particle's BASE cell, by any number of boxes as the reference's while loops do (petapm.c:905-906, 917-918):
+    // a position outside [0, BoxSize] must not become an index outside the mesh.  Once per axis and particle, and the division only
+    // for a cell outside [0, n): particles inside the box pay a compare.  (The slab kernels use it axis by axis.)
+    if((unsigned)i >= (unsigned)n) {
+        i %= n;
+        i = (i < 0) ? i + n : i;
+    }
+    return i;
+}
+
+__device__ __forceinline__ void fold3(int ic[3], int n)
+{
+    // fold() of the three axes behind ONE branch (the single-mesh kernels of every PM step: three branches cost the read-out 4 %)
+    if(((unsigned)ic[0] >= (unsigned)n) | ((unsigned)ic[1] >= (unsigned)n) | ((unsigned)ic[2] >= (unsigned)n)) {
+#pragma unroll
+        for(int k = 0; k < 3; k++)
+            ic[k] = fold(ic[k], n);
+    }
 }
 
 // put_particle_to_mesh through pm_iterate_one (petapm.c:955-1020, :1138-1144)
@@ -51,6 +73,7 @@ __global__ void __launch_bounds__(256) k_cic_deposit(int64_t n, const double *__
         ic[k] = (int)fl;
         res[k] = tmp - fl;
     }
+    fold3(ic, nmesh);
     const double m = (double)mass[i];
 #pragma unroll
     for(int c = 0; c < 8; c++) {
@@ -78,10 +101,15 @@ __global__ void __launch_bounds__(256) k_cell_keys(int64_t n, const double *__re
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= n)
         return;
+    int ic[3];
+#pragma unroll
+    for(int k = 0; k < 3; k++)
+        ic[k] = (int)floor(pos[3 * i + k] / cellsize);
+    fold3(ic, nmesh);
     unsigned long long lin = 0;
 #pragma unroll
     for(int k = 0; k < 3; k++)
-        lin = lin * (unsigned long long)nmesh + (unsigned long long)wrap((int)floor(pos[3 * i + k] / cellsize), nmesh);
+        lin = lin * (unsigned long long)nmesh + (unsigned long long)ic[k];
     keys[i] = (active && !active[i]) ? ~0ull : lin; // inactive particles sort to the end and are skipped
     idx[i] = (int)i;
 }
@@ -111,6 +139,7 @@ __global__ void __launch_bounds__(256) k_cic_deposit_sorted(int64_t n, const uns
                 ic[d] = (int)fl;
                 res[d] = tmp - fl;
             }
+            fold3(ic, nmesh);
             const double m = (double)mass[i];
 #pragma unroll
             for(int c = 0; c < 8; c++) {
@@ -437,6 +466,7 @@ __global__ void __launch_bounds__(256) k_cic_readout(int64_t n, const double *__
         ic[k] = (int)fl;
         res[k] = tmp - fl;
     }
+    fold3(ic, nmesh);
     double acc = 0;
 #pragma unroll
     for(int c = 0; c < 8; c++) {
@@ -485,15 +515,20 @@ __global__ void __launch_bounds__(256) k_cic_readout_stencil(int64_t n, const do
     size_t wi[3][6]; // wrapped cell indices ic-2 .. ic+3 per axis, times the axis stride
     double res[3];
     const size_t stride[3] = {(size_t)nmesh * nmesh, (size_t)nmesh, 1};
+    int ic[3];
 #pragma unroll
     for(int k = 0; k < 3; k++) {
         const double tmp = pos[3 * i + k] / cellsize;
         const double fl = floor(tmp);
         res[k] = tmp - fl;
-        const int c = wrap((int)fl, nmesh);
+        ic[k] = (int)fl;
+    }
+    fold3(ic, nmesh);
+#pragma unroll
+    for(int k = 0; k < 3; k++) {
 #pragma unroll
         for(int j = 0; j < 6; j++)
-            wi[k][j] = (size_t)wrap(c - 2 + j, nmesh) * stride[k];
+            wi[k][j] = (size_t)wrap(ic[k] - 2 + j, nmesh) * stride[k];
     }
     const double c1 = 2.0 / 3.0, c2 = 1.0 / 12.0;
     double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
@@ -982,8 +1017,8 @@ __global__ void __launch_bounds__(256) k_cic_deposit_slab(int64_t n, const doubl
         return;
     const double tx = pos[3 * i + 0] / cellsize;
     const double fx = floor(tx);
-    const int ix = (int)fx;
-    const int p0 = wrap(ix, nmesh) - x0, p1 = wrap(ix + 1, nmesh) - x0; // planes relative to the slab
+    const int ix = fold((int)fx, nmesh);
+    const int p0 = ix - x0, p1 = wrap(ix + 1, nmesh) - x0; // planes relative to the slab
     const bool in0 = p0 >= 0 && p0 < P, in1 = p1 >= 0 && p1 < P;
     if(!in0 && !in1)
         return;
@@ -994,7 +1029,7 @@ __global__ void __launch_bounds__(256) k_cic_deposit_slab(int64_t n, const doubl
     for(int k = 0; k < 2; k++) {
         const double tmp = pos[3 * i + 1 + k] / cellsize;
         const double fl = floor(tmp);
-        ic[k] = (int)fl;
+        ic[k] = fold((int)fl, nmesh);
         res[k] = tmp - fl;
     }
     const double m = (double)mass[i];
@@ -1216,7 +1251,7 @@ __global__ void __launch_bounds__(256) k_cic_readout_slab_stencil(int64_t nt, co
         const double tmp = pos[3 * i] / cellsize;
         const double fl = floor(tmp);
         res[0] = tmp - fl;
-        const int px = wrap((int)fl, nmesh) - x0;
+        const int px = fold((int)fl, nmesh) - x0;
         if(px < 0 || px >= P) { // not this rank's slab: an error in a caller's target list
             if(targets)
                 atomicExch(err, 1u);
@@ -1231,7 +1266,7 @@ __global__ void __launch_bounds__(256) k_cic_readout_slab_stencil(int64_t nt, co
         const double tmp = pos[3 * i + k] / cellsize;
         const double fl = floor(tmp);
         res[k] = tmp - fl;
-        const int c = wrap((int)fl, nmesh);
+        const int c = fold((int)fl, nmesh);
 #pragma unroll
         for(int j = 0; j < 6; j++)
             wi[k][j] = (size_t)wrap(c - 2 + j, nmesh) * stride[k];
