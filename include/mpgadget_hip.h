@@ -298,6 +298,60 @@ int mpg_hydro_force(mpg_engine *eng, const mpg_particle_view *pv, const mpg_sph_
  * [2] successful distance tests / hydro pairs evaluated, [3] candidates distance-tested */
 int mpg_sph_get_stats(mpg_engine *eng, int64_t stats[4]);
 
+/* ---- DM velocity dispersion of gas and black holes: winds_find_vel_disp, libgadget/veldisp.c:375-466 (run.c:646-647) ---------
+ * For every active gas particle that may form stars during the next PM step (winds_veldisp_haswork, veldisp.c:348-371:
+ * Density / densfac^3 >= 0.1 sfr_density_threshold, densfac = min(1, (Hsml + DtHsml ddrift) / Hsml)) the radius loop of
+ * treewalk_do_hsml_loop finds the 40 +- 1 nearest DM particles - five trial radii per pass, ngb_narrow_down between the passes - and
+ * stores their one-dimensional velocity dispersion, Hubble flow included, in vdisp; every active black hole receives the dispersion
+ * of the DM inside its Hsml (blackhole_veldisp, one pass).  The engine does not evaluate the star-formation model: the caller passes
+ * sfr_density_threshold(Time) and ddrift = get_exact_drift_factor(Ti_Current, Ti_Current + PM_length).  The kick factors of
+ * DM_VelPred (density.c:106-112) are FgravkickB and gravkicks[] of mpg_sph_times; its other members are not read.
+ * Garbage and swallowed particles carry type 7 (as everywhere in the dev calls); the host forms derive it from the flags.
+ * vdisp is in/out, in particle order: entries of gas targets are SphP.VDisp, of black-hole targets BHP.VDisp; an entry is written
+ * only where the reference writes it (a positive variance; a black hole with at least one DM neighbour), every other entry is
+ * left as it was.  vel, hsml, density and vdisp are required; NULL for gacc, gpm, tb_grav, dthsml means zero.
+ * THE TREE: when a gas particle qualifies or the table holds a black hole, the call rebuilds the engine's current tree as the tree
+ * of the DM particles (DMMASK, no moments), as the reference does (veldisp.c:414); that is the current tree when the call returns,
+ * so a density / hydro loop after it needs its gas tree rebuilt (mpg_dev_force_tree_rebuild_mask; the host forms mpg_density /
+ * mpg_set_init_hsml rebuild it themselves).  When nothing qualifies and there is no black hole, no tree is built or demanded,
+ * nothing is written and the current tree stays.  More than 400 iterations (the reference's endrun(1155)) is an error return.
+ * One rank only: there is no mpg_dist_* form. */
+typedef struct mpg_veldisp_params {
+    double Time;                  /* scale factor a */
+    double hubble;                /* hubble_function(a) */
+    double ddrift;                /* drift factor over the next PM step */
+    double sfr_density_threshold; /* sfr_density_threshold(Time); the engine takes a tenth of it */
+} mpg_veldisp_params;
+typedef struct mpg_veldisp_arrays {
+    const double *vel;            /* [n][3]  P.Vel */
+    const double *gacc;           /* [n][3]  P.FullTreeGravAccel */
+    const double *gpm;            /* [n][3]  P.GravPM */
+    const uint8_t *tb_grav;       /* P.TimeBinGravity */
+    const double *hsml;           /* P.Hsml */
+    const double *dthsml;         /* P.DtHsml */
+    const double *density;        /* SphP.Density */
+    double *vdisp;                /* in/out  SphP.VDisp / BHP.VDisp */
+} mpg_veldisp_arrays;
+/* on the bound particles; d_active NULL = all particles */
+int mpg_dev_find_vel_disp(mpg_engine *eng, const mpg_veldisp_arrays *A, const mpg_sph_times *T, const mpg_veldisp_params *par, const int *d_active,
+                          int64_t nactive);
+/* host form: `pv` supplies Pos / Mass / Type / flags, `A` holds HOST arrays in particle order (the shim gathers SphP / BHP into them) */
+int mpg_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_veldisp_arrays *A, const mpg_sph_times *T,
+                      const mpg_veldisp_params *par, const int *ActiveParticle, int64_t NumActiveParticle);
+/* on a resident gas run (mpg_resident_sph_begin): Vel, FullTreeGravAccel, GravPM, TimeBinGravity, Hsml, DtHsml and Density are the
+ * resident ones; only `vdisp` (a HOST array of n entries, in/out) travels */
+int mpg_resident_sph_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, const mpg_sph_times *T, const mpg_veldisp_params *par,
+                                   const int *ActiveParticle, int64_t NumActiveParticle, double *vdisp);
+/* statistics of the last call: [0] iterations of the gas loop, [1] gas targets summed over the iterations, [2] candidates found inside
+ * the search radius (gas and black-hole passes), [3] candidates distance-tested, [4] gas targets that ended through the tight bracket
+ * (Right - Left <= 5e-6 Left) with a count outside 39 .. 41 */
+int mpg_veldisp_get_stats(mpg_engine *eng, int64_t stats[5]);
+/* the loop's per-target results of the last call into host arrays of n entries (each may be NULL): the trial radius the final sums were
+ * taken at (a black hole: its Hsml), the passes the target took (-1: not a target), its final count and maxcmpte; and the queue length
+ * of the first queue_capacity iterations (0 beyond the last) */
+int mpg_veldisp_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iterations, int32_t *numngb, int32_t *maxcmpte, int64_t *queue_lengths,
+                       int64_t queue_capacity);
+
 /* ---- introspection (tests, bench roofline accounting) ----------------------------------------- */
 typedef struct mpg_tree_stats {
     int64_t NumParticles; /* particles in the tree */

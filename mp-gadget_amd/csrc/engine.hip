@@ -3080,6 +3080,149 @@ int mpg_sph_get_stats(mpg_engine *eng, int64_t stats[4])
     API_END
 }
 
+/* ------------------------------ DM velocity dispersion (veldisp.c) ------------------------------ */
+
+int mpg_dev_find_vel_disp(mpg_engine *eng, const mpg_veldisp_arrays *A, const mpg_sph_times *T, const mpg_veldisp_params *par, const int *d_active,
+                          int64_t nactive)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A && T && par, "null argument");
+    MPG_CHECK(A->vel && A->hsml && A->density && A->vdisp, "find_vel_disp: the arrays vel, hsml, density and vdisp are required");
+    MPG_CHECK(eng->d_pos || eng->n == 0, "find_vel_disp: no particles bound");
+    MPG_HIP(hipSetDevice(eng->device));
+    VdispView v{};
+    v.pos = eng->d_pos;
+    v.type = eng->d_type;
+    v.vel = A->vel;
+    v.gacc = A->gacc;
+    v.gpm = A->gpm;
+    v.tb_grav = A->tb_grav;
+    v.hsml = A->hsml;
+    v.dthsml = A->dthsml;
+    v.density = A->density;
+    v.vdisp = A->vdisp;
+    VdispScalars S;
+    S.box = eng->box;
+    S.hubble_a2 = par->hubble * par->Time * par->Time; // veldisp.c:265
+    S.ddrift = par->ddrift;
+    S.dens_threshold = 0.1 * par->sfr_density_threshold; // veldisp.c:362
+    const uint8_t *flags = eng->sph.mark_active(d_active, nactive, eng->n, eng->stream);
+    // nothing qualifies and the table holds no black hole: nothing is built, nothing is written (veldisp.c:413)
+    if(eng->vdisp.make_queues(v, S, flags, eng->n, eng->stream)) {
+        // force_tree_rebuild_mask(tree, ddecomp, DMMASK, NULL), veldisp.c:414: the engine's current tree is, from here on, the tree of the
+        // DM particles without moments
+        if(mpg_dev_force_tree_rebuild_mask(eng, 2 /* DMMASK */, 0))
+            throw Error(g_err);
+        if(eng->vdisp.nbh > 0 || eng->vdisp.ngas > 0)
+            eng->vdisp.search(eng->tree, v, *T, S, eng->stream);
+    }
+    API_END
+}
+
+int mpg_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_veldisp_arrays *A, const mpg_sph_times *T,
+                      const mpg_veldisp_params *par, const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A && T && par, "null argument");
+    MPG_CHECK(A->vel && A->hsml && A->density && A->vdisp, "find_vel_disp: the arrays vel, hsml, density and vdisp are required");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    const size_t n = (size_t)pv->n;
+    // fields of mpg_veldisp_arrays in order: vel[3], gacc[3], gpm[3], tb_grav (bytes), hsml, dthsml, density, vdisp
+    const int width[8] = {3, 3, 3, 0, 1, 1, 1, 1};
+    void *const *hp = (void *const *)A;
+    mpg_veldisp_arrays d;
+    void **dp = (void **)&d;
+    for(int f = 0; f < 8; f++) {
+        dp[f] = nullptr;
+        if(!hp[f])
+            continue;
+        if(width[f] == 0) {
+            eng->vd_stage_tb.reserve(n + 1);
+            dp[f] = eng->vd_stage_tb.p;
+            MPG_HIP(hipMemcpyAsync(dp[f], hp[f], n, hipMemcpyHostToDevice, eng->stream));
+        }
+        else {
+            eng->vd_stage[f].reserve(n * width[f] + 1);
+            dp[f] = eng->vd_stage[f].p;
+            MPG_HIP(hipMemcpyAsync(dp[f], hp[f], n * width[f] * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        }
+    }
+    const int *d_act = nullptr;
+    if(ActiveParticle) {
+        eng->s_active.reserve((size_t)NumActiveParticle + 1);
+        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
+        d_act = eng->s_active.p;
+    }
+    if(mpg_dev_find_vel_disp(eng, &d, T, par, d_act, NumActiveParticle))
+        throw Error(g_err);
+    MPG_HIP(hipMemcpyAsync(A->vdisp, d.vdisp, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}
+
+int mpg_resident_sph_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, const mpg_sph_times *T, const mpg_veldisp_params *par,
+                                   const int *ActiveParticle, int64_t NumActiveParticle, double *vdisp)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && T && par && vdisp, "null argument");
+    resident_sph_check(eng, pv);
+    const size_t n = (size_t)pv->n;
+    const mpg_sph_arrays &r = eng->res_sph_dev;
+    mpg_veldisp_arrays d;
+    d.vel = r.vel;
+    d.gacc = r.gacc;
+    d.gpm = r.gpm;
+    d.tb_grav = r.tb_grav;
+    d.hsml = r.hsml;
+    d.dthsml = r.dthsml;
+    d.density = r.density;
+    eng->vd_stage[7].reserve(n + 1);
+    d.vdisp = eng->vd_stage[7].p;
+    MPG_HIP(hipMemcpyAsync(d.vdisp, vdisp, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+    const int *d_act = resident_active(eng, ActiveParticle, NumActiveParticle);
+    if(mpg_dev_find_vel_disp(eng, &d, T, par, d_act, NumActiveParticle))
+        throw Error(g_err);
+    MPG_HIP(hipMemcpyAsync(vdisp, d.vdisp, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}
+
+int mpg_veldisp_get_stats(mpg_engine *eng, int64_t stats[5])
+{
+    API_BEGIN
+    MPG_CHECK(eng && stats, "null argument");
+    stats[0] = eng->vdisp.last_iterations;
+    stats[1] = eng->vdisp.last_targets;
+    stats[2] = eng->vdisp.last_neighbours;
+    stats[3] = eng->vdisp.last_candidates;
+    stats[4] = eng->vdisp.last_tight;
+    API_END
+}
+
+int mpg_veldisp_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iterations, int32_t *numngb, int32_t *maxcmpte, int64_t *queue_lengths,
+                       int64_t queue_capacity)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    VdispEngine &V = eng->vdisp;
+    MPG_CHECK(n == V.n_state, "mpg_veldisp_export: n is not the particle number of the last find_vel_disp call");
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    if(radius && n > 0)
+        MPG_HIP(hipMemcpy(radius, V.evalradius.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if(iterations && n > 0)
+        MPG_HIP(hipMemcpy(iterations, V.niter.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(numngb && n > 0)
+        MPG_HIP(hipMemcpy(numngb, V.ngb.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(maxcmpte && n > 0)
+        MPG_HIP(hipMemcpy(maxcmpte, V.maxcmpte.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(queue_lengths)
+        for(int64_t k = 0; k < queue_capacity; k++)
+            queue_lengths[k] = k < (int64_t)V.queue_lengths.size() ? V.queue_lengths[k] : 0;
+    API_END
+}
+
 /* ------------------------------ introspection ------------------------------ */
 
 int mpg_tree_get_stats(mpg_engine *eng, mpg_tree_stats *st)

@@ -5,6 +5,7 @@
 #include "mpg_common.h"
 #include "pm.h"
 #include "sph.h"
+#include "veldisp.h"
 #include "timestep.h"
 #include "peano.h"
 #include "planes.h"
@@ -282,6 +283,10 @@ struct mpg_engine {
     std::thread prefetch_thread;
     std::string prefetch_error;
     mpg_particle_view prefetch_view{};
+    // DM velocity dispersion (veldisp.c): the loop's state, and the staging of the host form's arrays (fields of mpg_veldisp_arrays)
+    VdispEngine vdisp;
+    DevBuf<double> vd_stage[8];
+    DevBuf<uint8_t> vd_stage_tb;
     void prefetch_join()
     {
         if(prefetch_thread.joinable())

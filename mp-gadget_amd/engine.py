@@ -93,6 +93,19 @@ class SphArraysC(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in SPH_ARRAY_FIELDS]
 
 
+VELDISP_ARRAY_FIELDS = ("vel", "gacc", "gpm", "tb_grav", "hsml", "dthsml", "density", "vdisp")
+
+
+class VelDispArraysC(C.Structure):
+    """mpg_veldisp_arrays"""
+    _fields_ = [(k, C.c_void_p) for k in VELDISP_ARRAY_FIELDS]
+
+
+class VelDispParams(C.Structure):
+    """mpg_veldisp_params"""
+    _fields_ = [("Time", C.c_double), ("hubble", C.c_double), ("ddrift", C.c_double), ("sfr_density_threshold", C.c_double)]
+
+
 DENSITY_KERNEL_CUBIC_SPLINE, DENSITY_KERNEL_QUINTIC_SPLINE, DENSITY_KERNEL_QUARTIC_SPLINE = 1, 2, 4   # densitykernel.h:17-21
 
 _lib = None
@@ -986,6 +999,59 @@ class Engine:
         c = (C.c_int64 * 4)()
         self._ck(self.lib.mpg_sph_get_stats(self.h, c))
         return dict(iterations=c[0], targets=c[1], interactions=c[2], candidates=c[3])
+
+    # ------------------------------------------------------------------ DM velocity dispersion (winds_find_vel_disp, veldisp.c:375-466)
+    # `arrays` maps the field names of mpg_veldisp_arrays to device tensors (dev form) / contiguous numpy arrays (host form); vdisp is
+    # in/out.  After a call that found work the engine's current tree is the DM tree (include/mpgadget_hip.h).
+    def dev_find_vel_disp(self, arrays, times, Time, hubble, ddrift, sfr_density_threshold, active=None):
+        a = VelDispArraysC()
+        for k in VELDISP_ARRAY_FIELDS:
+            t = arrays.get(k)
+            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        p = VelDispParams(Time, hubble, ddrift, sfr_density_threshold)
+        nact = 0 if active is None else active.shape[0]
+        self._ck(self.lib.mpg_dev_find_vel_disp(self.h, C.byref(a), C.byref(times), C.byref(p), _ptr(active), C.c_int64(nact)))
+
+    def find_vel_disp(self, P, BoxSize, arrays, times, Time, hubble, ddrift, sfr_density_threshold, ActiveParticle=None):
+        v = self._view(P)
+        a = VelDispArraysC()
+        for k in VELDISP_ARRAY_FIELDS:
+            t = arrays.get(k)
+            if t is not None:
+                want = np.uint8 if k == "tb_grav" else np.float64
+                if t.dtype != want or not t.flags["C_CONTIGUOUS"]:
+                    raise EngineError("velocity-dispersion host array %s must be contiguous %s" % (k, want.__name__))
+            setattr(a, k, None if t is None else t.ctypes.data)
+        p = VelDispParams(Time, hubble, ddrift, sfr_density_threshold)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_find_vel_disp(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), C.byref(p),
+                                            None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+
+    def resident_sph_find_vel_disp(self, P, times, Time, hubble, ddrift, sfr_density_threshold, vdisp, ActiveParticle=None):
+        """on a resident gas run: only `vdisp` (numpy float64 [n], in/out) travels"""
+        v = self._view(P)
+        if vdisp.dtype != np.float64 or not vdisp.flags["C_CONTIGUOUS"] or len(vdisp) != len(P):
+            raise EngineError("vdisp must be a contiguous float64 array of len(P)")
+        p = VelDispParams(Time, hubble, ddrift, sfr_density_threshold)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_resident_sph_find_vel_disp(self.h, C.byref(v), C.byref(times), C.byref(p),
+                                                         None if act is None else act.ctypes.data_as(C.c_void_p),
+                                                         C.c_int64(0 if act is None else len(act)), C.c_void_p(vdisp.ctypes.data)))
+
+    def veldisp_stats(self):
+        c = (C.c_int64 * 5)()
+        self._ck(self.lib.mpg_veldisp_get_stats(self.h, c))
+        return dict(iterations=c[0], targets=c[1], neighbours=c[2], candidates=c[3], tight=c[4])
+
+    def veldisp_export(self, n):
+        """per-particle results of the last call's loop (iterations -1: not a target) and the queue length of every iteration"""
+        d = dict(radius=np.zeros(n), iterations=np.zeros(n, np.int32), numngb=np.zeros(n, np.int32), maxcmpte=np.zeros(n, np.int32))
+        ql = np.zeros(max(self.veldisp_stats()["iterations"], 1), np.int64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.mpg_veldisp_export(self.h, C.c_int64(n), p(d["radius"]), p(d["iterations"]), p(d["numngb"]), p(d["maxcmpte"]),
+                                             p(ql), C.c_int64(len(ql))))
+        d["queue_lengths"] = [int(x) for x in ql[:self.veldisp_stats()["iterations"]]]
+        return d
 
     # ------------------------------------------------------------------ introspection
     def tree_stats(self):

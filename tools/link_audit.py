@@ -29,8 +29,9 @@ RENAMES = {
     "timestep.c": ["apply_half_kick", "apply_PM_half_kick", "find_hydro_timesteps", "find_timesteps", "apply_hydro_half_kick",
                    "hierarchical_gravity_and_timesteps", "hierarchical_gravity_accelerations"],
     "drift.c": ["drift_all_particles"],
+    "veldisp.c": ["winds_find_vel_disp"],
 }
-SHIM_C = ["gravity-hip.c", "sph-hip.c", "forcetree-hip.c", "timestep-hip.c", "mpg_mpi_comm.c", "mpg_rccl_mpi.c"]
+SHIM_C = ["gravity-hip.c", "sph-hip.c", "forcetree-hip.c", "timestep-hip.c", "veldisp-hip.c", "mpg_mpi_comm.c", "mpg_rccl_mpi.c"]
 EXTERNAL = [("pfft", r"^pfft_"), ("fftw", r"^fftw_"), ("gsl", r"^gsl_"), ("mpi", r"^P?MPI_"), ("openmp", r"^(GOMP_|omp_)"),
             ("hdf5", r"^H5")]
 

@@ -12,8 +12,8 @@
 #   1. copy the checkout (the reference tree itself is never modified);
 #   2. copy shim/*.c, shim/*.h and include/mpgadget_hip.h into <copy>/libgadget/;
 #   3. patch <copy>/libgadget/Makefile: drop gravpm.o gravshort-tree.o gravshort-pair.o gravity.o from GADGET_OBJS and add the shim
-#      objects; rename the five tree constructors in forcetree.o and the eight integrator entry points in timestep.o / drift.o
-#      (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
+#      objects; rename the five tree constructors in forcetree.o, the eight integrator entry points in timestep.o / drift.o and
+#      winds_find_vel_disp in veldisp.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
 #   4. add the two parameter hooks (set_densitypar, set_hydro_params), the accessors of mpg_shim.h and the
 #      mpg_shim_particles_changed() calls listed in INTEGRATION.md ("Where P[] is reordered") with sed;
 #   5. build the library of this repository, then `make` in the copy with LIBS += -L<repo>/mp-gadget_amd -lmpgadget_hip -lmpi.
@@ -22,11 +22,11 @@ REF=${1:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 WORK=${2:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 CHECK=${3:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
+SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
 SHIM_H="mpg_shim.h mpg_shim_epoch.h mpg_mpi_comm.h"
 REF_FILES="libgadget/Makefile libgadget/gravpm.c libgadget/gravshort-tree.c libgadget/gravshort-pair.c libgadget/gravity.c libgadget/forcetree.c
            libgadget/density.c libgadget/hydra.c libgadget/timestep.c libgadget/drift.c libgadget/timebinmgr.c libgadget/run.c libgadget/domain.c
-           libgadget/exchange.c libgadget/fof.c libgadget/slotsmanager.c gadget/Makefile Makefile.rules Options.mk.example"
+           libgadget/exchange.c libgadget/fof.c libgadget/slotsmanager.c libgadget/veldisp.c libgadget/sfr_eff.c gadget/Makefile Makefile.rules Options.mk.example"
 
 echo "== 0. inputs"
 for f in $REF_FILES; do test -f "$REF/$f" || { echo "missing in the reference checkout: $f"; exit 1; }; done
@@ -62,7 +62,7 @@ echo "== 3. libgadget/Makefile"
 MK="$T/libgadget/Makefile"
 sed -i -e 's/\bgravshort-tree\.o gravshort-pair\.o hydra\.o/hydra.o/' -e 's/\bgravpm\.o powerspectrum\.o/powerspectrum.o/' \
        -e 's/\bpetapm\.o gravity\.o/petapm.o/' "$MK"
-sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
+sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
 cat >> "$MK" <<MKEOF
 
 # ---- MP-Gadget on libmpgadget_hip (tools/link_reference.sh)
@@ -70,6 +70,7 @@ CFLAGS += -DMPGADGET_HIP -I$ROOT/include
 .objs/forcetree.o: CFLAGS += -Dforce_tree_full=cpu_force_tree_full -Dforce_tree_rebuild_mask=cpu_force_tree_rebuild_mask -Dforce_tree_active_moments=cpu_force_tree_active_moments -Dforce_tree_calc_moments=cpu_force_tree_calc_moments -Dforce_tree_free=cpu_force_tree_free
 .objs/timestep.o: CFLAGS += -Dapply_half_kick=cpu_apply_half_kick -Dapply_PM_half_kick=cpu_apply_PM_half_kick -Dfind_hydro_timesteps=cpu_find_hydro_timesteps -Dfind_timesteps=cpu_find_timesteps -Dapply_hydro_half_kick=cpu_apply_hydro_half_kick -Dhierarchical_gravity_and_timesteps=cpu_hierarchical_gravity_and_timesteps -Dhierarchical_gravity_accelerations=cpu_hierarchical_gravity_accelerations
 .objs/drift.o: CFLAGS += -Ddrift_all_particles=cpu_drift_all_particles
+.objs/veldisp.o: CFLAGS += -Dwinds_find_vel_disp=cpu_winds_find_vel_disp
 MKEOF
 
 echo "== 4. hooks in the reference sources (INTEGRATION.md lists them; each is one line)"
@@ -143,12 +144,13 @@ PYEOF
 
 if [ "$CHECK" = "--check" ]; then
     # the patched reference files and the renamed objects still parse (nothing is compiled to an object, linked or run)
-    for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c; do
+    for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c; do
         extra=""
         case $f in
             forcetree.c) extra="-Dforce_tree_full=cpu_force_tree_full -Dforce_tree_rebuild_mask=cpu_force_tree_rebuild_mask -Dforce_tree_active_moments=cpu_force_tree_active_moments -Dforce_tree_calc_moments=cpu_force_tree_calc_moments -Dforce_tree_free=cpu_force_tree_free";;
             timestep.c) extra="-Dapply_half_kick=cpu_apply_half_kick -Dapply_PM_half_kick=cpu_apply_PM_half_kick -Dfind_hydro_timesteps=cpu_find_hydro_timesteps -Dfind_timesteps=cpu_find_timesteps -Dapply_hydro_half_kick=cpu_apply_hydro_half_kick -Dhierarchical_gravity_and_timesteps=cpu_hierarchical_gravity_and_timesteps -Dhierarchical_gravity_accelerations=cpu_hierarchical_gravity_accelerations";;
             drift.c) extra="-Ddrift_all_particles=cpu_drift_all_particles";;
+            veldisp.c) extra="-Dwinds_find_vel_disp=cpu_winds_find_vel_disp";;
         esac
         if ! gcc -std=gnu11 -fopenmp -fsyntax-only -DMPGADGET_HIP $extra -I "$STUB" -I "$MPIINC" -I "$ROOT/include" -I "$T/libgadget" -I "$T" "$T/libgadget/$f" 2> "$STUB/err"; then
             if grep -q 'gsl/.*No such file' "$STUB/err"; then
