@@ -1268,7 +1268,7 @@ static void tree_build_local(mpg_dist *d, int64_t n_own, int64_t nl, hipStream_t
         hipLaunchKernelGGL(k_local_types, dim3(nblk(nl)), dim3(256), 0, st, nl, n_own, d->d_skip, d->ltype.p);
         ltype = d->ltype.p;
     }
-    MPG_CHECK(mpg_dev_bind_particles(e, nl, d->lpos.p, d->lmass.p, ltype, d->box) == 0, mpg_last_error());
+    MPG_CALL(mpg_dev_bind_particles(e, nl, d->lpos.p, d->lmass.p, ltype, d->box));
     e->tree.force_internal_above = d->La;
     try {
         engine_tree_build_on(e, 63, st);
@@ -1515,8 +1515,7 @@ void stage_own(mpg_dist *d, const mpg_particle_view *P)
     hipStream_t st = d->eng->stream;
     d->hbuf.resize(3 * (size_t)n + 3);
     d->hbuf_f.resize((size_t)n + 1);
-    const mpg_particle_view V = *P;
-    const char *b = (const char *)P->base;
+    const HostTable T(*P);
     double *hd = d->hbuf.data();
     float *hf = d->hbuf_f.data();
     // IsGarbage (bit 0) and Swallowed (bit 1) of the flag byte (partmanager.h:24-44): such particles stay where they are in P[] and are
@@ -1528,13 +1527,12 @@ void stage_own(mpg_dist *d, const mpg_particle_view *P)
     parallel_for(n, [=, &bad](int64_t lo, int64_t hi) {
         int any = 0;
         for(int64_t i = lo; i < hi; i++) {
-            const char *rec = b + i * V.stride;
-            const double *pp = (const double *)(rec + V.off_pos);
+            const double *pp = T.pos(i);
             hd[3 * i] = pp[0];
             hd[3 * i + 1] = pp[1];
             hd[3 * i + 2] = pp[2];
-            hf[i] = *(const float *)(rec + V.off_mass);
-            hb[i] = (V.off_flags >= 0 && (*(const uint8_t *)(rec + V.off_flags) & 3)) ? 1 : 0;
+            hf[i] = T.mass(i);
+            hb[i] = skipped_in_place(T.flags(i)) ? 1 : 0;
             any |= hb[i];
         }
         if(any)
@@ -1543,10 +1541,10 @@ void stage_own(mpg_dist *d, const mpg_particle_view *P)
     if(bad[0]) {
         d->o_skip.reserve((size_t)n + 1);
         MPG_HIP(hipMemcpyAsync(d->o_skip.p, hb, (size_t)n, hipMemcpyHostToDevice, st));
-        MPG_CHECK(mpg_dist_dev_set_garbage(d, n, d->o_skip.p) == 0, mpg_last_error());
+        MPG_CALL(mpg_dist_dev_set_garbage(d, n, d->o_skip.p));
     }
     else
-        MPG_CHECK(mpg_dist_dev_set_garbage(d, n, nullptr) == 0, mpg_last_error());
+        MPG_CALL(mpg_dist_dev_set_garbage(d, n, nullptr));
     d->o_pos.reserve(3 * (size_t)n + 3);
     d->o_mass.reserve((size_t)n + 1);
     d->o_gravpm.reserve(3 * (size_t)n + 3);
@@ -1566,13 +1564,12 @@ void column_up(mpg_dist *d, const mpg_particle_view *P, int64_t off, int w, doub
 {
     const int64_t n = P->n;
     d->hbuf.resize((size_t)w * n + 3);
-    const mpg_particle_view V = *P;
-    const char *b = (const char *)P->base;
+    const HostTable T(*P);
     double *hd = d->hbuf.data();
     parallel_for(n, [=](int64_t lo, int64_t hi) {
         for(int64_t i = lo; i < hi; i++)
             for(int k = 0; k < w; k++)
-                hd[w * i + k] = ((const double *)(b + i * V.stride + off))[k];
+                hd[w * i + k] = T.vec(i, off)[k];
     });
     if(n > 0)
         MPG_HIP(hipMemcpyAsync(dev, hd, (size_t)w * n * sizeof(double), hipMemcpyHostToDevice, d->eng->stream));
@@ -1607,31 +1604,29 @@ int mpg_dist_gravpm_force(mpg_dist *d, const mpg_particle_view *P)
         MPG_CHECK(P->off_type >= 0, "gravpm_force: the hybrid-neutrino deposit mask needs the particle type in the view");
         std::vector<uint8_t> ht((size_t)n + 1); // (not hbuf_b: it keeps the garbage flags of stage_own for the walk)
         uint8_t *hb = ht.data();
-        const mpg_particle_view V = *P;
-        const char *b = (const char *)P->base;
+        const HostTable T(*P);
         parallel_for(n, [=](int64_t lo, int64_t hi) {
             for(int64_t i = lo; i < hi; i++)
-                hb[i] = *(const uint8_t *)(b + i * V.stride + V.off_type) & 7;
+                hb[i] = T.type(i);
         });
         d->o_u8[0].reserve((size_t)n + 1);
         if(n > 0)
             MPG_HIP(hipMemcpyAsync(d->o_u8[0].p, hb, (size_t)n, hipMemcpyHostToDevice, d->eng->stream));
-        MPG_CHECK(mpg_dist_dev_set_types(d, n, d->o_u8[0].p) == 0, mpg_last_error());
+        MPG_CALL(mpg_dist_dev_set_types(d, n, d->o_u8[0].p));
         sync(d);
     }
     if(n > 0)
         MPG_HIP(hipMemsetAsync(d->o_pot.p, 0, (size_t)n * sizeof(double), d->eng->stream));
-    MPG_CHECK(mpg_dist_dev_gravpm_force(d, n, d->o_pos.p, d->o_mass.p, d->o_gravpm.p, d->o_pot.p) == 0, mpg_last_error());
-    const mpg_particle_view V = *P;
-    char *b = (char *)P->base;
+    MPG_CALL(mpg_dist_dev_gravpm_force(d, n, d->o_pos.p, d->o_mass.p, d->o_gravpm.p, d->o_pot.p));
+    const HostTable T(*P);
     column_down(d, n, 3, d->o_gravpm.p, [=](int64_t i, const double *v) {
-        double *g = (double *)(b + i * V.stride + V.off_gravpm);
+        double *g = T.vec_mut(i, T.V.off_gravpm);
         g[0] = v[0];
         g[1] = v[1];
         g[2] = v[2];
     });
     if(P->off_potential >= 0)
-        column_down(d, n, 1, d->o_pot.p, [=](int64_t i, const double *v) { *(double *)(b + i * V.stride + V.off_potential) += v[0]; });
+        column_down(d, n, 1, d->o_pot.p, [=](int64_t i, const double *v) { T.scalar_mut(i, T.V.off_potential) += v[0]; });
     API_END
 }
 
@@ -1641,7 +1636,7 @@ int mpg_dist_force_tree_full(mpg_dist *d, const mpg_particle_view *P)
     MPG_CHECK(d && P, "null argument");
     MPG_HIP(hipSetDevice(d->eng->device));
     stage_own(d, P);
-    MPG_CHECK(mpg_dist_dev_force_tree_build(d, P->n, d->o_pos.p, d->o_mass.p) == 0, mpg_last_error());
+    MPG_CALL(mpg_dist_dev_force_tree_build(d, P->n, d->o_pos.p, d->o_mass.p));
     API_END
 }
 
@@ -1663,21 +1658,13 @@ int mpg_dist_grav_short_tree_active(mpg_dist *d, const mpg_particle_view *P, con
     // OldAcc = |FullTreeGravAccel + GravPM| / G of the table as it stands (grav_get_abs_accel, gravshort.h:70-80)
     column_up(d, P, P->off_accel, 3, d->o_prev.p);
     column_up(d, P, P->off_gravpm, 3, d->o_gravpm.p);
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        d->o_act.reserve((size_t)NumActiveParticle + 1);
-        if(NumActiveParticle > 0)
-            MPG_HIP(hipMemcpyAsync(d->o_act.p, ActiveParticle, (size_t)NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, d->eng->stream));
-        d_act = d->o_act.p;
-    }
+    const int *d_act = upload_active(d->o_act, ActiveParticle, NumActiveParticle, d->eng->stream);
     const bool pot = P->off_potential >= 0;
-    MPG_CHECK(mpg_dist_dev_grav_short_tree_active(d, d_act, NumActiveParticle, nullptr, d->o_prev.p, d->o_gravpm.p, d->o_acc.p,
-                                                  pot ? d->o_pot.p : nullptr, rho0) == 0,
-              mpg_last_error());
+    MPG_CALL(mpg_dist_dev_grav_short_tree_active(d, d_act, NumActiveParticle, nullptr, d->o_prev.p, d->o_gravpm.p, d->o_acc.p,
+                                                 pot ? d->o_pot.p : nullptr, rho0));
     // results of the walked particles into the table: P[i].FullTreeGravAccel (full particle tree, gravshort.h:57-62), AccelStore[i],
     // P[i].Potential
-    const mpg_particle_view V = *P;
-    char *b = (char *)P->base;
+    const HostTable T(*P);
     d->hbuf.resize(4 * (size_t)n + 4);
     double *ha = d->hbuf.data(), *hp = ha + 3 * (size_t)n;
     if(n > 0) {
@@ -1693,14 +1680,7 @@ int mpg_dist_grav_short_tree_active(mpg_dist *d, const mpg_particle_view *P, con
             const int64_t i = ActiveParticle ? ActiveParticle[k] : k;
             if(dead && dead[i])
                 continue; // garbage / swallowed: not walked, nothing to write (treewalk.c:234)
-            double *a = (double *)(b + i * V.stride + V.off_accel);
-            for(int j = 0; j < 3; j++) {
-                a[j] = ha[3 * i + j];
-                if(AccelStore)
-                    AccelStore[i][j] = ha[3 * i + j];
-            }
-            if(pot)
-                *(double *)(b + i * V.stride + V.off_potential) = hp[i];
+            store_walk_result(T, i, ha + 3 * i, pot ? hp + i : nullptr, AccelStore, true);
         }
     });
     API_END
@@ -1789,8 +1769,8 @@ int mpg_dist_dev_density_active(mpg_dist *d, int64_t n_own, const uint8_t *d_typ
         hipLaunchKernelGGL(k_unpack_sph_in, dim3(nblk(pl.nrecv)), dim3(256), 0, st, pl.nrecv, (const double *)d->recvbuf.p, loc, n_own);
     // the gas tree of the local set (force_tree_rebuild_mask(GASMASK), run.c:466); it REPLACES the gravity tree in the engine
     d->grav_tree_valid = false;
-    MPG_CHECK(mpg_dev_bind_particles(e, nl, d->lpos.p, d->lmass.p, d->s_type.p, d->box) == 0, mpg_last_error());
-    MPG_CHECK(mpg_dev_force_tree_rebuild_mask(e, 1, 0) == 0, mpg_last_error());
+    MPG_CALL(mpg_dev_bind_particles(e, nl, d->lpos.p, d->lmass.p, d->s_type.p, d->box));
+    MPG_CALL(mpg_dev_force_tree_rebuild_mask(e, 1, 0));
     sph_targets(d, n_own, d_active, nactive, 1); // (black holes are density targets whatever BlackHoleOn says: density_haswork)
     if(d_active && n_own > 0) {
         // a sub-step: the inactive own particles keep the results of their last density loop, which the hydro loop of this sub-step
@@ -1828,7 +1808,7 @@ int mpg_dist_dev_density_active(mpg_dist *d, int64_t n_own, const uint8_t *d_typ
     L.hydroacc_out = d->s_out[7].p;
     L.dtentropy_out = d->s_out[8].p;
     L.maxsignalvel = d->s_out[9].p;
-    MPG_CHECK(mpg_dev_density(e, &L, T, d->gas.p, d->ngas, update_hsml, DoEgyDensity, d->blackholes) == 0, mpg_last_error());
+    MPG_CALL(mpg_dev_density(e, &L, T, d->gas.p, d->ngas, update_hsml, DoEgyDensity, d->blackholes));
     // every neighbour within a smoothing length must be local: the largest one against the domain margin
     d->scount.reserve(4);
     MPG_HIP(hipMemsetAsync(d->scount.p, 0, sizeof(unsigned long long), st));
@@ -1884,7 +1864,7 @@ int mpg_dist_dev_hydro_force_active(mpg_dist *d, int64_t n_own, const mpg_sph_ar
     exchange_rows(d, pl, d->sendbuf.p, d->recvbuf.p, false, 48);
     if(pl.nrecv > 0)
         hipLaunchKernelGGL(k_unpack_sph_mid, dim3(nblk(pl.nrecv)), dim3(256), 0, st, pl.nrecv, (const double *)d->recvbuf.p, n_own, hs, de, eg, dh, dv, cv);
-    MPG_CHECK(mpg_dev_force_tree_calc_hmax(e) == 0, mpg_last_error()); // force_tree_calc_moments of the gas tree, run.c:477
+    MPG_CALL(mpg_dev_force_tree_calc_hmax(e)); // force_tree_calc_moments of the gas tree, run.c:477
     mpg_sph_arrays L;
     memset(&L, 0, sizeof(L));
     L.hsml = hs;
@@ -1911,7 +1891,7 @@ int mpg_dist_dev_hydro_force_active(mpg_dist *d, int64_t n_own, const mpg_sph_ar
         MPG_HIP(hipMemcpyAsync(L.dtentropy_out, A->dtentropy_out, (size_t)n_own * sizeof(double), hipMemcpyDeviceToDevice, st));
         MPG_HIP(hipMemcpyAsync(L.maxsignalvel, A->maxsignalvel, (size_t)n_own * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
-    MPG_CHECK(mpg_dev_hydro_force(e, &L, T, d->gas.p, d->ngas) == 0, mpg_last_error());
+    MPG_CALL(mpg_dev_hydro_force(e, &L, T, d->gas.p, d->ngas));
     if(n_own > 0) {
         MPG_HIP(hipMemcpyAsync(A->hydroacc_out, L.hydroacc_out, (size_t)3 * n_own * sizeof(double), hipMemcpyDeviceToDevice, st));
         MPG_HIP(hipMemcpyAsync(A->dtentropy_out, L.dtentropy_out, (size_t)n_own * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -2416,7 +2396,7 @@ int mpg_dist_dev_fof_fof(mpg_dist *d, int64_t n_own, const double *d_pos, const 
         hipLaunchKernelGGL(k_unpack_idtype, dim3(nblk(pl.nrecv)), dim3(256), 0, st, pl.nrecv, (const IdRow *)d->recvbuf.p, d->f_id.p + n_own,
                            d->f_type.p + n_own);
     d->grav_tree_valid = false; // (the tree of the primary types replaces the gravity tree in the engine)
-    MPG_CHECK(mpg_dev_bind_particles(e, nl, d->lpos.p, d->lmass.p, d->f_type.p, d->box) == 0, mpg_last_error());
+    MPG_CALL(mpg_dev_bind_particles(e, nl, d->lpos.p, d->lmass.p, d->f_type.p, d->box));
     e->tree.build(nl, d->lpos.p, d->lmass.p, d->f_type.p, par->FOFPrimaryLinkTypes, d->box, st, &e->timer, nullptr);
     e->tree_allocated = true;
     e->tree_mask = par->FOFPrimaryLinkTypes;
@@ -2650,112 +2630,38 @@ int mpg_dist_fof_groups(mpg_dist *d, const mpg_fof_groups *out)
  * slots), after mpg_dist_force_tree_full on the same table ------------------------------------------------------------------ */
 namespace {
 
-struct SphField {
-    int w;       // doubles per particle
-    bool in, out_density, out_hydro;
-};
-// the double-valued members of mpg_sph_arrays in declaration order, without the two time-bin byte arrays
-const SphField SPH_FIELDS[17] = {{1, true, true, false},   // hsml
-                                 {1, false, true, false},  // dthsml
-                                 {3, true, false, false},  // vel
-                                 {3, true, false, false},  // gacc
-                                 {3, true, false, false},  // gpm
-                                 {3, true, false, false},  // hydroacc_in
-                                 {1, true, false, false},  // entropy
-                                 {1, true, false, false},  // dtentropy_in
-                                 {1, false, true, false},  // density
-                                 {1, false, true, false},  // egywtdensity
-                                 {1, false, true, false},  // dhsmlegyfac
-                                 {1, false, true, false},  // divvel
-                                 {1, false, true, false},  // curlvel
-                                 {3, false, true, false},  // gradrho
-                                 {3, false, false, true},  // hydroacc_out
-                                 {1, false, false, true},  // dtentropy_out
-                                 {1, false, false, true}}; // maxsignalvel
-
-// pointers of the 17 double fields of a mpg_sph_arrays, in the order of SPH_FIELDS
-void sph_field_ptrs(const mpg_sph_arrays *A, const double *p[17])
-{
-    p[0] = A->hsml;
-    p[1] = A->dthsml;
-    p[2] = A->vel;
-    p[3] = A->gacc;
-    p[4] = A->gpm;
-    p[5] = A->hydroacc_in;
-    p[6] = A->entropy;
-    p[7] = A->dtentropy_in;
-    p[8] = A->density;
-    p[9] = A->egywtdensity;
-    p[10] = A->dhsmlegyfac;
-    p[11] = A->divvel;
-    p[12] = A->curlvel;
-    p[13] = A->gradrho;
-    p[14] = A->hydroacc_out;
-    p[15] = A->dtentropy_out;
-    p[16] = A->maxsignalvel;
-}
-
-// device copy of the host arrays: inputs uploaded, outputs allocated; returns the device-side struct
+// device copy of the host arrays (SPH_FIELDS, host_table.h): inputs uploaded, outputs allocated; returns the device-side struct
 mpg_sph_arrays stage_sph(mpg_dist *d, const mpg_sph_arrays *A, int64_t n, bool upload, bool upload_density_out, bool upload_hydro_out)
 {
     hipStream_t st = d->eng->stream;
-    const double *hp[17];
-    sph_field_ptrs(A, hp);
-    double *dp[17];
-    for(int k = 0; k < 17; k++) {
-        dp[k] = nullptr;
-        if(!hp[k])
-            continue;
-        d->o_sph[k].reserve((size_t)SPH_FIELDS[k].w * n + 3);
-        dp[k] = d->o_sph[k].p;
-        const bool up = (upload && SPH_FIELDS[k].in) || (upload_density_out && SPH_FIELDS[k].out_density) ||
-                        (upload_hydro_out && SPH_FIELDS[k].out_hydro);
-        if(up && n > 0)
-            MPG_HIP(hipMemcpyAsync(dp[k], hp[k], (size_t)SPH_FIELDS[k].w * n * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    const uint8_t *hb[2] = {A->tb_hydro, A->tb_grav};
-    uint8_t *db[2] = {nullptr, nullptr};
-    for(int k = 0; k < 2; k++)
-        if(hb[k]) {
-            d->o_u8[1 + k].reserve((size_t)n + 1);
-            db[k] = d->o_u8[1 + k].p;
-            if(upload && n > 0)
-                MPG_HIP(hipMemcpyAsync(db[k], hb[k], (size_t)n, hipMemcpyHostToDevice, st));
-        }
-    sync(d);
     mpg_sph_arrays D;
-    memset(&D, 0, sizeof(D));
-    D.hsml = dp[0];
-    D.dthsml = dp[1];
-    D.vel = dp[2];
-    D.gacc = dp[3];
-    D.gpm = dp[4];
-    D.hydroacc_in = dp[5];
-    D.tb_hydro = db[0];
-    D.tb_grav = db[1];
-    D.entropy = dp[6];
-    D.dtentropy_in = dp[7];
-    D.density = dp[8];
-    D.egywtdensity = dp[9];
-    D.dhsmlegyfac = dp[10];
-    D.divvel = dp[11];
-    D.curlvel = dp[12];
-    D.gradrho = dp[13];
-    D.hydroacc_out = dp[14];
-    D.dtentropy_out = dp[15];
-    D.maxsignalvel = dp[16];
+    for(const SphField &F : SPH_FIELDS) {
+        void *h = field_get(*A, F.off), *dv = nullptr;
+        bool up = upload && (F.role & SPH_IN);
+        if(h && F.width == 0) {
+            d->o_u8[1 + F.slot].reserve((size_t)n + 1);
+            dv = d->o_u8[1 + F.slot].p;
+        }
+        else if(h) {
+            d->o_sph[F.slot].reserve((size_t)F.width * n + 3);
+            dv = d->o_sph[F.slot].p;
+            up = up || (upload_density_out && (F.role & SPH_OUT_DENSITY)) || (upload_hydro_out && (F.role & SPH_OUT_HYDRO));
+        }
+        if(dv && up && n > 0)
+            MPG_HIP(hipMemcpyAsync(dv, h, sph_field_bytes(F, n), hipMemcpyHostToDevice, st));
+        field_set(D, F.off, dv);
+    }
+    sync(d);
     return D;
 }
 
 void download_sph(mpg_dist *d, const mpg_sph_arrays *A, int64_t n, bool hydro)
 {
     hipStream_t st = d->eng->stream;
-    const double *hp[17];
-    sph_field_ptrs(A, hp);
-    for(int k = 0; k < 17; k++) {
-        const bool want = hydro ? SPH_FIELDS[k].out_hydro : SPH_FIELDS[k].out_density;
-        if(want && hp[k] && n > 0)
-            MPG_HIP(hipMemcpyAsync((double *)hp[k], d->o_sph[k].p, (size_t)SPH_FIELDS[k].w * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    for(const SphField &F : SPH_FIELDS) {
+        void *h = field_get(*A, F.off);
+        if(h && n > 0 && (F.role & (hydro ? SPH_OUT_HYDRO : SPH_OUT_DENSITY)))
+            MPG_HIP(hipMemcpyAsync(h, d->o_sph[F.slot].p, sph_field_bytes(F, n), hipMemcpyDeviceToHost, st));
     }
     sync(d);
 }
@@ -2765,17 +2671,11 @@ const uint8_t *stage_types(mpg_dist *d, const mpg_particle_view *P)
 {
     const int64_t n = P->n;
     std::vector<uint8_t> ty((size_t)n + 1);
-    const mpg_particle_view V = *P;
-    const char *b = (const char *)P->base;
+    const HostTable T(*P);
     uint8_t *t = ty.data();
     parallel_for(n, [=](int64_t lo, int64_t hi) {
         for(int64_t i = lo; i < hi; i++)
-        {
-            t[i] = V.off_type >= 0 ? (uint8_t)(*(const uint8_t *)(b + i * V.stride + V.off_type) & 7) : (uint8_t)1;
-            // garbage and swallowed black holes are no targets and no neighbours (density.c:521-530, forcetree.c:357-365): type 7
-            if(V.off_flags >= 0 && (*(const uint8_t *)(b + i * V.stride + V.off_flags) & 3))
-                t[i] = 7;
-        }
+            t[i] = no_sph_particle(T.flags(i)) ? (uint8_t)7 : T.type(i);
     });
     d->o_u8[0].reserve((size_t)n + 1);
     if(n > 0)
@@ -2786,17 +2686,6 @@ const uint8_t *stage_types(mpg_dist *d, const mpg_particle_view *P)
 } // namespace
 
 extern "C" {
-
-// ActiveParticle of a host call onto the device (null: all)
-static const int *stage_active(mpg_dist *d, const int *ActiveParticle, int64_t n)
-{
-    if(!ActiveParticle)
-        return nullptr;
-    d->o_act.reserve((size_t)n + 1);
-    if(n > 0)
-        MPG_HIP(hipMemcpy(d->o_act.p, ActiveParticle, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    return d->o_act.p;
-}
 
 int mpg_dist_set_sph_options(mpg_dist *d, int BlackHoleOn)
 {
@@ -2834,7 +2723,7 @@ int mpg_dist_gravpm_get_powerspectrum(mpg_dist *d, double BoxSize_in_MPC, double
     sync(d);
     allreduce_host_f64(d, acc.data(), (int64_t)(2 * nb + 1), 0);
     allreduce_i64(d, modes.data(), (int64_t)nb, 0);
-    MPG_CHECK(mpg_powerspectrum_sum((int)nb, acc.data(), modes.data(), BoxSize_in_MPC, kk, Power, Nmodes, nonzero) == 0, mpg_last_error());
+    MPG_CALL(mpg_powerspectrum_sum((int)nb, acc.data(), modes.data(), BoxSize_in_MPC, kk, Power, Nmodes, nonzero));
     API_END
 }
 
@@ -2848,8 +2737,9 @@ int mpg_dist_density(mpg_dist *d, const mpg_particle_view *P, const mpg_sph_arra
     const uint8_t *ty = stage_types(d, P);
     // (a sub-step also uploads the density-loop results the inactive particles hold)
     const mpg_sph_arrays D = stage_sph(d, A, P->n, true, ActiveParticle != nullptr, false);
-    const int *act = stage_active(d, ActiveParticle, NumActiveParticle);
-    MPG_CHECK(mpg_dist_dev_density_active(d, P->n, ty, &D, T, act, NumActiveParticle, update_hsml, DoEgyDensity) == 0, mpg_last_error());
+    const int *act = upload_active(d->o_act, ActiveParticle, NumActiveParticle, d->eng->stream);
+    sync(d); // (on the device before the call returns to a caller that may reuse the list)
+    MPG_CALL(mpg_dist_dev_density_active(d, P->n, ty, &D, T, act, NumActiveParticle, update_hsml, DoEgyDensity));
     download_sph(d, A, P->n, false);
     API_END
 }
@@ -2863,8 +2753,9 @@ int mpg_dist_hydro_force(mpg_dist *d, const mpg_particle_view *P, const mpg_sph_
     MPG_HIP(hipSetDevice(d->eng->device));
     // (the inputs are the library's from the density call; a sub-step uploads the hydro results the inactive particles hold)
     const mpg_sph_arrays D = stage_sph(d, A, P->n, false, false, ActiveParticle != nullptr);
-    const int *act = stage_active(d, ActiveParticle, NumActiveParticle);
-    MPG_CHECK(mpg_dist_dev_hydro_force_active(d, P->n, &D, T, act, NumActiveParticle) == 0, mpg_last_error());
+    const int *act = upload_active(d->o_act, ActiveParticle, NumActiveParticle, d->eng->stream);
+    sync(d); // (on the device before the call returns to a caller that may reuse the list)
+    MPG_CALL(mpg_dist_dev_hydro_force_active(d, P->n, &D, T, act, NumActiveParticle));
     download_sph(d, A, P->n, true);
     API_END
 }
@@ -2927,8 +2818,8 @@ extern "C" int mpg_dist_dev_grav_short_tree_active_tree(mpg_dist *d, int64_t n_a
     }
     sync(d); // (`all` is read by the copies)
     d->grav_tree_valid = false;
-    MPG_CHECK(mpg_dev_bind_particles(e, ntot, d->lpos.p, d->lmass.p, nullptr, d->box) == 0, mpg_last_error());
-    MPG_CHECK(mpg_dev_force_tree_build(e, 63) == 0, mpg_last_error());
+    MPG_CALL(mpg_dev_bind_particles(e, ntot, d->lpos.p, d->lmass.p, nullptr, d->box));
+    MPG_CALL(mpg_dev_force_tree_build(e, 63));
     e->full_particle_tree = false; // (force_tree_active_moments, forcetree.c:129-148: P[].Potential and FullTreeGravAccel are not this walk's)
     if(n_act == 0)
         return 0;
@@ -2947,7 +2838,7 @@ extern "C" int mpg_dist_dev_grav_short_tree_active_tree(mpg_dist *d, int64_t n_a
     if(d_oldacc)
         MPG_HIP(hipMemcpyAsync(d->o_prev.p + off, d_oldacc, (size_t)n_act * sizeof(double), hipMemcpyDeviceToDevice, st));
     (void)d_potential; // (left alone: the tree does not hold every particle, gravshort.h:57-67)
-    MPG_CHECK(mpg_dev_grav_short_tree(e, d->o_prev.p, nullptr, nullptr, d->targets.p, n_act, d->o_acc.p, nullptr, rho0) == 0, mpg_last_error());
+    MPG_CALL(mpg_dev_grav_short_tree(e, d->o_prev.p, nullptr, nullptr, d->targets.p, n_act, d->o_acc.p, nullptr, rho0));
     MPG_HIP(hipMemcpyAsync(d_accel, d->o_acc.p + 3 * off, (size_t)n_act * 24, hipMemcpyDeviceToDevice, st));
     sync(d);
     d->o_n = -1; // (the staging columns of the host drop-in calls were reused)
@@ -2967,12 +2858,13 @@ extern "C" int mpg_dist_grav_short_tree_active_tree(mpg_dist *d, const mpg_parti
     MPG_HIP(hipSetDevice(d->eng->device));
     hipStream_t st = d->eng->stream;
     // the live members of the list (garbage and swallowed particles are skipped in place: treewalk.c:234, forcetree.c:806)
+    const HostTable T(*P);
     std::vector<int64_t> live;
     live.reserve((size_t)nlist);
     for(int64_t k = 0; k < nlist; k++) {
         const int64_t i = ActiveParticle ? ActiveParticle[k] : k;
         MPG_CHECK(i >= 0 && i < P->n, "ActiveParticle index out of range");
-        if(P->off_flags >= 0 && (*((const uint8_t *)P->base + i * P->stride + P->off_flags) & 3))
+        if(skipped_in_place(T.flags(i)))
             continue;
         live.push_back(i);
     }
@@ -2980,22 +2872,19 @@ extern "C" int mpg_dist_grav_short_tree_active_tree(mpg_dist *d, const mpg_parti
     const int64_t *lv = live.data();
     std::vector<double> hp(3 * (size_t)n + 3), ho((size_t)n + 1);
     std::vector<float> hm((size_t)n + 1);
-    const mpg_particle_view V = *P;
-    const char *b = (const char *)P->base;
     const double G = d->eng->pm.G;
     double *pp = hp.data(), *po = ho.data();
     float *pm = hm.data();
     parallel_for(n, [=](int64_t lo, int64_t hi) {
         for(int64_t k = lo; k < hi; k++) {
             const int64_t i = lv[k];
-            const char *rec = b + i * V.stride;
-            const double *x = (const double *)(rec + V.off_pos), *a = (const double *)(rec + V.off_accel), *g = (const double *)(rec + V.off_gravpm);
+            const double *x = T.pos(i), *a = T.vec(i, T.V.off_accel), *g = T.vec(i, T.V.off_gravpm);
             double s2 = 0;
             for(int j = 0; j < 3; j++) {
                 pp[3 * k + j] = x[j];
                 s2 += (a[j] + g[j]) * (a[j] + g[j]);
             }
-            pm[k] = *(const float *)(rec + V.off_mass);
+            pm[k] = T.mass(i);
             po[k] = sqrt(s2) / G; // grav_get_abs_accel, gravshort.h:70-80
         }
     });
@@ -3011,7 +2900,7 @@ extern "C" int mpg_dist_grav_short_tree_active_tree(mpg_dist *d, const mpg_parti
         MPG_HIP(hipMemcpyAsync(dm.p, pm, (size_t)n * sizeof(float), hipMemcpyHostToDevice, st));
     }
     sync(d);
-    MPG_CHECK(mpg_dist_dev_grav_short_tree_active_tree(d, n, dp.p, dm.p, dold.p, dacc.p, nullptr, rho0) == 0, mpg_last_error());
+    MPG_CALL(mpg_dist_dev_grav_short_tree_active_tree(d, n, dp.p, dm.p, dold.p, dacc.p, nullptr, rho0));
     if(n > 0)
         MPG_HIP(hipMemcpyAsync(pp, dacc.p, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     sync(d);

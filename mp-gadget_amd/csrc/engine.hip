@@ -6,8 +6,6 @@
 // return codes here; the in-tree shim maps failures to endrun()).  There is no CPU fallback anywhere:
 // without a HIP device mpg_engine_create fails.
 #include "engine_internal.h"
-#include <atomic>
-#include <chrono>
 #include <cstdio>
 
 static thread_local std::string g_err;
@@ -348,7 +346,7 @@ static bool tree_walk_copies(mpg_engine *eng, hipStream_t st, bool leaf_blocks =
 }
 
 // a tree build on `st` overwrites what a leaf-block kernel still running on the tree stream reads
-static void wait_for_leaf_blocks(mpg_engine *eng, hipStream_t st)
+void wait_for_leaf_blocks(mpg_engine *eng, hipStream_t st)
 {
     if(eng->pad_pending && st != eng->aux_stream)
         MPG_HIP(hipStreamWaitEvent(st, eng->ev_pad_done, 0));
@@ -979,8 +977,7 @@ int mpg_gravpm_get_powerspectrum(mpg_engine *eng, double BoxSize_in_MPC, double 
     MPG_HIP(hipMemcpyAsync(acc.data(), eng->pm.ps_acc.p, (2 * nb + 1) * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
     MPG_HIP(hipMemcpyAsync(modes.data(), eng->pm.ps_modes.p, nb * sizeof(int64_t), hipMemcpyDeviceToHost, eng->stream));
     MPG_HIP(hipStreamSynchronize(eng->stream));
-    if(mpg_powerspectrum_sum((int)nb, acc.data(), modes.data(), BoxSize_in_MPC, kk, Power, Nmodes, nonzero) != 0)
-        throw Error(g_err);
+    MPG_CALL(mpg_powerspectrum_sum((int)nb, acc.data(), modes.data(), BoxSize_in_MPC, kk, Power, Nmodes, nonzero));
     API_END
 }
 
@@ -1465,982 +1462,6 @@ int mpg_dev_hierarchical_gravity_accelerations(mpg_engine *eng, const mpg_hiergr
     API_END
 }
 
-/* ------------------------------ host (AoS) path ------------------------------ */
-
-// The host <-> device staging of the AoS path is cut into chunks so that packing / unpacking on the host threads overlaps the
-// PCIe transfers of the neighbouring chunks (pinned buffers: the copies are asynchronous).
-constexpr int HOST_CHUNKS = 8;
-// MPG_HOST_TIMING=1: wall-clock marks of the host forms' phases on stderr (a diagnostic)
-struct HostClock {
-    bool on;
-    const char *name;
-    double t0;
-    std::string line;
-    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-    explicit HostClock(const char *n) : on(getenv("MPG_HOST_TIMING") != nullptr), name(n), t0(now()) {}
-    void mark(const char *what)
-    {
-        if(!on)
-            return;
-        const double t = now();
-        char buf[96];
-        snprintf(buf, sizeof(buf), " %s %.2f", what, t - t0);
-        line += buf;
-        t0 = t;
-    }
-    ~HostClock()
-    {
-        if(on)
-            fprintf(stderr, "HOST_TIMING %s:%s\n", name, line.c_str());
-    }
-};
-static inline void chunk_range(int64_t n, int c, int64_t &lo, int64_t &hi)
-{
-    lo = n * c / HOST_CHUNKS;
-    hi = n * (c + 1) / HOST_CHUNKS;
-}
-
-} // extern "C" (a template)
-// unpack(lo, hi) runs on the host for each chunk as soon as the device -> host copies issue(lo, hi) queued for it have landed
-template <class Issue, class Unpack> static void download_chunks(mpg_engine *eng, int64_t n, Issue issue, Unpack unpack)
-{
-    for(int c = 0; c < HOST_CHUNKS; c++) {
-        int64_t lo, hi;
-        chunk_range(n, c, lo, hi);
-        if(hi > lo)
-            issue(lo, hi);
-        if(!eng->chunk_ev[c])
-            MPG_HIP(hipEventCreateWithFlags(&eng->chunk_ev[c], hipEventDisableTiming));
-        MPG_HIP(hipEventRecord(eng->chunk_ev[c], eng->stream));
-    }
-    for(int c = 0; c < HOST_CHUNKS; c++) {
-        int64_t lo, hi;
-        chunk_range(n, c, lo, hi);
-        MPG_HIP(hipEventSynchronize(eng->chunk_ev[c]));
-        if(hi > lo)
-            parallel_for(hi - lo, [=](int64_t a, int64_t b) { unpack(lo + a, lo + b); });
-    }
-}
-extern "C" {
-
-static void stage_particles_body(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, bool on_prefetch_thread);
-static void stage_particles(mpg_engine *eng, const mpg_particle_view *P, double BoxSize)
-{
-    eng->prefetch_join(); // (a prefetch of this epoch ends here; the write-back thread of gravpm_force is waited for only if P[] is read again)
-    if(!eng->prefetch_error.empty()) {
-        const std::string e = eng->prefetch_error;
-        eng->prefetch_error.clear();
-        MPG_CHECK(false, "host path: the prefetch of the particle table failed: " + e);
-    }
-    stage_particles_body(eng, P, BoxSize, false);
-}
-static void stage_particles_body(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, bool on_prefetch_thread)
-{
-    MPG_CHECK(P && (P->n == 0 || P->base), "null particle view");
-    MPG_CHECK(P->off_pos >= 0 && P->off_mass >= 0, "particle view needs Pos and Mass");
-    const int64_t n = P->n;
-    if(eng->resident && eng->res_base == P->base) { // resident mode: the table is the device's
-        MPG_CHECK(eng->res_n == n && eng->box == BoxSize && eng->d_pos == eng->s_pos.p,
-                  "resident mode: the particle table changed size, box or binding (mpg_resident_end / _begin around anything that reorders P[])");
-        return;
-    }
-    // positions, masses and types of this very table are on the device already (mpg_set_particle_epoch)
-    if(eng->host_epoch != 0 && eng->staged_epoch == eng->host_epoch && eng->staged_base == P->base && eng->staged_n == n &&
-       eng->staged_box == BoxSize && eng->d_pos == eng->s_pos.p)
-        return;
-    if(!on_prefetch_thread) // (mpg_host_prefetch joined before it started this thread)
-        eng->host_join();   // a pending write-back of the last epoch's GravPM touches the records this pass reads
-    eng->h_d.reserve(3 * (size_t)n + 1);
-    eng->h_f.reserve((size_t)n + 1);
-    eng->h_b.reserve((size_t)n + 1);
-    eng->s_pos.reserve(3 * (size_t)n + 1);
-    eng->s_mass.reserve((size_t)n + 1);
-    eng->s_type.reserve((size_t)n + 1);
-    const char *b = (const char *)P->base;
-    double *hd = eng->h_d.p;
-    float *hf = eng->h_f.p;
-    uint8_t *hb = eng->h_b.p;
-    const mpg_particle_view V = *P;
-    // with overlap, the same pass also takes what the epoch's later calls would read from P[] again: Potential (gravpm_force accumulates
-    // into it) and FullTreeGravAccel (the walk's opening criterion)
-    const bool extras = eng->host_overlap && eng->host_epoch != 0 && V.off_accel >= 0;
-    const bool xpot = extras && V.off_potential >= 0;
-    double *hacc = nullptr, *hpot = nullptr;
-    if(extras) {
-        eng->h_acc.reserve(3 * (size_t)n + 1);
-        eng->s_prevacc.reserve(3 * (size_t)n + 1);
-        hacc = eng->h_acc.p;
-        if(xpot) {
-            eng->h_gpot.reserve((size_t)n + 1);
-            eng->s_pot.reserve((size_t)n + 1);
-            hpot = eng->h_gpot.p;
-        }
-    }
-    int any_dead_store[HOST_CHUNKS] = {};
-    int *any_dead = any_dead_store;
-    for(int c = 0; c < HOST_CHUNKS; c++) {
-        int64_t lo, hi;
-        chunk_range(n, c, lo, hi);
-        if(hi <= lo)
-            continue;
-        parallel_for(hi - lo, [=](int64_t a0, int64_t a1) {
-            for(int64_t i = lo + a0; i < lo + a1; i++) {
-                const char *rec = b + i * V.stride;
-                const double *pp = (const double *)(rec + V.off_pos);
-                hd[3 * i + 0] = pp[0];
-                hd[3 * i + 1] = pp[1];
-                hd[3 * i + 2] = pp[2];
-                hf[i] = *(const float *)(rec + V.off_mass);
-                uint8_t ty = V.off_type >= 0 ? (*(const uint8_t *)(rec + V.off_type) & 7) : 1;
-                // garbage / swallowed-BH particles never enter the tree (forcetree.c:806): give them type 7 (no mask bit)
-                if(V.off_flags >= 0) {
-                    const uint8_t fl = *(const uint8_t *)(rec + V.off_flags);
-                    if((fl & 1) || ((fl & 2) && ty == 5))
-                        ty = 7;
-                }
-                hb[i] = ty;
-                if(ty == 7)
-                    any_dead[c] = 1;
-                if(hacc) {
-                    const double *aa = (const double *)(rec + V.off_accel);
-                    hacc[3 * i + 0] = aa[0];
-                    hacc[3 * i + 1] = aa[1];
-                    hacc[3 * i + 2] = aa[2];
-                    if(hpot)
-                        hpot[i] = *(const double *)(rec + V.off_potential);
-                }
-            }
-        });
-        MPG_HIP(hipMemcpyAsync(eng->s_pos.p + 3 * lo, hd + 3 * lo, 3 * (hi - lo) * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-        MPG_HIP(hipMemcpyAsync(eng->s_mass.p + lo, hf + lo, (hi - lo) * sizeof(float), hipMemcpyHostToDevice, eng->stream));
-        MPG_HIP(hipMemcpyAsync(eng->s_type.p + lo, hb + lo, (hi - lo) * sizeof(uint8_t), hipMemcpyHostToDevice, eng->stream));
-        if(hpot)
-            MPG_HIP(hipMemcpyAsync(eng->s_pot.p + lo, hpot + lo, (hi - lo) * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-    }
-    eng->staged_extra_epoch = extras ? eng->host_epoch : -1;
-    eng->gravpm_epoch = -1;
-    // garbage and swallowed particles are not deposited and receive no mesh force either (gravpm.c:176-179: region -2): the PM takes a
-    // live flag per particle when the table holds any
-    bool dead = false;
-    for(int c = 0; c < HOST_CHUNKS; c++)
-        dead = dead || any_dead[c];
-    eng->pm_live = nullptr;
-    if(dead) {
-        eng->s_live.reserve((size_t)n + 1);
-        MPG_HIP(hipStreamSynchronize(eng->stream)); // (the type bytes have left the staging buffer, which now takes the flags)
-        parallel_for(n, [=](int64_t lo, int64_t hi) {
-            for(int64_t i = lo; i < hi; i++)
-                hb[i] = hb[i] != 7;
-        });
-        MPG_HIP(hipMemcpyAsync(eng->s_live.p, hb, (size_t)n, hipMemcpyHostToDevice, eng->stream));
-        eng->pm_live = eng->s_live.p;
-    }
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-    if(hacc) { // (needed by the walk only: on the copy stream it travels while the PM step computes; its staging buffer is its own)
-        if(!eng->copy_stream) {
-            MPG_HIP(hipStreamCreateWithFlags(&eng->copy_stream, hipStreamNonBlocking));
-            MPG_HIP(hipEventCreateWithFlags(&eng->ev_pm_done, hipEventDisableTiming));
-        }
-        if(!eng->ev_acc_up)
-            MPG_HIP(hipEventCreateWithFlags(&eng->ev_acc_up, hipEventDisableTiming));
-        MPG_HIP(hipMemcpyAsync(eng->s_prevacc.p, hacc, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->copy_stream));
-        MPG_HIP(hipEventRecord(eng->ev_acc_up, eng->copy_stream));
-    }
-    eng->n = n;
-    eng->d_pos = eng->s_pos.p;
-    eng->d_mass = eng->s_mass.p;
-    eng->d_type = eng->s_type.p;
-    eng->box = BoxSize;
-    eng->staged_epoch = eng->host_epoch;
-    eng->staged_base = P->base;
-    eng->staged_n = n;
-    eng->staged_box = BoxSize;
-}
-
-int mpg_set_particle_epoch(mpg_engine *eng, int64_t epoch)
-{
-    API_BEGIN
-    MPG_CHECK(eng, "null engine");
-    if(epoch != eng->host_epoch)
-        eng->host_join(); // (a prefetch reads host_epoch on its own thread)
-    eng->host_epoch = epoch;
-    API_END
-}
-
-// The epoch's one packing pass and its uploads, started EARLY: a caller that knows P[] is final for the step - the end of
-// drift_all_particles (drift.c:84-102), where nothing of run.c touches Pos / Mass / FullTreeGravAccel / Potential again before gravpm_force
-// (run.c:420-522: domain_maintain reads them; an exchange or a garbage collection declares a new epoch, and this upload is then simply not used)
-// - calls this after mpg_set_particle_epoch; the pass runs on a host thread of its own and the first entry point of the epoch joins it
-// instead of packing.  Needs the overlap mode (the pass must also take Potential / FullTreeGravAccel); without it, or resident, a no-op.
-int mpg_host_prefetch(mpg_engine *eng, const mpg_particle_view *P, double BoxSize)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && BoxSize > 0, "mpg_host_prefetch: bad argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    eng->host_join();
-    if(!eng->host_overlap || eng->host_epoch == 0 || eng->resident || P->n == 0) {
-        mpg_err_slot().clear();
-        return 0;
-    }
-    eng->prefetch_error.clear();
-    eng->prefetch_view = *P;
-    eng->prefetch_thread = std::thread([eng, BoxSize] {
-        try {
-            MPG_HIP(hipSetDevice(eng->device));
-            stage_particles_body(eng, &eng->prefetch_view, BoxSize, true);
-        }
-        catch(const std::exception &e) {
-            eng->prefetch_error = e.what();
-        }
-    });
-    API_END
-}
-
-int mpg_set_host_overlap(mpg_engine *eng, int on)
-{
-    API_BEGIN
-    MPG_CHECK(eng, "null engine");
-    eng->host_join();
-    eng->host_overlap = on != 0;
-    eng->host_slices = on > 1 ? on : 0; // (2 .. 8: that many slices of the walk whatever the size - the tests' way to the sliced path)
-    API_END
-}
-
-int mpg_host_results_sync(mpg_engine *eng)
-{
-    API_BEGIN
-    MPG_CHECK(eng, "null engine");
-    eng->host_join();
-    MPG_CHECK(eng->unpack_error.empty(), "host path: the write-back of GravPM failed: " + eng->unpack_error);
-    API_END
-}
-
-int mpg_gravpm_force(mpg_engine *eng, const mpg_particle_view *P)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P, "null argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    MPG_CHECK(eng->pm.nmesh > 0, "gravpm_force called before gravpm_init_periodic");
-    MPG_CHECK(P->off_gravpm >= 0, "particle view needs GravPM");
-    MPG_CHECK(!eng->pm.hybrid_tracer || P->off_type >= 0, "gravpm_force: the hybrid-neutrino deposit mask needs the particle type in the view");
-    HostClock hc("gravpm_force");
-    eng->host_join(); // (the write-back of an earlier call)
-    MPG_CHECK(eng->unpack_error.empty(), "host path: the write-back of GravPM failed: " + eng->unpack_error);
-    stage_particles(eng, P, eng->pm.box);
-    hc.mark("stage");
-    const int64_t n = P->n;
-    if(eng->resident && eng->res_base == P->base) { // results stay in HBM: GravPM assigned, Potential accumulated (gravpm.c:499-501)
-        if(eng->pm_live) // (gravpm.c:88-92 zeroes GravPM of every particle; the readout reaches the live ones)
-            MPG_HIP(hipMemsetAsync(eng->r_gravpm.p, 0, 3 * (size_t)n * sizeof(double), eng->stream));
-        eng->pm.force(n, eng->d_pos, eng->pm.tracer_mass(n, eng->d_mass, eng->d_type, eng->stream), eng->pm_live, eng->r_gravpm.p, eng->r_pot.p,
-                      eng->stream, &eng->timer);
-        mpg_err_slot().clear();
-        return 0;
-    }
-    eng->s_gravpm.reserve(3 * (size_t)n + 1);
-    const bool wantpot = P->off_potential >= 0;
-    char *b = (char *)P->base;
-    const mpg_particle_view V = *P;
-    eng->h_d2.reserve(3 * (size_t)n + 1);
-    eng->h_d3.reserve((size_t)n + 1);
-    double *hg = eng->h_d2.p, *hp = eng->h_d3.p;
-    const bool overlap = eng->host_overlap && eng->host_epoch != 0;
-    if(wantpot && !(overlap && eng->staged_extra_epoch == eng->host_epoch)) { // (with overlap the Potential went up with the positions)
-        // readout_potential accumulates into P.Potential (gravpm.c:499-501), which is NOT zeroed first
-        eng->s_pot.reserve((size_t)n + 1);
-        parallel_for(n, [=](int64_t lo, int64_t hi) {
-            for(int64_t i = lo; i < hi; i++)
-                hp[i] = *(const double *)(b + i * V.stride + V.off_potential);
-        });
-        MPG_HIP(hipMemcpyAsync(eng->s_pot.p, hp, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-    }
-    if(eng->pm_live)
-        MPG_HIP(hipMemsetAsync(eng->s_gravpm.p, 0, 3 * (size_t)n * sizeof(double), eng->stream));
-    eng->pm.force(n, eng->d_pos, eng->pm.tracer_mass(n, eng->d_mass, eng->d_type, eng->stream), eng->pm_live, eng->s_gravpm.p,
-                  wantpot ? eng->s_pot.p : nullptr, eng->stream, &eng->timer);
-    eng->gravpm_epoch = eng->host_epoch;
-    const double *dg = eng->s_gravpm.p, *dp = eng->s_pot.p;
-    if(overlap) {
-        // the results leave on a copy stream behind the PM step and are written into P[] by a host thread, chunk by chunk, while this
-        // thread returns and queues the tree build and the walk (the walk reads GravPM and the Potential it accumulates onto from the
-        // device buffers, which nothing overwrites before the next gravpm_force)
-        if(!eng->copy_stream) {
-            MPG_HIP(hipStreamCreateWithFlags(&eng->copy_stream, hipStreamNonBlocking));
-            MPG_HIP(hipEventCreateWithFlags(&eng->ev_pm_done, hipEventDisableTiming));
-        }
-        eng->h_gpm.reserve(3 * (size_t)n + 1);
-        double *ag = eng->h_gpm.p, *ap = nullptr;
-        if(wantpot) {
-            eng->h_gpot.reserve((size_t)n + 1);
-            ap = eng->h_gpot.p;
-        }
-        MPG_HIP(hipEventRecord(eng->ev_pm_done, eng->stream));
-        MPG_HIP(hipStreamWaitEvent(eng->copy_stream, eng->ev_pm_done, 0));
-        for(int c = 0; c < HOST_CHUNKS; c++) {
-            int64_t lo, hi;
-            chunk_range(n, c, lo, hi);
-            if(hi > lo) {
-                MPG_HIP(hipMemcpyAsync(ag + 3 * lo, dg + 3 * lo, 3 * (hi - lo) * sizeof(double), hipMemcpyDeviceToHost, eng->copy_stream));
-                if(wantpot)
-                    MPG_HIP(hipMemcpyAsync(ap + lo, dp + lo, (hi - lo) * sizeof(double), hipMemcpyDeviceToHost, eng->copy_stream));
-            }
-            if(!eng->gchunk_ev[c])
-                MPG_HIP(hipEventCreateWithFlags(&eng->gchunk_ev[c], hipEventDisableTiming));
-            MPG_HIP(hipEventRecord(eng->gchunk_ev[c], eng->copy_stream));
-        }
-        eng->unpack_error.clear();
-        const int device = eng->device;
-        eng->unpack_thread = std::thread([=] {
-            if(hipSetDevice(device) != hipSuccess) {
-                eng->unpack_error = "hipSetDevice";
-                return;
-            }
-            for(int c = 0; c < HOST_CHUNKS; c++) {
-                int64_t lo, hi;
-                chunk_range(n, c, lo, hi);
-                if(hipEventSynchronize(eng->gchunk_ev[c]) != hipSuccess) {
-                    eng->unpack_error = "hipEventSynchronize";
-                    return;
-                }
-                if(hi > lo)
-                    parallel_for(hi - lo, [=](int64_t a0, int64_t a1) {
-                        for(int64_t i = lo + a0; i < lo + a1; i++) {
-                            double *g = (double *)(b + i * V.stride + V.off_gravpm);
-                            g[0] = ag[3 * i + 0];
-                            g[1] = ag[3 * i + 1];
-                            g[2] = ag[3 * i + 2];
-                            if(ap)
-                                *(double *)(b + i * V.stride + V.off_potential) = ap[i];
-                        }
-                    });
-            }
-        });
-        hc.mark("queued");
-        mpg_err_slot().clear();
-        return 0;
-    }
-    hipStream_t st = eng->stream;
-    download_chunks(
-        eng, n,
-        [=](int64_t lo, int64_t hi) {
-            MPG_HIP(hipMemcpyAsync(hg + 3 * lo, dg + 3 * lo, 3 * (hi - lo) * sizeof(double), hipMemcpyDeviceToHost, st));
-            if(wantpot)
-                MPG_HIP(hipMemcpyAsync(hp + lo, dp + lo, (hi - lo) * sizeof(double), hipMemcpyDeviceToHost, st));
-        },
-        [=](int64_t lo, int64_t hi) {
-            for(int64_t i = lo; i < hi; i++) {
-                double *g = (double *)(b + i * V.stride + V.off_gravpm);
-                g[0] = hg[3 * i + 0];
-                g[1] = hg[3 * i + 1];
-                g[2] = hg[3 * i + 2];
-                if(wantpot)
-                    *(double *)(b + i * V.stride + V.off_potential) = hp[i];
-            }
-        });
-    API_END
-}
-
-int mpg_force_tree_rebuild_mask(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, int mask)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P, "null argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    stage_particles(eng, P, BoxSize);
-    wait_for_leaf_blocks(eng, eng->stream);
-    eng->tree.build(eng->n, eng->d_pos, eng->d_mass, eng->d_type, mask, BoxSize, eng->stream, &eng->timer);
-    eng->tree.calc_moments(nullptr, eng->stream, &eng->timer);
-    eng->tree_allocated = true;
-    eng->tree_mask = mask;
-    eng->full_particle_tree = (eng->tree.npart == eng->n) || mask == 63;
-    API_END
-}
-
-int mpg_force_tree_full(mpg_engine *eng, const mpg_particle_view *P, double BoxSize)
-{
-    return mpg_force_tree_rebuild_mask(eng, P, BoxSize, 63 /* ALLMASK, forcetree.h:22 */);
-}
-
-int mpg_force_tree_free(mpg_engine *eng)
-{
-    API_BEGIN
-    MPG_CHECK(eng, "null engine");
-    eng->tree_allocated = false;
-    eng->full_particle_tree = false;
-    eng->tree.has_moments = false;
-    API_END
-}
-
-// the results of the targets [lo, hi) of the tree order, compacted in that order for a contiguous copy to the host
-__global__ void __launch_bounds__(256) k_gather_results(int64_t lo, int64_t hi, const int *__restrict__ order, const double *__restrict__ acc,
-                                                        const double *__restrict__ pot, double *__restrict__ acc_t, double *__restrict__ pot_t)
-{
-    const int64_t j = lo + (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if(j >= hi)
-        return;
-    const int64_t i = order[j];
-    acc_t[3 * j + 0] = acc[3 * i + 0];
-    acc_t[3 * j + 1] = acc[3 * i + 1];
-    acc_t[3 * j + 2] = acc[3 * i + 2];
-    if(pot_t)
-        pot_t[j] = pot[i];
-}
-
-int mpg_grav_short_tree(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
-                        double (*AccelStore)[3], double rho0)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P, "null argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    MPG_CHECK(eng->tree_allocated && eng->tree.has_moments, "Gravtree called before tree moments computed!");
-    MPG_CHECK(P->n == eng->n, "grav_short_tree: particle table changed size since the tree was built");
-    MPG_CHECK(P->off_accel >= 0 && P->off_gravpm >= 0, "particle view needs FullTreeGravAccel and GravPM");
-    const int64_t n = P->n;
-    if(eng->resident && eng->res_base == P->base) {
-        // OldAcc from the resident FullTreeGravAccel + GravPM (grav_get_abs_accel, gravshort.h:70-80), results into the resident
-        // FullTreeGravAccel / Potential in place: a target's old value is read before its new one is written, and no walk reads
-        // another target's acceleration.  AccelStore (host) receives a copy when given (timestep.c:454-456).
-        const int *d_act = nullptr;
-        if(ActiveParticle) {
-            eng->s_active.reserve((size_t)NumActiveParticle + 1);
-            MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-            d_act = eng->s_active.p;
-        }
-        const bool full = eng->full_particle_tree;
-        double *out = eng->r_accel.p;
-        if(!full) { // (a tree of a subset: results go to AccelStore only, gravshort.h:54-66)
-            eng->s_accel.reserve(3 * (size_t)n + 1);
-            MPG_HIP(hipMemsetAsync(eng->s_accel.p, 0, 3 * n * sizeof(double), eng->stream));
-            out = eng->s_accel.p;
-        }
-        if(mpg_dev_grav_short_tree(eng, nullptr, eng->r_accel.p, eng->r_gravpm.p, d_act, NumActiveParticle, out, full ? eng->r_pot.p : nullptr, rho0))
-            throw Error(g_err);
-        if(AccelStore) {
-            eng->h_d2.reserve(3 * (size_t)n + 1);
-            double *ha = eng->h_d2.p;
-            MPG_HIP(hipMemcpyAsync(ha, out, 3 * n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-            MPG_HIP(hipStreamSynchronize(eng->stream));
-            const int64_t m = ActiveParticle ? NumActiveParticle : n;
-            parallel_for(m, [=](int64_t lo, int64_t hi) {
-                for(int64_t k = lo; k < hi; k++) {
-                    const int64_t i = ActiveParticle ? ActiveParticle[k] : k;
-                    AccelStore[i][0] = ha[3 * i + 0];
-                    AccelStore[i][1] = ha[3 * i + 1];
-                    AccelStore[i][2] = ha[3 * i + 2];
-                }
-            });
-        }
-        mpg_err_slot().clear();
-        return 0;
-    }
-    const char *b = (const char *)P->base;
-    const mpg_particle_view V = *P;
-    // OldAcc = |FullTreeGravAccel + GravPM| / G (grav_short_copy, gravshort.h:82-86).  With overlap, and when this epoch's first call
-    // uploaded FullTreeGravAccel and this epoch's gravpm_force left GravPM on the device, it is taken there (k_oldacc / the list kernel:
-    // the same arithmetic); otherwise from P[] on the host.
-    HostClock hc("grav_short_tree");
-    const bool dev_old = eng->host_overlap && eng->host_epoch != 0 && eng->staged_extra_epoch == eng->host_epoch &&
-                         eng->gravpm_epoch == eng->host_epoch && eng->staged_base == P->base && eng->staged_n == n;
-    eng->s_accel.reserve(3 * (size_t)n + 1);
-    eng->s_pot.reserve((size_t)n + 1);
-    if(!dev_old) {
-        eng->host_join(); // (GravPM is read from P[])
-        eng->h_d3.reserve((size_t)n + 1);
-        double *old = eng->h_d3.p;
-        const double G = eng->pm.G;
-        parallel_for(n, [=](int64_t lo, int64_t hi) {
-            for(int64_t i = lo; i < hi; i++) {
-                const double *a = (const double *)(b + i * V.stride + V.off_accel);
-                const double *g = (const double *)(b + i * V.stride + V.off_gravpm);
-                double s2 = 0;
-                for(int j = 0; j < 3; j++) {
-                    const double ax = a[j] + g[j];
-                    s2 += ax * ax;
-                }
-                old[i] = sqrt(s2) / G;
-            }
-        });
-        eng->s_old.reserve((size_t)n + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_old.p, old, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-    }
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    const bool full = eng->full_particle_tree;
-    const bool wantpot = full && P->off_potential >= 0;
-    MPG_HIP(hipMemsetAsync(eng->s_accel.p, 0, 3 * n * sizeof(double), eng->stream));
-    if(dev_old && eng->ev_acc_up) // (FullTreeGravAccel went up on the copy stream)
-        MPG_HIP(hipStreamWaitEvent(eng->stream, eng->ev_acc_up, 0));
-    // ---- with overlap, all particles active, a tree of all of them: the walk in SLICES of the tree order, the results of slice k copied
-    // down (compacted in tree order: one contiguous copy) and written into P[] by a host thread while slice k + 1 is walked.  The slices
-    // are cut at multiples of 8 targets, i.e. between the waves of the list kernel: every target's lists, and with them its sums, are
-    // those of the unsliced walk bit for bit.  What stays on the critical path is the last slice's copy and write-back.
-    static const int nslices_env = getenv("MPG_HOST_WALK_SLICES") ? atoi(getenv("MPG_HOST_WALK_SLICES")) : 5;
-    const int64_t npart = eng->tree.npart;
-    const int nslices = eng->host_slices > 1 ? eng->host_slices : (npart >= (1 << 20) ? nslices_env : 1); // (small walks: not worth the calls)
-    if(eng->host_overlap && dev_old && !ActiveParticle && !AccelStore && full && eng->copy_stream && nslices > 1 && npart >= 8 * nslices) {
-        const int S = nslices < 8 ? nslices : 8;
-        const int *d_order = (const int *)eng->tree.idx_b.p; // tree slot -> particle
-        eng->h_order.reserve((size_t)npart + 1);
-        eng->s_acc_t.reserve(3 * (size_t)npart + 1);
-        eng->h_acc_t.reserve(3 * (size_t)npart + 1);
-        if(wantpot) {
-            eng->s_pot_t.reserve((size_t)npart + 1);
-            eng->h_pot_t.reserve((size_t)npart + 1);
-            eng->s_pot2.reserve((size_t)n + 1);
-        }
-        int *h_order = eng->h_order.p;
-        double *hat = eng->h_acc_t.p, *hpt = wantpot ? eng->h_pot_t.p : nullptr;
-        double *dat = eng->s_acc_t.p, *dpt = wantpot ? eng->s_pot_t.p : nullptr;
-        for(int k = 0; k <= S; k++)
-            if(!eng->slice_ev[k])
-                MPG_HIP(hipEventCreateWithFlags(&eng->slice_ev[k], hipEventDisableTiming));
-        // the tree order for the host thread (the tree is complete: force_tree_full waited for it)
-        MPG_HIP(hipMemcpyAsync(h_order, d_order, (size_t)npart * sizeof(int), hipMemcpyDeviceToHost, eng->copy_stream));
-        // (what nothing hides is the write-back that is still running when the last walk ends.  The writer needs about half as long for a slice's
-        // results as the walk of that slice took, so slice k + 1 may be about half of slice k and still cover it: the slices shrink geometrically,
-        // MPG_HOST_SLICE_RATIO per step, and the last - the one nothing covers - is the smallest.  1 = equal slices)
-        static const double ratio_env = getenv("MPG_HOST_SLICE_RATIO") ? atof(getenv("MPG_HOST_SLICE_RATIO")) : 0.55;
-        const double ratio = (ratio_env > 0.05 && ratio_env < 1.0) ? ratio_env : 1.0;
-        int64_t cut[9];
-        {
-            double w = 1.0, tot = 0.0, acc = 0.0;
-            for(int k = 0; k < S; k++, w *= ratio)
-                tot += w;
-            w = 1.0;
-            for(int k = 0; k <= S; k++) {
-                cut[k] = k == S ? npart : ((int64_t)((double)npart * (acc / tot)) & ~(int64_t)7);
-                acc += w;
-                w *= ratio;
-            }
-        }
-        char *wbs = (char *)P->base;
-        std::string therr;
-        std::thread writer;
-        std::atomic<int> issued{0}; // slices whose copies are queued and whose event is recorded (an event not yet recorded "is complete")
-        std::atomic<bool> abandon{false};
-        // (an error thrown below while the writer runs: tell it to stop and wait for it - a joinable std::thread must not be destroyed)
-        struct JoinOnExit {
-            std::thread &t;
-            std::atomic<bool> &stop;
-            ~JoinOnExit()
-            {
-                if(t.joinable()) {
-                    stop = true;
-                    t.join();
-                }
-            }
-        } join_on_exit{writer, abandon};
-        for(int k = 0; k < S; k++) {
-            const int64_t lo = cut[k], hi = cut[k + 1];
-            if(hi > lo) {
-                if(mpg_dev_grav_short_tree(eng, nullptr, eng->s_prevacc.p, eng->s_gravpm.p, d_order + lo, hi - lo, eng->s_accel.p,
-                                           wantpot ? eng->s_pot2.p : nullptr, rho0))
-                    throw Error(g_err);
-                hipLaunchKernelGGL(k_gather_results, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, eng->stream, lo, hi, d_order, eng->s_accel.p,
-                                   wantpot ? eng->s_pot2.p : nullptr, dat, dpt);
-            }
-            MPG_HIP(hipEventRecord(eng->ev_pm_done, eng->stream)); // (re-used as "slice k gathered")
-            MPG_HIP(hipStreamWaitEvent(eng->copy_stream, eng->ev_pm_done, 0));
-            if(hi > lo) {
-                MPG_HIP(hipMemcpyAsync(hat + 3 * lo, dat + 3 * lo, 3 * (size_t)(hi - lo) * sizeof(double), hipMemcpyDeviceToHost, eng->copy_stream));
-                if(wantpot)
-                    MPG_HIP(hipMemcpyAsync(hpt + lo, dpt + lo, (size_t)(hi - lo) * sizeof(double), hipMemcpyDeviceToHost, eng->copy_stream));
-            }
-            MPG_HIP(hipEventRecord(eng->slice_ev[k], eng->copy_stream));
-            issued = k + 1;
-            if(k == 0) {
-                // (the PM step's GravPM / Potential must be in P[] before the tree's Potential goes over it)
-                eng->host_join();
-                MPG_CHECK(eng->unpack_error.empty(), "host path: the write-back of GravPM failed: " + eng->unpack_error);
-                const int device = eng->device;
-                mpg_engine *e = eng;
-                writer = std::thread([=, &therr, &issued, &abandon] {
-                    if(hipSetDevice(device) != hipSuccess) {
-                        therr = "hipSetDevice";
-                        return;
-                    }
-                    for(int q = 0; q < S; q++) {
-                        while(issued.load() <= q) { // (the main thread is inside the walk of slice q)
-                            if(abandon.load())
-                                return;
-                            std::this_thread::sleep_for(std::chrono::microseconds(50));
-                        }
-                        if(hipEventSynchronize(e->slice_ev[q]) != hipSuccess) {
-                            therr = "hipEventSynchronize";
-                            return;
-                        }
-                        const int64_t a = cut[q], b = cut[q + 1];
-                        if(b > a)
-                            parallel_for(b - a, [=](int64_t j0, int64_t j1) {
-                                for(int64_t j = a + j0; j < a + j1; j++) {
-                                    const int64_t i = h_order[j];
-                                    double *acc = (double *)(wbs + i * V.stride + V.off_accel);
-                                    acc[0] = hat[3 * j + 0];
-                                    acc[1] = hat[3 * j + 1];
-                                    acc[2] = hat[3 * j + 2];
-                                    if(hpt)
-                                        *(double *)(wbs + i * V.stride + V.off_potential) = hpt[j];
-                                }
-                            });
-                    }
-                });
-            }
-        }
-        hc.mark("walk (sliced)");
-        writer.join();
-        MPG_CHECK(therr.empty(), "host path: the write-back of the walk's results failed: " + therr);
-        hc.mark("last slice down");
-        //  P[].FullTreeGravAccel now holds THIS walk's result: the copy staged at the epoch's first upload is no longer
-        // what grav_short_copy (gravshort.h:82-86) would read.  A second walk of the same epoch takes OldAcc from P[] again.
-        eng->staged_extra_epoch = -1;
-        mpg_err_slot().clear();
-        return 0;
-    }
-    // (with overlap the PM step's Potential may still be on its way down from s_pot: the tree's goes to a buffer of its own)
-    double *d_treepot = eng->s_pot.p;
-    if(eng->host_overlap && wantpot) {
-        eng->s_pot2.reserve((size_t)n + 1);
-        d_treepot = eng->s_pot2.p;
-    }
-    int rc = dev_old ? mpg_dev_grav_short_tree(eng, nullptr, eng->s_prevacc.p, eng->s_gravpm.p, d_act, NumActiveParticle, eng->s_accel.p,
-                                               wantpot ? d_treepot : nullptr, rho0)
-                     : mpg_dev_grav_short_tree(eng, eng->s_old.p, nullptr, nullptr, d_act, NumActiveParticle, eng->s_accel.p,
-                                               wantpot ? d_treepot : nullptr, rho0);
-    if(rc)
-        throw Error(g_err);
-    hc.mark("walk");
-    // (the PM step's GravPM / Potential must be in P[] before this call's Potential - the tree's, gravshort.h:94-95 - goes over it)
-    eng->host_join();
-    hc.mark("join");
-    MPG_CHECK(eng->unpack_error.empty(), "host path: the write-back of GravPM failed: " + eng->unpack_error);
-    eng->h_d2.reserve(3 * (size_t)n + 1);
-    eng->h_d3.reserve((size_t)n + 1);
-    double *ha = eng->h_d2.p, *hp = eng->h_d3.p; // (OldAcc has been uploaded: its staging buffer is free again)
-    char *wb = (char *)P->base;
-    // (garbage / swallowed particles are no walk targets, treewalk.c:234: their fields stay as they are.  eng->h_b holds the live flags
-    // of the staged table whenever it has dead records: stage_particles)
-    const uint8_t *liveflag = eng->pm_live ? eng->h_b.p : nullptr;
-    auto put = [=](int64_t i) {
-        if(liveflag && !liveflag[i])
-            return;
-        if(AccelStore) {
-            AccelStore[i][0] = ha[3 * i + 0];
-            AccelStore[i][1] = ha[3 * i + 1];
-            AccelStore[i][2] = ha[3 * i + 2];
-        }
-        if(full) { // gravshort.h:54-66
-            double *a = (double *)(wb + i * V.stride + V.off_accel);
-            a[0] = ha[3 * i + 0];
-            a[1] = ha[3 * i + 1];
-            a[2] = ha[3 * i + 2];
-            if(wantpot)
-                *(double *)(wb + i * V.stride + V.off_potential) = hp[i];
-        }
-    };
-    const double *da = eng->s_accel.p, *dpot = d_treepot;
-    hipStream_t st = eng->stream;
-    if(!ActiveParticle) // all particles: unpack chunk by chunk while the later chunks are still on the bus
-        download_chunks(
-            eng, n,
-            [=](int64_t lo, int64_t hi) {
-                MPG_HIP(hipMemcpyAsync(ha + 3 * lo, da + 3 * lo, 3 * (hi - lo) * sizeof(double), hipMemcpyDeviceToHost, st));
-                if(wantpot)
-                    MPG_HIP(hipMemcpyAsync(hp + lo, dpot + lo, (hi - lo) * sizeof(double), hipMemcpyDeviceToHost, st));
-            },
-            [=](int64_t lo, int64_t hi) {
-                for(int64_t i = lo; i < hi; i++)
-                    put(i);
-            });
-    else {
-        MPG_HIP(hipMemcpyAsync(ha, da, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-        if(wantpot)
-            MPG_HIP(hipMemcpyAsync(hp, dpot, n * sizeof(double), hipMemcpyDeviceToHost, st));
-        MPG_HIP(hipStreamSynchronize(st));
-        parallel_for(NumActiveParticle, [=](int64_t lo, int64_t hi) {
-            for(int64_t k = lo; k < hi; k++)
-                put(ActiveParticle[k]);
-        });
-    }
-    hc.mark("download+unpack");
-    if(full) // (as above: a walk wrote P[].FullTreeGravAccel; the staged copy of the old one must not open nodes for a second walk of the epoch)
-        eng->staged_extra_epoch = -1;
-    API_END
-}
-
-/* ---- device-resident drop-in mode ------------------------------------------------------------------------------------------
- * The host-pointer calls above move Pos / Mass up and GravPM / FullTreeGravAccel / Potential down on every call because the caller
- * may have changed P[] in between: at 256^3 that is half of a step (bench.py host_path).  A caller that lets the engine integrate -
- * mpg_dev_drift_all_particles, mpg_dev_apply_pm_half_kick, mpg_dev_apply_half_kick on the arrays of mpg_resident_arrays - declares
- * the table resident: one upload, then gravpm_force / force_tree_* / grav_short_tree on the same mpg_particle_view run on the device
- * copies and leave their results there; the host asks for the columns its other modules read (mpg_resident_fetch) and hands back
- * what they changed (mpg_resident_push).  Anything that reorders or resizes P[] (domain exchange, garbage collection) goes between
- * mpg_resident_end and a new mpg_resident_begin. */
-namespace {
-// one column of the AoS table <-> a device array of w doubles per particle
-void column_to_device(mpg_engine *eng, const mpg_particle_view &V, int64_t off, int w, double *dev)
-{
-    const int64_t n = V.n;
-    eng->h_d.reserve((size_t)w * n + 1);
-    double *h = eng->h_d.p;
-    const char *b = (const char *)V.base;
-    const int64_t stride = V.stride;
-    for(int c = 0; c < HOST_CHUNKS; c++) {
-        int64_t lo, hi;
-        chunk_range(n, c, lo, hi);
-        if(hi <= lo)
-            continue;
-        parallel_for(hi - lo, [=](int64_t a0, int64_t a1) {
-            for(int64_t i = lo + a0; i < lo + a1; i++)
-                for(int k = 0; k < w; k++)
-                    h[w * i + k] = ((const double *)(b + i * stride + off))[k];
-        });
-        MPG_HIP(hipMemcpyAsync(dev + w * lo, h + w * lo, (size_t)w * (hi - lo) * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-    }
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-}
-
-void column_to_host(mpg_engine *eng, const mpg_particle_view &V, int64_t off, int w, const double *dev)
-{
-    const int64_t n = V.n;
-    eng->h_d.reserve((size_t)w * n + 1);
-    double *h = eng->h_d.p;
-    char *b = (char *)V.base;
-    const int64_t stride = V.stride;
-    hipStream_t st = eng->stream;
-    download_chunks(
-        eng, n, [=](int64_t lo, int64_t hi) { MPG_HIP(hipMemcpyAsync(h + w * lo, dev + w * lo, (size_t)w * (hi - lo) * sizeof(double), hipMemcpyDeviceToHost, st)); },
-        [=](int64_t lo, int64_t hi) {
-            for(int64_t i = lo; i < hi; i++)
-                for(int k = 0; k < w; k++)
-                    ((double *)(b + i * stride + off))[k] = h[w * i + k];
-        });
-}
-
-void resident_check(mpg_engine *eng, const mpg_particle_view *P)
-{
-    MPG_CHECK(eng && P, "null argument");
-    MPG_CHECK(eng->resident && eng->res_base == P->base && eng->res_n == P->n, "not the resident particle table (mpg_resident_begin first)");
-    MPG_HIP(hipSetDevice(eng->device));
-}
-} // namespace
-
-int mpg_resident_begin(mpg_engine *eng, const mpg_particle_view *P, double BoxSize)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P, "null argument");
-    MPG_CHECK(P->off_accel >= 0 && P->off_gravpm >= 0 && P->off_potential >= 0, "resident mode needs FullTreeGravAccel, GravPM and Potential in the view");
-    MPG_HIP(hipSetDevice(eng->device));
-    eng->host_join(); // (a prefetch in flight writes the staging state set below)
-    eng->resident = false;
-    eng->staged_epoch = -1; // (force the upload whatever epoch the caller declared)
-    stage_particles(eng, P, BoxSize);
-    const size_t n = (size_t)P->n;
-    eng->r_accel.reserve(3 * n + 3);
-    eng->r_gravpm.reserve(3 * n + 3);
-    eng->r_pot.reserve(n + 1);
-    column_to_device(eng, *P, P->off_accel, 3, eng->r_accel.p);
-    column_to_device(eng, *P, P->off_gravpm, 3, eng->r_gravpm.p);
-    column_to_device(eng, *P, P->off_potential, 1, eng->r_pot.p);
-    eng->res_has_vel = P->off_vel >= 0;
-    if(eng->res_has_vel) {
-        eng->r_vel.reserve(3 * n + 3);
-        column_to_device(eng, *P, P->off_vel, 3, eng->r_vel.p);
-    }
-    eng->resident = true;
-    eng->res_base = P->base;
-    eng->res_n = P->n;
-    API_END
-}
-
-int mpg_resident_arrays(mpg_engine *eng, mpg_resident_view *out)
-{
-    API_BEGIN
-    MPG_CHECK(eng && out && eng->resident, "mpg_resident_arrays: no resident table");
-    out->n = eng->res_n;
-    out->d_pos = eng->s_pos.p;
-    out->d_mass = eng->s_mass.p;
-    out->d_type = eng->s_type.p;
-    out->d_vel = eng->res_has_vel ? eng->r_vel.p : nullptr; // (a buffer left by an earlier session is not this table's Vel)
-    out->d_fulltree_accel = eng->r_accel.p;
-    out->d_gravpm = eng->r_gravpm.p;
-    out->d_potential = eng->r_pot.p;
-    API_END
-}
-
-int mpg_resident_fetch(mpg_engine *eng, const mpg_particle_view *P, unsigned fields)
-{
-    API_BEGIN
-    resident_check(eng, P);
-    if(fields & MPG_FIELD_POS)
-        column_to_host(eng, *P, P->off_pos, 3, eng->s_pos.p);
-    if((fields & MPG_FIELD_VEL) && P->off_vel >= 0 && eng->res_has_vel)
-        column_to_host(eng, *P, P->off_vel, 3, eng->r_vel.p);
-    if(fields & MPG_FIELD_ACCEL)
-        column_to_host(eng, *P, P->off_accel, 3, eng->r_accel.p);
-    if(fields & MPG_FIELD_GRAVPM)
-        column_to_host(eng, *P, P->off_gravpm, 3, eng->r_gravpm.p);
-    if(fields & MPG_FIELD_POTENTIAL)
-        column_to_host(eng, *P, P->off_potential, 1, eng->r_pot.p);
-    API_END
-}
-
-int mpg_resident_push(mpg_engine *eng, const mpg_particle_view *P, unsigned fields)
-{
-    API_BEGIN
-    resident_check(eng, P);
-    if(fields & MPG_FIELD_POS) {
-        column_to_device(eng, *P, P->off_pos, 3, eng->s_pos.p);
-        eng->pm_queued = false;
-    }
-    if((fields & MPG_FIELD_VEL) && P->off_vel >= 0) {
-        eng->r_vel.reserve(3 * (size_t)P->n + 3);
-        column_to_device(eng, *P, P->off_vel, 3, eng->r_vel.p);
-        eng->res_has_vel = true;
-    }
-    if(fields & MPG_FIELD_ACCEL)
-        column_to_device(eng, *P, P->off_accel, 3, eng->r_accel.p);
-    if(fields & MPG_FIELD_GRAVPM)
-        column_to_device(eng, *P, P->off_gravpm, 3, eng->r_gravpm.p);
-    if(fields & MPG_FIELD_POTENTIAL)
-        column_to_device(eng, *P, P->off_potential, 1, eng->r_pot.p);
-    API_END
-}
-
-int mpg_resident_end(mpg_engine *eng, const mpg_particle_view *P)
-{
-    API_BEGIN
-    resident_check(eng, P);
-    if(mpg_resident_fetch(eng, P, MPG_FIELD_POS | MPG_FIELD_VEL | MPG_FIELD_ACCEL | MPG_FIELD_GRAVPM | MPG_FIELD_POTENTIAL))
-        throw Error(g_err);
-    MPG_CHECK(!eng->sph_resident, "mpg_resident_end: the gas arrays are still resident (mpg_resident_sph_end first)");
-    if(eng->r_stored_host) { // the StoredGravAccel of a split-gravity step left between its two halves goes back to the caller's array
-        MPG_HIP(hipMemcpyAsync(eng->r_stored_host, eng->r_stored.p, 3 * (size_t)P->n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-        MPG_HIP(hipStreamSynchronize(eng->stream));
-        eng->r_stored_host = nullptr;
-    }
-    eng->resident = false;
-    eng->res_has_vel = false;
-    eng->res_base = nullptr;
-    eng->res_n = -1;
-    eng->staged_epoch = -1;
-    API_END
-}
-
-/* ---- potential planes on a host table (write_plane, plane.c:572-683; the kernels are planes.hip's) ----------------------------------- */
-namespace {
-// IsGarbage / Swallowed of the records -> device bytes (null when the view has no flags).  In resident mode the host records are stale in
-// every column the engine integrates, but nothing on the device sets or clears these two bits, so they are read from the host table.
-const uint8_t *stage_plane_flags(mpg_engine *eng, const mpg_particle_view *P)
-{
-    if(P->off_flags < 0 || P->n == 0)
-        return nullptr;
-    const int64_t n = P->n;
-    // (not h_b: inside a declared epoch it holds the live flags the write-back of mpg_grav_short_tree reads)
-    eng->h_plane_flags.reserve((size_t)n + 1);
-    eng->plane_flags.reserve((size_t)n + 1);
-    uint8_t *hb = eng->h_plane_flags.p;
-    const char *b = (const char *)P->base;
-    const mpg_particle_view V = *P;
-    parallel_for(n, [=](int64_t lo, int64_t hi) {
-        for(int64_t i = lo; i < hi; i++)
-            hb[i] = *(const uint8_t *)(b + i * V.stride + V.off_flags) & 3;
-    });
-    MPG_HIP(hipMemcpyAsync(eng->plane_flags.p, hb, (size_t)n, hipMemcpyHostToDevice, eng->stream));
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-    return eng->plane_flags.p;
-}
-
-void host_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *par, double *planes, int64_t *npart)
-{
-    int64_t ncuts = 0;
-    MPG_CHECK(mpg_plane_count(eng, par, 0.0, &ncuts) == 0, mpg_last_error());
-    MPG_CHECK(par->Resolution >= 1, "potential planes: Resolution must be at least 1");
-    MPG_CHECK(par->Resolution <= 32768, "potential planes: Resolution above 32768");
-    const size_t tot = (size_t)ncuts * (size_t)(par->nnormals > 0 ? par->nnormals : 0) * (size_t)par->Resolution * par->Resolution;
-    MPG_CHECK(tot == 0 || (planes && npart), "potential planes: null output");
-    eng->plane_out.reserve(tot + 1);
-    const uint8_t *fl = stage_plane_flags(eng, P);
-    planes_run(eng, par, fl, eng->plane_out.p, npart, nullptr);
-    if(tot)
-        MPG_HIP(hipMemcpyAsync(planes, eng->plane_out.p, tot * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-}
-} // namespace
-
-int mpg_potential_planes(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, const mpg_plane_params *params, double *planes, int64_t *npart)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && params, "null argument");
-    MPG_CHECK(BoxSize > 0, "potential planes: BoxSize must be positive");
-    MPG_HIP(hipSetDevice(eng->device));
-    eng->host_join(); // (a running prefetch is joined, a write-back of the last PM step finished)
-    MPG_CHECK(eng->unpack_error.empty(), "host path: the write-back of GravPM failed: " + eng->unpack_error);
-    stage_particles(eng, P, BoxSize);
-    host_planes(eng, P, params, planes, npart);
-    API_END
-}
-
-int mpg_resident_potential_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *params, double *planes, int64_t *npart)
-{
-    API_BEGIN
-    resident_check(eng, P);
-    MPG_CHECK(params, "null argument");
-    MPG_CHECK(eng->d_pos == eng->s_pos.p && eng->n == P->n, "resident mode: the binding changed (mpg_resident_end / _begin)");
-    host_planes(eng, P, params, planes, npart);
-    API_END
-}
-
-int mpg_grav_short_pair(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle, double Rcut, double rho0)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P, "null argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    MPG_CHECK(eng->tree_allocated, "grav_short_pair: no tree");
-    MPG_CHECK(P->n == eng->n, "grav_short_pair: particle table changed size since the tree was built");
-    MPG_CHECK(P->off_accel >= 0, "particle view needs FullTreeGravAccel");
-    const int64_t n = P->n;
-    eng->s_accel.reserve(3 * (size_t)n + 1);
-    eng->s_pot.reserve((size_t)n + 1);
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    const bool full = eng->full_particle_tree;
-    const bool wantpot = full && P->off_potential >= 0;
-    MPG_HIP(hipMemsetAsync(eng->s_accel.p, 0, 3 * n * sizeof(double), eng->stream));
-    if(mpg_dev_grav_short_pair(eng, d_act, NumActiveParticle, Rcut, eng->s_accel.p, wantpot ? eng->s_pot.p : nullptr, rho0))
-        throw Error(g_err);
-    eng->h_d2.reserve(3 * (size_t)n + 1);
-    eng->h_d3.reserve((size_t)n + 1);
-    double *ha = eng->h_d2.p, *hp = eng->h_d3.p;
-    MPG_HIP(hipMemcpyAsync(ha, eng->s_accel.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    if(wantpot)
-        MPG_HIP(hipMemcpyAsync(hp, eng->s_pot.p, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-    if(full) { // the pair-wise result reaches the caller only through P (gravshort.h:54-66): priv.Accel is freed on return
-        const int64_t nt = ActiveParticle ? NumActiveParticle : n;
-        char *wb = (char *)P->base;
-        const mpg_particle_view V = *P;
-        parallel_for(nt, [=](int64_t lo, int64_t hi) {
-            for(int64_t k = lo; k < hi; k++) {
-                const int64_t i = ActiveParticle ? ActiveParticle[k] : k;
-                double *a = (double *)(wb + i * V.stride + V.off_accel);
-                a[0] = ha[3 * i + 0];
-                a[1] = ha[3 * i + 1];
-                a[2] = ha[3 * i + 2];
-                if(wantpot)
-                    *(double *)(wb + i * V.stride + V.off_potential) = hp[i];
-            }
-        });
-    }
-    API_END
-}
-
 /* ------------------------------ SPH ------------------------------ */
 
 int mpg_set_densitypar(mpg_engine *eng, const mpg_density_params *dp)
@@ -2541,24 +1562,6 @@ int mpg_dev_force_tree_active_moments(mpg_engine *eng, const int *d_active, int6
     API_END
 }
 
-int mpg_force_tree_active_moments(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, const int *ActiveParticle,
-                                  int64_t NumActiveParticle, int HybridNuTracer)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P, "null argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    stage_particles(eng, P, BoxSize);
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    if(mpg_dev_force_tree_active_moments(eng, d_act, NumActiveParticle, HybridNuTracer))
-        throw Error(g_err);
-    API_END
-}
-
 int mpg_dev_set_init_hsml(mpg_engine *eng, const mpg_sph_arrays *A, double MeanGasSeparation)
 {
     API_BEGIN
@@ -2620,455 +1623,6 @@ int mpg_dev_hydro_force(mpg_engine *eng, const mpg_sph_arrays *A, const mpg_sph_
     API_END
 }
 
-/* host-pointer SPH path: stage every array of mpg_sph_arrays in HBM (doubles: hsml, dthsml, vel[3], gacc[3], gpm[3],
- * hydroacc_in[3], entropy, dtentropy_in, density, egywtdensity, dhsmlegyfac, divvel, curlvel, gradrho[3], hydroacc_out[3],
- * dtentropy_out, maxsignalvel; bytes: tb_hydro, tb_grav) */
-namespace {
-struct SphField {
-    int idx;      // slot in h_sph (or h_sph_u8 when width == 0)
-    int width;    // doubles per particle; 0 = uint8
-    bool in, out; // copied to / from the device
-};
-// order = field order of mpg_sph_arrays
-const SphField SPH_FIELDS[19] = {{0, 1, true, true},  {1, 1, false, true}, {2, 3, true, false},  {3, 3, true, false}, {4, 3, true, false},
-                                 {5, 3, true, false}, {0, 0, true, false}, {1, 0, true, false},  {6, 1, true, false}, {7, 1, true, false},
-                                 {8, 1, true, true},  {9, 1, true, true},  {10, 1, true, true},  {11, 1, true, true}, {12, 1, true, true},
-                                 {13, 3, false, true}, {14, 3, false, true}, {15, 1, false, true}, {16, 1, false, true}};
-
-void stage_sph(mpg_engine *eng, const mpg_sph_arrays *host, mpg_sph_arrays *dev, int64_t n)
-{
-    // (the staging buffers ARE the resident copies of a gas run: another array set must wait for mpg_resident_sph_end)
-    MPG_CHECK(!eng->sph_resident, "SPH host call with arrays other than the resident gas run's (mpg_resident_sph_end first)");
-    void *const *hp = (void *const *)host;
-    void **dp = (void **)dev;
-    for(int f = 0; f < 19; f++) {
-        dp[f] = nullptr;
-        if(!hp[f])
-            continue;
-        const SphField &F = SPH_FIELDS[f];
-        if(F.width == 0) {
-            eng->h_sph_u8[F.idx].reserve((size_t)n + 1);
-            dp[f] = eng->h_sph_u8[F.idx].p;
-            MPG_HIP(hipMemcpyAsync(dp[f], hp[f], (size_t)n, hipMemcpyHostToDevice, eng->stream));
-        }
-        else {
-            eng->h_sph[F.idx].reserve((size_t)n * F.width + 1);
-            dp[f] = eng->h_sph[F.idx].p;
-            if(F.in)
-                MPG_HIP(hipMemcpyAsync(dp[f], hp[f], (size_t)n * F.width * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-            else
-                MPG_HIP(hipMemsetAsync(dp[f], 0, (size_t)n * F.width * sizeof(double), eng->stream));
-        }
-    }
-}
-
-void unstage_sph(mpg_engine *eng, const mpg_sph_arrays *host, const mpg_sph_arrays *dev, int64_t n, bool hydro)
-{
-    void *const *hp = (void *const *)host;
-    void *const *dp = (void *const *)dev;
-    for(int f = 0; f < 19; f++) {
-        const SphField &F = SPH_FIELDS[f];
-        if(!hp[f] || !F.out || F.width == 0)
-            continue;
-        const bool hydro_field = (f >= 16);          // hydroacc_out, dtentropy_out, maxsignalvel
-        if(hydro != hydro_field)
-            continue;
-        MPG_HIP(hipMemcpyAsync(hp[f], dp[f], (size_t)n * F.width * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    }
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-}
-// the host arrays of a resident gas run (mpg_resident_sph_begin): their device copies are current, nothing is staged
-bool sph_is_resident(mpg_engine *eng, const mpg_particle_view *P, const mpg_sph_arrays *A)
-{
-    return eng->sph_resident && eng->resident && eng->res_base == P->base && A->hsml == eng->res_sph_host.hsml;
-}
-} // namespace
-
-int mpg_set_init_hsml(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, const mpg_sph_arrays *A, double MeanGasSeparation)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && A, "null argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    stage_particles(eng, P, BoxSize);
-    mpg_sph_arrays d;
-    stage_sph(eng, A, &d, P->n);
-    // the reference calls it on the GAS+BH tree with moments (init.c:485-511, test_density.c:86-87)
-    if(mpg_dev_force_tree_rebuild_mask(eng, 1 + 32, 1) || mpg_dev_set_init_hsml(eng, &d, MeanGasSeparation))
-        throw Error(g_err);
-    MPG_HIP(hipMemcpyAsync(A->hsml, d.hsml, P->n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-    API_END
-}
-
-int mpg_density(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, const mpg_sph_arrays *A, const mpg_sph_times *T,
-                const int *ActiveParticle, int64_t NumActiveParticle, int update_hsml, int DoEgyDensity, int BlackHoleOn)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && A && T, "null argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    stage_particles(eng, P, BoxSize);
-    mpg_sph_arrays d;
-    const bool res = sph_is_resident(eng, P, A); // a resident gas run: the arrays are in HBM already and stay there
-    if(res)
-        d = eng->res_sph_dev;
-    else
-        stage_sph(eng, A, &d, P->n);
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    if(mpg_dev_force_tree_rebuild_mask(eng, 1 /* GASMASK */, 0) ||
-       mpg_dev_density(eng, &d, T, d_act, NumActiveParticle, update_hsml, DoEgyDensity, BlackHoleOn) ||
-       (update_hsml && mpg_dev_force_tree_calc_hmax(eng)))
-        throw Error(g_err);
-    if(!res)
-        unstage_sph(eng, A, &d, P->n, false);
-    API_END
-}
-
-int mpg_hydro_force(mpg_engine *eng, const mpg_particle_view *P, const mpg_sph_arrays *A, const mpg_sph_times *T,
-                    const int *ActiveParticle, int64_t NumActiveParticle)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && A && T, "null argument");
-    MPG_HIP(hipSetDevice(eng->device));
-    MPG_CHECK(eng->tree_allocated && eng->tree.has_hmax, "Hydro called before hmax computed"); // hydra.c:172-173
-    MPG_CHECK(P->n == eng->n, "hydro_force: particle table changed size since density()");
-    mpg_sph_arrays d;
-    const bool res = sph_is_resident(eng, P, A);
-    if(res)
-        d = eng->res_sph_dev;
-    else
-        stage_sph(eng, A, &d, P->n);
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    if(mpg_dev_hydro_force(eng, &d, T, d_act, NumActiveParticle))
-        throw Error(g_err);
-    if(!res)
-        unstage_sph(eng, A, &d, P->n, true);
-    API_END
-}
-
-/* ---- a resident gas run: the SPH arrays stay in HBM between the calls, the integrator runs there (include/mpgadget_hip.h) ---- */
-namespace {
-__global__ void __launch_bounds__(256) k_flags_from_type(int64_t n, const uint8_t *__restrict__ type, uint8_t *__restrict__ flags)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if(i < n)
-        flags[i] = (type[i] & 7) == 7 ? 1 : 0; // (stage_particles gave garbage and swallowed particles type 7)
-}
-void resident_sph_check(mpg_engine *eng, const mpg_particle_view *P)
-{
-    resident_check(eng, P);
-    MPG_CHECK(eng->sph_resident, "no resident gas arrays (mpg_resident_sph_begin first)");
-}
-} // namespace
-
-int mpg_resident_sph_begin(mpg_engine *eng, const mpg_particle_view *P, const mpg_sph_arrays *A)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && A, "null argument");
-    resident_check(eng, P);
-    MPG_CHECK(eng->res_has_vel, "mpg_resident_sph_begin: the resident table has no Vel column (the view's off_vel)");
-    MPG_CHECK(A->hsml && A->entropy && A->density && A->dhsmlegyfac && A->divvel && A->curlvel && A->hydroacc_out && A->dtentropy_out &&
-                  A->maxsignalvel,
-              "mpg_resident_sph_begin: hsml, entropy, density, dhsmlegyfac, divvel, curlvel, hydroacc_out, dtentropy_out and maxsignalvel are required");
-    const int64_t n = P->n;
-    mpg_sph_arrays d;
-    stage_sph(eng, A, &d, n);
-    // the arrays stage_sph only clears hold state of the previous step that the predictions and the drift read: DtHsml, HydroAccel, DtEntropy
-    void *const *hp = (void *const *)A;
-    void **dp = (void **)&d;
-    for(int f = 0; f < 19; f++) {
-        const SphField &F = SPH_FIELDS[f];
-        if(hp[f] && F.width > 0 && !F.in)
-            MPG_HIP(hipMemcpyAsync(dp[f], hp[f], (size_t)n * F.width * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-    }
-    // one field each in the reference: SphP.HydroAccel and SphP.DtEntropy are what the next step's predictions read; P[].Vel,
-    // FullTreeGravAccel and GravPM are the resident table's
-    d.hydroacc_in = d.hydroacc_out;
-    d.dtentropy_in = d.dtentropy_out;
-    d.vel = eng->r_vel.p;
-    d.gacc = eng->r_accel.p;
-    d.gpm = eng->r_gravpm.p;
-    eng->r_flags.reserve((size_t)n + 1);
-    if(n > 0)
-        hipLaunchKernelGGL(k_flags_from_type, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, eng->stream, n, eng->s_type.p, eng->r_flags.p);
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-    eng->res_sph_host = *A;
-    eng->res_sph_dev = d;
-    eng->sph_resident = true;
-    API_END
-}
-
-int mpg_resident_sph_arrays(mpg_engine *eng, mpg_sph_arrays *out)
-{
-    API_BEGIN
-    MPG_CHECK(eng && out && eng->sph_resident, "mpg_resident_sph_arrays: no resident gas arrays");
-    *out = eng->res_sph_dev;
-    API_END
-}
-
-int mpg_resident_sph_end(mpg_engine *eng, const mpg_sph_arrays *A)
-{
-    API_BEGIN
-    MPG_CHECK(eng && A && eng->sph_resident, "mpg_resident_sph_end: no resident gas arrays");
-    MPG_CHECK(A->hsml == eng->res_sph_host.hsml, "mpg_resident_sph_end: not the arrays mpg_resident_sph_begin took");
-    MPG_HIP(hipSetDevice(eng->device));
-    const int64_t n = eng->res_n;
-    void *const *hp = (void *const *)A;
-    void *const *dp = (void *const *)&eng->res_sph_dev;
-    for(int f = 0; f < 19; f++) {
-        const SphField &F = SPH_FIELDS[f];
-        // everything the device may have changed: the outputs, Entropy (kicks), the time bins; not the aliases of the table's columns
-        const bool table_alias = (f >= 2 && f <= 4), pred_alias = (f == 5 || f == 9);
-        if(!hp[f] || table_alias || pred_alias)
-            continue;
-        const size_t bytes = F.width == 0 ? (size_t)n : (size_t)n * F.width * sizeof(double);
-        MPG_HIP(hipMemcpyAsync(hp[f], dp[f], bytes, hipMemcpyDeviceToHost, eng->stream));
-    }
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-    eng->sph_resident = false;
-    API_END
-}
-
-// the resident time bins into host arrays (n bytes each; either may be NULL): build_active_particles (timestep.c:1333-1420) reads
-// P[].TimeBinHydro / TimeBinGravity on the host at the top of every step
-int mpg_resident_fetch_timebins(mpg_engine *eng, unsigned char *tb_hydro, unsigned char *tb_grav)
-{
-    API_BEGIN
-    MPG_CHECK(eng && eng->sph_resident, "mpg_resident_fetch_timebins: no resident gas arrays");
-    MPG_HIP(hipSetDevice(eng->device));
-    const int64_t n = eng->res_n;
-    const mpg_sph_arrays &d = eng->res_sph_dev;
-    MPG_CHECK((!tb_hydro || d.tb_hydro) && (!tb_grav || d.tb_grav), "mpg_resident_fetch_timebins: the resident arrays have no such bins");
-    if(tb_hydro)
-        MPG_HIP(hipMemcpyAsync(tb_hydro, d.tb_hydro, (size_t)n, hipMemcpyDeviceToHost, eng->stream));
-    if(tb_grav)
-        MPG_HIP(hipMemcpyAsync(tb_grav, d.tb_grav, (size_t)n, hipMemcpyDeviceToHost, eng->stream));
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-    API_END
-}
-
-int mpg_resident_drift_all_particles(mpg_engine *eng, const mpg_particle_view *P, double ddrift, const double random_shift[3])
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && random_shift, "null argument");
-    resident_check(eng, P);
-    MPG_CHECK(eng->res_has_vel, "resident drift: the resident table has no Vel column");
-    const bool gas = eng->sph_resident;
-    eng->r_flags.reserve((size_t)P->n + 1);
-    if(!gas && P->n > 0)
-        hipLaunchKernelGGL(k_flags_from_type, dim3((unsigned)((P->n + 255) / 256)), dim3(256), 0, eng->stream, P->n, eng->s_type.p, eng->r_flags.p);
-    if(mpg_dev_drift_all_particles(eng, P->n, eng->s_pos.p, eng->r_vel.p, eng->s_type.p, eng->r_flags.p, gas ? eng->res_sph_dev.hsml : nullptr,
-                                   gas ? eng->res_sph_dev.dthsml : nullptr, ddrift, eng->box, random_shift))
-        throw Error(g_err);
-    API_END
-}
-
-int mpg_resident_apply_pm_half_kick(mpg_engine *eng, const mpg_particle_view *P, double Fgravkick)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P, "null argument");
-    resident_check(eng, P);
-    MPG_CHECK(eng->res_has_vel, "resident kick: the resident table has no Vel column");
-    eng->r_flags.reserve((size_t)P->n + 1);
-    if(!eng->sph_resident && P->n > 0)
-        hipLaunchKernelGGL(k_flags_from_type, dim3((unsigned)((P->n + 255) / 256)), dim3(256), 0, eng->stream, P->n, eng->s_type.p, eng->r_flags.p);
-    if(mpg_dev_apply_pm_half_kick(eng, P->n, eng->r_vel.p, eng->r_gravpm.p, eng->r_flags.p, Fgravkick))
-        throw Error(g_err);
-    API_END
-}
-
-int mpg_resident_apply_half_kick(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
-                                 const mpg_kick_factors *K)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && K, "null argument");
-    resident_sph_check(eng, P);
-    const mpg_sph_arrays &d = eng->res_sph_dev;
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    if(mpg_dev_apply_half_kick(eng, P->n, d_act, NumActiveParticle, eng->r_vel.p, eng->r_accel.p, eng->s_type.p, eng->r_flags.p, d.tb_grav, d.tb_hydro,
-                               d.hydroacc_out, (double *)d.entropy, d.dtentropy_out, K))
-        throw Error(g_err);
-    API_END
-}
-
-int mpg_resident_find_hydro_timesteps(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
-                                      mpg_drift_kick_times *times, const mpg_timeline *timeline, const mpg_timestep_params *par, double CourantFac,
-                                      double atime, double hubble, int isFirstTimeStep, mpg_hydrostep_result *out)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && times && out, "null argument");
-    resident_sph_check(eng, P);
-    const mpg_sph_arrays &d = eng->res_sph_dev;
-    MPG_CHECK(d.tb_hydro, "resident find_hydro_timesteps: the gas arrays have no TimeBinHydro");
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    mpg_hydrostep_arrays H{};
-    H.d_type = eng->s_type.p;
-    H.d_flags = eng->r_flags.p;
-    H.d_hsml = d.hsml;
-    H.d_dthsml = d.dthsml;
-    H.d_maxsignalvel = d.maxsignalvel;
-    H.d_tb_grav = d.tb_grav;
-    H.d_tb_hydro = (unsigned char *)d.tb_hydro;
-    if(mpg_dev_find_hydro_timesteps(eng, &H, d_act, NumActiveParticle, times, timeline, par, CourantFac, atime, hubble, out) ||
-       mpg_dev_hydro_timesteps_finish(eng, out->mTimeBin, isFirstTimeStep, P->n, eng->s_type.p, (unsigned char *)d.tb_hydro, times))
-        throw Error(g_err);
-    API_END
-}
-
-int mpg_resident_find_timesteps(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
-                                mpg_drift_kick_times *times, const mpg_timeline *timeline, const mpg_timestep_params *par, double CourantFac,
-                                double atime, double hubble, int64_t dti_max_pm, mpg_timestep_result *out)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && times && out, "null argument");
-    resident_sph_check(eng, P);
-    const mpg_sph_arrays &d = eng->res_sph_dev;
-    MPG_CHECK(d.tb_hydro && d.tb_grav, "resident find_timesteps: the gas arrays have no time bins");
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    mpg_hydrostep_arrays H{};
-    H.d_type = eng->s_type.p;
-    H.d_flags = eng->r_flags.p;
-    H.d_hsml = d.hsml;
-    H.d_dthsml = d.dthsml;
-    H.d_maxsignalvel = d.maxsignalvel;
-    H.d_tb_grav = d.tb_grav;
-    H.d_tb_hydro = (unsigned char *)d.tb_hydro;
-    if(mpg_dev_find_timesteps(eng, &H, eng->r_accel.p, eng->r_gravpm.p, (unsigned char *)d.tb_grav, d_act, NumActiveParticle, times, timeline, par,
-                              CourantFac, atime, hubble, dti_max_pm, out) ||
-       mpg_find_timesteps_finish(out->mTimeBin, out->maxTimeBin, out->isPM, times))
-        throw Error(g_err);
-    API_END
-}
-
-int mpg_resident_apply_hydro_half_kick(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
-                                       const mpg_kick_factors *K)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && K, "null argument");
-    resident_sph_check(eng, P);
-    const mpg_sph_arrays &d = eng->res_sph_dev;
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    if(mpg_dev_apply_hydro_half_kick(eng, P->n, d_act, NumActiveParticle, eng->r_vel.p, eng->s_type.p, eng->r_flags.p, d.tb_hydro, d.hydroacc_out,
-                                     (double *)d.entropy, d.dtentropy_out, K))
-        throw Error(g_err);
-    API_END
-}
-
-/* The branch of run.c WITH SplitGravityTimestepsOn (run.c:497-499, 536-540, 766-775) on a resident run: the level loop of
- * mpg_dev_hierarchical_* on the resident table - Vel, GravPM, FullTreeGravAccel and Potential are its columns, TimeBinGravity the resident gas
- * run's tb_grav (mpg_resident_sph_begin, as for mpg_resident_find_timesteps), the flags those of the resident table.  The trees of the levels
- * are built from the resident positions.  StoredGravAccel: the device copy r_stored stands for the caller's host array (include/mpgadget_hip.h).
- * Carried: one rank, dark matter and gas.  Not carried: several ranks (the level loop's trees are local), black holes, and star particles
- * created during the step (the reference's extra StoredGravAccel rows, run.c:537-538: only the first n rows exist here). */
-namespace {
-void resident_hier_arrays(mpg_engine *eng, const mpg_particle_view *P, double (*StoredGravAccel)[3], mpg_hiergrav_arrays *A)
-{
-    resident_sph_check(eng, P);
-    MPG_CHECK(eng->res_has_vel, "resident hierarchical gravity: the resident table has no Vel column");
-    const mpg_sph_arrays &d = eng->res_sph_dev;
-    MPG_CHECK(d.tb_grav, "resident hierarchical gravity: the gas arrays have no TimeBinGravity");
-    stage_particles(eng, P, eng->box); // (resident: checks that the device binding is still the table's)
-    const int64_t n = P->n;
-    A->d_vel = eng->r_vel.p;
-    A->d_gravpm = eng->r_gravpm.p;
-    A->d_fulltree_accel = eng->r_accel.p;
-    A->d_potential = eng->r_pot.p;
-    A->d_tb_grav = (unsigned char *)d.tb_grav;
-    A->d_flags = eng->r_flags.p;
-    A->d_stored_accel = nullptr;
-    if(!StoredGravAccel)
-        return; // FullTreeGravAccel plays the part of the stored array
-    if(StoredGravAccel != eng->r_stored_host) {
-        MPG_CHECK(!eng->r_stored_host, "resident hierarchical gravity: another StoredGravAccel array is still held (hierarchical_gravity_and_timesteps "
-                                       "or mpg_resident_end releases it)");
-        eng->r_stored.reserve(3 * (size_t)n + 3);
-        if(n > 0) { // (a host array the engine does not hold yet: its first n rows)
-            MPG_HIP(hipMemcpyAsync(eng->r_stored.p, StoredGravAccel, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-            MPG_HIP(hipStreamSynchronize(eng->stream));
-        }
-        eng->r_stored_host = StoredGravAccel;
-    }
-    A->d_stored_accel = eng->r_stored.p;
-}
-const int *resident_active(mpg_engine *eng, const int *ActiveParticle, int64_t NumActiveParticle)
-{
-    if(!ActiveParticle)
-        return nullptr;
-    eng->s_active.reserve((size_t)NumActiveParticle + 1);
-    MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-    return eng->s_active.p;
-}
-} // namespace
-
-int mpg_resident_hierarchical_gravity_accelerations(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
-                                                    int64_t NumActiveGravity, mpg_drift_kick_times *times, double rho0, int HybridNuGrav,
-                                                    mpg_gravkick_fn gravkick, void *gravkick_ctx, double (*StoredGravAccel)[3])
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && times && gravkick && NumActiveParticle >= 0 && NumActiveGravity >= 0, "null argument");
-    MPG_CHECK(!ActiveParticle || NumActiveParticle <= P->n, "resident hierarchical gravity: more active particles than particles");
-    mpg_hiergrav_arrays A;
-    resident_hier_arrays(eng, P, StoredGravAccel, &A);
-    const int *d_act = resident_active(eng, ActiveParticle, NumActiveParticle);
-    if(!ActiveParticle) // every particle is active (build_active_particles on a PM step: NumActiveParticle = NumPart)
-        NumActiveParticle = P->n;
-    if(mpg_dev_hierarchical_gravity_accelerations(eng, &A, d_act, NumActiveParticle, NumActiveGravity, times, rho0, HybridNuGrav, gravkick, gravkick_ctx))
-        throw Error(g_err);
-    API_END
-}
-
-int mpg_resident_hierarchical_gravity_and_timesteps(mpg_engine *eng, const mpg_particle_view *P, const int *ActiveParticle, int64_t NumActiveParticle,
-                                                    int64_t NumActiveGravity, mpg_drift_kick_times *times, const mpg_timeline *timeline,
-                                                    const mpg_timestep_params *par, double atime, double hubble, int64_t dti_max_pm, double rho0,
-                                                    int HybridNuGrav, mpg_gravkick_fn gravkick, void *gravkick_ctx, double (*StoredGravAccel)[3],
-                                                    int64_t *badstepsizecount)
-{
-    API_BEGIN
-    MPG_CHECK(eng && P && times && timeline && par && gravkick && badstepsizecount && NumActiveParticle >= 0 && NumActiveGravity >= 0, "null argument");
-    MPG_CHECK(!ActiveParticle || NumActiveParticle <= P->n, "resident hierarchical gravity: more active particles than particles");
-    mpg_hiergrav_arrays A;
-    resident_hier_arrays(eng, P, StoredGravAccel, &A);
-    const int *d_act = resident_active(eng, ActiveParticle, NumActiveParticle);
-    if(!ActiveParticle)
-        NumActiveParticle = P->n;
-    if(mpg_dev_hierarchical_gravity_and_timesteps(eng, &A, d_act, NumActiveParticle, NumActiveGravity, times, timeline, par, atime, hubble, dti_max_pm,
-                                                  rho0, HybridNuGrav, gravkick, gravkick_ctx, badstepsizecount))
-        throw Error(g_err);
-    // the step has consumed the stored accelerations: the reference frees the array here (timestep.c:417-418)
-    if(StoredGravAccel)
-        eng->r_stored_host = nullptr;
-    API_END
-}
-
 int mpg_sph_get_stats(mpg_engine *eng, int64_t stats[4])
 {
     API_BEGIN
@@ -3111,80 +1665,10 @@ int mpg_dev_find_vel_disp(mpg_engine *eng, const mpg_veldisp_arrays *A, const mp
     if(eng->vdisp.make_queues(v, S, flags, eng->n, eng->stream)) {
         // force_tree_rebuild_mask(tree, ddecomp, DMMASK, NULL), veldisp.c:414: the engine's current tree is, from here on, the tree of the
         // DM particles without moments
-        if(mpg_dev_force_tree_rebuild_mask(eng, 2 /* DMMASK */, 0))
-            throw Error(g_err);
+        MPG_CALL(mpg_dev_force_tree_rebuild_mask(eng, 2 /* DMMASK */, 0));
         if(eng->vdisp.nbh > 0 || eng->vdisp.ngas > 0)
             eng->vdisp.search(eng->tree, v, *T, S, eng->stream);
     }
-    API_END
-}
-
-int mpg_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_veldisp_arrays *A, const mpg_sph_times *T,
-                      const mpg_veldisp_params *par, const int *ActiveParticle, int64_t NumActiveParticle)
-{
-    API_BEGIN
-    MPG_CHECK(eng && pv && A && T && par, "null argument");
-    MPG_CHECK(A->vel && A->hsml && A->density && A->vdisp, "find_vel_disp: the arrays vel, hsml, density and vdisp are required");
-    MPG_HIP(hipSetDevice(eng->device));
-    stage_particles(eng, pv, BoxSize);
-    const size_t n = (size_t)pv->n;
-    // fields of mpg_veldisp_arrays in order: vel[3], gacc[3], gpm[3], tb_grav (bytes), hsml, dthsml, density, vdisp
-    const int width[8] = {3, 3, 3, 0, 1, 1, 1, 1};
-    void *const *hp = (void *const *)A;
-    mpg_veldisp_arrays d;
-    void **dp = (void **)&d;
-    for(int f = 0; f < 8; f++) {
-        dp[f] = nullptr;
-        if(!hp[f])
-            continue;
-        if(width[f] == 0) {
-            eng->vd_stage_tb.reserve(n + 1);
-            dp[f] = eng->vd_stage_tb.p;
-            MPG_HIP(hipMemcpyAsync(dp[f], hp[f], n, hipMemcpyHostToDevice, eng->stream));
-        }
-        else {
-            eng->vd_stage[f].reserve(n * width[f] + 1);
-            dp[f] = eng->vd_stage[f].p;
-            MPG_HIP(hipMemcpyAsync(dp[f], hp[f], n * width[f] * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-        }
-    }
-    const int *d_act = nullptr;
-    if(ActiveParticle) {
-        eng->s_active.reserve((size_t)NumActiveParticle + 1);
-        MPG_HIP(hipMemcpyAsync(eng->s_active.p, ActiveParticle, NumActiveParticle * sizeof(int), hipMemcpyHostToDevice, eng->stream));
-        d_act = eng->s_active.p;
-    }
-    if(mpg_dev_find_vel_disp(eng, &d, T, par, d_act, NumActiveParticle))
-        throw Error(g_err);
-    MPG_HIP(hipMemcpyAsync(A->vdisp, d.vdisp, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    MPG_HIP(hipStreamSynchronize(eng->stream));
-    API_END
-}
-
-int mpg_resident_sph_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, const mpg_sph_times *T, const mpg_veldisp_params *par,
-                                   const int *ActiveParticle, int64_t NumActiveParticle, double *vdisp)
-{
-    API_BEGIN
-    MPG_CHECK(eng && pv && T && par && vdisp, "null argument");
-    resident_sph_check(eng, pv);
-    const size_t n = (size_t)pv->n;
-    const mpg_sph_arrays &r = eng->res_sph_dev;
-    mpg_veldisp_arrays d;
-    d.vel = r.vel;
-    d.gacc = r.gacc;
-    d.gpm = r.gpm;
-    d.tb_grav = r.tb_grav;
-    d.hsml = r.hsml;
-    d.dthsml = r.dthsml;
-    d.density = r.density;
-    eng->vd_stage[7].reserve(n + 1);
-    d.vdisp = eng->vd_stage[7].p;
-    MPG_HIP(hipMemcpyAsync(d.vdisp, vdisp, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-    const int *d_act = resident_active(eng, ActiveParticle, NumActiveParticle);
-    if(mpg_dev_find_vel_disp(eng, &d, T, par, d_act, NumActiveParticle))
-        throw Error(g_err);
-    MPG_HIP(hipMemcpyAsync(vdisp, d.vdisp, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
-    MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }
 

@@ -1,4 +1,4 @@
-// engine_internal.h -- the engine object behind the C-ABI handle (include/mpgadget_hip.h), shared by engine.hip and dist.hip
+// engine_internal.h -- the engine object behind the C-ABI handle (include/mpgadget_hip.h), shared by engine.hip, host_forms.hip, resident.hip and dist.hip
 #pragma once
 #include "../../include/mpgadget_hip.h"
 #include "grav_walk.h"
@@ -13,155 +13,17 @@
 #include "fof.h"
 #include "snapshot_io.h"
 #include "tree_build.h"
+#include "host_table.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
 #include <thread>
 #include <vector>
 
 using namespace mpg;
 
 std::string &mpg_err_slot(); // thread-local text of the last error (mpg_last_error)
-
-// ---- host-side staging helpers of the AoS (host pointer) path -------------------------------------------------------------
-// Pinned, growable host buffer: transfers from / to pageable std::vector memory run at a fraction of the PCIe rate.
-template <typename T> struct HostBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    void reserve(size_t n)
-    {
-        if(n <= cap)
-            return;
-        release();
-        const size_t want = n + n / 16 + 64;
-        MPG_HIP(hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault));
-        cap = want;
-    }
-    void release()
-    {
-        if(p)
-            (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    ~HostBuf() { release(); }
-    HostBuf() = default;
-    HostBuf(const HostBuf &) = delete;
-    HostBuf &operator=(const HostBuf &) = delete;
-};
-
-// f(lo, hi) over [0, n) on up to 32 host threads: packing 160-byte records into arrays (and back) is memory-bound and one
-// thread moves ~2 GB/s of them; the reference's callers have the cores of the rank idle while the GPU works anyway.
-// The threads are persistent (round 5): a pass over the table is cut into 8 chunks that overlap the PCIe transfers, i.e. 8 calls, and
-// creating 32 threads per call cost 0.3 - 0.5 ms of each (three passes per step on the critical path of the host forms).  A second
-// caller that finds the pool busy (the write-back thread of mpg_gravpm_force beside the main thread) starts its own threads as before.
-class HostPool {
-    std::vector<std::thread> th;
-    std::mutex m, busy;
-    std::condition_variable cv_work, cv_done;
-    const std::function<void(int64_t, int64_t)> *job = nullptr;
-    int64_t n = 0, chunk = 0;
-    unsigned gen = 0, pending = 0;
-    bool stop = false;
-    void worker(unsigned t)
-    {
-        unsigned seen = 0;
-        for(;;) {
-            const std::function<void(int64_t, int64_t)> *f;
-            int64_t lo, hi;
-            {
-                std::unique_lock<std::mutex> lk(m);
-                cv_work.wait(lk, [&] { return stop || gen != seen; });
-                if(stop)
-                    return;
-                seen = gen;
-                f = job;
-                lo = (int64_t)t * chunk;
-                hi = lo + chunk < n ? lo + chunk : n;
-            }
-            if(lo < hi)
-                (*f)(lo, hi);
-            {
-                std::lock_guard<std::mutex> lk(m);
-                if(--pending == 0)
-                    cv_done.notify_all();
-            }
-        }
-    }
-
-  public:
-    explicit HostPool(unsigned T)
-    {
-        for(unsigned t = 0; t < T; t++)
-            th.emplace_back([this, t] { worker(t); });
-    }
-    ~HostPool()
-    {
-        {
-            std::lock_guard<std::mutex> lk(m);
-            stop = true;
-        }
-        cv_work.notify_all();
-        for(auto &x : th)
-            x.join();
-    }
-    unsigned size() const { return (unsigned)th.size(); }
-    // false: the pool is in use by another caller
-    bool run(int64_t count, const std::function<void(int64_t, int64_t)> &f)
-    {
-        std::unique_lock<std::mutex> one(busy, std::try_to_lock);
-        if(!one.owns_lock())
-            return false;
-        std::unique_lock<std::mutex> lk(m);
-        job = &f;
-        n = count;
-        chunk = (count + size() - 1) / size();
-        pending = size();
-        gen++;
-        cv_work.notify_all();
-        cv_done.wait(lk, [&] { return pending == 0; });
-        return true;
-    }
-};
-
-inline HostPool &host_pool(unsigned T)
-{
-    static HostPool pool(T); // ONE pool per process (not one per instantiation of parallel_for); lives until the process ends
-    return pool;
-}
-
-template <class F> inline void parallel_for(int64_t n, F f)
-{
-    static const unsigned cap = getenv("MPG_HOST_THREADS") ? (unsigned)atoi(getenv("MPG_HOST_THREADS")) : 32u;
-    unsigned T = std::thread::hardware_concurrency();
-    if(T > cap)
-        T = cap;
-    if(T < 2 || n < 131072) {
-        f((int64_t)0, n);
-        return;
-    }
-    static const bool use_pool = getenv("MPG_HOST_NO_POOL") == nullptr;
-    if(use_pool) {
-        const std::function<void(int64_t, int64_t)> fn = [&f](int64_t lo, int64_t hi) { f(lo, hi); };
-        if(host_pool(T).run(n, fn))
-            return;
-    }
-    const int64_t chunk = (n + T - 1) / T;
-    std::vector<std::thread> th;
-    th.reserve(T);
-    for(unsigned t = 0; t < T; t++) {
-        const int64_t lo = (int64_t)t * chunk, hi = lo + chunk < n ? lo + chunk : n;
-        if(lo >= hi)
-            break;
-        th.emplace_back([=] { f(lo, hi); });
-    }
-    for(auto &x : th)
-        x.join();
-}
 
 struct mpg_engine {
     int device = 0;
@@ -213,16 +75,7 @@ struct mpg_engine {
     const float *d_mass = nullptr;
     const uint8_t *d_type = nullptr;
     double box = 0;
-    // staging for the host SPH path: one device buffer per mpg_sph_arrays field
-    DevBuf<double> h_sph[19];
-    DevBuf<uint8_t> h_sph_u8[2];
-    // staging for the host (AoS) path
-    DevBuf<double> s_pos, s_accel, s_gravpm, s_pot, s_prev, s_old;
     DevBuf<double> w_old; // OldAcc of a walk that writes over its own opening input (mpg_dev_grav_short_tree)
-    DevBuf<float> s_mass;
-    DevBuf<uint8_t> s_type, s_live;
-    const uint8_t *pm_live = nullptr; // host path: 0 for garbage / swallowed particles when the staged table holds any (else null)
-    DevBuf<int> s_active;
     DevBuf<unsigned> ts_flag;
     DevBuf<uint8_t> tree_incl; // particles included in an active-particle tree
     // hierarchical gravity (timestep.c:239-599): active sublists (ping-pong), the per-level acceleration array, scratch
@@ -235,6 +88,17 @@ struct mpg_engine {
     DomainScratch domain;
     FofEngine fof;
     PlaneEngine planes;
+    VdispEngine vdisp; // DM velocity dispersion (veldisp.c): the loop's state
+    // ---- everything below is the host-pointer ("drop-in") layer's: host_forms.hip and resident.hip (the engine only destroys it) ----
+    // staging for the host SPH path: one device buffer per mpg_sph_arrays field
+    DevBuf<double> h_sph[19];
+    DevBuf<uint8_t> h_sph_u8[2];
+    // staging for the host (AoS) path
+    DevBuf<double> s_pos, s_accel, s_gravpm, s_pot, s_prev, s_old;
+    DevBuf<float> s_mass;
+    DevBuf<uint8_t> s_type, s_live;
+    const uint8_t *pm_live = nullptr; // host path: 0 for garbage / swallowed particles when the staged table holds any (else null)
+    DevBuf<int> s_active;
     DevBuf<uint8_t> plane_flags; // host forms of the potential planes: IsGarbage / Swallowed of the table ...
     HostBuf<uint8_t> h_plane_flags; // ... staged through a pinned buffer of their own (h_b holds the live flags of the staged epoch)
     DevBuf<double> plane_out;
@@ -283,8 +147,7 @@ struct mpg_engine {
     std::thread prefetch_thread;
     std::string prefetch_error;
     mpg_particle_view prefetch_view{};
-    // DM velocity dispersion (veldisp.c): the loop's state, and the staging of the host form's arrays (fields of mpg_veldisp_arrays)
-    VdispEngine vdisp;
+    // the staging of the velocity dispersion's host form (fields of mpg_veldisp_arrays)
     DevBuf<double> vd_stage[8];
     DevBuf<uint8_t> vd_stage_tb;
     void prefetch_join()
@@ -301,6 +164,12 @@ struct mpg_engine {
 };
 
 extern "C" void engine_tree_build_on(mpg_engine *eng, int mask, hipStream_t st); // engine.hip
+extern "C" void wait_for_leaf_blocks(mpg_engine *eng, hipStream_t st);            // engine.hip
+// host_forms.hip, also used by resident.hip: Pos / Mass / Type of the table onto the device and bound (or, resident / same epoch: checked);
+// the host arrays of the SPH forms staged, `dev` filled with their device copies; the planes of a staged or resident table
+void stage_particles(mpg_engine *eng, const mpg_particle_view *P, double BoxSize);
+void stage_sph(mpg_engine *eng, const mpg_sph_arrays *host, mpg_sph_arrays *dev, int64_t n);
+void host_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *par, double *planes, int64_t *npart);
 
 // potential planes (planes.hip).  red: the sums over the ranks of the several-GPU form (dist.hip), or null; sum_device returns with the
 // device array summed and usable on the engine's stream

@@ -162,6 +162,47 @@ def test_host_path_skips_garbage_in_place(pkg, engine, orc):
     assert np.all(P["GravPM"][di] == 0.0) and np.all(P["FullTreeGravAccel"][di] == 9.0)
 
 
+@pytest.mark.parametrize("overlap", [0, 1])
+def test_host_path_swallowed_non_black_hole_takes_part(pkg, engine, overlap):
+    """The record classification of the host forms, third case: Swallowed on a type that is not 5.  The host staging drops garbage and
+    swallowed BLACK HOLES only (forcetree.c:806), so such a record keeps its type: it is deposited, enters the tree, is walked and gets
+    GravPM / FullTreeGravAccel / Potential written - what the same table gives with those flags cleared: FullTreeGravAccel and Potential
+    bit for bit.  GravPM cannot be pinned to the bit: the CIC deposit sums with floating-point atomics whose order changes from run to run
+    (two runs of the SAME table differ by 2 - 3e-19 at |GravPM| ~ 1e-4, one unit in the last place), so it is held to the bound this suite
+    uses for two identical PM steps, 1e-10 of the largest component (test_host_path_particle_epoch); the marked records are given
+    mass 50 each so that leaving them out of the deposit or the tree would change every force by far more than that.  8^3 particles at
+    Nmesh 16 (a tree with internal nodes and a mesh both exist), synchronous and overlapped, at a non-zero epoch."""
+    n, nmesh = 8, 16
+    pos, mass, box = pkg.ics.s_zel(n)
+    N = len(pos)
+    src = np.sort(np.random.RandomState(11).choice(N, 7, replace=False))
+    npos = np.insert(pos, src, pos[src] + 1e-3 * box / n, axis=0)
+    nmass = np.insert(mass, src, np.float32(50.0))
+    marked = src + np.arange(len(src))
+    setup_engine(engine, box, n, nmesh, TreeUseBH=0)
+    engine.set_host_overlap(overlap)
+    out = []
+    for k, flag in enumerate((2, 0)):
+        P = pkg.make_particles(npos, nmass)
+        P["Flags"][marked] = flag                 # Swallowed ...
+        P["Type"][marked] = 1                     # ... but no black hole
+        P["Potential"] = 0.125
+        engine.set_particle_epoch(4100 + 10 * overlap + k)
+        engine.gravpm_force(P)
+        engine.force_tree_full(P, box)
+        assert engine.tree_stats().NumParticles == N + len(src)
+        engine.grav_short_tree(P)
+        engine.host_results_sync()
+        out.append((P["GravPM"].copy(), P["FullTreeGravAccel"].copy(), P["Potential"].copy()))
+    engine.set_particle_epoch(0)
+    engine.set_host_overlap(False)
+    (g2, a2, p2), (g0, a0, p0) = out
+    print("max |diff| GravPM %.3e FullTreeGravAccel %.3e Potential %.3e" % (np.abs(g2 - g0).max(), np.abs(a2 - a0).max(), np.abs(p2 - p0).max()))
+    assert np.all(g0[marked] != 0) and np.all(a0[marked] != 0) and np.all(p0[marked] != 0.125)
+    assert np.abs(g2 - g0).max() <= 1e-10 * np.abs(g0).max()
+    assert np.array_equal(a2, a0) and np.array_equal(p2, p0)
+
+
 def test_pm_linearity_and_momentum(pkg, engine):
     """Size-independent properties: the PM force is linear in the masses and conserves momentum (sum m a = 0)."""
     n, nmesh = 24, 48

@@ -5,7 +5,7 @@
 //   (b) a device kernel GATHERING Pos / Mass / flags / Type straight from the registered records (zero copy, one thread per record)
 //   (c) a device kernel SCATTERING GravPM + Potential (32 B) and FullTreeGravAccel + Potential straight into the records
 //   (d) the staged way: host threads pack the columns into pinned buffers + hipMemcpyAsync (and back: copy + host threads unpack)
-// so that csrc/engine.hip's host forms can take the cheaper one.
+// so that csrc/host_forms.hip's host forms can take the cheaper one.
 #include <hip/hip_runtime.h>
 #include <omp.h>
 #include <chrono>
