@@ -352,6 +352,106 @@ int mpg_veldisp_get_stats(mpg_engine *eng, int64_t stats[5]);
 int mpg_veldisp_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iterations, int32_t *numngb, int32_t *maxcmpte, int64_t *queue_lengths,
                        int64_t queue_capacity);
 
+/* ---- radiative cooling of gas: cooling_direct, libgadget/sfr_eff.c:463-514 (cooling_and_starformation, run.c:663-664) ---------
+ * For every listed gas particle (Type == 0, not garbage, Mass > 0; sfr_eff.c:229) DoCooling (cooling.c:57-138) finds the internal energy
+ * after the particle's hydro step dtime = dloga_bin[TimeBinHydro] / hubble by bracketing (x 1.1, / 1.1) and bisecting
+ * u - u_old - LambdaNet(u) dt; every LambdaNet solves the ionisation network of cooling_rates.c (get_heatingcooling_rate :1248-1310,
+ * get_equilib_ne / scipy_optimize_fixed_point :779-827, ne_internal :755-765) with the fits recomb = Cen92 / Verner96 / Badnell06 and
+ * cooling = KWH92 / Enzo2Nyx / Sherwood, tabulated in 13 tables of 1000 entries exactly as init_cooling_rates does (:1153-1171) and
+ * evaluated directly outside them.  The particle gets Ne, Entropy = unew / entropy_to_u(Density, a3inv) and Sfr = 0; one that was
+ * reionised during its step (HIReionTemp > 0, zreion in [redshift, lastred[bin]), sfr_eff.c:488-501) is set to HIReionTemp instead.
+ * The engine reads no files and evaluates no star-formation criterion: the caller decides who is listed (the particles for which
+ * cooling_and_starformation takes the `else cooling_direct` branch, sfr_eff.c:270-271) and passes the step's UV background
+ * (get_global_UVBG, cooling_rates.c:365-397), get_long_mean_free_path_heating(redshift) (cooling_qso_lightup.c:258) and per hydro bin
+ * lastred = 1 / exp(loga_from_ti(Ti_Current - dti_from_timebin(bin))) - 1 (sfr_eff.c:483-484).
+ * Not carried: the UV-fluctuation table (get_local_UVBG_from_global with UVF.enabled), EXCUR_REION's local_J21, cooling_relaxed, star
+ * formation and winds; several ranks each call this form on their own gas (the loop is per particle).
+ * Every loop is bounded: the two limits of 1000 are the reference's (cooling.c:32, cooling_rates.c:768); the two bracketing loops, which the
+ * reference leaves unbounded, stop after 8192 steps.  A particle that hits a limit, or whose electron abundance is not finite, keeps its
+ * Entropy / Ne / Sfr, counts in stats[5], and makes the call return non-zero after all other particles are done (the reference: endrun). */
+/* struct UVBG, cooling.h:9-19 (same members, same order) */
+typedef struct mpg_uvbg {
+    double J_UV, gJH0, gJHep, gJHe0, epsH0, epsHep, epsHe0, self_shield_dens, zreion;
+} mpg_uvbg;
+typedef struct mpg_cooling_params {
+    /* struct cooling_params, cooling_rates.h:23-58 (PhotoIonizationOn, PhotoIonizeFactor, UVRedshiftThreshold and HydrogenHeatAmp act in
+     * get_global_UVBG / load_treecool only, i.e. on the caller's side; they are carried for completeness and not read) */
+    int recomb;  /* enum RecombType: 0 Cen92, 1 Verner96, 2 Badnell06 */
+    int cooling; /* enum CoolingType: 0 KWH92, 1 Enzo2Nyx, 2 Sherwood */
+    int SelfShieldingOn;
+    int PhotoIonizationOn;
+    double fBar;
+    double PhotoIonizeFactor;
+    double CMBTemperature;
+    double MinGasTemp;
+    double UVRedshiftThreshold;
+    double HydrogenHeatAmp;
+    int HeliumHeatOn;
+    double HeliumHeatThresh;
+    double HeliumHeatAmp;
+    double HeliumHeatExp;
+    double rho_crit_baryon;
+    /* struct cooling_units, cooling.h:32-44 */
+    int CoolingOn;
+    double density_in_phys_cgs;
+    double uu_in_cgs;
+    double tt_in_s;
+    double units_rho_crit_baryon; /* cooling_units.rho_crit_baryon */
+    /* of sfr_params (sfr_eff.c:69-71, 498, 505) */
+    double sfr_MinGasTemp;
+    double temp_to_u;
+    double HIReionTemp;
+    /* tests only: a limit for the fixed-point iteration of the network in place of its 1000; 0 = the reference's */
+    int test_network_maxiter;
+} mpg_cooling_params;
+typedef struct mpg_cooling_step {
+    mpg_uvbg uvbg;                      /* get_global_UVBG(redshift) */
+    double long_mean_free_path_heating; /* get_long_mean_free_path_heating(redshift), erg/s/cm^3 */
+    double lastred[47];                 /* per hydro time bin: the redshift at the start of the particle's step */
+    double redshift;                    /* mpg_dev_cooling_state only (mpg_dev_cooling takes 1 / T->atime - 1) */
+    double helium;                      /* mpg_dev_cooling_state only: helium mass fraction; 0 = 1 - HYDROGEN_MASSFRAC */
+} mpg_cooling_step;
+typedef struct mpg_cooling_arrays {
+    const double *density;        /* SphP.Density */
+    double *entropy;              /* in/out SphP.Entropy */
+    double *ne;                   /* in/out SphP.Ne */
+    double *sfr;                  /* in/out SphP.Sfr (set to 0 for every treated particle) */
+    const double *metallicity;    /* SphP.Metallicity; NULL = 0 */
+    const uint8_t *heiii_ionized; /* P.HeIIIionized; NULL = 0 */
+    const uint8_t *tb_hydro;      /* P.TimeBinHydro; NULL = 0 */
+} mpg_cooling_arrays;
+/* set_coolpar / init_cooling (cooling_rates.c:1071, cooling.c:22-30): stores the parameters and fills the 13 rate tables */
+int mpg_set_cooling_params(mpg_engine *eng, const mpg_cooling_params *par);
+/* InitMetalCooling (cooling_uvfluc.c:265-305): the three bin vectors (of which, as in the reference, only the ends and the lengths
+ * count) and NetCoolingRate[nz][nnh][nt] from HOST memory; zbins == NULL removes the table (MetalCoolFile == "") */
+int mpg_set_metal_cooling_table(mpg_engine *eng, int nz, const double *zbins, int nnh, const double *nhbins, int nt, const double *tbins,
+                                const double *rate);
+/* on the bound particles (types from the bound table, garbage as type 7); arrays in particle order; d_active NULL = all particles;
+ * atime, hubble and dloga_bin of T are read */
+int mpg_dev_cooling(mpg_engine *eng, const mpg_cooling_arrays *A, const mpg_sph_times *T, const mpg_cooling_step *step, const int *d_active,
+                    int64_t nactive);
+/* host form: `pv` supplies Mass / Type / flags, `A` holds HOST arrays in particle order (the shim gathers SphP into them) */
+int mpg_cooling(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_cooling_arrays *A, const mpg_sph_times *T,
+                const mpg_cooling_step *step, const int *ActiveParticle, int64_t NumActiveParticle);
+/* on a resident gas run (mpg_resident_sph_begin): Density, Entropy and TimeBinHydro are the resident columns; `ne` (HOST, n entries,
+ * in/out) travels, as do the optional HOST inputs metallicity and heiii_ionized (NULL = 0).  Sfr is not a resident column: the caller
+ * zeroes it for the listed gas. */
+int mpg_resident_sph_cooling(mpg_engine *eng, const mpg_particle_view *pv, const mpg_sph_times *T, const mpg_cooling_step *step,
+                             const int *ActiveParticle, int64_t NumActiveParticle, double *ne, const double *metallicity,
+                             const uint8_t *heiii_ionized);
+/* the network alone, in physical cgs units (density in protons/cm^3, energy in erg/g), for n independent points on the device:
+ * get_heatingcooling_rate with zero metallicity (erg/s/g), the temperature (get_temp, K) and the neutral hydrogen fraction
+ * (get_neutral_fraction_phys_cgs) at the equilibrium; d_ne_inout holds ne / nH as the start value and returns the equilibrium.  The three
+ * outputs may each be NULL.  GetNeutralFraction (cooling.c:166-176) of a snapshot is this call on density_in_phys_cgs / PROTONMASS *
+ * rho and uu_in_cgs * u. */
+int mpg_dev_cooling_state(mpg_engine *eng, int64_t n, const double *d_rho, const double *d_u, double *d_ne_inout, double *d_lambdanet,
+                          double *d_temp, double *d_nh0, const mpg_cooling_step *step);
+/* statistics of the last mpg_dev_cooling: [0] particles treated, [1] evaluations of the network (ne_internal) summed, [2] bisection steps
+ * summed, [3] particles that ended on the energy floor, [4] particles in the HIReionTemp branch, [5] particles that hit a limit */
+int mpg_cooling_get_stats(mpg_engine *eng, int64_t stats[6]);
+/* the evaluations of the network of every particle in the last mpg_dev_cooling (host array of n entries; -1: not treated) */
+int mpg_cooling_export(mpg_engine *eng, int64_t n, int32_t *evaluations);
+
 /* ---- introspection (tests, bench roofline accounting) ----------------------------------------- */
 typedef struct mpg_tree_stats {
     int64_t NumParticles; /* particles in the tree */

@@ -1707,6 +1707,77 @@ int mpg_veldisp_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iter
     API_END
 }
 
+/* ------------------------------ radiative cooling (cooling.c, cooling_rates.c, sfr_eff.c:463-514) ------------------------------ */
+
+int mpg_set_cooling_params(mpg_engine *eng, const mpg_cooling_params *par)
+{
+    API_BEGIN
+    MPG_CHECK(eng && par, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    eng->cooling.set_params(*par, eng->stream);
+    API_END
+}
+
+int mpg_set_metal_cooling_table(mpg_engine *eng, int nz, const double *zbins, int nnh, const double *nhbins, int nt, const double *tbins,
+                                const double *rate)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream)); // (a kernel in flight may still read the table this call replaces)
+    eng->cooling.set_metal_table(nz, zbins, nnh, nhbins, nt, tbins, rate, eng->stream);
+    API_END
+}
+
+int mpg_dev_cooling(mpg_engine *eng, const mpg_cooling_arrays *A, const mpg_sph_times *T, const mpg_cooling_step *step, const int *d_active,
+                    int64_t nactive)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A && T && step, "null argument");
+    MPG_CHECK(nactive >= 0, "cooling: negative list length");
+    MPG_CHECK(eng->n == 0 || (A->density && A->entropy && A->ne && A->sfr), "cooling: the arrays density, entropy, ne and sfr are required");
+    MPG_CHECK(eng->d_mass || eng->n == 0, "cooling: no particles bound");
+    MPG_HIP(hipSetDevice(eng->device));
+    const int64_t bad = eng->cooling.run(*A, eng->d_type, eng->d_mass, *T, *step, d_active, nactive, eng->n, eng->stream);
+    // the reference's endrun(1 / 10): every other particle of the call has been treated
+    MPG_CHECK(bad == 0, "cooling: " + std::to_string(bad) + " particle(s) hit an iteration limit of DoCooling or of the ionisation network, or reached an "
+                                                           "electron abundance that is not finite; they keep their Entropy and Ne");
+    API_END
+}
+
+int mpg_dev_cooling_state(mpg_engine *eng, int64_t n, const double *d_rho, const double *d_u, double *d_ne_inout, double *d_lambdanet,
+                          double *d_temp, double *d_nh0, const mpg_cooling_step *step)
+{
+    API_BEGIN
+    MPG_CHECK(eng && step && n >= 0, "null argument");
+    MPG_CHECK(n == 0 || (d_rho && d_u && d_ne_inout), "cooling_state: rho, u and ne are required");
+    MPG_HIP(hipSetDevice(eng->device));
+    const int64_t bad = eng->cooling.state(n, d_rho, d_u, d_ne_inout, d_lambdanet, d_temp, d_nh0, *step, eng->stream);
+    MPG_CHECK(bad == 0, "cooling_state: the ionisation network did not converge for " + std::to_string(bad) + " point(s)");
+    API_END
+}
+
+int mpg_cooling_get_stats(mpg_engine *eng, int64_t stats[6])
+{
+    API_BEGIN
+    MPG_CHECK(eng && stats, "null argument");
+    for(int k = 0; k < 6; k++)
+        stats[k] = eng->cooling.stats[k];
+    API_END
+}
+
+int mpg_cooling_export(mpg_engine *eng, int64_t n, int32_t *evaluations)
+{
+    API_BEGIN
+    MPG_CHECK(eng && evaluations, "null argument");
+    MPG_CHECK(n == eng->cooling.n_evals, "mpg_cooling_export: n is not the particle number of the last cooling call");
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    if(n > 0)
+        MPG_HIP(hipMemcpy(evaluations, eng->cooling.d_evals.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    API_END
+}
+
 /* ------------------------------ introspection ------------------------------ */
 
 int mpg_tree_get_stats(mpg_engine *eng, mpg_tree_stats *st)

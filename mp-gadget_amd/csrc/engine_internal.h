@@ -6,6 +6,7 @@
 #include "pm.h"
 #include "sph.h"
 #include "veldisp.h"
+#include "cooling.h"
 #include "timestep.h"
 #include "peano.h"
 #include "planes.h"
@@ -150,6 +151,10 @@ struct mpg_engine {
     // the staging of the velocity dispersion's host form (fields of mpg_veldisp_arrays)
     DevBuf<double> vd_stage[8];
     DevBuf<uint8_t> vd_stage_tb;
+    // radiative cooling (cooling.hip): parameters, tables and counters; the staging of its host forms (fields of mpg_cooling_arrays)
+    CoolingEngine cooling;
+    DevBuf<double> cl_stage[5];
+    DevBuf<uint8_t> cl_stage_u8[2];
     void prefetch_join()
     {
         if(prefetch_thread.joinable())

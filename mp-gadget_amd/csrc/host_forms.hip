@@ -900,3 +900,41 @@ int mpg_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, double BoxSi
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }
+
+// cooling_direct for the listed particles of a host table (sfr_eff.c:463-514).  The results are copied back even when a particle hit an
+// iteration limit: that particle's entries come back as they went up, all others are final.
+int mpg_cooling(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_cooling_arrays *A, const mpg_sph_times *T,
+                const mpg_cooling_step *step, const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A && T && step, "null argument");
+    MPG_CHECK(pv->n == 0 || (A->density && A->entropy && A->ne && A->sfr), "cooling: the arrays density, entropy, ne and sfr are required");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    const size_t n = (size_t)pv->n;
+    mpg_cooling_arrays d;
+    for(int f = 0; f < COOL_NFIELDS; f++) { // every given array goes up
+        const CoolField &F = COOL_FIELDS[f];
+        void *h = field_get(*A, F.off), *dv = nullptr;
+        if(h && F.width == 0) {
+            eng->cl_stage_u8[F.slot].reserve(n + 1);
+            dv = eng->cl_stage_u8[F.slot].p;
+            MPG_HIP(hipMemcpyAsync(dv, h, n, hipMemcpyHostToDevice, eng->stream));
+        }
+        else if(h) {
+            eng->cl_stage[F.slot].reserve(n + 1);
+            dv = eng->cl_stage[F.slot].p;
+            MPG_HIP(hipMemcpyAsync(dv, h, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        }
+        field_set(d, F.off, dv);
+    }
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    const int rc = mpg_dev_cooling(eng, &d, T, step, d_act, NumActiveParticle);
+    const std::string err = rc ? mpg_last_error() : "";
+    for(int f = 0; f < COOL_NFIELDS; f++)
+        if(COOL_FIELDS[f].out && n > 0)
+            MPG_HIP(hipMemcpyAsync(field_get(*A, COOL_FIELDS[f].off), field_get(d, COOL_FIELDS[f].off), n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    MPG_CHECK(rc == 0, err);
+    API_END
+}

@@ -1,5 +1,5 @@
 // host_table.h -- the marshalling layer of the host-pointer ("drop-in") forms: everything that reads or writes the caller's records
-// (mpg_particle_view) and host arrays (mpg_sph_arrays, mpg_veldisp_arrays).  Used by host_forms.hip, resident.hip and dist.hip; no
+// (mpg_particle_view) and host arrays (mpg_sph_arrays, mpg_veldisp_arrays, mpg_cooling_arrays).  Used by host_forms.hip, resident.hip and dist.hip; no
 // engine state lives here.
 #pragma once
 #include "../../include/mpgadget_hip.h"
@@ -314,3 +314,18 @@ const VdispField VDISP_FIELDS[VDISP_NFIELDS] = {
     {offsetof(mpg_veldisp_arrays, tb_grav), 0}, {offsetof(mpg_veldisp_arrays, hsml), 1}, {offsetof(mpg_veldisp_arrays, dthsml), 1},
     {offsetof(mpg_veldisp_arrays, density), 1}, {offsetof(mpg_veldisp_arrays, vdisp), 1}};
 static_assert(sizeof(mpg_veldisp_arrays) == VDISP_NFIELDS * sizeof(void *), "VDISP_FIELDS describes every member of mpg_veldisp_arrays");
+
+// ... and of the cooling: density, metallicity and the two byte columns are inputs, entropy / ne / sfr go up and come back
+struct CoolField {
+    size_t off; // of the member in mpg_cooling_arrays
+    int width;  // doubles per particle; 0: one byte per particle
+    int slot;   // ordinal among the double (or the byte) members: the staging buffer
+    bool out;
+};
+constexpr int COOL_NFIELDS = 7;
+const CoolField COOL_FIELDS[COOL_NFIELDS] = {
+    {offsetof(mpg_cooling_arrays, density), 1, 0, false},     {offsetof(mpg_cooling_arrays, entropy), 1, 1, true},
+    {offsetof(mpg_cooling_arrays, ne), 1, 2, true},           {offsetof(mpg_cooling_arrays, sfr), 1, 3, true},
+    {offsetof(mpg_cooling_arrays, metallicity), 1, 4, false}, {offsetof(mpg_cooling_arrays, heiii_ionized), 0, 0, false},
+    {offsetof(mpg_cooling_arrays, tb_hydro), 0, 1, false}};
+static_assert(sizeof(mpg_cooling_arrays) == COOL_NFIELDS * sizeof(void *), "COOL_FIELDS describes every member of mpg_cooling_arrays");

@@ -466,3 +466,43 @@ int mpg_resident_sph_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv,
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }
+
+// cooling_direct on a resident gas run: Density, Entropy and TimeBinHydro are the resident columns, so the new entropies are where the
+// next density / hydro loop and the integrator read them; ne travels (as vdisp does above), with the two optional inputs
+int mpg_resident_sph_cooling(mpg_engine *eng, const mpg_particle_view *pv, const mpg_sph_times *T, const mpg_cooling_step *step,
+                             const int *ActiveParticle, int64_t NumActiveParticle, double *ne, const double *metallicity,
+                             const uint8_t *heiii_ionized)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && T && step && ne, "null argument");
+    resident_sph_check(eng, pv);
+    const size_t n = (size_t)pv->n;
+    const mpg_sph_arrays &r = eng->res_sph_dev;
+    MPG_CHECK(r.density && r.entropy, "resident cooling: the gas arrays have no Density / Entropy");
+    mpg_cooling_arrays d{};
+    d.density = r.density;
+    d.entropy = (double *)r.entropy;
+    d.tb_hydro = r.tb_hydro;
+    eng->cl_stage[2].reserve(n + 1);
+    d.ne = eng->cl_stage[2].p;
+    MPG_HIP(hipMemcpyAsync(d.ne, ne, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+    eng->cl_stage[3].reserve(n + 1); // Sfr is no resident column: a scratch column takes the zeros
+    d.sfr = eng->cl_stage[3].p;
+    if(metallicity) {
+        eng->cl_stage[4].reserve(n + 1);
+        MPG_HIP(hipMemcpyAsync(eng->cl_stage[4].p, metallicity, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        d.metallicity = eng->cl_stage[4].p;
+    }
+    if(heiii_ionized) {
+        eng->cl_stage_u8[0].reserve(n + 1);
+        MPG_HIP(hipMemcpyAsync(eng->cl_stage_u8[0].p, heiii_ionized, n, hipMemcpyHostToDevice, eng->stream));
+        d.heiii_ionized = eng->cl_stage_u8[0].p;
+    }
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    const int rc = mpg_dev_cooling(eng, &d, T, step, d_act, NumActiveParticle);
+    const std::string err = rc ? mpg_last_error() : "";
+    MPG_HIP(hipMemcpyAsync(ne, d.ne, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    MPG_CHECK(rc == 0, err);
+    API_END
+}

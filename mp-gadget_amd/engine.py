@@ -106,6 +106,38 @@ class VelDispParams(C.Structure):
     _fields_ = [("Time", C.c_double), ("hubble", C.c_double), ("ddrift", C.c_double), ("sfr_density_threshold", C.c_double)]
 
 
+COOLING_ARRAY_FIELDS = ("density", "entropy", "ne", "sfr", "metallicity", "heiii_ionized", "tb_hydro")
+COOLING_BYTE_FIELDS = ("heiii_ionized", "tb_hydro")
+RECOMB_CEN92, RECOMB_VERNER96, RECOMB_BADNELL06 = 0, 1, 2      # enum RecombType, cooling_rates.h:10-14
+COOLING_KWH92, COOLING_ENZO2NYX, COOLING_SHERWOOD = 0, 1, 2    # enum CoolingType, cooling_rates.h:16-20
+
+
+class CoolingArraysC(C.Structure):
+    """mpg_cooling_arrays"""
+    _fields_ = [(k, C.c_void_p) for k in COOLING_ARRAY_FIELDS]
+
+
+class Uvbg(C.Structure):
+    """mpg_uvbg: struct UVBG, cooling.h:9-19"""
+    _fields_ = [(k, C.c_double) for k in ("J_UV", "gJH0", "gJHep", "gJHe0", "epsH0", "epsHep", "epsHe0", "self_shield_dens", "zreion")]
+
+
+class CoolingParams(C.Structure):
+    """mpg_cooling_params: struct cooling_params (cooling_rates.h:23-58), struct cooling_units (cooling.h:32-44), three members of sfr_params"""
+    _fields_ = [("recomb", C.c_int), ("cooling", C.c_int), ("SelfShieldingOn", C.c_int), ("PhotoIonizationOn", C.c_int), ("fBar", C.c_double),
+                ("PhotoIonizeFactor", C.c_double), ("CMBTemperature", C.c_double), ("MinGasTemp", C.c_double), ("UVRedshiftThreshold", C.c_double),
+                ("HydrogenHeatAmp", C.c_double), ("HeliumHeatOn", C.c_int), ("HeliumHeatThresh", C.c_double), ("HeliumHeatAmp", C.c_double),
+                ("HeliumHeatExp", C.c_double), ("rho_crit_baryon", C.c_double), ("CoolingOn", C.c_int), ("density_in_phys_cgs", C.c_double),
+                ("uu_in_cgs", C.c_double), ("tt_in_s", C.c_double), ("units_rho_crit_baryon", C.c_double), ("sfr_MinGasTemp", C.c_double),
+                ("temp_to_u", C.c_double), ("HIReionTemp", C.c_double), ("test_network_maxiter", C.c_int)]
+
+
+class CoolingStep(C.Structure):
+    """mpg_cooling_step"""
+    _fields_ = [("uvbg", Uvbg), ("long_mean_free_path_heating", C.c_double), ("lastred", C.c_double * 47), ("redshift", C.c_double),
+                ("helium", C.c_double)]
+
+
 DENSITY_KERNEL_CUBIC_SPLINE, DENSITY_KERNEL_QUINTIC_SPLINE, DENSITY_KERNEL_QUARTIC_SPLINE = 1, 2, 4   # densitykernel.h:17-21
 
 _lib = None
@@ -471,6 +503,12 @@ class Engine:
     def resident_sph_end(self, arrays):
         a = self._sph_host_arrays(arrays)
         self._ck(self.lib.mpg_resident_sph_end(self.h, C.byref(a)))
+
+    def resident_sph_arrays(self):
+        """device pointers of a resident gas run's SPH arrays (mpg_resident_sph_arrays): dict of ints by the field names of mpg_sph_arrays, 0 = absent"""
+        a = SphArraysC()
+        self._ck(self.lib.mpg_resident_sph_arrays(self.h, C.byref(a)))
+        return {k: (getattr(a, k) or 0) for k in SPH_ARRAY_FIELDS}
 
     def resident_drift_all_particles(self, P, ddrift, random_shift=(0.0, 0.0, 0.0)):
         v = self._view(P)
@@ -1052,6 +1090,97 @@ class Engine:
                                              p(ql), C.c_int64(len(ql))))
         d["queue_lengths"] = [int(x) for x in ql[:self.veldisp_stats()["iterations"]]]
         return d
+
+    # ------------------------------------------------------------------ radiative cooling (cooling_direct, sfr_eff.c:463-514)
+    # `par` is a dict of the members of mpg_cooling_params (or a CoolingParams), `step` a dict with uvbg (dict of struct UVBG's members),
+    # long_mean_free_path_heating, lastred (47 values or one), redshift and helium (or a CoolingStep).  `arrays` maps the field names of
+    # mpg_cooling_arrays to device tensors (dev form) / contiguous numpy arrays (host form); entropy, ne and sfr are in/out.
+    def set_cooling_params(self, par):
+        if not isinstance(par, CoolingParams):
+            par = CoolingParams(**par)
+        self._ck(self.lib.mpg_set_cooling_params(self.h, C.byref(par)))
+
+    def set_metal_cooling_table(self, zbins=None, nhbins=None, tbins=None, rate=None):
+        """InitMetalCooling: the three bin vectors and NetCoolingRate[nz][nnh][nt]; no arguments removes the table"""
+        if zbins is None:
+            self._ck(self.lib.mpg_set_metal_cooling_table(self.h, 0, None, 0, None, 0, None, None))
+            return
+        z, h, t = (np.ascontiguousarray(a, np.float64) for a in (zbins, nhbins, tbins))
+        r = np.ascontiguousarray(rate, np.float64)
+        if r.shape != (len(z), len(h), len(t)):
+            raise EngineError("metal cooling table: rate must have the shape (len(zbins), len(nhbins), len(tbins))")
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.mpg_set_metal_cooling_table(self.h, len(z), p(z), len(h), p(h), len(t), p(t), p(r)))
+
+    @staticmethod
+    def cooling_step(step):
+        if isinstance(step, CoolingStep):
+            return step
+        s = CoolingStep()
+        for k, v in step.get("uvbg", {}).items():
+            setattr(s.uvbg, k, v)
+        s.long_mean_free_path_heating = step.get("long_mean_free_path_heating", 0.0)
+        lr = np.broadcast_to(np.asarray(step.get("lastred", 0.0), np.float64), (47,))
+        for b in range(47):
+            s.lastred[b] = lr[b]
+        s.redshift = step.get("redshift", 0.0)
+        s.helium = step.get("helium", 0.0)
+        return s
+
+    def dev_cooling(self, arrays, times, step, active=None, nactive=None):
+        """active: int32 device tensor of caller indices, or a raw device pointer (int) with `nactive` entries"""
+        a = CoolingArraysC()
+        for k in COOLING_ARRAY_FIELDS:
+            t = arrays.get(k)
+            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        s = self.cooling_step(step)
+        nact = 0 if active is None else (int(nactive) if nactive is not None else active.shape[0])
+        self._ck(self.lib.mpg_dev_cooling(self.h, C.byref(a), C.byref(times), C.byref(s), _ptr(active), C.c_int64(nact)))
+
+    def cooling(self, P, BoxSize, arrays, times, step, ActiveParticle=None):
+        v = self._view(P)
+        a = CoolingArraysC()
+        for k in COOLING_ARRAY_FIELDS:
+            t = arrays.get(k)
+            if t is not None:
+                want = np.uint8 if k in COOLING_BYTE_FIELDS else np.float64
+                if t.dtype != want or not t.flags["C_CONTIGUOUS"] or len(t) != len(P):
+                    raise EngineError("cooling host array %s must be contiguous %s of len(P)" % (k, want.__name__))
+            setattr(a, k, None if t is None else t.ctypes.data)
+        s = self.cooling_step(step)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_cooling(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), C.byref(s),
+                                      None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+
+    def resident_sph_cooling(self, P, times, step, ne, metallicity=None, heiii_ionized=None, ActiveParticle=None):
+        """on a resident gas run: `ne` (numpy float64 [n], in/out) travels, with the optional inputs metallicity (float64) and heiii_ionized (uint8)"""
+        v = self._view(P)
+        for name, t, want in (("ne", ne, np.float64), ("metallicity", metallicity, np.float64), ("heiii_ionized", heiii_ionized, np.uint8)):
+            if t is not None and (t.dtype != want or not t.flags["C_CONTIGUOUS"] or len(t) != len(P)):
+                raise EngineError("%s must be a contiguous %s array of len(P)" % (name, want.__name__))
+        s = self.cooling_step(step)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        hp = lambda t: None if t is None else C.c_void_p(t.ctypes.data)
+        self._ck(self.lib.mpg_resident_sph_cooling(self.h, C.byref(v), C.byref(times), C.byref(s),
+                                                   None if act is None else act.ctypes.data_as(C.c_void_p),
+                                                   C.c_int64(0 if act is None else len(act)), hp(ne), hp(metallicity), hp(heiii_ionized)))
+
+    def dev_cooling_state(self, rho, u, ne, step, lambdanet=None, temp=None, nh0=None):
+        """the network alone on device tensors (float64 [n]) in physical cgs units; ne is in/out, the three outputs are optional"""
+        s = self.cooling_step(step)
+        self._ck(self.lib.mpg_dev_cooling_state(self.h, C.c_int64(rho.shape[0]), _ptr(rho), _ptr(u), _ptr(ne), _ptr(lambdanet), _ptr(temp),
+                                                _ptr(nh0), C.byref(s)))
+
+    def cooling_stats(self):
+        c = (C.c_int64 * 6)()
+        self._ck(self.lib.mpg_cooling_get_stats(self.h, c))
+        return dict(treated=c[0], evaluations=c[1], bisections=c[2], floor=c[3], reion=c[4], errors=c[5])
+
+    def cooling_export(self, n):
+        """network evaluations of every particle in the last cooling call (-1: not treated)"""
+        ev = np.zeros(n, np.int32)
+        self._ck(self.lib.mpg_cooling_export(self.h, C.c_int64(n), ev.ctypes.data_as(C.c_void_p)))
+        return ev
 
     # ------------------------------------------------------------------ introspection
     def tree_stats(self):

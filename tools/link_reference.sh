@@ -13,7 +13,7 @@
 #   2. copy shim/*.c, shim/*.h and include/mpgadget_hip.h into <copy>/libgadget/;
 #   3. patch <copy>/libgadget/Makefile: drop gravpm.o gravshort-tree.o gravshort-pair.o gravity.o from GADGET_OBJS and add the shim
 #      objects; rename the five tree constructors in forcetree.o, the eight integrator entry points in timestep.o / drift.o and
-#      winds_find_vel_disp in veldisp.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
+#      winds_find_vel_disp in veldisp.o and cooling_and_starformation in sfr_eff.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
 #   4. add the two parameter hooks (set_densitypar, set_hydro_params), the accessors of mpg_shim.h and the
 #      mpg_shim_particles_changed() calls listed in INTEGRATION.md ("Where P[] is reordered") with sed;
 #   5. build the library of this repository, then `make` in the copy with LIBS += -L<repo>/mp-gadget_amd -lmpgadget_hip -lmpi.
@@ -22,11 +22,12 @@ REF=${1:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 WORK=${2:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 CHECK=${3:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
+SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
 SHIM_H="mpg_shim.h mpg_shim_epoch.h mpg_mpi_comm.h"
 REF_FILES="libgadget/Makefile libgadget/gravpm.c libgadget/gravshort-tree.c libgadget/gravshort-pair.c libgadget/gravity.c libgadget/forcetree.c
            libgadget/density.c libgadget/hydra.c libgadget/timestep.c libgadget/drift.c libgadget/timebinmgr.c libgadget/run.c libgadget/domain.c
-           libgadget/exchange.c libgadget/fof.c libgadget/slotsmanager.c libgadget/veldisp.c libgadget/sfr_eff.c gadget/Makefile Makefile.rules Options.mk.example"
+           libgadget/exchange.c libgadget/fof.c libgadget/slotsmanager.c libgadget/veldisp.c libgadget/sfr_eff.c libgadget/cooling.c libgadget/cooling_rates.c
+           libgadget/cooling_uvfluc.c gadget/Makefile Makefile.rules Options.mk.example"
 
 echo "== 0. inputs"
 for f in $REF_FILES; do test -f "$REF/$f" || { echo "missing in the reference checkout: $f"; exit 1; }; done
@@ -62,7 +63,7 @@ echo "== 3. libgadget/Makefile"
 MK="$T/libgadget/Makefile"
 sed -i -e 's/\bgravshort-tree\.o gravshort-pair\.o hydra\.o/hydra.o/' -e 's/\bgravpm\.o powerspectrum\.o/powerspectrum.o/' \
        -e 's/\bpetapm\.o gravity\.o/petapm.o/' "$MK"
-sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
+sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
 cat >> "$MK" <<MKEOF
 
 # ---- MP-Gadget on libmpgadget_hip (tools/link_reference.sh)
@@ -71,6 +72,7 @@ CFLAGS += -DMPGADGET_HIP -I$ROOT/include
 .objs/timestep.o: CFLAGS += -Dapply_half_kick=cpu_apply_half_kick -Dapply_PM_half_kick=cpu_apply_PM_half_kick -Dfind_hydro_timesteps=cpu_find_hydro_timesteps -Dfind_timesteps=cpu_find_timesteps -Dapply_hydro_half_kick=cpu_apply_hydro_half_kick -Dhierarchical_gravity_and_timesteps=cpu_hierarchical_gravity_and_timesteps -Dhierarchical_gravity_accelerations=cpu_hierarchical_gravity_accelerations
 .objs/drift.o: CFLAGS += -Ddrift_all_particles=cpu_drift_all_particles
 .objs/veldisp.o: CFLAGS += -Dwinds_find_vel_disp=cpu_winds_find_vel_disp
+.objs/sfr_eff.o: CFLAGS += -Dcooling_and_starformation=cpu_cooling_and_starformation
 MKEOF
 
 echo "== 4. hooks in the reference sources (INTEGRATION.md lists them; each is one line)"
@@ -133,6 +135,27 @@ append(T + "/libgadget/timestep.c", "double mpg_shim_max_gas_vel(void) { return 
        "{ return get_PM_timestep_ti(times, atime, CP, FastParticleType, asmth); }")
 append(T + "/libgadget/timebinmgr.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_timeline(mpg_timeline *tl)\n{\n    static double loga[8192];\n    int i;\n"
        "    for(i = 0; i < NSyncPoints && i < 8192; i++)\n        loga[i] = SyncPoints[i].loga;\n    tl->nsync = NSyncPoints;\n    tl->loga = loga;\n}")
+# the cooling (cooling-hip.c): accessors next to the file-static parameters, and the two hooks of a star-forming run in sfr_eff.c
+append(T + "/libgadget/cooling_rates.c", "struct cooling_params mpg_shim_cooling_params(void) { return CoolingParams; }")
+append(T + "/libgadget/cooling.c", "struct cooling_units mpg_shim_cooling_units(void) { return coolunits; }")
+append(T + "/libgadget/cooling_uvfluc.c", "int mpg_shim_uvf_in_use(void) { return UVF.enabled || uvf_params.ExcursionSetReionOn; }\n"
+       "int mpg_shim_metal_table(int *n, double **bins, double **rate)\n{\n    if(MetalCool.CoolingNoMetal)\n        return 0;\n"
+       "    n[0] = MetalCool.NRedshift_bins; n[1] = MetalCool.NHydrogenNumberDensity_bins; n[2] = MetalCool.NTemperature_bins;\n"
+       "    bins[0] = MetalCool.Redshift_bins; bins[1] = MetalCool.HydrogenNumberDensity_bins; bins[2] = MetalCool.Temperature_bins;\n"
+       "    *rate = MetalCool.Lmet_table;\n    return 1;\n}")
+append(T + "/libgadget/sfr_eff.c", "void mpg_shim_sfr_cooling(int *StarformationOn, double *MinGasTemp, double *temp_to_u, double *HIReionTemp)\n"
+       "{\n    *StarformationOn = sfr_params.StarformationOn;\n    *MinGasTemp = sfr_params.MinGasTemp;\n    *temp_to_u = sfr_params.temp_to_u;\n"
+       "    *HIReionTemp = sfr_params.HIReionTemp;\n}")
+def replace_once(path, old, new):
+    s = open(path).read()
+    if s.count(old) != 1:
+        raise SystemExit("%s: expected exactly one %r" % (path, old))
+    open(path, "w").write(s.replace(old, new))
+replace_once(T + "/libgadget/sfr_eff.c", "            else\n                cooling_direct(p_i, redshift, a3inv, hubble, &GlobalUVBG);",
+             "            else { extern int mpg_shim_cooling_queue(int); if(!mpg_shim_cooling_queue(p_i))\n                cooling_direct(p_i, redshift, a3inv, hubble, &GlobalUVBG); }")
+replace_once(T + "/libgadget/sfr_eff.c", '    walltime_measure("/Cooling/Cooling");',
+             '    { extern void mpg_shim_cooling_flush(double, double, const struct UVBG *); mpg_shim_cooling_flush(Time, hubble, &GlobalUVBG); }\n'
+             '    walltime_measure("/Cooling/Cooling");')
 # P[] is reordered / exchanged: the shim's upload cache must hear of it (the 64-record hash of mpg_shim_epoch.h is only a backstop)
 hook = "{ extern void mpg_shim_particles_changed(void); mpg_shim_particles_changed(); }"
 for path, func in (("/libgadget/domain.c", "domain_decompose_full"), ("/libgadget/domain.c", "domain_maintain"),
@@ -143,16 +166,18 @@ print("hooks written")
 PYEOF
 
 if [ "$CHECK" = "--check" ]; then
-    # the patched reference files and the renamed objects still parse (nothing is compiled to an object, linked or run)
-    for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c; do
+    # the patched reference files and the renamed objects still parse (nothing is compiled to an object, linked or run); cooling_rates.c,
+    # which only gains one accessor line, calls GSL and cannot be parsed with the typedef-only stand-in
+    for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c sfr_eff.c cooling.c cooling_uvfluc.c; do
         extra=""
         case $f in
             forcetree.c) extra="-Dforce_tree_full=cpu_force_tree_full -Dforce_tree_rebuild_mask=cpu_force_tree_rebuild_mask -Dforce_tree_active_moments=cpu_force_tree_active_moments -Dforce_tree_calc_moments=cpu_force_tree_calc_moments -Dforce_tree_free=cpu_force_tree_free";;
             timestep.c) extra="-Dapply_half_kick=cpu_apply_half_kick -Dapply_PM_half_kick=cpu_apply_PM_half_kick -Dfind_hydro_timesteps=cpu_find_hydro_timesteps -Dfind_timesteps=cpu_find_timesteps -Dapply_hydro_half_kick=cpu_apply_hydro_half_kick -Dhierarchical_gravity_and_timesteps=cpu_hierarchical_gravity_and_timesteps -Dhierarchical_gravity_accelerations=cpu_hierarchical_gravity_accelerations";;
             drift.c) extra="-Ddrift_all_particles=cpu_drift_all_particles";;
             veldisp.c) extra="-Dwinds_find_vel_disp=cpu_winds_find_vel_disp";;
+            sfr_eff.c) extra="-Dcooling_and_starformation=cpu_cooling_and_starformation";;
         esac
-        if ! gcc -std=gnu11 -fopenmp -fsyntax-only -DMPGADGET_HIP $extra -I "$STUB" -I "$MPIINC" -I "$ROOT/include" -I "$T/libgadget" -I "$T" "$T/libgadget/$f" 2> "$STUB/err"; then
+        if ! gcc -std=gnu11 -fopenmp -fsyntax-only -DMPGADGET_HIP $extra -I "$STUB" -I "$MPIINC" -I "$ROOT/include" -I "$T/libgadget" -I "$T" -I "$REF/depends/bigfile/src" "$T/libgadget/$f" 2> "$STUB/err"; then
             if grep -q 'gsl/.*No such file' "$STUB/err"; then
                 echo "   ($f includes GSL headers this image lacks: not parsed here)"
             else
