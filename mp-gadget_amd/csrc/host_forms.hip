@@ -841,8 +841,7 @@ int mpg_density(mpg_engine *eng, const mpg_particle_view *P, double BoxSize, con
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
     MPG_CALL(mpg_dev_force_tree_rebuild_mask(eng, 1 /* GASMASK */, 0));
     MPG_CALL(mpg_dev_density(eng, &d, T, d_act, NumActiveParticle, update_hsml, DoEgyDensity, BlackHoleOn));
-    if(update_hsml)
-        MPG_CALL(mpg_dev_force_tree_calc_hmax(eng));
+    MPG_CALL(mpg_dev_force_tree_calc_hmax(eng)); // (update_hsml = 0: from the caller's Hsml, see SphEngine::density)
     if(!res)
         unstage_sph(eng, A, &d, P->n, false);
     API_END

@@ -1001,10 +1001,12 @@ void SphEngine::density(TreeBuilder &tree, const SphView &A, const mpg_sph_times
         if(nq > 0 && last_iterations > 400) // MAXITER, treewalk.c:1362-1364
             fail(__FILE__, __LINE__, "failed to converge density for " + std::to_string(nq) + " particles");
     }
-    if(update_hsml && tv.npart > 0) {
+    if(tv.npart > 0) {
         // update_tree_hmax_father for every finished particle (density.c:551-553) == leaf hmax from the final Hsml
         // (gathered in calc_hmax, from the array as it is then: with distributed particles the smoothing lengths of the ghost
-        // particles are refreshed from their owners between density() and the hmax pass)
+        // particles are refreshed from their owners between density() and the hmax pass).  update_hsml = 0 leaves the caller's Hsml
+        // as they are, and they are what the hmax pass then gathers: force_tree_calc_moments takes P[].Hsml whoever set it
+        // (forcetree.c:1353), so density at prescribed radii -> hmax -> hydro_force is a legal sequence.
         hsml_view = A;
         hmax_pending = true;
     }

@@ -78,71 +78,108 @@ def kernel_W(kernel, r, H):
     return W, dWdr, dWdH
 
 
-def _pairs(pos, box):
+def _pairs(pos, box, t=None):
+    """x_ij = x_i - x_j on the nearest image and |x_ij| for the targets i in t (None: all) against every particle j"""
     pos = np.asarray(pos, float)
-    d = pos[:, None, :] - pos[None, :, :]
+    d = (pos if t is None else pos[t])[:, None, :] - pos[None, :, :]
     d -= box * np.rint(d / box)                 # x_ij = x_i - x_j on the nearest image
     r = np.sqrt((d ** 2).sum(-1))
     return d, r
 
 
-def paper_density(pos, mass, vel, A, H, box, kernel=1, formulation="density"):
-    """The density loop for every particle as target (S05 eq 5, SH02 eqs 27-28, H13 eq 19), all pairs.  vel / A are the velocities and
-    entropic functions the SUMS see - the predicted ones when particles carry pending kicks.  Returns a dict of per-particle fields:
-    density, dhsml (SH02's f), divvel, curlvel, and for the pressure-entropy form y, dy_dH, egywtdensity, dhsmlegy."""
+def _blocks(N, targets, chunk):
+    """The index blocks a loop over `targets` (None: every particle) is evaluated in: at most `chunk` targets each (None: one block)."""
+    t = np.arange(N) if targets is None else np.asarray(targets, np.int64)
+    step = max(len(t), 1) if chunk is None else int(chunk)
+    return [t[k:k + step] for k in range(0, max(len(t), 1), step)]
+
+
+def _concat(parts):
+    return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+
+def paper_density(pos, mass, vel, A, H, box, kernel=1, formulation="density", targets=None, chunk=None):
+    """The density loop (S05 eq 5, SH02 eqs 27-28, H13 eq 19), all pairs.  vel / A are the velocities and entropic functions the SUMS see -
+    the predicted ones when particles carry pending kicks.  targets: the particles evaluated as targets (an index array; None: all), in
+    blocks of `chunk` targets x all particles (None: one block) - a target's sums run over all particles whatever the blocking, so the rows
+    do not depend on it.  Returns a dict of per-target fields (rows in the order of `targets`): density, dhsml (SH02's f), divvel, curlvel,
+    and for the pressure-entropy form y, dy_dH, egywtdensity, dhsmlegy.  For tolerances: nngb = #{j : r_ij <= H_i} (the target itself
+    included: what a neighbour search must find), graddenom = 1 + (H / 3 rho) d rho / dH, and for every signed sum the sum of the absolute
+    values of its pair terms, scaled like the sum - abs_divvel, abs_curlvel [.,3] (per component of the curl vector), abs_dhsmlegy."""
     pos = np.asarray(pos, float)
     N = len(pos)
     m = np.asarray(mass, float)
     u = np.asarray(vel, float)
     A = np.asarray(A, float)
     H = np.asarray(H, float)
-    d, r = _pairs(pos, box)
-    du = u[:, None, :] - u[None, :, :]          # u_ij
-    offd = ~np.eye(N, dtype=bool)
+    return _concat([_density_block(pos, N, m, u, A, H, box, kernel, formulation, t) for t in _blocks(N, targets, chunk)])
+
+
+def _density_block(pos, N, m, u, A, H, box, kernel, formulation, t):
+    Ht = H[t]
+    d, r = _pairs(pos, box, t)
+    du = u[t][:, None, :] - u[None, :, :]          # u_ij
+    offd = t[:, None] != np.arange(N)[None, :]
     rs = np.where(offd, r, 1.0)
-    Wi, dWi, dWHi = kernel_W(kernel, r, H[:, None])        # kernels of i's support, [i, j]
-    inside = r < H[:, None]
+    Wi, dWi, dWHi = kernel_W(kernel, r, Ht[:, None])        # kernels of i's support, [i, j]
+    inside = r < Ht[:, None]
     Wi, dWi, dWHi = Wi * inside, dWi * inside, dWHi * inside
     rho = (m[None, :] * Wi).sum(1)
     drho_dH = (m[None, :] * dWHi).sum(1)
-    f_grad = 1.0 / (1.0 + H / (3.0 * rho) * drho_dH)       # SH02: f_i = [1 + (h_i / 3 rho_i) d rho_i / d h_i]^-1
+    f_grad = 1.0 / (1.0 + Ht / (3.0 * rho) * drho_dH)       # SH02: f_i = [1 + (h_i / 3 rho_i) d rho_i / d h_i]^-1
     gradW_i = (dWi / rs)[:, :, None] * d * offd[:, :, None]          # grad_i W_ij(H_i)
-    divu = -(m[None, :] * (du * gradW_i).sum(-1)).sum(1) / rho      # (1/rho_i) sum_j m_j (u_j - u_i) . grad_i W_ij
+    divterm = m[None, :] * (du * gradW_i).sum(-1)
+    divu = -divterm.sum(1) / rho      # (1/rho_i) sum_j m_j (u_j - u_i) . grad_i W_ij
     curl = np.cross(du, gradW_i)
-    curlu = np.linalg.norm((m[None, :, None] * curl).sum(1), axis=1) / rho
+    curlterm = m[None, :, None] * curl
+    curlu = np.linalg.norm(curlterm.sum(1), axis=1) / rho
     out = dict(density=rho, dhsml=f_grad, divvel=divu, curlvel=curlu)
+    out["nngb"] = (r <= Ht[:, None]).sum(1)
+    out["graddenom"] = 1.0 + Ht / (3.0 * rho) * drho_dH
+    out["abs_divvel"] = np.abs(divterm).sum(1) / rho
+    out["abs_curlvel"] = np.abs(curlterm).sum(1) / rho[:, None]
     if formulation != "density":
         # H13 eq 19: y_i = Pbar_i^(1/gamma) = sum_j m_j A_j^(1/gamma) W_ij(h_i)
         a_g = A ** (1.0 / GAMMA)
         y = (m[None, :] * a_g[None, :] * Wi).sum(1)
         dy_dH = (m[None, :] * a_g[None, :] * dWHi).sum(1)
         out["y"] = y
-        out["egywtdensity"] = y / a_g                       # "energy weighted density" (the reference's EgyWtDensity)
+        out["egywtdensity"] = y / a_g[t]                    # "energy weighted density" (the reference's EgyWtDensity)
         # H13 eq 18 with the smoothing length tied to rho (x~_j = m_j, y~ = rho):
         # f_ij - 1 = -(1 / A_j^(1/gamma)) (h_i / 3 rho_i) (d y_i / d h_i) [1 + (h_i / 3 rho_i) d rho_i / d h_i]^-1
-        out["dhsmlegy"] = -(dy_dH * H / (3.0 * y)) * f_grad   # the reference stores this combination (times y/rho it is the bracket)
+        out["dhsmlegy"] = -(dy_dH * Ht / (3.0 * y)) * f_grad  # the reference stores this combination (times y/rho it is the bracket)
+        out["abs_dhsmlegy"] = np.abs(m[None, :] * a_g[None, :] * dWHi).sum(1) * Ht / (3.0 * y) * np.abs(f_grad)
     return out
 
 
 def paper_hydro(pos, mass, vel, A, H, box, F, atime=1.0, hubble=0.0, alpha=0.75, kernel=1, formulation="density", dlna=None,
-                contrast_limit=None):
-    """The hydro force of every particle as target from per-particle FIELDS F (what paper_density returns, or the stored / predicted values
-    of particles that were not active in the density loop): density, dhsml, divvel, curlvel and, pressure-entropy, egywtdensity and dhsmlegy.
-    vel / A as in paper_density.  contrast_limit (pressure-entropy; a limiter of the code, not of H13): the grad-h correction of a particle is
-    scaled down where its y / (A^(1/gamma) rho) exceeds the limit (None: no limit)."""
+                contrast_limit=None, targets=None, chunk=None):
+    """The hydro force from per-particle FIELDS F of ALL particles (what paper_density returns for all targets, or the stored / predicted
+    values of particles that were not active in the density loop): density, dhsml, divvel, curlvel and, pressure-entropy, egywtdensity and
+    dhsmlegy.  vel / A, targets / chunk and the order of the rows as in paper_density.  contrast_limit (pressure-entropy; a limiter of the
+    code, not of H13): the grad-h correction of a particle is scaled down where its y / (A^(1/gamma) rho) exceeds the limit (None: no
+    limit).  For tolerances: npairs = #{j != i : r_ij < H_i or r_ij < H_j} and the sums of the absolute pair terms abs_hydroacc [.,3],
+    abs_dtentropy."""
     pos = np.asarray(pos, float)
     N = len(pos)
     m = np.asarray(mass, float)
     u = np.asarray(vel, float)
     A = np.asarray(A, float)
     H = np.asarray(H, float)
-    d, r = _pairs(pos, box)
-    du = u[:, None, :] - u[None, :, :]
-    offd = ~np.eye(N, dtype=bool)
+    dl = None if dlna is None else np.asarray(dlna, float)
+    return _concat([_hydro_block(pos, N, m, u, A, H, box, F, atime, hubble, alpha, kernel, formulation, dl, contrast_limit, t)
+                    for t in _blocks(N, targets, chunk)])
+
+
+def _hydro_block(pos, N, m, u, A, H, box, F, atime, hubble, alpha, kernel, formulation, dlna, contrast_limit, t):
+    Ht = H[t]
+    d, r = _pairs(pos, box, t)
+    du = u[t][:, None, :] - u[None, :, :]
+    offd = t[:, None] != np.arange(N)[None, :]
     rs = np.where(offd, r, 1.0)
     rho, f_grad, divu, curlu = (np.asarray(F[k], float) for k in ("density", "dhsml", "divvel", "curlvel"))
-    _, dWi, _ = kernel_W(kernel, r, H[:, None])
-    dWi = dWi * (r < H[:, None])
+    _, dWi, _ = kernel_W(kernel, r, Ht[:, None])
+    dWi = dWi * (r < Ht[:, None])
     out = {}
     if formulation == "density":
         P = A * rho ** GAMMA
@@ -159,12 +196,12 @@ def paper_hydro(pos, mass, vel, A, H, box, F, atime=1.0, hubble=0.0, alpha=0.75,
 
     Wj, dWj, _ = kernel_W(kernel, r, H[None, :])             # kernels of j's support, [i, j]
     dWj = dWj * (r < H[None, :])
-    pair = offd & ((r < H[:, None]) | (r < H[None, :]))
+    pair = offd & ((r < Ht[:, None]) | (r < H[None, :]))
     dWi_f = dWi                                              # W'_ij(H_i) (zero outside its own support)
     # pressure terms
     if formulation == "density":
         # S05 eq 7: -sum_j m_j [ f_i P_i/rho_i^2 grad_i W_ij(h_i) + f_j P_j/rho_j^2 grad_i W_ij(h_j) ]
-        ti = (f_grad * P / rho ** 2)[:, None] * dWi_f
+        ti = (f_grad * P / rho ** 2)[t][:, None] * dWi_f
         tj = (f_grad * P / rho ** 2)[None, :] * dWj
     else:
         # H13 eq 21: -sum_j m_j (A_i A_j)^(1/gamma) [ f_ij Pbar_i^(1-2/gamma) grad_i W_ij(h_i) + f_ji Pbar_j^(1-2/gamma) grad_i W_ij(h_j) ]
@@ -173,11 +210,11 @@ def paper_hydro(pos, mass, vel, A, H, box, F, atime=1.0, hubble=0.0, alpha=0.75,
         if contrast_limit is not None:
             rr = eom / rho
             corr = corr * np.minimum(rr, contrast_limit) / rr
-        f_ij = 1.0 - corr[:, None] / a_g[None, :]
-        f_ji = 1.0 - corr[None, :] / a_g[:, None]
+        f_ij = 1.0 - corr[t][:, None] / a_g[None, :]
+        f_ji = 1.0 - corr[None, :] / a_g[t][:, None]
         pw = P ** (1.0 - 2.0 / GAMMA)
-        aa = a_g[:, None] * a_g[None, :]
-        ti = aa * f_ij * pw[:, None] * dWi_f
+        aa = a_g[t][:, None] * a_g[None, :]
+        ti = aa * f_ij * pw[t][:, None] * dWi_f
         tj = aa * f_ji * pw[None, :] * dWj
     hfc = m[None, :] * (ti + tj) / rs
     # viscosity, S05 eqs 13-14 with the Balsara factors (eq 17)
@@ -185,24 +222,27 @@ def paper_hydro(pos, mass, vel, A, H, box, F, atime=1.0, hubble=0.0, alpha=0.75,
     mu = fac_mu * vdotr2 / rs
     appr = pair & (vdotr2 < 0)
     fbal = np.abs(divu) / (np.abs(divu) + curlu + 0.0001 * c / H / fac_mu)
-    vsig = c[:, None] + c[None, :] - 3.0 * mu
-    rho_ij = 0.5 * (rho[:, None] + rho[None, :])
-    Pi = np.where(appr, 0.5 * alpha * vsig * (-mu) / rho_ij * 0.5 * (fbal[:, None] + fbal[None, :]), 0.0)
+    vsig = c[t][:, None] + c[None, :] - 3.0 * mu
+    rho_ij = 0.5 * (rho[t][:, None] + rho[None, :])
+    Pi = np.where(appr, 0.5 * alpha * vsig * (-mu) / rho_ij * 0.5 * (fbal[t][:, None] + fbal[None, :]), 0.0)
     dWsum = dWi_f + dWj
     if dlna is not None:
-        dl = 2.0 * np.maximum(np.asarray(dlna, float)[:, None], np.asarray(dlna, float)[None, :])
+        dl = 2.0 * np.maximum(dlna[t][:, None], dlna[None, :])
         with np.errstate(divide="ignore", invalid="ignore"):
-            bound = 0.5 * (hubble * atime ** (3 * (GAMMA - 1))) * vdotr2 / (0.5 * (m[:, None] + m[None, :]) * dWsum * rs * dl)
+            bound = 0.5 * (hubble * atime ** (3 * (GAMMA - 1))) * vdotr2 / (0.5 * (m[t][:, None] + m[None, :]) * dWsum * rs * dl)
         lim = appr & (dl > 0) & (dWsum < 0)
         Pi = np.where(lim, np.minimum(Pi, bound), Pi)
     hfc_visc = 0.5 * m[None, :] * Pi * dWsum / rs                     # m_j Pi_ij Wbar'_ij / r, Wbar' = (W'_i + W'_j) / 2
     hfc = np.where(pair, hfc + hfc_visc, 0.0)
     acc = -(hfc[:, :, None] * d).sum(1)
+    heat = 0.5 * np.where(pair, hfc_visc, 0.0) * vdotr2
     with np.errstate(divide="ignore", invalid="ignore"):
-        dA = (0.5 * np.where(pair, hfc_visc, 0.0) * vdotr2).sum(1) * (GAMMA - 1) / (hubble_a2 * rho ** (GAMMA - 1))
-    sig = np.where(pair, c[:, None] + c[None, :], 0.0)
+        dA = heat.sum(1) * (GAMMA - 1) / (hubble_a2 * rho[t] ** (GAMMA - 1))
+        abs_dA = np.abs(heat).sum(1) * (GAMMA - 1) / (hubble_a2 * rho[t] ** (GAMMA - 1))
+    sig = np.where(pair, c[t][:, None] + c[None, :], 0.0)
     sig = np.where(appr, np.maximum(sig, vsig), sig)
-    out.update(hydroacc=acc, dtentropy=dA, maxsignalvel=np.maximum(c, sig.max(1)), pressure=P, soundspeed=c, balsara=fbal)
+    out.update(hydroacc=acc, dtentropy=dA, maxsignalvel=np.maximum(c[t], sig.max(1)), pressure=P[t], soundspeed=c[t], balsara=fbal[t])
+    out.update(npairs=pair.sum(1), abs_hydroacc=np.abs(hfc[:, :, None] * d).sum(1), abs_dtentropy=abs_dA)
     return out
 
 
