@@ -43,8 +43,6 @@ struct alignas(16) RRow { // a PM result on the wire
 };
 static_assert(sizeof(PRow) == 32 && sizeof(RRow) == 32, "wire rows are 32 bytes");
 
-inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 __device__ __forceinline__ int wrapi(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
 
 // slab owner(s) of a particle's CIC cloud: the planes floor(x / cellsize) and that + 1 (periodic), P planes per rank

@@ -308,8 +308,6 @@ void toptree_assign_balanced(TopNode *t, int size, int *leaf_topnode, int nleave
 
 // ---- device passes -----------------------------------------------------------------------------------------------------
 namespace {
-static inline int nblk(int64_t n, int b = 256) { return (int)((n + b - 1) / b); }
-
 __global__ void __launch_bounds__(256) k_garbage_keys(int64_t n, const uint8_t *__restrict__ garbage, uint64_t *__restrict__ keys,
                                                       unsigned long long *__restrict__ ngarbage)
 {

@@ -79,12 +79,10 @@ __global__ void __launch_bounds__(256) k_fof_walk(const TreeView tv, const doubl
 {
     __shared__ unsigned s_stack[4 * 8 * SPH_STK];
     __shared__ unsigned s_llist[4 * 8 * SPH_LCAP];
-    const int lane = threadIdx.x & 63;
-    const int grp = lane >> 3, s = lane & 7, gshift = grp * 8;
-    unsigned *stack = s_stack + ((threadIdx.x >> 6) * 8 + grp) * SPH_STK;
-    unsigned *llist = s_llist + ((threadIdx.x >> 6) * 8 + grp) * SPH_LCAP;
-    const int64_t q = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + grp;
-    const bool valid = q < ntargets;
+    NgbGroup g = ngb_group(s_stack, s_llist, ntargets);
+    const int s = g.s;
+    const int64_t q = g.q;
+    const bool valid = g.valid;
     int ci = 0;
     double px = 0, py = 0, pz = 0, radius = LL;
     if(valid) {
@@ -111,39 +109,11 @@ __global__ void __launch_bounds__(256) k_fof_walk(const TreeView tv, const doubl
     const double h2 = radius * radius;
     double best_r2 = 1e300;
     int best_j = -1;
-    int sp = 0;
-    if(valid) {
-        if(s == 0)
-            stack[0] = (0u << 4) | 1u; // the root
-        sp = 1;
-    }
-    bool overflow = false;
-    for(;;) {
-        int nl = 0;
-        for(;;) { // phase A: walk; opened leaves go to the group's list
-            const bool go = sp > 0 && nl + 16 <= SPH_LCAP;
-            if(ballot64(go) == 0)
-                break;
-            nl = walk_stepk<false, 2, true>(tv, tv.geoB, nullptr, stack, sp, go, s, gshift, radius, px, py, pz, llist, nl, overflow); // (two child ranges per step, sibling leaves joined: ngb_walk.h)
-            if(ballot64(overflow) != 0)
-                break;
-        }
-        if(ballot64(overflow) != 0)
-            break;
-        // phase B: every group takes its next leaf; lane s <-> particle s.  (The particle of the NEXT leaf is requested before this one
-        // is tested, as in the SPH loops: sph.hip.  Lanes beyond a leaf's count read its first particle.)
-        unsigned e = (0 < nl) ? llist[0] : 0u;
-        int ps = (int)(e >> 4), pc = (int)(e & 15u);
-        Src4 o = tv.src[ps + (s < pc ? s : 0)];
-        for(int it = 0;; it++) {
-            const bool has = it < nl;
-            if(ballot64(has) == 0)
-                break;
-            const unsigned e_n = (it + 1 < nl) ? llist[it + 1] : 0u;
-            const int ps_n = (int)(e_n >> 4), pc_n = (int)(e_n & 15u);
-            const Src4 o_n = tv.src[ps_n + (s < pc_n ? s : 0)];
-            if(s < pc) {
-                const int j = ps + s;
+    // (two child ranges per step, sibling leaves joined, NEAREST() throughout: ngb_walk.h)
+    ngb_search<false, 2, true, true>(
+        tv, tv.geoB, nullptr, g, radius, px, py, pz, [&](const int slot) { return tv.src[slot]; },
+        [&](const Src4 &o, const int j, const bool live) {
+            if(live) {
                 const double d0 = nearest_img(px - o.x, tv.box, 1.0 / tv.box);
                 const double d1 = nearest_img(py - o.y, tv.box, 1.0 / tv.box);
                 const double d2 = nearest_img(pz - o.z, tv.box, 1.0 / tv.box);
@@ -159,18 +129,10 @@ __global__ void __launch_bounds__(256) k_fof_walk(const TreeView tv, const doubl
                     }
                 }
             }
-            o = o_n;
-            ps = ps_n;
-            pc = pc_n;
-        }
-        if(ballot64(sp > 0) == 0)
-            break;
-    }
-    if(ballot64(overflow) != 0) {
-        if(lane == 0)
-            atomicExch(err, 1u);
+        },
+        [] {});
+    if(ngb_overflowed(g, err))
         return;
-    }
     if(MODE == 1) {
         for(int off = 1; off < 8; off <<= 1) { // nearest over the 8 lanes of the group (ties: the lower tree slot)
             const double r2o = __shfl_xor(best_r2, off);
@@ -432,8 +394,6 @@ __global__ void __launch_bounds__(256) k_fof_export(int64_t ng, const unsigned l
         for(int c = 0; c < 9; c++)
             out.Imom[9 * g + c] = a[16 + c];
 }
-
-inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 } // namespace
 

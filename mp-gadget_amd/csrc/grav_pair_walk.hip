@@ -29,12 +29,10 @@ __global__ void __launch_bounds__(256) k_grav_short_pair(const TreeView tv, cons
             s_wp[NTAB - 1] = WTab{0, 0};
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int grp = lane >> 3, s = lane & 7, gshift = grp * 8;
-    unsigned *stack = s_stack + ((threadIdx.x >> 6) * 8 + grp) * SPH_STK;
-    unsigned *llist = s_llist + ((threadIdx.x >> 6) * 8 + grp) * SPH_LCAP;
-    const int64_t q = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + grp;
-    const bool valid = q < io.ntargets;
+    NgbGroup g = ngb_group(s_stack, s_llist, io.ntargets);
+    const int s = g.s;
+    const int64_t q = g.q;
+    const bool valid = g.valid;
     int ci = 0;
     double px = 0, py = 0, pz = 0;
     if(valid) {
@@ -45,33 +43,11 @@ __global__ void __launch_bounds__(256) k_grav_short_pair(const TreeView tv, cons
     }
     const double rcut2 = rcut_abs * rcut_abs;
     double ax = 0, ay = 0, az = 0, pot = 0;
-    int sp = 0;
-    if(valid) {
-        if(s == 0)
-            stack[0] = (0u << 4) | 1u; // the root
-        sp = 1;
-    }
-    bool overflow = false;
-    for(;;) {
-        int nl = 0;
-        for(;;) { // phase A: walk; opened leaves go to the group's list
-            const bool go = sp > 0 && nl + 16 <= SPH_LCAP;
-            if(ballot64(go) == 0)
-                break;
-            nl = walk_stepk<false, 2, true>(tv, tv.geoB, nullptr, stack, sp, go, s, gshift, rcut_abs, px, py, pz, llist, nl, overflow); // (two child ranges per step: ngb_walk.h)
-            if(ballot64(overflow) != 0)
-                break;
-        }
-        if(ballot64(overflow) != 0)
-            break;
-        for(int it = 0;; it++) { // phase B: every group takes its next leaf; lane s <-> particle s
-            const bool has = it < nl;
-            if(ballot64(has) == 0)
-                break;
-            const unsigned e = has ? llist[it] : 0u;
-            const int ps = (int)(e >> 4), pc = (int)(e & 15u);
-            if(s < pc) {
-                const Src4 o = tv.src[ps + s];
+    // (two child ranges per step, sibling leaves joined, NEAREST() throughout: ngb_walk.h)
+    ngb_search<false, 2, true, true>(
+        tv, tv.geoB, nullptr, g, rcut_abs, px, py, pz, [&](const int slot) { return tv.src[slot]; },
+        [&](const Src4 &o, const int, const bool live) {
+            if(live) {
                 // dist = I.Pos - P[other].Pos (treewalk.c:968-975); pair_force takes source - target = -dist
                 const double d0 = nearest_img(px - o.x, tv.box, 1.0 / tv.box);
                 const double d1 = nearest_img(py - o.y, tv.box, 1.0 / tv.box);
@@ -79,15 +55,10 @@ __global__ void __launch_bounds__(256) k_grav_short_pair(const TreeView tv, cons
                 if(d0 * d0 + d1 * d1 + d2 * d2 <= rcut2)
                     pair_force<POT>(o, -d0, -d1, -d2, gp, s_wf, s_wp, ax, ay, az, pot);
             }
-        }
-        if(ballot64(sp > 0) == 0)
-            break;
-    }
-    if(ballot64(overflow) != 0) {
-        if(lane == 0)
-            atomicExch(err, 1u);
+        },
+        [] {});
+    if(ngb_overflowed(g, err))
         return;
-    }
     ax = group_sum(ax);
     ay = group_sum(ay);
     az = group_sum(az);

@@ -66,6 +66,9 @@ template <typename T> struct DevBuf {
     DevBuf &operator=(const DevBuf &) = delete;
 };
 
+// blocks of b threads for n elements, one each
+inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+
 constexpr int MAXLEVEL = 21;      // octree levels below the root carried in a 63-bit key
 constexpr int NMAXCHILD = 8;      // particles per leaf, forcetree.h:13
 constexpr int NTAB = 512;         // rows of the short-range window table, gravity.c:16

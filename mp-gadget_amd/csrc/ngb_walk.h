@@ -1,7 +1,11 @@
 // ngb_walk.h -- group-cooperative neighbour search over the level-ordered tree (treewalk_visit_ngbiter / _nolist_ngbiter,
-// treewalk.c:930-1265), shared by the SPH loops (sph.hip) and the pair-wise short-range gravity check (grav_pair_walk.hip).
+// treewalk.c:930-1265) and the host's radius iteration around it (treewalk_do_hsml_loop, treewalk.c:1269-1367).  One search behind
+// five callers: k_density and k_hydro (sph.hip), k_vdisp<BH> (veldisp.hip), k_fof_walk<MODE> (fof.hip) and k_grav_short_pair<POT>
+// (grav_pair_walk.hip).  A kernel declares the LDS, loads its target and says what a candidate is (fetch) and what is done with it
+// (visit); the control flow - set-up, walk, list, pause and resume, overflow - is ngb_group / ngb_search / ngb_overflowed below.
 #pragma once
 #include "mpg_common.h"
+#include <vector>
 
 namespace mpg {
 
@@ -46,7 +50,7 @@ __device__ __forceinline__ unsigned long long cull_mask(const NodeGeo &g, double
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Group-cooperative neighbour search (both SPH loops).  A wave is 8 groups of 8 lanes; a group owns ONE target and walks
+// Group-cooperative neighbour search.  A wave is 8 groups of 8 lanes; a group owns ONE target and walks
 // the level-ordered copy of the tree (children of a node contiguous): one step pops a child range from the group's LIFO in
 // LDS, the 8 lanes cull the <= 8 children (treewalk.c:1015-1042) with one coalesced read each, internal survivors push their
 // own child range, and the surviving leaves are evaluated at once, lane s <-> particle s of the leaf (one coalesced read
@@ -61,6 +65,12 @@ constexpr int SPH_STK = 160; // pending child ranges per group: <= 7 per level +
 constexpr int SPH_LCAP = 120; // leaf entries per group; phase A pauses when a group may not fit 8 more per child range of a step
 
 __device__ __forceinline__ double group_sum(double v)
+{
+    for(int off = 1; off < 8; off <<= 1)
+        v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ int group_sum_int(int v)
 {
     for(int off = 1; off < 8; off <<= 1)
         v += __shfl_xor(v, off);
@@ -164,6 +174,175 @@ __device__ __forceinline__ int walk_stepk(const TreeView &tv, const NodeGeo *__r
         nl += can ? __popc(gl[k]) : 0;
     }
     return nl;
+}
+
+// The state of one group's search: who the lane is, the group's LIFO and leaf list in LDS, the queue slot of its target.
+struct NgbGroup {
+    int lane, s, gshift; // lane of the wave, lane of the group, the group's first bit in a wave mask
+    unsigned *stack, *llist;
+    int64_t q;           // queue slot of the group's target
+    bool valid;          // q < ntargets
+    int sp;              // entries on the LIFO
+    bool overflow;       // the LIFO would not hold a step's children (walk_stepk)
+};
+
+// Group set-up for blocks of 256 threads (32 targets): s_stack / s_llist are the kernel's __shared__ unsigned[4 * 8 * SPH_STK] and
+// [4 * 8 * SPH_LCAP].  A group with a target starts with the root on its LIFO.
+__device__ __forceinline__ NgbGroup ngb_group(unsigned *s_stack, unsigned *s_llist, const int64_t ntargets)
+{
+    NgbGroup g;
+    g.lane = threadIdx.x & 63;
+    const int grp = g.lane >> 3, slot = (threadIdx.x >> 6) * 8 + grp;
+    g.s = g.lane & 7;
+    g.gshift = grp * 8;
+    g.stack = s_stack + slot * SPH_STK;
+    g.llist = s_llist + slot * SPH_LCAP;
+    g.q = (int64_t)blockIdx.x * 32 + slot;
+    g.valid = g.q < ntargets;
+    g.sp = 0;
+    g.overflow = false;
+    if(g.valid) {
+        if(g.s == 0)
+            g.stack[0] = (0u << 4) | 1u; // the root
+        g.sp = 1;
+    }
+    return g;
+}
+
+// The whole search of a group, in batches until the LIFO is empty.  The walk and the leaf work are separated in time (SPH_LCAP above):
+//   phase A  walk_stepk until the LIFO is empty or the list may not fit one more step (nl + 8 K <= SPH_LCAP before every step: a step
+//            lists at most 8 entries per child range).  A paused walk loses nothing: its pending ranges stay on the LIFO.
+//   phase B  one list entry per iteration, lane s <-> particle s of the entry: visit(record, tree slot, live), live = s < count.  The
+//            record of the NEXT entry is requested (fetch(tree slot)) before this one is visited: an iteration is a dependent LDS read ->
+//            gather -> test chain, and 4 waves per SIMD do not hide the gather's latency.  Lanes beyond an entry's count fetch its first
+//            particle (no exec-mask region around the load) and visit with live = false.
+//   between() runs after a batch when some group of the wave has ranges left; `radius` is read again by every step, so a caller may
+//            shrink it there (k_vdisp<false>).
+// Ends at once when a group's LIFO overflowed: the caller ends with ngb_overflowed().  (Both ends leave through the one exit below the outer
+// loop: with a `return` at each of them hipcc allocated k_density 58 and k_vdisp<false> 283 spilled registers instead of 0 and 40.)
+template <bool SYM, int K, bool MERGE, bool WRAP, class Fetch, class Visit, class Between>
+__device__ __forceinline__ void ngb_search(const TreeView &tv, const NodeGeo *__restrict__ sgeo, const double *__restrict__ shm, NgbGroup &g,
+                                           const double &radius, const double px, const double py, const double pz, Fetch &&fetch, Visit &&visit,
+                                           Between &&between)
+{
+    const int s = g.s;
+    for(;;) {
+        int nl = 0;
+        for(;;) {
+            const bool go = g.sp > 0 && nl + 8 * K <= SPH_LCAP;
+            if(ballot64(go) == 0)
+                break;
+            nl = walk_stepk<SYM, K, MERGE, WRAP>(tv, sgeo, shm, g.stack, g.sp, go, s, g.gshift, radius, px, py, pz, g.llist, nl, g.overflow);
+            if(ballot64(g.overflow) != 0)
+                break;
+        }
+        if(ballot64(g.overflow) != 0)
+            break;
+        unsigned e = (0 < nl) ? g.llist[0] : 0u;
+        int ps = (int)(e >> 4), pc = (int)(e & 15u);
+        auto rec = fetch(ps + (s < pc ? s : 0));
+        for(int it = 0;; it++) {
+            const bool has = it < nl;
+            if(ballot64(has) == 0)
+                break;
+            const unsigned e_n = (it + 1 < nl) ? g.llist[it + 1] : 0u;
+            const int ps_n = (int)(e_n >> 4), pc_n = (int)(e_n & 15u);
+            const auto rec_n = fetch(ps_n + (s < pc_n ? s : 0));
+            visit(rec, ps + s, s < pc);
+            rec = rec_n;
+            ps = ps_n;
+            pc = pc_n;
+        }
+        if(ballot64(g.sp > 0) == 0)
+            break;
+        between();
+    }
+}
+
+// The end of a search whose LIFO overflowed in some group of the wave: the wave flags `err` and the kernel returns without results.
+__device__ __forceinline__ bool ngb_overflowed(const NgbGroup &g, unsigned *__restrict__ err)
+{
+    if(ballot64(g.overflow) == 0)
+        return false;
+    if(g.lane == 0)
+        atomicExch(err, 1u);
+    return true;
+}
+
+// wave-aggregated append of `value` for the lanes with `flag`: one atomic per wave (same-address atomics serialise)
+__device__ __forceinline__ void wave_append(const bool flag, const int value, int *__restrict__ queue, unsigned *__restrict__ counter)
+{
+    const unsigned long long m = ballot64(flag);
+    if(m == 0)
+        return;
+    const int lane = threadIdx.x & 63;
+    const int leader = __ffsll((long long)m) - 1;
+    unsigned basepos = 0;
+    if(lane == leader)
+        basepos = atomicAdd(counter, (unsigned)__popcll(m));
+    basepos = __shfl(basepos, leader);
+    if(flag)
+        queue[basepos + __popcll(m & ((1ull << lane) - 1ull))] = value;
+}
+
+// pass statistics: the wave's sums of two per-lane counters to stats[0], stats[1], its number of lanes with `third` to stats[2]
+__device__ __forceinline__ void wave_stats(unsigned long long *__restrict__ stats, const unsigned n0, const unsigned n1, const bool third = false)
+{
+    unsigned long long c0 = n0, c1 = n1;
+    for(int off = 32; off > 0; off >>= 1) {
+        c0 += __shfl_down(c0, off);
+        c1 += __shfl_down(c1, off);
+    }
+    const unsigned long long m = ballot64(third);
+    if((threadIdx.x & 63) == 0 && stats) {
+        atomicAdd(&stats[0], c0);
+        atomicAdd(&stats[1], c1);
+        if(m != 0)
+            atomicAdd(&stats[2], (unsigned long long)__popcll(m));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The host side.  treewalk_do_hsml_loop, treewalk.c:1292-1364: passes over a shrinking queue until no target asks for another.  launch(queue,
+// n, redo) starts one pass of n targets that appends its unfinished targets to `redo` and counts them in *d_nredo; d_err (at most 7 words
+// behind d_nredo, read back with it) is the search's overflow flag.  Adds the passes and the targets they took to `iterations` and `targets`;
+// `lengths`, when given, gets the queue length of every pass.
+template <class Launch>
+inline void ngb_hsml_loop(int *qa, int *qb, unsigned nq, unsigned *d_nredo, const unsigned *d_err, const int maxiter, const char *who, hipStream_t st,
+                          int64_t &iterations, int64_t &targets, std::vector<int64_t> *lengths, Launch &&launch)
+{
+    const size_t nw = (size_t)(d_err - d_nredo) + 1;
+    MPG_CHECK(nw >= 2 && nw <= 8, "ngb_hsml_loop: the overflow flag does not follow the redo counter");
+    while(nq > 0) {
+        iterations++;
+        targets += nq;
+        if(lengths)
+            lengths->push_back(nq);
+        MPG_HIP(hipMemsetAsync(d_nredo, 0, sizeof(unsigned), st));
+        launch(qa, nq, qb);
+        MPG_HIP(hipGetLastError());
+        unsigned w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        MPG_HIP(hipMemcpyAsync(w, d_nredo, nw * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+        MPG_HIP(hipStreamSynchronize(st));
+        MPG_CHECK(w[nw - 1] == 0, std::string(who) + ": neighbour-search stack overflow (tree deeper than the walk supports)");
+        nq = w[0];
+        int *t = qa;
+        qa = qb;
+        qb = t;
+        if(nq > 0 && iterations > maxiter) // MAXITER, endrun(1155), treewalk.c:1361-1364
+            fail(__FILE__, __LINE__, std::string(who) + ": failed to converge for " + std::to_string(nq) + " particles");
+    }
+}
+
+// the end of a loop: its first `n` statistics words, after the check of the overflow flag
+inline void ngb_read_stats(const unsigned long long *d_stats, const int n, unsigned long long *out, const unsigned *d_err, const char *who,
+                           hipStream_t st)
+{
+    unsigned e = 0;
+    MPG_HIP(hipMemcpyAsync(out, d_stats, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipMemcpyAsync(&e, d_err, sizeof(e), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipStreamSynchronize(st));
+    MPG_CHECK(e == 0, std::string(who) + ": neighbour-search stack overflow (tree deeper than the walk supports)");
 }
 
 } // namespace mpg

@@ -219,7 +219,7 @@ __device__ __forceinline__ int cbuf_push(int *cbuf, const int head, int cnt, con
 // The end of a density pass for one target (the 8 lanes of its group hold partial sums): density_reduce + density_postprocess +
 // density_check_neighbours (density.c:374-409, 532-689), the append of an unfinished target to `redo`, the pass statistics.
 __device__ __forceinline__ void density_finish(const TreeView &tv, const SphView &A, const mpg_density_params &P, const DensityCtl &C, DensAcc &a,
-                                               const bool valid, const int s, const int lane, const int i, const int ty, const double hsml,
+                                               const bool valid, const int s, const int i, const int ty, const double hsml,
                                                int *__restrict__ redo, unsigned *__restrict__ nredo, unsigned long long *__restrict__ stats,
                                                const unsigned n_int, const unsigned n_cand)
 {
@@ -331,29 +331,9 @@ __device__ __forceinline__ void density_finish(const TreeView &tv, const SphView
                 A.dthsml[i] = (1.0 / NUMDIMS) * divvel * newh;
         }
     }
-    // wave-aggregated append of the unfinished targets (one atomic per wave)
-    {
-        const unsigned long long m = ballot64(notdone);
-        if(m != 0) {
-            unsigned basepos = 0;
-            const int leader = __ffsll((long long)m) - 1;
-            if(lane == leader)
-                basepos = atomicAdd(nredo, (unsigned)__popcll(m));
-            basepos = __shfl(basepos, leader);
-            if(notdone)
-                redo[basepos + __popcll(m & ((1ull << lane) - 1ull))] = i;
-        }
-    }
+    wave_append(notdone, i, redo, nredo); // the unfinished targets
     // statistics: successful distance tests (the reference's ninteractions) and candidates tested
-    unsigned long long c_int = n_int, c_cand = n_cand;
-    for(int off = 32; off > 0; off >>= 1) {
-        c_int += __shfl_down(c_int, off);
-        c_cand += __shfl_down(c_cand, off);
-    }
-    if(lane == 0 && stats) {
-        atomicAdd(&stats[0], c_int);
-        atomicAdd(&stats[1], c_cand);
-    }
+    wave_stats(stats, n_int, n_cand);
 }
 
 // One density pass over the current queue: treewalk_visit_nolist_ngbiter + density_ngbiter + density_reduce +
@@ -366,14 +346,12 @@ __global__ void __launch_bounds__(256, 4) k_density(const TreeView tv, const Sph
     __shared__ unsigned s_stack[4 * 8 * SPH_STK];
     __shared__ int s_cbuf[4 * 8 * SPH_CBUF];
     __shared__ unsigned s_llist[4 * 8 * SPH_LCAP];
-    const int lane = threadIdx.x & 63;
-    const int grp = lane >> 3, s = lane & 7, gshift = grp * 8;
-    unsigned *stack = s_stack + ((threadIdx.x >> 6) * 8 + grp) * SPH_STK;
-    int *cbuf = s_cbuf + ((threadIdx.x >> 6) * 8 + grp) * SPH_CBUF;
-    unsigned *llist = s_llist + ((threadIdx.x >> 6) * 8 + grp) * SPH_LCAP;
+    NgbGroup g = ngb_group(s_stack, s_llist, nqueue);
+    const int s = g.s, gshift = g.gshift;
+    int *cbuf = s_cbuf + ((threadIdx.x >> 6) * 8 + (g.lane >> 3)) * SPH_CBUF;
     int cnt = 0, head = 0; // survivors waiting in the group's ring buffer, its first slot (group-uniform)
-    const int64_t q = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + grp;
-    const bool valid = q < nqueue;
+    const int64_t q = g.q;
+    const bool valid = g.valid;
     unsigned n_int = 0, n_cand = 0;
     int i = 0, ty = 0;
     double px = 0, py = 0, pz = 0, hsml = 0;
@@ -400,48 +378,18 @@ __global__ void __launch_bounds__(256, 4) k_density(const TreeView tv, const Sph
     const double kvol = NORM_COEFF * p3(kern.H);
     const double h2 = hsml * hsml;
     DensAcc a;
-    int sp = 0;
-    if(valid) {
-        if(s == 0)
-            stack[0] = (0u << 4) | 1u; // the root
-        sp = 1;
-    }
-    bool overflow = false;
     // the search and the pair loops, with (WRAP) or without NEAREST(): see interior_wave, ngb_walk.h
     auto loops = [&](auto wrap_tag) {
     constexpr bool WRAP = decltype(wrap_tag)::value;
-    for(;;) {
-        // ---- phase A: walk; opened leaves go to the group's list
-        int nl = 0;
-        for(;;) {
-            const bool go = sp > 0 && nl + 8 * SPH_WALK_K <= SPH_LCAP;
-            if(ballot64(go) == 0)
-                break;
-            nl = walk_stepk<false, SPH_WALK_K, SPH_MERGE, WRAP>(tv, sgeo, nullptr, stack, sp, go, s, gshift, hsml, px, py, pz, llist, nl, overflow);
-            if(ballot64(overflow) != 0)
-                break;
-        }
-        if(ballot64(overflow) != 0)
-            break;
-        // ---- phase B: every group takes its next leaf; lane s <-> particle s
-        // (the candidate of the NEXT leaf is requested before this one is tested: an iteration is a dependent LDS read -> gather -> test ->
-        // LDS append chain, and 4 waves per SIMD do not hide the gather's latency.  Lanes beyond the leaf's count read its first particle.)
-        unsigned e = (0 < nl) ? llist[0] : 0u;
-        int ps = (int)(e >> 4), pc = (int)(e & 15u);
-        Src4 cand = tv.src[ps + (s < pc ? s : 0)];
-        for(int it = 0;; it++) {
-            const bool has = it < nl;
-            if(ballot64(has) == 0)
-                break;
-            const unsigned e_n = (it + 1 < nl) ? llist[it + 1] : 0u;
-            const int ps_n = (int)(e_n >> 4), pc_n = (int)(e_n & 15u);
-            const Src4 cand_n = tv.src[ps_n + (s < pc_n ? s : 0)];
+    ngb_search<false, SPH_WALK_K, SPH_MERGE, WRAP>(
+        tv, sgeo, nullptr, g, hsml, px, py, pz, [&](const int slot) { return tv.src[slot]; },
+        [&](const Src4 &cand, const int slot, const bool live) {
             bool keep = false;
-            if(s < pc) {
+            if(live) {
                 n_cand++;
                 keep = density_test<WRAP>(cand, px, py, pz, h2, kern.HH, tv.box, n_int);
             }
-            cnt = cbuf_push(cbuf, head, cnt, keep, ps + s, s, gshift);
+            cnt = cbuf_push(cbuf, head, cnt, keep, slot, s, gshift);
             if(ballot64(cnt >= SPH_TRIG) != 0) {
                 if(cnt >= 8) {
                     const int sidx = cbuf[(head + s) & (SPH_CBUF - 1)];
@@ -450,14 +398,9 @@ __global__ void __launch_bounds__(256, 4) k_density(const TreeView tv, const Sph
                     cnt -= 8;
                 }
             }
-            cand = cand_n;
-            ps = ps_n;
-            pc = pc_n;
-        }
-        if(ballot64(sp > 0) == 0)
-            break;
-    }
-    if(ballot64(overflow) != 0)
+        },
+        [] {});
+    if(ballot64(g.overflow) != 0)
         return;
     while(ballot64(cnt > 0) != 0) { // drain the survivor buffers
         if(s < cnt) {
@@ -472,12 +415,9 @@ __global__ void __launch_bounds__(256, 4) k_density(const TreeView tv, const Sph
         loops(std::false_type{});
     else
         loops(std::true_type{});
-    if(ballot64(overflow) != 0) {
-        if(lane == 0)
-            atomicExch(err, 1u);
+    if(ngb_overflowed(g, err))
         return;
-    }
-    density_finish(tv, A, P, C, a, valid, s, lane, i, ty, hsml, redo, nredo, stats, n_int, n_cand);
+    density_finish(tv, A, P, C, a, valid, s, i, ty, hsml, redo, nredo, stats, n_int, n_cand);
 }
 
 // marks the active particles (caller indices) in a byte map
@@ -507,16 +447,7 @@ __global__ void __launch_bounds__(256) k_queue_treeorder(int64_t npart, const in
     }
     const int ty = (act && A.type) ? (A.type[i] & 7) : 0;
     const bool work = act && (ty == 0 || (!gas_only && ty == 5)); // density_haswork (density.c:521-530) / hydro_haswork
-    // wave-aggregated append: one atomic per wave (same-address atomics serialise)
-    const unsigned long long m = ballot64(work);
-    unsigned basepos = 0;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)m) - 1;
-    if(work && lane == leader)
-        basepos = atomicAdd(nqueue, (unsigned)__popcll(m));
-    basepos = __shfl(basepos, leader < 0 ? 0 : leader);
-    if(work)
-        queue[basepos + __popcll(m & ((1ull << lane) - 1ull))] = i;
+    wave_append(work, i, queue, nqueue);
 }
 
 // The black holes are targets of the density loop (density_haswork, density.c:521-530) but no neighbours: the search takes gas only
@@ -532,15 +463,7 @@ __global__ void __launch_bounds__(256) k_queue_blackholes(int64_t n, const uint8
         C.NumNgb[i] = 0;
         C.Left[i] = 0;
     }
-    const unsigned long long m = ballot64(work);
-    unsigned basepos = 0;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)m) - 1;
-    if(work && lane == leader)
-        basepos = atomicAdd(nqueue, (unsigned)__popcll(m));
-    basepos = __shfl(basepos, leader < 0 ? 0 : leader);
-    if(work)
-        queue[basepos + __popcll(m & ((1ull << lane) - 1ull))] = (int)i;
+    wave_append(work, (int)i, queue, nqueue);
 }
 
 // hsml of the gas particles of the tree in tree order (negative: does not contribute), for force_tree hmax
@@ -741,7 +664,7 @@ __device__ __forceinline__ void hydro_eval(const Src4 s, const HydroSrc &o, cons
 
 // The end of the hydro loop for one target: hydro_reduce (assign) + hydro_postprocess (hydra.c:279-294, 514-528) and the statistics.
 __device__ __forceinline__ void hydro_finish(const SphView &A, const HydroCtl &C, HydroAcc &a, const HydroTarget &t, const bool valid, const int s,
-                                             const int lane, const int i, unsigned long long *__restrict__ stats, const unsigned n_cand,
+                                             const int i, unsigned long long *__restrict__ stats, const unsigned n_cand,
                                              const unsigned n_pair)
 {
     a.Acc0 = group_sum(a.Acc0);
@@ -758,18 +681,10 @@ __device__ __forceinline__ void hydro_finish(const SphView &A, const HydroCtl &C
         A.maxsignalvel[i] = a.MaxSignalVel;
         A.dtentropy_out[i] = a.DtEntropy * (SPH_GAMMA_MINUS1 / (C.hubble_a2 * pow(t.IDensity, SPH_GAMMA_MINUS1)));
     }
-    unsigned long long c_cand = n_cand, c_pair = n_pair;
-    for(int off = 32; off > 0; off >>= 1) {
-        c_cand += __shfl_down(c_cand, off);
-        c_pair += __shfl_down(c_pair, off);
-    }
-    if(lane == 0 && stats) {
-        atomicAdd(&stats[0], c_cand);
-        atomicAdd(&stats[1], c_pair);
-    }
+    wave_stats(stats, n_cand, n_pair);
 }
 
-// hydro_force loop: group-cooperative walk with the symmetric cull (see k_density)
+// hydro_force loop: the group-cooperative search of ngb_walk.h with the symmetric cull
 __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphView A, const mpg_sph_times T, const mpg_hydro_params HP,
                                                const HydroCtl C, const HydroSrc *__restrict__ hs, const double *__restrict__ hsml_t,
                                                const int *__restrict__ slot_of,
@@ -779,14 +694,12 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
     __shared__ unsigned s_stack[4 * 8 * SPH_STK];
     __shared__ int s_cbuf[4 * 8 * SPH_CBUF];
     __shared__ unsigned s_llist[4 * 8 * SPH_LCAP];
-    const int lane = threadIdx.x & 63;
-    const int grp = lane >> 3, s = lane & 7, gshift = grp * 8;
-    unsigned *stack = s_stack + ((threadIdx.x >> 6) * 8 + grp) * SPH_STK;
-    int *cbuf = s_cbuf + ((threadIdx.x >> 6) * 8 + grp) * SPH_CBUF;
-    unsigned *llist = s_llist + ((threadIdx.x >> 6) * 8 + grp) * SPH_LCAP;
+    NgbGroup g = ngb_group(s_stack, s_llist, ntargets); // the queue holds gas particles only (hydro_haswork)
+    const int s = g.s, gshift = g.gshift;
+    int *cbuf = s_cbuf + ((threadIdx.x >> 6) * 8 + (g.lane >> 3)) * SPH_CBUF;
     int cnt = 0, head = 0; // survivors waiting in the group's ring buffer, its first slot (group-uniform)
-    const int64_t q = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + grp;
-    const bool valid = q < ntargets; // the queue holds gas particles only (hydro_haswork)
+    const int64_t q = g.q;
+    const bool valid = g.valid;
     unsigned n_cand = 0, n_pair = 0;
     int i = 0;
     HydroTarget t{};
@@ -823,49 +736,22 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
     const DKernel kernel_i = kernel_init(t.me.hsml, C.ktype);
     HydroAcc a;
     a.MaxSignalVel = t.soundspeed_i;
-    int sp = 0;
-    if(valid) {
-        if(s == 0)
-            stack[0] = (0u << 4) | 1u; // the root
-        sp = 1;
-    }
-    bool overflow = false;
-    auto loops = [&](auto wrap_tag) { // (see k_density)
+    struct Cand { // what a pair test reads of a candidate
+        Src4 p;
+        double hsml;
+    };
+    auto loops = [&](auto wrap_tag) { // the search and the pair loops, with (WRAP) or without NEAREST(): see interior_wave, ngb_walk.h
     constexpr bool WRAP = decltype(wrap_tag)::value;
-    for(;;) {
-        // ---- phase A: walk; opened leaves go to the group's list
-        int nl = 0;
-        for(;;) {
-            const bool go = sp > 0 && nl + 8 * SPH_WALK_K <= SPH_LCAP;
-            if(ballot64(go) == 0)
-                break;
-            nl = walk_stepk<true, SPH_WALK_K, SPH_MERGE, WRAP>(tv, sgeo, shm, stack, sp, go, s, gshift, t.me.hsml, t.px, t.py, t.pz, llist, nl, overflow);
-            if(ballot64(overflow) != 0)
-                break;
-        }
-        if(ballot64(overflow) != 0)
-            break;
-        // ---- phase B: every group takes its next leaf; lane s <-> particle s
-        // (the candidate of the next leaf is requested before this one is tested: see k_density)
-        unsigned e = (0 < nl) ? llist[0] : 0u;
-        int ps = (int)(e >> 4), pc = (int)(e & 15u);
-        Src4 cand = tv.src[ps + (s < pc ? s : 0)];
-        double cand_h = hsml_t[ps + (s < pc ? s : 0)];
-        for(int it = 0;; it++) {
-            const bool has = it < nl;
-            if(ballot64(has) == 0)
-                break;
-            const unsigned e_n = (it + 1 < nl) ? llist[it + 1] : 0u;
-            const int ps_n = (int)(e_n >> 4), pc_n = (int)(e_n & 15u);
-            const Src4 cand_n = tv.src[ps_n + (s < pc_n ? s : 0)];
-            const double cand_hn = hsml_t[ps_n + (s < pc_n ? s : 0)];
+    ngb_search<true, SPH_WALK_K, SPH_MERGE, WRAP>(
+        tv, sgeo, shm, g, t.me.hsml, t.px, t.py, t.pz, [&](const int slot) { return Cand{tv.src[slot], hsml_t[slot]}; },
+        [&](const Cand &cand, const int slot, const bool live) {
             bool keep = false;
-            if(s < pc) {
+            if(live) {
                 n_cand++;
-                keep = hydro_test<WRAP>(cand, cand_h, t, kernel_i, C, tv.box);
+                keep = hydro_test<WRAP>(cand.p, cand.hsml, t, kernel_i, C, tv.box);
                 n_pair += keep ? 1u : 0u;
             }
-            cnt = cbuf_push(cbuf, head, cnt, keep, ps + s, s, gshift);
+            cnt = cbuf_push(cbuf, head, cnt, keep, slot, s, gshift);
             if(ballot64(cnt >= SPH_TRIG) != 0) {
                 if(cnt >= 8) {
                     const int sidx = cbuf[(head + s) & (SPH_CBUF - 1)];
@@ -874,15 +760,9 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
                     cnt -= 8;
                 }
             }
-            cand = cand_n;
-            cand_h = cand_hn;
-            ps = ps_n;
-            pc = pc_n;
-        }
-        if(ballot64(sp > 0) == 0)
-            break;
-    }
-    if(ballot64(overflow) != 0)
+        },
+        [] {});
+    if(ballot64(g.overflow) != 0)
         return;
     while(ballot64(cnt > 0) != 0) { // drain the survivor buffers
         if(s < cnt) {
@@ -898,12 +778,9 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
         loops(std::false_type{});
     else
         loops(std::true_type{});
-    if(ballot64(overflow) != 0) {
-        if(lane == 0)
-            atomicExch(err, 1u);
+    if(ngb_overflowed(g, err))
         return;
-    }
-    hydro_finish(A, C, a, t, valid, s, lane, i, stats, n_cand, n_pair);
+    hydro_finish(A, C, a, t, valid, s, i, stats, n_cand, n_pair);
 }
 
 __global__ void __launch_bounds__(256) k_slot_of(int64_t npart, const int *__restrict__ order, int *__restrict__ slot_of)
@@ -913,7 +790,7 @@ __global__ void __launch_bounds__(256) k_slot_of(int64_t npart, const int *__res
         slot_of[order[k]] = (int)k;
 }
 
-static inline unsigned nblk(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+constexpr int CTR_QUEUE = 0, CTR_REDO = 1, CTR_ERR = 7; // words of SphEngine::ctr: queue length, redo queue's length, search overflow flag
 
 static int kernel_index(int enumtype)
 {
@@ -972,34 +849,25 @@ void SphEngine::density(TreeBuilder &tree, const SphView &A, const mpg_sph_times
     const uint8_t *flags = mark_active(d_active, nact, n, st);
     if(tv.npart > 0 && nact > 0)
         hipLaunchKernelGGL(k_queue_treeorder<true>, dim3(nblk(tv.npart)), dim3(256), 0, st, tv.npart, tv.order, flags, A, C, tv.box, false,
-                           queue_a.p, ctr.p);
+                           queue_a.p, ctr.p + CTR_QUEUE);
     if(!bh_in_tree && A.type && n > 0 && nact > 0)
-        hipLaunchKernelGGL(k_queue_blackholes, dim3(nblk(n)), dim3(256), 0, st, n, flags, A, C, tv.box, queue_a.p, ctr.p);
+        hipLaunchKernelGGL(k_queue_blackholes, dim3(nblk(n)), dim3(256), 0, st, n, flags, A, C, tv.box, queue_a.p, ctr.p + CTR_QUEUE);
     unsigned nq = 0;
-    MPG_HIP(hipMemcpyAsync(&nq, ctr.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipMemcpyAsync(&nq, ctr.p + CTR_QUEUE, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     MPG_HIP(hipStreamSynchronize(st));
     last_iterations = 0;
     last_targets = 0;
-    int *qa = queue_a.p, *qb = queue_b.p;
-    while(nq > 0) {
-        last_iterations++;
-        last_targets += nq;
-        MPG_HIP(hipMemsetAsync(ctr.p + 1, 0, sizeof(unsigned), st));
-        hipLaunchKernelGGL(k_density, dim3(nblk(nq, 32)), dim3(256), 0, st, tv, A, T, P, C, aux.p, qa, (int64_t)nq, qb, ctr.p + 1, stats.p,
-                           ctr.p + 7);
+    unsigned *const nredo = ctr.p + CTR_REDO, *const err = ctr.p + CTR_ERR;
+    const auto pass = [&](const int *queue, const unsigned nqueue, int *redo) {
+        hipLaunchKernelGGL(k_density, dim3(nblk(nqueue, 32)), dim3(256), 0, st, tv, A, T, P, C, aux.p, queue, (int64_t)nqueue, redo, nredo, stats.p, err);
+    };
+    if(update_hsml)
+        ngb_hsml_loop(queue_a.p, queue_b.p, nq, nredo, err, 400, "density", st, last_iterations, last_targets, nullptr, pass);
+    else if(nq > 0) { // one pass at the caller's radii; nobody reads what it appends to the redo queue
+        last_iterations = 1;
+        last_targets = nq;
+        pass(queue_a.p, nq, queue_b.p);
         MPG_HIP(hipGetLastError());
-        if(!update_hsml)
-            break;
-        unsigned nr[7] = {0, 0, 0, 0, 0, 0, 0};
-        MPG_HIP(hipMemcpyAsync(nr, ctr.p + 1, sizeof(nr), hipMemcpyDeviceToHost, st));
-        MPG_HIP(hipStreamSynchronize(st));
-        MPG_CHECK(nr[6] == 0, "density: neighbour-search stack overflow (tree deeper than the walk supports)");
-        nq = nr[0];
-        int *t = qa;
-        qa = qb;
-        qb = t;
-        if(nq > 0 && last_iterations > 400) // MAXITER, treewalk.c:1362-1364
-            fail(__FILE__, __LINE__, "failed to converge density for " + std::to_string(nq) + " particles");
     }
     if(tv.npart > 0) {
         // update_tree_hmax_father for every finished particle (density.c:551-553) == leaf hmax from the final Hsml
@@ -1011,11 +879,7 @@ void SphEngine::density(TreeBuilder &tree, const SphView &A, const mpg_sph_times
         hmax_pending = true;
     }
     unsigned long long hs[2] = {0, 0};
-    unsigned e = 0;
-    MPG_HIP(hipMemcpyAsync(hs, stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
-    MPG_HIP(hipMemcpyAsync(&e, ctr.p + 7, sizeof(e), hipMemcpyDeviceToHost, st));
-    MPG_HIP(hipStreamSynchronize(st));
-    MPG_CHECK(e == 0, "density: neighbour-search stack overflow (tree deeper than the walk supports)");
+    ngb_read_stats(stats.p, 2, hs, err, "density", st);
     last_interactions = (int64_t)hs[0];
     last_candidates = (int64_t)hs[1];
 }
@@ -1090,20 +954,16 @@ void SphEngine::hydro_force(TreeBuilder &tree, const SphView &A, const mpg_sph_t
     unsigned nt = 0;
     if(tv.npart > 0 && (!d_active || nactive > 0)) {
         hipLaunchKernelGGL(k_queue_treeorder<false>, dim3(nblk(tv.npart)), dim3(256), 0, st, tv.npart, tv.order, flags, A, DensityCtl{}, tv.box, true,
-                           queue_a.p, ctr.p);
-        MPG_HIP(hipMemcpyAsync(&nt, ctr.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+                           queue_a.p, ctr.p + CTR_QUEUE);
+        MPG_HIP(hipMemcpyAsync(&nt, ctr.p + CTR_QUEUE, sizeof(unsigned), hipMemcpyDeviceToHost, st));
         MPG_HIP(hipStreamSynchronize(st));
     }
     if(nt > 0)
         hipLaunchKernelGGL(k_hydro, dim3(nblk(nt, 32)), dim3(256), 0, st, tv, A, T, HP, C, hsrc.p, hsml_t.p, slot_of.p, queue_a.p, (int64_t)nt, stats.p,
-                           ctr.p + 7);
+                           ctr.p + CTR_ERR);
     MPG_HIP(hipGetLastError());
     unsigned long long hs[2] = {0, 0};
-    unsigned e = 0;
-    MPG_HIP(hipMemcpyAsync(hs, stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
-    MPG_HIP(hipMemcpyAsync(&e, ctr.p + 7, sizeof(e), hipMemcpyDeviceToHost, st));
-    MPG_HIP(hipStreamSynchronize(st));
-    MPG_CHECK(e == 0, "hydro_force: neighbour-search stack overflow (tree deeper than the walk supports)");
+    ngb_read_stats(stats.p, 2, hs, ctr.p + CTR_ERR, "hydro_force", st);
     last_candidates = (int64_t)hs[0];
     last_interactions = (int64_t)hs[1];
 }

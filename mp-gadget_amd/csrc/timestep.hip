@@ -543,8 +543,6 @@ __global__ void __launch_bounds__(256) k_sublist_flags(const int *__restrict__ l
     keep[k] = ok ? 1 : 0;
 }
 
-static inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 void launch_timestep_gravity(int64_t n, const double *gacc, const double *gpm, double atime, double hubble, double errtol, double soft,
                              double *dloga, hipStream_t st)
 {

@@ -575,8 +575,6 @@ __global__ void __launch_bounds__(256) k_hsmax_leaf(int64_t nnodes, const NodeLi
     hsmax[j] = hm;
 }
 
-static inline int nblk(int64_t n, int b = 256) { return (int)((n + b - 1) / b); }
-
 void TreeBuilder::calc_search_boxes(hipStream_t st)
 {
     ensure_level_order(st);

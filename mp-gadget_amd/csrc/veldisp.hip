@@ -28,8 +28,6 @@
 
 namespace mpg {
 
-static inline int nblk(int64_t n, int b = 256) { return (int)((n + b - 1) / b); }
-
 #ifndef VD_K
 #define VD_K 2
 #endif
@@ -140,25 +138,11 @@ __global__ void __launch_bounds__(256) k_vd_predict(int64_t npart, const int *__
     velpred[k] = Aux4{v[0], v[1], v[2], 0.0};
 }
 
-// wave-aggregated append of `i` for the lanes with `work` (one atomic per wave)
-__device__ __forceinline__ void vd_append(const bool work, const int i, int *__restrict__ queue, unsigned *__restrict__ nqueue)
-{
-    const unsigned long long m = ballot64(work);
-    if(m == 0)
-        return;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)m) - 1;
-    unsigned basepos = 0;
-    if(lane == leader)
-        basepos = atomicAdd(nqueue, (unsigned)__popcll(m));
-    basepos = __shfl(basepos, leader);
-    if(work)
-        queue[basepos + __popcll(m & ((1ull << lane) - 1ull))] = i;
-}
-
 // The two queues of winds_find_vel_disp: the gas of winds_veldisp_haswork (veldisp.c:348-371; garbage and swallowed particles carry
-// type 7) with the initial state of :441-450, and the active black holes (blackhole_dynfric_haswork :53-57).  ctr[0] gas targets,
-// ctr[1] black-hole targets, ctr[2] black holes in the table, active or not (totbh, :409).
+// type 7) with the initial state of :441-450, and the active black holes (blackhole_dynfric_haswork :53-57).
+// Words of VdispEngine::ctr: gas targets, black-hole targets, black holes in the table, active or not (totbh, :409), the redo queue's
+// length, the search's overflow flag.
+constexpr int CTR_GAS = 0, CTR_BH = 1, CTR_TOTBH = 2, CTR_REDO = 3, CTR_ERR = 7;
 __global__ void __launch_bounds__(256) k_vd_queues(int64_t n, const uint8_t *__restrict__ flags, const VdispView A, const VdispScalars S,
                                                    const VdispState W, int *__restrict__ queue_gas, int *__restrict__ queue_bh,
                                                    unsigned *__restrict__ ctr)
@@ -185,18 +169,11 @@ __global__ void __launch_bounds__(256) k_vd_queues(int64_t n, const uint8_t *__r
     const bool bh = act && ty == 5;
     if(bh)
         W.niter[i] = 0;
-    vd_append(gas, (int)i, queue_gas, ctr);
-    vd_append(bh, (int)i, queue_bh, ctr + 1);
+    wave_append(gas, (int)i, queue_gas, ctr + CTR_GAS);
+    wave_append(bh, (int)i, queue_bh, ctr + CTR_BH);
     const unsigned long long mb = ballot64(inb && ty == 5);
     if(mb != 0 && (threadIdx.x & 63) == 0)
-        atomicAdd(ctr + 2, (unsigned)__popcll(mb));
-}
-
-__device__ __forceinline__ int group_sum_int(int v)
-{
-    for(int off = 1; off < 8; off <<= 1)
-        v += __shfl_xor(v, off);
-    return v;
+        atomicAdd(ctr + CTR_TOTBH, (unsigned)__popcll(mb));
 }
 
 // One pass over the current queue.  BH = false: treewalk_visit_nolist_ngbiter + wind_vdisp_ngbiter + wind_vdisp_postprocess for the
@@ -211,12 +188,10 @@ __global__ void __launch_bounds__(256, VD_OCC) k_vdisp(const TreeView tv, const 
     constexpr int NR = BH ? 1 : NWINDHSML;
     __shared__ unsigned s_stack[4 * 8 * SPH_STK];
     __shared__ unsigned s_llist[4 * 8 * SPH_LCAP];
-    const int lane = threadIdx.x & 63;
-    const int grp = lane >> 3, s = lane & 7, gshift = grp * 8;
-    unsigned *stack = s_stack + ((threadIdx.x >> 6) * 8 + grp) * SPH_STK;
-    unsigned *llist = s_llist + ((threadIdx.x >> 6) * 8 + grp) * SPH_LCAP;
-    const int64_t q = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + grp;
-    const bool valid = q < nqueue;
+    NgbGroup g = ngb_group(s_stack, s_llist, nqueue);
+    const int s = g.s;
+    const int64_t q = g.q;
+    const bool valid = g.valid;
     unsigned n_int = 0, n_cand = 0;
     int i = 0;
     double px = 0, py = 0, pz = 0;
@@ -255,42 +230,13 @@ __global__ void __launch_bounds__(256, VD_OCC) k_vdisp(const TreeView tv, const 
         cnt[j] = 0;
         V2[j] = V1x[j] = V1y[j] = V1z[j] = 0;
     }
-    int sp = 0;
-    if(valid) {
-        if(s == 0)
-            stack[0] = (0u << 4) | 1u; // the root
-        sp = 1;
-    }
-    bool overflow = false;
     // the search and the candidate loop, with (WRAP) or without NEAREST(): see interior_wave, ngb_walk.h
     auto loops = [&](auto wrap_tag) {
         constexpr bool WRAP = decltype(wrap_tag)::value;
-        for(;;) {
-            // ---- phase A: walk; opened leaves go to the group's list
-            int nl = 0;
-            for(;;) {
-                const bool go = sp > 0 && nl + 8 * VD_WALK_K <= SPH_LCAP;
-                if(ballot64(go) == 0)
-                    break;
-                nl = walk_stepk<false, VD_WALK_K, VD_MERGE, WRAP>(tv, tv.geoB, nullptr, stack, sp, go, s, gshift, hs, px, py, pz, llist, nl, overflow);
-                if(ballot64(overflow) != 0)
-                    break;
-            }
-            if(ballot64(overflow) != 0)
-                break;
-            // ---- phase B: every group takes its next list entry; lane s <-> particle s (the next entry's candidate is requested before
-            // this one is tested, as in k_density)
-            unsigned e = (0 < nl) ? llist[0] : 0u;
-            int ps = (int)(e >> 4), pc = (int)(e & 15u);
-            Src4 cand = tv.src[ps + (s < pc ? s : 0)];
-            for(int it = 0;; it++) {
-                const bool has = it < nl;
-                if(ballot64(has) == 0)
-                    break;
-                const unsigned e_n = (it + 1 < nl) ? llist[it + 1] : 0u;
-                const int ps_n = (int)(e_n >> 4), pc_n = (int)(e_n & 15u);
-                const Src4 cand_n = tv.src[ps_n + (s < pc_n ? s : 0)];
-                if(s < pc) {
+        ngb_search<false, VD_WALK_K, VD_MERGE, WRAP>(
+            tv, tv.geoB, nullptr, g, hs, px, py, pz, [&](const int slot) { return tv.src[slot]; },
+            [&](const Src4 &cand, const int slot, const bool live) {
+                if(live) {
                     n_cand++;
                     // the distance vector points to 'other': I.Pos - P[other].Pos (treewalk.c:1223-1233)
                     const double d0 = near_img<WRAP>(px - cand.x, tv.box, 1.0 / tv.box);
@@ -299,7 +245,7 @@ __global__ void __launch_bounds__(256, VD_OCC) k_vdisp(const TreeView tv, const 
                     const double r2 = d0 * d0 + d1 * d1 + d2 * d2;
                     if(!(r2 > h2)) {
                         n_int++;
-                        const Aux4 o = velpred[ps + s];
+                        const Aux4 o = velpred[slot];
                         double v0 = o.x - ivel[0], v1 = o.y - ivel[1], v2 = o.z - ivel[2];
                         if(!BH) { // the Hubble flow of the separation (veldisp.c:265)
                             v0 += S.hubble_a2 * d0;
@@ -319,32 +265,25 @@ __global__ void __launch_bounds__(256, VD_OCC) k_vdisp(const TreeView tv, const 
                         }
                     }
                 }
-                cand = cand_n;
-                ps = ps_n;
-                pc = pc_n;
-            }
-            if(ballot64(sp > 0) == 0)
-                break;
-            if(!BH) {
-                // between two batches: a partial count above 40 inside rad[j] means the complete one is too, so nothing beyond rad[j] can
-                // reach an entry that is read (the header's argument); the nodes already on the LIFO were kept by a larger radius
+            },
+            [&] {
+                if(!BH) {
+                    // between two batches: a partial count above 40 inside rad[j] means the complete one is too, so nothing beyond rad[j] can
+                    // reach an entry that is read (the header's argument); the nodes already on the LIFO were kept by a larger radius
 #pragma unroll
-                for(int j = NR - 1; j >= 0; j--)
-                    if(group_sum_int(cnt[j]) > NUMDMNGB && rad[j] < hs)
-                        hs = rad[j];
-                h2 = hs * hs;
-            }
-        }
+                    for(int j = NR - 1; j >= 0; j--)
+                        if(group_sum_int(cnt[j]) > NUMDMNGB && rad[j] < hs)
+                            hs = rad[j];
+                    h2 = hs * hs;
+                }
+            });
     };
     if(interior_wave(valid, px, py, pz, hs, tv.box))
         loops(std::false_type{});
     else
         loops(std::true_type{});
-    if(ballot64(overflow) != 0) {
-        if(lane == 0)
-            atomicExch(err, 1u);
+    if(ngb_overflowed(g, err))
         return;
-    }
     // sum over the 8 lanes of the group
     double num[NWINDHSML] = {0, 0, 0, 0, 0};
 #pragma unroll
@@ -404,31 +343,10 @@ __global__ void __launch_bounds__(256, VD_OCC) k_vdisp(const TreeView tv, const 
             }
         }
     }
-    if(!BH) { // wave-aggregated append of the unfinished targets (one atomic per wave)
-        const unsigned long long m = ballot64(notdone);
-        if(m != 0) {
-            unsigned basepos = 0;
-            const int leader = __ffsll((long long)m) - 1;
-            if(lane == leader)
-                basepos = atomicAdd(nredo, (unsigned)__popcll(m));
-            basepos = __shfl(basepos, leader);
-            if(notdone)
-                redo[basepos + __popcll(m & ((1ull << lane) - 1ull))] = i;
-        }
-    }
+    if(!BH)
+        wave_append(notdone, i, redo, nredo); // the unfinished targets
     // statistics: candidates inside the search radius, candidates tested, targets that ended through the tight bracket
-    unsigned long long c_int = n_int, c_cand = n_cand;
-    for(int off = 32; off > 0; off >>= 1) {
-        c_int += __shfl_down(c_int, off);
-        c_cand += __shfl_down(c_cand, off);
-    }
-    const unsigned long long mt = ballot64(tight);
-    if(lane == 0 && stats) {
-        atomicAdd(&stats[0], c_int);
-        atomicAdd(&stats[1], c_cand);
-        if(mt != 0)
-            atomicAdd(&stats[2], (unsigned long long)__popcll(mt));
-    }
+    wave_stats(stats, n_int, n_cand, tight);
 }
 
 bool VdispEngine::make_queues(const VdispView &A, const VdispScalars &S, const uint8_t *active_flags, int64_t n, hipStream_t st)
@@ -455,9 +373,9 @@ bool VdispEngine::make_queues(const VdispView &A, const VdispScalars &S, const u
     unsigned c[3] = {0, 0, 0};
     MPG_HIP(hipMemcpyAsync(c, ctr.p, sizeof(c), hipMemcpyDeviceToHost, st));
     MPG_HIP(hipStreamSynchronize(st));
-    ngas = c[0];
-    nbh = c[1];
-    nbh_exist = c[2];
+    ngas = c[CTR_GAS];
+    nbh = c[CTR_BH];
+    nbh_exist = c[CTR_TOTBH];
     last_iterations = last_targets = last_neighbours = last_candidates = last_tight = 0;
     queue_lengths.clear();
     return ngas > 0 || nbh_exist > 0; // veldisp.c:413
@@ -475,35 +393,16 @@ void VdispEngine::search(TreeBuilder &tree, const VdispView &A, const mpg_sph_ti
     // the black holes first (veldisp.c:419-421): one pass
     if(nbh > 0)
         hipLaunchKernelGGL(k_vdisp<true>, dim3(nblk(nbh, 32)), dim3(256), 0, st, tv, A, S, W, velpred.p, queue_bh.p, nbh, (int *)nullptr,
-                           (unsigned *)nullptr, stats.p, ctr.p + 7);
+                           (unsigned *)nullptr, stats.p, ctr.p + CTR_ERR);
     MPG_HIP(hipGetLastError());
-    unsigned nq = (unsigned)ngas;
-    int *qa = queue_a.p, *qb = queue_b.p;
-    while(nq > 0) { // treewalk_do_hsml_loop, treewalk.c:1292-1364
-        last_iterations++;
-        last_targets += nq;
-        queue_lengths.push_back(nq);
-        MPG_HIP(hipMemsetAsync(ctr.p + 3, 0, sizeof(unsigned), st));
-        hipLaunchKernelGGL(k_vdisp<false>, dim3(nblk(nq, 32)), dim3(256), 0, st, tv, A, S, W, velpred.p, qa, (int64_t)nq, qb, ctr.p + 3, stats.p,
-                           ctr.p + 7);
-        MPG_HIP(hipGetLastError());
-        unsigned nr[5] = {0, 0, 0, 0, 0}; // ctr[3] the redo queue's length ... ctr[7] the overflow flag
-        MPG_HIP(hipMemcpyAsync(nr, ctr.p + 3, sizeof(nr), hipMemcpyDeviceToHost, st));
-        MPG_HIP(hipStreamSynchronize(st));
-        MPG_CHECK(nr[4] == 0, "find_vel_disp: neighbour-search stack overflow (tree deeper than the walk supports)");
-        nq = nr[0];
-        int *t = qa;
-        qa = qb;
-        qb = t;
-        if(nq > 0 && last_iterations > VD_MAXITER) // endrun(1155), treewalk.c:1361-1363
-            fail(__FILE__, __LINE__, "failed to converge the DM velocity dispersion radius for " + std::to_string(nq) + " particles");
-    }
+    unsigned *const nredo = ctr.p + CTR_REDO, *const err = ctr.p + CTR_ERR;
+    ngb_hsml_loop(queue_a.p, queue_b.p, (unsigned)ngas, nredo, err, VD_MAXITER, "find_vel_disp", st, last_iterations, last_targets, &queue_lengths,
+                  [&](const int *queue, const unsigned nqueue, int *redo) {
+                      hipLaunchKernelGGL(k_vdisp<false>, dim3(nblk(nqueue, 32)), dim3(256), 0, st, tv, A, S, W, velpred.p, queue, (int64_t)nqueue, redo,
+                                         nredo, stats.p, err);
+                  });
     unsigned long long hs[3] = {0, 0, 0};
-    unsigned e = 0;
-    MPG_HIP(hipMemcpyAsync(hs, stats.p, sizeof(hs), hipMemcpyDeviceToHost, st));
-    MPG_HIP(hipMemcpyAsync(&e, ctr.p + 7, sizeof(e), hipMemcpyDeviceToHost, st));
-    MPG_HIP(hipStreamSynchronize(st));
-    MPG_CHECK(e == 0, "find_vel_disp: neighbour-search stack overflow (tree deeper than the walk supports)");
+    ngb_read_stats(stats.p, 3, hs, err, "find_vel_disp", st);
     last_neighbours = (int64_t)hs[0];
     last_candidates = (int64_t)hs[1];
     last_tight = (int64_t)hs[2];
