@@ -21,6 +21,7 @@
 // The library links neither MPI nor RCCL; the collectives are the caller's (mpg_comm).  All ordering is on the engine's stream;
 // a callback is entered with the stream idle.
 #include "engine_internal.h"
+#include "pm_cic.h"
 #include "peano_tables.h"
 #include <algorithm>
 #include <chrono>
@@ -43,20 +44,6 @@ struct alignas(16) RRow { // a PM result on the wire
 };
 static_assert(sizeof(PRow) == 32 && sizeof(RRow) == 32, "wire rows are 32 bytes");
 
-__device__ __forceinline__ int wrapi(int i, int n) { return i < 0 ? i + n : (i >= n ? i - n : i); }
-
-// slab owner(s) of a particle's CIC cloud: the planes floor(x / cellsize) and that + 1 (periodic), P planes per rank
-__device__ __forceinline__ void pm_owners(double x, double cellsize, int nmesh, int P, int &o0, int &o1)
-{
-    int ix = (int)floor(x / cellsize);
-    if((unsigned)ix >= (unsigned)nmesh) { // the base cell folds by any number of boxes, as fold() of pm.hip: the owner is a rank that exists
-        ix %= nmesh;
-        ix = ix < 0 ? ix + nmesh : ix;
-    }
-    o0 = ix / P;
-    o1 = wrapi(ix + 1, nmesh) / P;
-}
-
 // skip (may be null): garbage and swallowed particles take no part in the force (gravpm.c:176-179, forcetree.c:806): they go nowhere
 __global__ void __launch_bounds__(256) k_pm_mask(int64_t n, const double *__restrict__ pos, double cellsize, int nmesh, int P,
                                                  const unsigned char *__restrict__ skip, unsigned long long *__restrict__ mask)
@@ -65,7 +52,7 @@ __global__ void __launch_bounds__(256) k_pm_mask(int64_t n, const double *__rest
     if(i >= n)
         return;
     int o0, o1;
-    pm_owners(pos[3 * i], cellsize, nmesh, P, o0, o1);
+    mpg::pm_owners(pos[3 * i], cellsize, nmesh, P, o0, o1);
     mask[i] = (skip && skip[i]) ? 0ull : ((1ull << o0) | (1ull << o1));
 }
 
@@ -255,7 +242,7 @@ __global__ void __launch_bounds__(256) k_scatter_results(int64_t ns, const int *
         d++;
     const int64_t i = idx[k];
     int o0, o1;
-    pm_owners(pos[3 * i], cellsize, nmesh, P, o0, o1);
+    mpg::pm_owners(pos[3 * i], cellsize, nmesh, P, o0, o1);
     if(o0 != d)
         return;
     const RRow r = rows[k];

@@ -4,6 +4,7 @@
 #include "mpg_common.h"
 #include "tree_build.h"
 #include <rocfft/rocfft.h>
+#include <cmath>
 #include <vector>
 
 namespace mpg {
@@ -46,6 +47,13 @@ struct PMesh {
     DevBuf<double> ps_acc;               // Power[Nmesh], kk[Nmesh], Norm
     DevBuf<unsigned long long> ps_modes; // Nmodes[Nmesh]
     void ps_zero(hipStream_t st);
+    // constants of the potential transfer (gravpm.c:388-389)
+    double asmth2() const { return pow((2 * M_PI) * Asmth / nmesh, 2); }
+    double pot_factor() const { return -G / (M_PI * box); }
+    // the transfer stage on a Fourier mesh in either layout, whole or in its two parts (pm.hip)
+    enum { TR_MEASURE = 1, TR_APPLY = 2, TR_BOTH = 3 };
+    template <bool XLAST, bool FUSE, bool NU> void measure_spectrum(double *rho, int ny, int y0, unsigned grid, hipStream_t st);
+    template <bool XLAST, bool FUSE> void transfer_stage(int parts, double *rho, int ny, int y0, unsigned grid, hipStream_t st);
     size_t ps_lds_bytes() const { return (size_t)nmesh * 3 * sizeof(double); }
 
     // massive-neutrino linear response (MassiveNuLinRespOn, gravpm.c:72-79, 303-326, 418-446).  With nu_fn set the transfer becomes
@@ -123,6 +131,7 @@ struct PMesh {
     void slab_inverse_c(const double *recvB, double *ghost_send, hipStream_t st);
     // ghost_recv[5][Nmesh^2] = the next rank's first 3 planes, then the previous rank's last 2; forces by differencing the
     // potential, CIC readout for `nt` targets (caller indices) that lie in the slab
+    void slab_take_ghosts(const double *ghost_recv, hipStream_t st);
     void slab_readout_rows(const double *ghost_recv, int64_t nrows, const double *d_pos, double *d_gravpm, double *d_potential, hipStream_t st);
     void slab_readout(const double *ghost_recv, const int *targets, int64_t nt, const double *d_pos, double *d_gravpm, double *d_potential,
                       hipStream_t st);

@@ -9,6 +9,7 @@
 // PFFT (third-party, not vendored) is an unnormalised DFT; the real-to-complex / complex-to-real transforms of rocFFT are the same transform.
 // All kernels are HBM-streaming: per PM step ~ N*(28+128) + 5*3*2*R + 5*2*R + N*(24+256+32) bytes, R = 8*Nmesh^3.
 #include "pm.h"
+#include "pm_cic.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -24,36 +25,6 @@ namespace mpg {
             ::mpg::fail(__FILE__, __LINE__, std::string("rocFFT error ") + std::to_string((int)_r) + " in " #expr); \
     } while(0)
 
-__device__ __forceinline__ int wrap(int i, int n)
-{
-    // periodic wrap of petapm.c:903-918 by one box: for a folded base cell plus the CIC corner or a stencil offset (-2 .. n + 2)
-    i = (i >= n) ? i - n : i;
-    i = (i < 0) ? i + n : i;
-    return i;
-}
-
-__device__ __forceinline__ int fold(int i, int n)
-{
-    // the same wrap for a particle's BASE cell, by any number of boxes as the reference's while loops do (petapm.c:905-906, 917-918):
-    // a position outside [0, BoxSize] must not become an index outside the mesh.  Once per axis and particle, and the division only
-    // for a cell outside [0, n): particles inside the box pay a compare.  (The slab kernels use it axis by axis.)
-    if((unsigned)i >= (unsigned)n) {
-        i %= n;
-        i = (i < 0) ? i + n : i;
-    }
-    return i;
-}
-
-__device__ __forceinline__ void fold3(int ic[3], int n)
-{
-    // fold() of the three axes behind ONE branch (the single-mesh kernels of every PM step: three branches cost the read-out 4 %)
-    if(((unsigned)ic[0] >= (unsigned)n) | ((unsigned)ic[1] >= (unsigned)n) | ((unsigned)ic[2] >= (unsigned)n)) {
-#pragma unroll
-        for(int k = 0; k < 3; k++)
-            ic[k] = fold(ic[k], n);
-    }
-}
-
 // put_particle_to_mesh through pm_iterate_one (petapm.c:955-1020, :1138-1144)
 __global__ void __launch_bounds__(256) k_cic_deposit(int64_t n, const double *__restrict__ pos, const float *__restrict__ mass,
                                                      const uint8_t *__restrict__ active, double cellsize, int nmesh,
@@ -66,26 +37,38 @@ __global__ void __launch_bounds__(256) k_cic_deposit(int64_t n, const double *__
         return;
     int ic[3];
     double res[3];
+    cic_cell3(pos + 3 * i, cellsize, nmesh, ic, res);
+    const double m = (double)mass[i];
 #pragma unroll
-    for(int k = 0; k < 3; k++) {
-        const double tmp = pos[3 * i + k] / cellsize;
-        const double fl = floor(tmp);
-        ic[k] = (int)fl;
-        res[k] = tmp - fl;
-    }
-    fold3(ic, nmesh);
+    for(int c = 0; c < 8; c++)
+        unsafeAtomicAdd(&mesh[cic_index(c, ic, nmesh)], cic_weight(c, res, 1.0) * m);
+}
+
+// the same onto the x-planes [x0, x0 + P) of a slab: the part of the particle's cloud that falls on them.  x is looked at first:
+// every rank sees particles of which most touch none of its planes
+__global__ void __launch_bounds__(256) k_cic_deposit_slab(int64_t n, const double *__restrict__ pos, const float *__restrict__ mass,
+                                                          const uint8_t *__restrict__ active, double cellsize, int nmesh, int x0, int P,
+                                                          double *__restrict__ slab)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n)
+        return;
+    if(active && !active[i])
+        return;
+    int ic[3];
+    double res[3];
+    ic[0] = cic_cell(pos[3 * i], cellsize, nmesh, res[0]);
+    if(!in_slab(ic[0], x0, P) && !in_slab(wrap(ic[0] + 1, nmesh), x0, P))
+        return;
+#pragma unroll
+    for(int k = 1; k < 3; k++)
+        ic[k] = cic_cell(pos[3 * i + k], cellsize, nmesh, res[k]);
     const double m = (double)mass[i];
 #pragma unroll
     for(int c = 0; c < 8; c++) {
-        double w = 1.0;
-        size_t lin = 0;
-#pragma unroll
-        for(int k = 0; k < 3; k++) {
-            const int off = (c >> k) & 1;
-            lin = lin * (size_t)nmesh + (size_t)wrap(ic[k] + off, nmesh);
-            w *= off ? res[k] : (1 - res[k]);
-        }
-        unsafeAtomicAdd(&mesh[lin], w * m);
+        size_t lin;
+        if(cic_index_slab(c, ic, nmesh, x0, P, lin))
+            unsafeAtomicAdd(&slab[lin], cic_weight(c, res, 1.0) * m);
     }
 }
 
@@ -102,15 +85,9 @@ __global__ void __launch_bounds__(256) k_cell_keys(int64_t n, const double *__re
     if(i >= n)
         return;
     int ic[3];
-#pragma unroll
-    for(int k = 0; k < 3; k++)
-        ic[k] = (int)floor(pos[3 * i + k] / cellsize);
-    fold3(ic, nmesh);
-    unsigned long long lin = 0;
-#pragma unroll
-    for(int k = 0; k < 3; k++)
-        lin = lin * (unsigned long long)nmesh + (unsigned long long)ic[k];
-    keys[i] = (active && !active[i]) ? ~0ull : lin; // inactive particles sort to the end and are skipped
+    double res[3];
+    cic_cell3(pos + 3 * i, cellsize, nmesh, ic, res);
+    keys[i] = (active && !active[i]) ? ~0ull : (unsigned long long)cic_index(0, ic, nmesh); // inactive particles sort to the end and are skipped
     idx[i] = (int)i;
 }
 
@@ -132,23 +109,11 @@ __global__ void __launch_bounds__(256) k_cic_deposit_sorted(int64_t n, const uns
         if(key != ~0ull) {
             const int i = sidx[k];
             double res[3];
-#pragma unroll
-            for(int d = 0; d < 3; d++) {
-                const double tmp = pos[3 * (int64_t)i + d] / cellsize;
-                const double fl = floor(tmp);
-                ic[d] = (int)fl;
-                res[d] = tmp - fl;
-            }
-            fold3(ic, nmesh);
+            cic_cell3(pos + 3 * (int64_t)i, cellsize, nmesh, ic, res);
             const double m = (double)mass[i];
 #pragma unroll
-            for(int c = 0; c < 8; c++) {
-                double x = m;
-#pragma unroll
-                for(int d = 0; d < 3; d++)
-                    x *= ((c >> d) & 1) ? res[d] : (1 - res[d]);
-                w[c] = x;
-            }
+            for(int c = 0; c < 8; c++)
+                w[c] = cic_weight(c, res, m); // the mass first: the run sums below add weights that carry it
         }
     }
     // segmented inclusive scan over the lanes of the wave (segments = runs of equal keys)
@@ -172,14 +137,9 @@ __global__ void __launch_bounds__(256) k_cic_deposit_sorted(int64_t n, const uns
     if(tail && key != ~0ull) {
 #pragma unroll
         for(int c = 0; c < 8; c++) {
-            const int px = wrap(ic[0] + (c & 1), nmesh) - x0;
-            if(px < 0 || px >= P)
-                continue;
-            size_t lin = (size_t)px;
-#pragma unroll
-            for(int d = 1; d < 3; d++)
-                lin = lin * (size_t)nmesh + (size_t)wrap(ic[d] + ((c >> d) & 1), nmesh);
-            unsafeAtomicAdd(&mesh[lin], w[c]);
+            size_t lin;
+            if(cic_index_slab(c, ic, nmesh, x0, P, lin))
+                unsafeAtomicAdd(&mesh[lin], w[c]);
         }
     }
 }
@@ -194,10 +154,50 @@ __device__ __forceinline__ double sinc_unnormed(double x)
     return sin(x) / x;
 }
 
+// ---- the Fourier-space rules, once.  Cell ip of a Fourier mesh that holds ny rows of ky starting at y0 (ny = nmesh, y0 = 0 on one
+// GPU; a ky-slab in the slab-decomposed form): its indices and k^2 of the signed mode (petapm_mesh_to_k, petapm.c:81-84; kz in
+// [0, N/2]).  Layout [kx][ky local][kz]; XLAST: [ky local][kz][kx] (kx fastest: the slab form after its transpose).
+struct FourierCell {
+    int ix, iy, iz;
+    long long k2;
+};
+template <bool XLAST>
+__device__ __forceinline__ FourierCell fourier_cell(size_t ip, int nmesh, int ny, int y0)
+{
+    const int nz = nmesh / 2 + 1;
+    FourierCell c;
+    if(XLAST) {
+        c.ix = (int)(ip % nmesh);
+        const size_t j = ip / nmesh;
+        c.iz = (int)(j % nz);
+        c.iy = y0 + (int)(j / nz);
+    }
+    else {
+        c.iz = (int)(ip % nz);
+        const size_t t = ip / nz;
+        c.iy = y0 + (int)(t % ny);
+        c.ix = (int)(t / ny);
+    }
+    const int kx = c.ix <= nmesh / 2 ? c.ix : c.ix - nmesh;
+    const int ky = c.iy <= nmesh / 2 ? c.iy : c.iy - nmesh;
+    const int kz = c.iz;
+    c.k2 = (long long)kx * kx + (long long)ky * ky + (long long)kz * kz;
+    return c;
+}
+
+// what a k2 > 0 mode of the density is multiplied by to become the potential (gravpm.c:403-421): pot_factor * smth * f * f,
+// smth = exp(-k2 asmth2) / k2, f = prod 1/sinc^2.  (exp(-k2 asmth2) / k2 and the bin below from tables indexed by k2 - 2.4 MB of them
+// at Nmesh 512 - measured SLOWER than the exp and the log: 1.06 against 0.64 ms, the gathers miss)
+__device__ __forceinline__ double potential_fac(long long k2, double asmth2, double pot_factor, double f)
+{
+    const double smth = exp(-(double)k2 * asmth2) / (double)k2;
+    return pot_factor * smth * f * f;
+}
+
+// logarithmic bin of |k| (powerspectrum_add_mode, gravpm.c:331-347); a bin >= Nmesh is not counted
+__device__ __forceinline__ int logk_bin(long long k2, double binsperunit) { return (int)floor(binsperunit * log((double)k2) / 2.); }
+
 // potential_transfer, gravpm.c:383-454, swept as pm_apply_transfer_function does (petapm.c:1092-1132).
-// Layout here: [kx][ky][kz], kz in [0, N/2].  k index -> signed mode: petapm_mesh_to_k, petapm.c:81-84.
-// ny rows of ky starting at y0 are held (ny = nmesh, y0 = 0 on one GPU; a ky-slab in the slab-decomposed form).
-// XLAST: the array is [ky local][kz][kx] (kx fastest: the slab form after its transpose) instead of [kx][ky local][kz].
 template <bool XLAST>
 __global__ void __launch_bounds__(256) k_potential_transfer(int nmesh, int ny, int y0, double asmth2, double pot_factor,
                                                             const double *__restrict__ invsinc2, double2 *__restrict__ cplx)
@@ -207,33 +207,14 @@ __global__ void __launch_bounds__(256) k_potential_transfer(int nmesh, int ny, i
     const size_t ip = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(ip >= total)
         return;
-    int ix, iy, iz;
-    if(XLAST) {
-        ix = (int)(ip % nmesh);
-        const size_t j = ip / nmesh;
-        iz = (int)(j % nz);
-        iy = y0 + (int)(j / nz);
-    }
-    else {
-        iz = (int)(ip % nz);
-        const size_t t = ip / nz;
-        iy = y0 + (int)(t % ny);
-        ix = (int)(t / ny);
-    }
-    const int kx = ix <= nmesh / 2 ? ix : ix - nmesh;
-    const int ky = iy <= nmesh / 2 ? iy : iy - nmesh;
-    const int kz = iz;
-    const long long k2 = (long long)kx * kx + (long long)ky * ky + (long long)kz * kz;
+    const FourierCell c = fourier_cell<XLAST>(ip, nmesh, ny, y0);
     double2 v = cplx[ip];
-    if(k2 == 0) {
+    if(c.k2 == 0) {
         v.x = 0.0;
         v.y = 0.0;
     }
     else {
-        const double smth = exp(-(double)k2 * asmth2) / (double)k2;
-        // f = prod 1/sinc^2 ; fac = pot_factor * smth * f * f
-        const double f = invsinc2[ix] * invsinc2[iy] * invsinc2[iz];
-        const double fac = pot_factor * smth * f * f;
+        const double fac = potential_fac(c.k2, asmth2, pot_factor, invsinc2[c.ix] * invsinc2[c.iy] * invsinc2[c.iz]);
         v.x *= fac;
         v.y *= fac;
     }
@@ -307,23 +288,8 @@ __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y
     const size_t total = (size_t)nmesh * ny * nz;
     const double binsperunit = (nbins - 1) / log(sqrt(3.0) * nmesh / 2.0);
     for(size_t ip = (size_t)blockIdx.x * blockDim.x + threadIdx.x; ip < total; ip += (size_t)gridDim.x * blockDim.x) {
-        int ix, iy, iz;
-        if(XLAST) {
-            ix = (int)(ip % nmesh);
-            const size_t j = ip / nmesh;
-            iz = (int)(j % nz);
-            iy = y0 + (int)(j / nz);
-        }
-        else {
-            iz = (int)(ip % nz);
-            const size_t t = ip / nz;
-            iy = y0 + (int)(t % ny);
-            ix = (int)(t / ny);
-        }
-        const int kx = ix <= nmesh / 2 ? ix : ix - nmesh;
-        const int ky = iy <= nmesh / 2 ? iy : iy - nmesh;
-        const int kz = iz;
-        const long long k2 = (long long)kx * kx + (long long)ky * ky + (long long)kz * kz;
+        const FourierCell fc = fourier_cell<XLAST>(ip, nmesh, ny, y0);
+        const long long k2 = fc.k2;
         double2 v = cplx[ip];
         if(k2 == 0) {
             const double m0 = v.x * v.x + v.y * v.y;
@@ -334,7 +300,7 @@ __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y
         }
         int kint = 0;
         if(NU) { // the mode times nufac before it is measured (gravpm.c:418-436)
-            kint = (int)floor(binsperunit * log((double)k2) / 2.);
+            kint = logk_bin(k2, binsperunit);
             const double nufac = nu_factor(log(sqrt((double)k2) * nu.kscale), kint < nbins ? kint : nbins - 1, s_lk, s_rt, s_gs, nu.nonzero,
                                            nu.prefac);
             v.x *= nufac;
@@ -343,18 +309,16 @@ __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y
                 cplx[ip] = v;
         }
         const double m = v.x * v.x + v.y * v.y;
-        const double f = invsinc2[ix] * invsinc2[iy] * invsinc2[iz];
-        if(FUSE) { // (k_potential_transfer, same expressions in the same order.  exp(-k2 asmth2) / k2 and the bin from tables indexed by k2 -
-                   // 2.4 MB of them at Nmesh 512 - measured SLOWER than the exp and the log: 1.06 against 0.64 ms, the gathers miss)
-            const double smth = exp(-(double)k2 * asmth2) / (double)k2;
-            const double fac = pot_factor * smth * f * f;
+        const double f = invsinc2[fc.ix] * invsinc2[fc.iy] * invsinc2[fc.iz];
+        if(FUSE) { // (k_potential_transfer's factor)
+            const double fac = potential_fac(k2, asmth2, pot_factor, f);
             cplx[ip] = make_double2(v.x * fac, v.y * fac);
         }
         if(!NU)
-            kint = (int)floor(binsperunit * log((double)k2) / 2.);
+            kint = logk_bin(k2, binsperunit);
         if(kint >= nbins)
             continue;
-        const int w = (kz == 0 || kz == nmesh / 2) ? 1 : 2;
+        const int w = (fc.iz == 0 || fc.iz == nmesh / 2) ? 1 : 2;
         __hip_atomic_fetch_add(&s_pow[kint], w * m * f * f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_add(&s_kk[kint], w * sqrt((double)k2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_add(&s_n[kint], (unsigned long long)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -386,17 +350,12 @@ __global__ void __launch_bounds__(256) k_nu_correction(int nmesh, double2 *__res
     const size_t total = (size_t)nmesh * nmesh * nz;
     const double binsperunit = (nbins - 1) / log(sqrt(3.0) * nmesh / 2.0);
     for(size_t ip = (size_t)blockIdx.x * blockDim.x + threadIdx.x; ip < total; ip += (size_t)gridDim.x * blockDim.x) {
-        const int iz = (int)(ip % nz);
-        const size_t t = ip / nz;
-        const int iy = (int)(t % nmesh), ix = (int)(t / nmesh);
-        const int kx = ix <= nmesh / 2 ? ix : ix - nmesh;
-        const int ky = iy <= nmesh / 2 ? iy : iy - nmesh;
-        const long long k2 = (long long)kx * kx + (long long)ky * ky + (long long)iz * iz;
+        const long long k2 = fourier_cell<false>(ip, nmesh, nmesh, 0).k2;
         if(k2 == 0) {
             cplx[ip] = make_double2(0.0, 0.0);
             continue;
         }
-        const int kint = (int)floor(binsperunit * log((double)k2) / 2.);
+        const int kint = logk_bin(k2, binsperunit);
         const double f = nu_factor(log(sqrt((double)k2) * nu.kscale), kint < nbins ? kint : nbins - 1, s_lk, s_rt, s_gs, nu.nonzero, nu.prefac) - 1;
         double2 v = cplx[ip];
         v.x *= f;
@@ -419,31 +378,18 @@ __global__ void __launch_bounds__(256) k_force_transfer(int nmesh, int ny, int y
     if(ip >= total)
         return;
     double2 v = src[ip];
-    const size_t rowsz = (size_t)ny * nz;
-    if(XLAST) { // same layout in and out
-        if(axis >= 0) {
-            const int ix = (int)(ip % nmesh);
-            const size_t j = ip / nmesh;
-            const int iz = (int)(j % nz), iy = y0 + (int)(j / nz);
-            const double fac = difffac[axis == 0 ? ix : (axis == 1 ? iy : iz)];
-            const double t0 = -v.y * fac, t1 = v.x * fac;
-            v.x = t0;
-            v.y = t1;
-        }
-        dst[ip] = v;
-        return;
-    }
-    const int ix = (int)(ip / rowsz);
+    const FourierCell fc = fourier_cell<XLAST>(ip, nmesh, ny, y0);
     if(axis >= 0) {
-        const int iz = (int)(ip % nz);
-        const int iy = y0 + (int)((ip / nz) % ny);
-        const int ii = axis == 0 ? ix : (axis == 1 ? iy : iz);
-        const double fac = difffac[ii];
+        const double fac = difffac[axis == 0 ? fc.ix : (axis == 1 ? fc.iy : fc.iz)];
         const double t0 = -v.y * fac, t1 = v.x * fac;
         v.x = t0;
         v.y = t1;
     }
-    dst[((size_t)ix * xmul + xoff) * rowsz + (ip - (size_t)ix * rowsz)] = v;
+    const size_t rowsz = (size_t)ny * nz;
+    if(XLAST) // same layout in and out
+        dst[ip] = v;
+    else
+        dst[((size_t)fc.ix * xmul + xoff) * rowsz + (ip - (size_t)fc.ix * rowsz)] = v;
 }
 
 // readout_potential / readout_force_{x,y,z} through pm_iterate_one (gravpm.c:499-510).
@@ -459,27 +405,11 @@ __global__ void __launch_bounds__(256) k_cic_readout(int64_t n, const double *__
         return;
     int ic[3];
     double res[3];
-#pragma unroll
-    for(int k = 0; k < 3; k++) {
-        const double tmp = pos[3 * i + k] / cellsize;
-        const double fl = floor(tmp);
-        ic[k] = (int)fl;
-        res[k] = tmp - fl;
-    }
-    fold3(ic, nmesh);
+    cic_cell3(pos + 3 * i, cellsize, nmesh, ic, res);
     double acc = 0;
 #pragma unroll
-    for(int c = 0; c < 8; c++) {
-        double w = 1.0;
-        size_t lin = 0;
-#pragma unroll
-        for(int k = 0; k < 3; k++) {
-            const int off = (c >> k) & 1;
-            lin = lin * (size_t)nmesh + (size_t)wrap(ic[k] + off, nmesh);
-            w *= off ? res[k] : (1 - res[k]);
-        }
-        acc += w * mesh[lin];
-    }
+    for(int c = 0; c < 8; c++)
+        acc += cic_weight(c, res, 1.0) * mesh[cic_index(c, ic, nmesh)];
     if(comp < 3)
         out[3 * i + comp] = acc;
     else
@@ -512,47 +442,53 @@ __global__ void __launch_bounds__(256) k_cic_readout_stencil(int64_t n, const do
         return;
     if(active && !active[i]) // garbage / swallowed: outside every region (gravpm.c:176-179)
         return;
-    size_t wi[3][6]; // wrapped cell indices ic-2 .. ic+3 per axis, times the axis stride
-    double res[3];
+    size_t wi[3][6]; // the six rows per axis, times the axis stride
+    double res[3], a[4];
     const size_t stride[3] = {(size_t)nmesh * nmesh, (size_t)nmesh, 1};
     int ic[3];
+    cic_cell3(pos + 3 * i, cellsize, nmesh, ic, res);
 #pragma unroll
-    for(int k = 0; k < 3; k++) {
-        const double tmp = pos[3 * i + k] / cellsize;
-        const double fl = floor(tmp);
-        res[k] = tmp - fl;
-        ic[k] = (int)fl;
-    }
-    fold3(ic, nmesh);
-#pragma unroll
-    for(int k = 0; k < 3; k++) {
-#pragma unroll
-        for(int j = 0; j < 6; j++)
-            wi[k][j] = (size_t)wrap(ic[k] - 2 + j, nmesh) * stride[k];
-    }
-    const double c1 = 2.0 / 3.0, c2 = 1.0 / 12.0;
-    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-#pragma unroll
-    for(int cc = 0; cc < 8; cc++) { // corner order and weight products as in k_cic_readout: bit 0 -> x, bit 1 -> y, bit 2 -> z
-        const int ox = cc & 1, oy = (cc >> 1) & 1, oz = (cc >> 2) & 1;
-        double w = 1.0;
-        w *= ox ? res[0] : (1 - res[0]);
-        w *= oy ? res[1] : (1 - res[1]);
-        w *= oz ? res[2] : (1 - res[2]);
-        const size_t bx = wi[0][2 + ox], by = wi[1][2 + oy], bz = wi[2][2 + oz];
-        a0 += w * phi[bx + by + bz];
-        a1 += w * (-(c1 * (phi[wi[0][3 + ox] + by + bz] - phi[wi[0][1 + ox] + by + bz]) - c2 * (phi[wi[0][4 + ox] + by + bz] - phi[wi[0][0 + ox] + by + bz])) * scale);
-        a2 += w * (-(c1 * (phi[bx + wi[1][3 + oy] + bz] - phi[bx + wi[1][1 + oy] + bz]) - c2 * (phi[bx + wi[1][4 + oy] + bz] - phi[bx + wi[1][0 + oy] + bz])) * scale);
-        a3 += w * (-(c1 * (phi[bx + by + wi[2][3 + oz]] - phi[bx + by + wi[2][1 + oz]]) - c2 * (phi[bx + by + wi[2][4 + oz]] - phi[bx + by + wi[2][0 + oz]])) * scale);
-    }
+    for(int k = 0; k < 3; k++)
+        stencil_rows(ic[k], nmesh, stride[k], wi[k]);
+    cic_stencil_gather(wi, res, scale, phi, a);
     if(potential)
-        potential[i] += a0;
-    gravpm[3 * i + 0] = a1;
-    gravpm[3 * i + 1] = a2;
-    gravpm[3 * i + 2] = a3;
+        potential[i] += a[0];
+#pragma unroll
+    for(int k = 0; k < 3; k++)
+        gravpm[3 * i + k] = a[1 + k];
 }
 
-static inline unsigned nblk(size_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+// the same for a slab: potential and forces of the listed targets in one pass from the slab's potential, which is stored with two ghost
+// planes below plane 0 and planes P .. P+2 above (x is not wrapped: the neighbours' planes are there; y and z wrap)
+__global__ void __launch_bounds__(256) k_cic_readout_slab_stencil(int64_t nt, const int *__restrict__ targets, const double *__restrict__ pos,
+                                                                  double cellsize, int nmesh, int x0, int P, double scale,
+                                                                  const double *__restrict__ phi /* plane -2 first */, double *__restrict__ gravpm,
+                                                                  double *__restrict__ potential, unsigned *__restrict__ err)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(t >= nt)
+        return;
+    const int64_t i = targets ? targets[t] : t; // (no list: every row whose base cell lies in the slab is a target, the others are skipped)
+    size_t wi[3][6];
+    double res[3], a[4];
+    const size_t stride[3] = {(size_t)nmesh * nmesh, (size_t)nmesh, 1};
+    const int ix = cic_cell(pos[3 * i], cellsize, nmesh, res[0]);
+    if(!in_slab(ix, x0, P)) { // not this rank's slab: an error in a caller's target list
+        if(targets)
+            atomicExch(err, 1u);
+        return;
+    }
+    stencil_rows_ghost(ix - x0, stride[0], wi[0]);
+#pragma unroll
+    for(int k = 1; k < 3; k++)
+        stencil_rows(cic_cell(pos[3 * i + k], cellsize, nmesh, res[k]), nmesh, stride[k], wi[k]);
+    cic_stencil_gather(wi, res, scale, phi, a);
+    if(potential)
+        potential[i] += a[0];
+#pragma unroll
+    for(int k = 0; k < 3; k++)
+        gravpm[3 * i + k] = a[1 + k];
+}
 
 void PMesh::init(double BoxSize, double Asmth_, int Nmesh_, double G_, hipStream_t st)
 {
@@ -743,9 +679,6 @@ void PMesh::destroy()
     nmesh = 0;
 }
 
-__global__ void k_cic_deposit_slab(int64_t n, const double *__restrict__ pos, const float *__restrict__ mass, double cellsize, int nmesh, int x0,
-                                   int P, double *__restrict__ slab);
-
 // CIC deposit onto the x-planes [x0, x0 + P) of `mesh` (zeroed by the caller): plain atomics, or cell-sorted with wave-aggregated
 // atomics; the first call and every 64th time both forms on the set at hand and keep the faster one.
 void PMesh::deposit(int64_t n, const double *d_pos, const float *d_mass, const uint8_t *d_active, double *mesh, int x0, int P, DepositState &ds,
@@ -757,7 +690,7 @@ void PMesh::deposit(int64_t n, const double *d_pos, const float *d_mass, const u
         if(whole)
             hipLaunchKernelGGL(k_cic_deposit, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_mass, d_active, cellsize, nmesh, mesh);
         else
-            hipLaunchKernelGGL(k_cic_deposit_slab, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_mass, cellsize, nmesh, x0, P, mesh);
+            hipLaunchKernelGGL(k_cic_deposit_slab, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_mass, d_active, cellsize, nmesh, x0, P, mesh);
     };
     auto sorted = [&]() {
         dep_keys_a.reserve((size_t)n + 1);
@@ -809,6 +742,47 @@ void PMesh::deposit(int64_t n, const double *d_pos, const float *d_mass, const u
         plain();
 }
 
+// One k_power_spectrum pass over rho (ny rows of ky from y0 in the layout XLAST) with `grid` blocks.  Without NU it starts a
+// measurement and zeroes the accumulators; with NU it is the second one, whose accumulators and table nu_table has just made.
+template <bool XLAST, bool FUSE, bool NU>
+void PMesh::measure_spectrum(double *rho, int ny, int y0, unsigned grid, hipStream_t st)
+{
+    if(!NU)
+        ps_zero(st);
+    const NuArgs na = NU ? NuArgs{nu_tab.p, nu_guess.p, nu_nonzero, nu_prefac, nu_normfac, 2 * M_PI / nu_box_mpc} : NuArgs{};
+    hipLaunchKernelGGL((k_power_spectrum<XLAST, FUSE, NU>), dim3(grid), dim3(256), NU ? ps_lds_bytes_nu() : ps_lds_bytes(), st, nmesh, ny, y0,
+                       invsinc2.p, (double2 *)rho, ps_acc.p, ps_modes.p, FUSE ? asmth2() : 0.0, FUSE ? pot_factor() : 0.0, na);
+}
+
+// The transfer stage: rho, the density in Fourier space, becomes the potential.  Three cases -
+//   measure            P(k) of the field as deposited (measure_power), then the potential transfer;
+//   neutrino response  (nu_fn) that measurement, the host step (the raw sums fetched, nu_table), then every mode times nufac, measured
+//                      again, and the transfer (see pm.h);
+//   fused              (FUSE: MPG_PM_FUSE_PS unset or not 0, single mesh only) the last measurement and the transfer in one pass over rho
+// - in two parts around the host step: the slab form runs them apart (forward_b1, forward_b2), the caller sums the bins over the
+// ranks and runs nu_table between them.
+template <bool XLAST, bool FUSE>
+void PMesh::transfer_stage(int parts, double *rho, int ny, int y0, unsigned grid, hipStream_t st)
+{
+    if((parts & TR_MEASURE) && (nu_fn || (measure_power && !FUSE)))
+        measure_spectrum<XLAST, false, false>(rho, ny, y0, grid, st);
+    if(parts == TR_BOTH && nu_fn) {
+        double *acc;
+        unsigned long long *modes;
+        nu_fetch(st, &acc, &modes);
+        nu_table(acc, modes, st);
+    }
+    if(!(parts & TR_APPLY))
+        return;
+    if(nu_fn)
+        measure_spectrum<XLAST, FUSE, true>(rho, ny, y0, grid, st);
+    else if(FUSE && measure_power)
+        measure_spectrum<XLAST, FUSE, false>(rho, ny, y0, grid, st);
+    if(!FUSE || !(nu_fn || measure_power))
+        hipLaunchKernelGGL(k_potential_transfer<XLAST>, dim3(nblk((size_t)nmesh * ny * (nmesh / 2 + 1))), dim3(256), 0, st, nmesh, ny, y0, asmth2(),
+                           pot_factor(), invsinc2.p, (double2 *)rho);
+}
+
 double PMesh::plane_nu_correction(int64_t n, const double *d_pos, const float *d_mass, const uint8_t *d_active, mpg_nu_response_fn fn, void *ctx,
                                   double box_mpc, hipStream_t st)
 {
@@ -855,9 +829,7 @@ double PMesh::plane_nu_correction(int64_t n, const double *d_pos, const float *d
     if(n > 0)
         deposit(n, d_pos, d_mass, d_active, real.p, 0, nmesh, dep_plane, st, nullptr);
     plan_r2c.exec(real.p, rho_k.p, st);
-    ps_zero(st);
-    hipLaunchKernelGGL((k_power_spectrum<false, false>), dim3(2048), dim3(256), ps_lds_bytes(), st, nmesh, nmesh, 0, invsinc2.p, (double2 *)rho_k.p,
-                       ps_acc.p, ps_modes.p, 0.0, 0.0, NuArgs{});
+    measure_spectrum<false, false, false>(rho_k.p, nmesh, 0, 2048, st);
     double total_mass = 0;
     MPG_HIP(hipMemcpyAsync(&total_mass, rho_k.p, sizeof(double), hipMemcpyDeviceToHost, st));
     double *acc;
@@ -884,7 +856,14 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
     ensure_single();
     const size_t nreal = (size_t)nmesh * nmesh * nmesh;
     const size_t ncplx = (size_t)nmesh * nmesh * (nmesh / 2 + 1);
-    float t_fft = 0, t_tr = 0, t_ro = 0, t;
+    float t_fft = 0, t_tr = 0, t_ro = 0;
+    auto lap = [&](float &sum) { // the time since the last lap is added to `sum`
+        float t;
+        if(tm) {
+            tm->lap(st, &t);
+            sum += t;
+        }
+    };
     if(tm)
         tm->start(st);
     // pm_init_regions zeroes the mesh (petapm.c:932-952); deposit
@@ -894,67 +873,24 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
     if(tm)
         tm->lap(st, &tm->t.pm_deposit);
     plan_r2c.exec(real.p, rho_k.p, st);
-    if(tm) {
-        tm->lap(st, &t);
-        t_fft += t;
-    }
-    const double asmth2 = pow((2 * M_PI) * Asmth / nmesh, 2);
-    const double pot_factor = -G / (M_PI * box);
+    lap(t_fft);
     static const bool fuse_ps = !(getenv("MPG_PM_FUSE_PS") && getenv("MPG_PM_FUSE_PS")[0] == '0');
-    if(nu_fn) { // neutrino linear response: measure, host step, then nufac + measurement + transfer (see pm.h)
-        ps_zero(st);
-        hipLaunchKernelGGL((k_power_spectrum<false, false>), dim3(2048), dim3(256), ps_lds_bytes(), st, nmesh, nmesh, 0, invsinc2.p,
-                           (double2 *)rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0, NuArgs{});
-        double *acc;
-        unsigned long long *modes;
-        nu_fetch(st, &acc, &modes);
-        nu_table(acc, modes, st);
-        const NuArgs na{nu_tab.p, nu_guess.p, nu_nonzero, nu_prefac, nu_normfac, 2 * M_PI / nu_box_mpc};
-        if(fuse_ps)
-            hipLaunchKernelGGL((k_power_spectrum<false, true, true>), dim3(2048), dim3(256), ps_lds_bytes_nu(), st, nmesh, nmesh, 0, invsinc2.p,
-                               (double2 *)rho_k.p, ps_acc.p, ps_modes.p, asmth2, pot_factor, na);
-        else {
-            hipLaunchKernelGGL((k_power_spectrum<false, false, true>), dim3(2048), dim3(256), ps_lds_bytes_nu(), st, nmesh, nmesh, 0, invsinc2.p,
-                               (double2 *)rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0, na);
-            hipLaunchKernelGGL(k_potential_transfer<false>, dim3(nblk(ncplx)), dim3(256), 0, st, nmesh, nmesh, 0, asmth2, pot_factor, invsinc2.p,
-                               (double2 *)rho_k.p);
-        }
-    }
-    else if(measure_power && fuse_ps) { // P(k) and the potential transfer in one pass over rho_k (round 6)
-        ps_zero(st);
-        hipLaunchKernelGGL((k_power_spectrum<false, true>), dim3(2048), dim3(256), ps_lds_bytes(), st, nmesh, nmesh, 0, invsinc2.p, (double2 *)rho_k.p,
-                           ps_acc.p, ps_modes.p, asmth2, pot_factor);
-    }
-    else {
-        if(measure_power) {
-            ps_zero(st);
-            hipLaunchKernelGGL((k_power_spectrum<false, false>), dim3(2048), dim3(256), ps_lds_bytes(), st, nmesh, nmesh, 0, invsinc2.p,
-                               (double2 *)rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0);
-        }
-        hipLaunchKernelGGL(k_potential_transfer<false>, dim3(nblk(ncplx)), dim3(256), 0, st, nmesh, nmesh, 0, asmth2, pot_factor, invsinc2.p,
-                           (double2 *)rho_k.p);
-    }
-    if(tm) {
-        tm->lap(st, &t);
-        t_tr += t;
-    }
+    if(fuse_ps) // P(k) and the potential transfer in one pass over rho_k (round 6)
+        transfer_stage<false, true>(TR_BOTH, rho_k.p, nmesh, 0, 2048, st);
+    else
+        transfer_stage<false, false>(TR_BOTH, rho_k.p, nmesh, 0, 2048, st);
+    lap(t_tr);
     // functions[] = Potential, ForceX, ForceY, ForceZ (gravpm.c:32-39).  Default: one inverse transform (the potential), the
     // forces by differencing it in real space (k_cic_readout_stencil: the same operator as force_transfer); kspace_force restores
     // the reference's four inverse transforms.
     if(!kspace_force) {
         plan_c2r.exec(rho_k.p, real.p, st); // rho_k is consumed: it is not needed again
-        if(tm) {
-            tm->lap(st, &t);
-            t_fft += t;
-        }
+        lap(t_fft);
         // potential and forces in one read-out pass straight from the potential mesh (k_cic_readout_stencil)
         if(n > 0)
             hipLaunchKernelGGL(k_cic_readout_stencil, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_active, cellsize, nmesh, (double)nmesh / box,
                                (const double *)real.p, d_gravpm, d_potential);
-        if(tm) {
-            tm->lap(st, &t);
-            t_ro += t;
-        }
+        lap(t_ro);
     }
     else
         for(int f = 0; f < 4; f++) {
@@ -963,25 +899,16 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
             continue;
         hipLaunchKernelGGL(k_force_transfer<false>, dim3(nblk(ncplx)), dim3(256), 0, st, nmesh, nmesh, 0, axis, difffac.p,
                            (const double2 *)rho_k.p, (double2 *)work_k.p, 1, 0);
-        if(tm) {
-            tm->lap(st, &t);
-            t_tr += t;
-        }
+        lap(t_tr);
         plan_c2r.exec(work_k.p, real.p, st);
-        if(tm) {
-            tm->lap(st, &t);
-            t_fft += t;
-        }
+        lap(t_fft);
         if(n > 0) {
             if(f == 0)
                 hipLaunchKernelGGL(k_cic_readout, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_active, cellsize, nmesh, real.p, 3, d_potential);
             else
                 hipLaunchKernelGGL(k_cic_readout, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_active, cellsize, nmesh, real.p, axis, d_gravpm);
         }
-        if(tm) {
-            tm->lap(st, &t);
-            t_ro += t;
-        }
+        lap(t_ro);
     }
     MPG_HIP(hipGetLastError());
     if(tm && tm->enabled) {
@@ -1008,47 +935,6 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
 //   inverse_c : unpack to [x local][ky][kz] -> 2-D c2r -> the potential slab; its first 3 / last 2 planes out as ghosts [ghost_send]
 //   neighbour exchange (caller) -> readout: forces by differencing the potential during the CIC readout (k_cic_readout_slab_stencil).
 // rocFFT transforms are unnormalised like PFFT's; the three 1-D stages compose to the same 3-D DFT.
-
-__global__ void __launch_bounds__(256) k_cic_deposit_slab(int64_t n, const double *__restrict__ pos, const float *__restrict__ mass,
-                                                          double cellsize, int nmesh, int x0, int P, double *__restrict__ slab)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= n)
-        return;
-    const double tx = pos[3 * i + 0] / cellsize;
-    const double fx = floor(tx);
-    const int ix = fold((int)fx, nmesh);
-    const int p0 = ix - x0, p1 = wrap(ix + 1, nmesh) - x0; // planes relative to the slab
-    const bool in0 = p0 >= 0 && p0 < P, in1 = p1 >= 0 && p1 < P;
-    if(!in0 && !in1)
-        return;
-    const double rx = tx - fx;
-    int ic[2];
-    double res[2];
-#pragma unroll
-    for(int k = 0; k < 2; k++) {
-        const double tmp = pos[3 * i + 1 + k] / cellsize;
-        const double fl = floor(tmp);
-        ic[k] = fold((int)fl, nmesh);
-        res[k] = tmp - fl;
-    }
-    const double m = (double)mass[i];
-#pragma unroll
-    for(int c = 0; c < 8; c++) {
-        const int offx = c & 1; // same corner order and weight product order as k_cic_deposit
-        if(offx ? !in1 : !in0)
-            continue;
-        double w = offx ? rx : (1 - rx);
-        size_t lin = (size_t)(offx ? p1 : p0);
-#pragma unroll
-        for(int k = 0; k < 2; k++) {
-            const int off = (c >> (k + 1)) & 1;
-            lin = lin * (size_t)nmesh + (size_t)wrap(ic[k] + off, nmesh);
-            w *= off ? res[k] : (1 - res[k]);
-        }
-        unsafeAtomicAdd(&slab[lin], w * m);
-    }
-}
 
 // C[xl][y][z] -> sendA[d][xl][yl][z], d = y / Py
 __global__ void __launch_bounds__(256) k_slab_pack_a(int nmesh, int P, int Py, const double2 *__restrict__ C, double2 *__restrict__ sendA)
@@ -1186,30 +1072,19 @@ void PMesh::slab_forward_b1(double *recvA, hipStream_t st)
     const dim3 tgrid_f((unsigned)((S + 31) / 32), (unsigned)((nmesh + 31) / 32));
     hipLaunchKernelGGL(k_transpose, tgrid_f, dim3(256), 0, st, nmesh, (int)S, (const double2 *)recvA, S, (double2 *)slab.rho_k.p, (size_t)nmesh);
     slab.p1d_fwd.exec(slab.rho_k.p, slab.rho_k.p, st);
-    if(measure_power || nu_fn) { // this rank's ky rows: the caller sums the raw accumulators over the ranks (powerspectrum_sum's Allreduce)
-        ps_zero(st);
-        hipLaunchKernelGGL((k_power_spectrum<true, false>), dim3(1024), dim3(256), ps_lds_bytes(), st, nmesh, slab.Py, y0, invsinc2.p,
-                           (double2 *)slab.rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0, NuArgs{});
-    }
+    // this rank's ky rows: the caller sums the raw accumulators over the ranks (powerspectrum_sum's Allreduce)
+    transfer_stage<true, false>(TR_MEASURE, slab.rho_k.p, slab.Py, y0, 1024, st);
 }
 
 void PMesh::slab_forward_b2(double *sendB, hipStream_t st)
 {
     MPG_CHECK(slab.ready, "pm_slab: not initialised");
     const int nz = nmesh / 2 + 1;
-    const size_t ncplx = (size_t)nmesh * slab.Py * nz;
     const int y0 = slab.rank * slab.Py;
     const size_t S = (size_t)slab.Py * nz;
     const dim3 tgrid_b((unsigned)((nmesh + 31) / 32), (unsigned)((S + 31) / 32));
-    const double asmth2 = pow((2 * M_PI) * Asmth / nmesh, 2);
-    const double pot_factor = -G / (M_PI * box);
-    if(nu_fn) { // the table is up (nu_table, after the bins were summed over the ranks): nufac + this rank's bins of the total matter
-        const NuArgs na{nu_tab.p, nu_guess.p, nu_nonzero, nu_prefac, nu_normfac, 2 * M_PI / nu_box_mpc};
-        hipLaunchKernelGGL((k_power_spectrum<true, false, true>), dim3(1024), dim3(256), ps_lds_bytes_nu(), st, nmesh, slab.Py, y0, invsinc2.p,
-                           (double2 *)slab.rho_k.p, ps_acc.p, ps_modes.p, 0.0, 0.0, na);
-    }
-    hipLaunchKernelGGL(k_potential_transfer<true>, dim3(nblk(ncplx)), dim3(256), 0, st, nmesh, slab.Py, y0, asmth2, pot_factor, invsinc2.p,
-                       (double2 *)slab.rho_k.p);
+    // with the response the table is up (nu_table, after the bins were summed over the ranks): nufac + this rank's bins of the total matter
+    transfer_stage<true, false>(TR_APPLY, slab.rho_k.p, slab.Py, y0, 1024, st);
     // only the potential is transformed back: the forces are its real-space differences (k_cic_readout_slab_stencil), which also cuts
     // the inverse all-to-all to a quarter
     slab.p1d_inv.exec(slab.rho_k.p, slab.rho_k.p, st);
@@ -1233,63 +1108,12 @@ void PMesh::slab_inverse_c(const double *recvB, double *ghost_send, hipStream_t 
     MPG_HIP(hipGetLastError());
 }
 
-// k_cic_readout_stencil for a slab: potential and forces of the listed targets in one pass from the slab's potential, which is stored with
-// two ghost planes below plane 0 and planes P .. P+2 above (x is not wrapped: the neighbours' planes are there; y and z wrap)
-__global__ void __launch_bounds__(256) k_cic_readout_slab_stencil(int64_t nt, const int *__restrict__ targets, const double *__restrict__ pos,
-                                                                  double cellsize, int nmesh, int x0, int P, double scale,
-                                                                  const double *__restrict__ phi /* plane -2 first */, double *__restrict__ gravpm,
-                                                                  double *__restrict__ potential, unsigned *__restrict__ err)
+// ghost_recv: planes P, P+1, P+2 (the next rank's first three), then planes -2, -1 (the previous rank's last two)
+void PMesh::slab_take_ghosts(const double *ghost_recv, hipStream_t st)
 {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if(t >= nt)
-        return;
-    const int64_t i = targets ? targets[t] : t; // (no list: every row whose base cell lies in the slab is a target, the others are skipped)
-    size_t wi[3][6];
-    double res[3];
-    const size_t stride[3] = {(size_t)nmesh * nmesh, (size_t)nmesh, 1};
-    {
-        const double tmp = pos[3 * i] / cellsize;
-        const double fl = floor(tmp);
-        res[0] = tmp - fl;
-        const int px = fold((int)fl, nmesh) - x0;
-        if(px < 0 || px >= P) { // not this rank's slab: an error in a caller's target list
-            if(targets)
-                atomicExch(err, 1u);
-            return;
-        }
-#pragma unroll
-        for(int j = 0; j < 6; j++)
-            wi[0][j] = (size_t)(px + j) * stride[0]; // (px - 2 + j) + 2 ghost planes
-    }
-#pragma unroll
-    for(int k = 1; k < 3; k++) {
-        const double tmp = pos[3 * i + k] / cellsize;
-        const double fl = floor(tmp);
-        res[k] = tmp - fl;
-        const int c = fold((int)fl, nmesh);
-#pragma unroll
-        for(int j = 0; j < 6; j++)
-            wi[k][j] = (size_t)wrap(c - 2 + j, nmesh) * stride[k];
-    }
-    const double c1 = 2.0 / 3.0, c2 = 1.0 / 12.0;
-    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-#pragma unroll
-    for(int cc = 0; cc < 8; cc++) {
-        const int ox = cc & 1, oy = (cc >> 1) & 1, oz = (cc >> 2) & 1;
-        double w = ox ? res[0] : (1 - res[0]);
-        w *= oy ? res[1] : (1 - res[1]);
-        w *= oz ? res[2] : (1 - res[2]);
-        const size_t bx = wi[0][2 + ox], by = wi[1][2 + oy], bz = wi[2][2 + oz];
-        a0 += w * phi[bx + by + bz];
-        a1 += w * (-(c1 * (phi[wi[0][3 + ox] + by + bz] - phi[wi[0][1 + ox] + by + bz]) - c2 * (phi[wi[0][4 + ox] + by + bz] - phi[wi[0][0 + ox] + by + bz])) * scale);
-        a2 += w * (-(c1 * (phi[bx + wi[1][3 + oy] + bz] - phi[bx + wi[1][1 + oy] + bz]) - c2 * (phi[bx + wi[1][4 + oy] + bz] - phi[bx + wi[1][0 + oy] + bz])) * scale);
-        a3 += w * (-(c1 * (phi[bx + by + wi[2][3 + oz]] - phi[bx + by + wi[2][1 + oz]]) - c2 * (phi[bx + by + wi[2][4 + oz]] - phi[bx + by + wi[2][0 + oz]])) * scale);
-    }
-    if(potential)
-        potential[i] += a0;
-    gravpm[3 * i + 0] = a1;
-    gravpm[3 * i + 1] = a2;
-    gravpm[3 * i + 2] = a3;
+    const size_t plane = (size_t)nmesh * nmesh;
+    MPG_HIP(hipMemcpyAsync(slab.phi.p + (size_t)(2 + slab.P) * plane, ghost_recv, 3 * plane * sizeof(double), hipMemcpyDeviceToDevice, st));
+    MPG_HIP(hipMemcpyAsync(slab.phi.p, ghost_recv + 3 * plane, 2 * plane * sizeof(double), hipMemcpyDeviceToDevice, st));
 }
 
 // slab_readout for ALL rows of d_pos whose base cell lies in the slab (the rows a rank received for its slab: a particle whose CIC cloud
@@ -1297,10 +1121,7 @@ __global__ void __launch_bounds__(256) k_cic_readout_slab_stencil(int64_t nt, co
 void PMesh::slab_readout_rows(const double *ghost_recv, int64_t nrows, const double *d_pos, double *d_gravpm, double *d_potential, hipStream_t st)
 {
     MPG_CHECK(slab.ready, "pm_slab: not initialised");
-    const size_t plane = (size_t)nmesh * nmesh;
-    double *phi0 = slab.phi.p + 2 * plane;
-    MPG_HIP(hipMemcpyAsync(phi0 + (size_t)slab.P * plane, ghost_recv, 3 * plane * sizeof(double), hipMemcpyDeviceToDevice, st));
-    MPG_HIP(hipMemcpyAsync(slab.phi.p, ghost_recv + 3 * plane, 2 * plane * sizeof(double), hipMemcpyDeviceToDevice, st));
+    slab_take_ghosts(ghost_recv, st);
     if(nrows > 0)
         hipLaunchKernelGGL(k_cic_readout_slab_stencil, dim3(nblk(nrows)), dim3(256), 0, st, nrows, (const int *)nullptr, d_pos, cellsize, nmesh,
                            slab.rank * slab.P, slab.P, (double)nmesh / box, (const double *)slab.phi.p, d_gravpm, d_potential, (unsigned *)nullptr);
@@ -1311,14 +1132,10 @@ void PMesh::slab_readout(const double *ghost_recv, const int *targets, int64_t n
                          hipStream_t st)
 {
     MPG_CHECK(slab.ready, "pm_slab: not initialised");
-    const size_t plane = (size_t)nmesh * nmesh;
     DevBuf<unsigned> &flag = slab_err;
     flag.reserve(1);
     MPG_HIP(hipMemsetAsync(flag.p, 0, sizeof(unsigned), st));
-    double *phi0 = slab.phi.p + 2 * plane;
-    // ghost_recv: planes P, P+1, P+2 (the next rank's first three), then planes -2, -1 (the previous rank's last two)
-    MPG_HIP(hipMemcpyAsync(phi0 + (size_t)slab.P * plane, ghost_recv, 3 * plane * sizeof(double), hipMemcpyDeviceToDevice, st));
-    MPG_HIP(hipMemcpyAsync(slab.phi.p, ghost_recv + 3 * plane, 2 * plane * sizeof(double), hipMemcpyDeviceToDevice, st));
+    slab_take_ghosts(ghost_recv, st);
     if(nt > 0)
         hipLaunchKernelGGL(k_cic_readout_slab_stencil, dim3(nblk(nt)), dim3(256), 0, st, nt, targets, d_pos, cellsize, nmesh, slab.rank * slab.P,
                            slab.P, (double)nmesh / box, (const double *)slab.phi.p, d_gravpm, d_potential, flag.p);
