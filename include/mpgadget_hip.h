@@ -452,6 +452,81 @@ int mpg_cooling_get_stats(mpg_engine *eng, int64_t stats[6]);
 /* the evaluations of the network of every particle in the last mpg_dev_cooling (host array of n entries; -1: not treated) */
 int mpg_cooling_export(mpg_engine *eng, int64_t n, int32_t *evaluations);
 
+/* ---- return of stellar mass and metals to the gas: metal_return, libgadget/metal_return.c (run.c:613) ----------------------------
+ * For every active star (Type == 4, not garbage) with massgenerated >= 1e-3 (Mass + TotalMassReturned) (metals_haswork, :714-724):
+ *   stellar_density (:930-1006)  the radius loop of treewalk_do_hsml_loop over the GAS around the star, ten trial radii per pass (effhsml
+ *       :778-804) and ngb_narrow_down between the passes, until the kernel-weighted neighbour number Ngb = sum wk kernel_volume is within
+ *       GetNumNgb +- MaxNgbDeviation (the kernel and eta of mpg_set_densitypar, i.e. mpg_get_numngb) or Right - Left < 1e-4 Left.  Hsml
+ *       is assigned on every pass; StarVolumeSPH = sum (Mass_j / Density_j) (x wk with SPHWeighting) is the one of the trial radius
+ *       closest to the wanted number, as in the reference (:848).
+ *   the return walk (:637-709)  every gas particle with 0 < r < Hsml receives returnfraction = wk (Mass_j / Density_j) / StarVolumeSPH
+ *       (wk = 1 without SPHWeighting) of massgenerated, metalgenerated and speciesgenerated[9]; the star loses what was accepted, adds
+ *       it to TotalMassReturned and takes LastEnrichmentMyr = stellarage (:623-631).
+ * The yields of a stellar population over its step (metal_return_init, metal_yield: quadrature over yield tables) are the caller's: per
+ * star the engine receives massgenerated (priv->MassReturn), metalgenerated and speciesgenerated as metal_return_copy leaves them
+ * (:581-611: scaled by the initial mass, negatives clamped) and stellarage.
+ * THE CAP.  The reference lets a gas particle take a contribution iff P.Mass + thismass <= MaxGasMass on the RUNNING mass, under a
+ * spinlock per particle: when several contributions of one call would each fit alone but not together, which of them it accepts depends
+ * on the order its threads arrive in.  The engine tests every contribution against the mass at CALL ENTRY and sums the accepted ones per
+ * gas particle (Mass / Density is invariant under the reference's update, so every returnfraction is the reference's):
+ *     Mnew = M + dM, Metals_k = (Metals_k M + dMetals_k) / Mnew, Metallicity likewise, Density *= Mnew / M, Mass = (float)Mnew.
+ * That equals the reference's sequential update in exact arithmetic wherever the reference's own result does not depend on thread order.
+ * ERRORS: a target with Hsml <= 0 (the reference repairs it from a tree node the star is not in, :786-791: the caller repairs Hsml
+ * before the call), a target that ends with StarVolumeSPH == 0 (endrun(3)), more than 400 iterations (endrun(1155)).
+ * THE TREE: the call runs on the engine's CURRENT tree, which must contain the gas (it is the tree hydro_force has just used); it builds
+ * no tree and leaves this one in place - the gas tree carries no moment that depends on a mass.  The engine's tree-order copies of the
+ * masses are those of the last build: the next tree build refreshes them.  With no target nothing is read beyond the queue pass, nothing
+ * is written and no tree is demanded.  Garbage and swallowed rows carry type 7 (as in every dev call); black holes in the tree are skipped.
+ * One rank only: there is no mpg_dist_* form. */
+typedef struct mpg_metal_params {
+    int SPHWeighting;       /* MetalParams.SPHWeighting */
+    double MaxNgbDeviation; /* MetalParams.MaxNgbDeviation */
+    double MaxGasMass;      /* 4 * AvgGasMass (metal_return.c:535) */
+} mpg_metal_params;
+/* all arrays in particle order, n entries (x 9 where noted); every one is required except the two outputs */
+typedef struct mpg_metal_arrays {
+    const double *massgenerated;    /* stars: mass returned by the population this step (priv->MassReturn) */
+    const double *metalgenerated;   /* stars: InitialMass * total_z_yield, >= 0 */
+    const double *speciesgenerated; /* stars: [n][9] InitialMass * MetalSpeciesGenerated, >= 0 */
+    const double *stellarage;       /* stars: priv->StellarAges (Myr) */
+    float *mass;                    /* in/out P.Mass (float, as in the reference) of stars and gas */
+    double *hsml;                   /* in/out P.Hsml of the stars */
+    double *totalmassreturned;      /* in/out STARP.TotalMassReturned */
+    double *lastenrichment;         /* in/out STARP.LastEnrichmentMyr */
+    double *density;                /* in/out SphP.Density */
+    double *metallicity;            /* in/out SphP.Metallicity */
+    double *metals;                 /* in/out [n][9] SphP.Metals */
+    double *massreturned;           /* out, optional: what every target star actually returned */
+    double *starvolume;             /* out, optional: StarVolumeSPH of every target star */
+} mpg_metal_arrays;
+int mpg_set_metal_params(mpg_engine *eng, const mpg_metal_params *par);
+/* on the bound particles and the current tree; d_active NULL = all particles */
+int mpg_dev_metal_return(mpg_engine *eng, const mpg_metal_arrays *A, const int *d_active, int64_t nactive);
+/* host form: `pv` supplies Pos / Mass / Type / flags and receives the new Mass (A->mass is not read); the other members of `A` are HOST
+ * arrays in particle order.  The gas tree is (re)built as mpg_density builds it, before the call knows whether it has a target: in this
+ * form a call without one still pays the build of the gas tree ("no tree is demanded" above holds for the dev and resident forms). */
+int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_metal_arrays *A, const int *ActiveParticle,
+                     int64_t NumActiveParticle);
+/* on a resident gas run (mpg_resident_sph_begin), on its current tree: Pos, Mass, Hsml and Density are the resident columns and are updated
+ * there (A->mass and A->density are not read); the new Mass is also written into the records of `pv`, which the end of the resident
+ * stretch does not fetch.  The metal columns and the per-star members of `A` (HOST arrays) travel.  The STARS' Hsml is read and written by
+ * this call alone, so A->hsml (HOST, optional) carries it both ways: its rows of type 4 replace the resident column's before the call (a
+ * caller's repair of Hsml == 0 arrives so) and the whole resident column comes back into it afterwards; NULL: the resident column as it is. */
+int mpg_resident_sph_metal_return(mpg_engine *eng, const mpg_particle_view *pv, const mpg_metal_arrays *A, const int *ActiveParticle,
+                                  int64_t NumActiveParticle);
+/* statistics of the last call: [0] iterations of the radius loop, [1] targets summed over the iterations, [2] gas candidates found inside
+ * the search radius (both walks), [3] candidates distance-tested, [4] contributions refused by the cap, [5] targets that ended through
+ * the tight bracket with a neighbour number outside the window */
+int mpg_metals_get_stats(mpg_engine *eng, int64_t stats[6]);
+/* device time of the last call (zeros when it had no target), in ms, from events on the engine's stream: [0] the radius loop (all iterations, with
+ * its read-backs), [1] the return walk with the clearing of its accumulators, [2] the apply pass */
+int mpg_metals_get_times(mpg_engine *eng, double ms[3]);
+/* the loop's per-target results of the last call into host arrays of n entries (each may be NULL): the trial radius the final sums were
+ * taken at, the passes the target took (-1: not a target), its final maxcmpte and `close`; and the queue length of the first
+ * queue_capacity iterations (0 beyond the last) */
+int mpg_metals_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iterations, int32_t *maxcmpte, int32_t *close, int64_t *queue_lengths,
+                      int64_t queue_capacity);
+
 /* ---- introspection (tests, bench roofline accounting) ----------------------------------------- */
 typedef struct mpg_tree_stats {
     int64_t NumParticles; /* particles in the tree */

@@ -1778,6 +1778,105 @@ int mpg_cooling_export(mpg_engine *eng, int64_t n, int32_t *evaluations)
     API_END
 }
 
+/* ------------------------------ stellar mass and metal return (metal_return.c) ------------------------------ */
+
+int mpg_set_metal_params(mpg_engine *eng, const mpg_metal_params *par)
+{
+    API_BEGIN
+    MPG_CHECK(eng && par, "null argument");
+    MPG_CHECK(par->MaxNgbDeviation >= 0 && par->MaxGasMass > 0, "metal parameters: MaxNgbDeviation >= 0 and MaxGasMass > 0 are required");
+    eng->metalpar = *par;
+    API_END
+}
+
+int mpg_dev_metal_return(mpg_engine *eng, const mpg_metal_arrays *A, const int *d_active, int64_t nactive)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A, "null argument");
+    MPG_CHECK(nactive >= 0, "metal_return: negative list length");
+    MPG_CHECK(A->massgenerated && A->metalgenerated && A->speciesgenerated && A->stellarage && A->mass && A->hsml && A->totalmassreturned &&
+                  A->lastenrichment && A->density && A->metallicity && A->metals,
+              "metal_return: every array but massreturned and starvolume is required");
+    MPG_CHECK(eng->d_pos || eng->n == 0, "metal_return: no particles bound");
+    MPG_CHECK(eng->metalpar.MaxGasMass > 0, "metal_return: no parameters (mpg_set_metal_params first)");
+    MPG_HIP(hipSetDevice(eng->device));
+    MetalView v{};
+    v.pos = eng->d_pos;
+    v.type = eng->d_type;
+    v.massgenerated = A->massgenerated;
+    v.metalgenerated = A->metalgenerated;
+    v.speciesgenerated = A->speciesgenerated;
+    v.stellarage = A->stellarage;
+    v.mass = A->mass;
+    v.hsml = A->hsml;
+    v.totalmassreturned = A->totalmassreturned;
+    v.lastenrichment = A->lastenrichment;
+    v.density = A->density;
+    v.metallicity = A->metallicity;
+    v.metals = A->metals;
+    v.massreturned = A->massreturned;
+    v.starvolume = A->starvolume;
+    MetalScalars S;
+    S.box = eng->box;
+    S.desnumngb = sph_desnumngb(eng->denspar); // GetNumNgb(GetDensityKernelType()), metal_return.c:960
+    S.maxdev = eng->metalpar.MaxNgbDeviation;
+    S.maxgasmass = eng->metalpar.MaxGasMass;
+    S.sphweight = eng->metalpar.SPHWeighting != 0;
+    S.ktype = kernel_index(eng->denspar.DensityKernelType);
+    const uint8_t *flags = eng->sph.mark_active(d_active, nactive, eng->n, eng->stream);
+    // no target: nothing further is read, nothing is written, no tree is demanded
+    if(eng->metals.make_queue(v, S, flags, eng->n, eng->stream) > 0) {
+        MPG_CHECK(eng->tree_allocated && (eng->tree_mask & 1) != 0, "metal_return: the current tree does not contain the gas (GASMASK)");
+        eng->metals.run(eng->tree, v, S, eng->n, eng->stream);
+    }
+    API_END
+}
+
+int mpg_metals_get_stats(mpg_engine *eng, int64_t stats[6])
+{
+    API_BEGIN
+    MPG_CHECK(eng && stats, "null argument");
+    stats[0] = eng->metals.last_iterations;
+    stats[1] = eng->metals.last_targets;
+    stats[2] = eng->metals.last_neighbours;
+    stats[3] = eng->metals.last_candidates;
+    stats[4] = eng->metals.last_refused;
+    stats[5] = eng->metals.last_tight;
+    API_END
+}
+
+int mpg_metals_get_times(mpg_engine *eng, double ms[3])
+{
+    API_BEGIN
+    MPG_CHECK(eng && ms, "null argument");
+    for(int k = 0; k < 3; k++)
+        ms[k] = eng->metals.last_ms[k];
+    API_END
+}
+
+int mpg_metals_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iterations, int32_t *maxcmpte, int32_t *close, int64_t *queue_lengths,
+                      int64_t queue_capacity)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    MetalsEngine &M = eng->metals;
+    MPG_CHECK(n == M.n_state, "mpg_metals_export: n is not the particle number of the last metal_return call");
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    if(radius && n > 0)
+        MPG_HIP(hipMemcpy(radius, M.evalradius.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if(iterations && n > 0)
+        MPG_HIP(hipMemcpy(iterations, M.niter.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(maxcmpte && n > 0)
+        MPG_HIP(hipMemcpy(maxcmpte, M.maxcmpte.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(close && n > 0)
+        MPG_HIP(hipMemcpy(close, M.close.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(queue_lengths)
+        for(int64_t k = 0; k < queue_capacity; k++)
+            queue_lengths[k] = k < (int64_t)M.queue_lengths.size() ? M.queue_lengths[k] : 0;
+    API_END
+}
+
 /* ------------------------------ introspection ------------------------------ */
 
 int mpg_tree_get_stats(mpg_engine *eng, mpg_tree_stats *st)

@@ -7,6 +7,7 @@
 #include "sph.h"
 #include "veldisp.h"
 #include "cooling.h"
+#include "metals.h"
 #include "timestep.h"
 #include "peano.h"
 #include "planes.h"
@@ -155,6 +156,11 @@ struct mpg_engine {
     CoolingEngine cooling;
     DevBuf<double> cl_stage[5];
     DevBuf<uint8_t> cl_stage_u8[2];
+    // stellar mass and metal return (metals.hip): parameters and the loop's state; the staging of its host forms (fields of mpg_metal_arrays)
+    mpg_metal_params metalpar{1, 2.0, 0.0};
+    MetalsEngine metals;
+    DevBuf<double> mt_stage[13];
+    HostBuf<float> mt_mass;
     void prefetch_join()
     {
         if(prefetch_thread.joinable())

@@ -937,3 +937,31 @@ int mpg_cooling(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, co
     MPG_CHECK(rc == 0, err);
     API_END
 }
+
+// metal_return for the listed particles of a host table: Mass is the records' column (staged with the table, written back into it), the
+// other arrays go through metal_stage / metal_unstage (host_table.h)
+int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_metal_arrays *A, const int *ActiveParticle,
+                     int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    const int64_t n = pv->n;
+    mpg_metal_arrays d{};
+    metal_stage(*A, d, eng->mt_stage, n, METAL_TABLE, eng->stream);
+    d.mass = eng->s_mass.p;
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    // the tree of the call: the gas tree as mpg_density builds it.  (Built before the dev call, which demands it only when it has a target;
+    // whether it has one is the device's knowledge, and a second queue pass here would cost what the build of a small tree costs.)
+    MPG_CALL(mpg_dev_force_tree_rebuild_mask(eng, 1 /* GASMASK */, 0));
+    MPG_CALL(mpg_dev_metal_return(eng, &d, d_act, NumActiveParticle));
+    metal_unstage(*A, d, n, METAL_TABLE, eng->stream);
+    if(eng->metals.ntargets > 0) {
+        eng->mt_mass.reserve((size_t)n + 1);
+        mass_to_records(*pv, eng->s_mass.p, eng->mt_mass.p, eng->stream);
+    }
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}
+

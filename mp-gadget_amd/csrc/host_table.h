@@ -1,5 +1,5 @@
 // host_table.h -- the marshalling layer of the host-pointer ("drop-in") forms: everything that reads or writes the caller's records
-// (mpg_particle_view) and host arrays (mpg_sph_arrays, mpg_veldisp_arrays, mpg_cooling_arrays).  Used by host_forms.hip, resident.hip and dist.hip; no
+// (mpg_particle_view) and host arrays (mpg_sph_arrays, mpg_veldisp_arrays, mpg_cooling_arrays, mpg_metal_arrays).  Used by host_forms.hip, resident.hip and dist.hip; no
 // engine state lives here.
 #pragma once
 #include "../../include/mpgadget_hip.h"
@@ -329,3 +329,84 @@ const CoolField COOL_FIELDS[COOL_NFIELDS] = {
     {offsetof(mpg_cooling_arrays, metallicity), 1, 4, false}, {offsetof(mpg_cooling_arrays, heiii_ionized), 0, 0, false},
     {offsetof(mpg_cooling_arrays, tb_hydro), 0, 1, false}};
 static_assert(sizeof(mpg_cooling_arrays) == COOL_NFIELDS * sizeof(void *), "COOL_FIELDS describes every member of mpg_cooling_arrays");
+
+// ... and of the stellar mass and metal return.  `mass` is the table's column in both host forms (P.Mass of the records), `hsml` and
+// `density` are resident columns on a resident gas run; everything else travels.
+enum MetalRole : unsigned {
+    METAL_IN = 1,        // read by the call
+    METAL_OUT = 2,       // comes back
+    METAL_OPTIONAL = 4,  // may be NULL
+    METAL_TABLE = 8,     // P.Mass: a column of the staged / resident table, never staged from `A`
+    METAL_SPH_ALIAS = 16 // resident gas run: aliases a column of the resident SPH arrays
+};
+struct MetalField {
+    const char *name;
+    size_t off; // of the member in mpg_metal_arrays
+    int width;  // doubles per particle
+    unsigned role;
+};
+#define MPG_METAL_FIELD(m, width, role) {#m, offsetof(mpg_metal_arrays, m), width, role}
+constexpr int METAL_NFIELDS = 13;
+constexpr int METAL_HSML_FIELD = 5; // index of `hsml` below (its staging buffer)
+const MetalField METAL_FIELDS[METAL_NFIELDS] = {
+    MPG_METAL_FIELD(massgenerated, 1, METAL_IN),
+    MPG_METAL_FIELD(metalgenerated, 1, METAL_IN),
+    MPG_METAL_FIELD(speciesgenerated, 9, METAL_IN),
+    MPG_METAL_FIELD(stellarage, 1, METAL_IN),
+    MPG_METAL_FIELD(mass, 0, METAL_TABLE),
+    MPG_METAL_FIELD(hsml, 1, METAL_IN | METAL_OUT | METAL_SPH_ALIAS),
+    MPG_METAL_FIELD(totalmassreturned, 1, METAL_IN | METAL_OUT),
+    MPG_METAL_FIELD(lastenrichment, 1, METAL_IN | METAL_OUT),
+    MPG_METAL_FIELD(density, 1, METAL_IN | METAL_OUT | METAL_SPH_ALIAS),
+    MPG_METAL_FIELD(metallicity, 1, METAL_IN | METAL_OUT),
+    MPG_METAL_FIELD(metals, 9, METAL_IN | METAL_OUT),
+    MPG_METAL_FIELD(massreturned, 1, METAL_OUT | METAL_OPTIONAL),
+    MPG_METAL_FIELD(starvolume, 1, METAL_OUT | METAL_OPTIONAL),
+};
+#undef MPG_METAL_FIELD
+static_assert(sizeof(mpg_metal_arrays) == METAL_NFIELDS * sizeof(void *), "METAL_FIELDS describes every member of mpg_metal_arrays");
+
+// The host arrays of `host` onto the device (stage[f], one buffer per field) and `dev` filled with the device pointers; fields with a
+// role in `skip` are left to the caller (dev keeps what it holds there).  A required array that is missing is an error.
+inline void metal_stage(const mpg_metal_arrays &host, mpg_metal_arrays &dev, mpg::DevBuf<double> *stage, int64_t n, unsigned skip, hipStream_t st)
+{
+    for(int f = 0; f < METAL_NFIELDS; f++) {
+        const MetalField &F = METAL_FIELDS[f];
+        if(F.role & skip)
+            continue;
+        void *h = field_get(host, F.off), *d = nullptr;
+        MPG_CHECK(h || (F.role & METAL_OPTIONAL), std::string("metal_return: the array ") + F.name + " is required");
+        if(h) {
+            const size_t bytes = (size_t)n * F.width * sizeof(double);
+            stage[f].reserve((size_t)n * F.width + 1);
+            d = stage[f].p;
+            // (the outputs go up too: the call writes the entries of its targets only, the others come back as they were)
+            MPG_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+        }
+        field_set(dev, F.off, d);
+    }
+}
+// ... and what the call wrote back into them (queued on st)
+inline void metal_unstage(const mpg_metal_arrays &host, const mpg_metal_arrays &dev, int64_t n, unsigned skip, hipStream_t st)
+{
+    for(int f = 0; f < METAL_NFIELDS; f++) {
+        const MetalField &F = METAL_FIELDS[f];
+        void *h = field_get(host, F.off);
+        if(h && (F.role & METAL_OUT) && !(F.role & skip))
+            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.width * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+}
+// the table's Mass column from the device into the records (`pinned`: n floats of pinned staging)
+inline void mass_to_records(const mpg_particle_view &V, const float *d_mass, float *pinned, hipStream_t st)
+{
+    const int64_t n = V.n;
+    if(n == 0)
+        return;
+    MPG_HIP(hipMemcpyAsync(pinned, d_mass, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipStreamSynchronize(st));
+    const HostTable T(V);
+    parallel_for(n, [=](int64_t lo, int64_t hi) {
+        for(int64_t i = lo; i < hi; i++)
+            *(float *)(T.rec(i) + T.V.off_mass) = pinned[i];
+    });
+}

@@ -1,5 +1,5 @@
 // resident.hip -- the host-pointer entry points on a device-RESIDENT particle table (mpg_resident_*): the table, a gas run's SPH arrays and
-// time bins, the integrator forwards, hierarchical gravity, planes and the velocity dispersion.
+// time bins, the integrator forwards, hierarchical gravity, planes, the velocity dispersion, the cooling and the metal return.
 #include "engine_internal.h"
 
 /* ---- device-resident drop-in mode ------------------------------------------------------------------------------------------
@@ -506,3 +506,40 @@ int mpg_resident_sph_cooling(mpg_engine *eng, const mpg_particle_view *pv, const
     MPG_CHECK(rc == 0, err);
     API_END
 }
+
+// metal_return on a resident gas run, on the run's current tree (the one hydro_force has just used): Mass, Hsml and Density are resident
+// columns; the new masses also go into the records, which mpg_resident_end does not fetch.  The STARS' Hsml belongs to this call alone (no
+// SPH loop reads or writes it): when A->hsml is given, its rows of type 4 replace the resident column's before the call - the caller's
+// repair of a zero Hsml arrives that way - and the whole column comes back into it afterwards.
+int mpg_resident_sph_metal_return(mpg_engine *eng, const mpg_particle_view *pv, const mpg_metal_arrays *A, const int *ActiveParticle,
+                                  int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A, "null argument");
+    resident_sph_check(eng, pv);
+    const int64_t n = pv->n;
+    const mpg_sph_arrays &r = eng->res_sph_dev;
+    mpg_metal_arrays d{};
+    metal_stage(*A, d, eng->mt_stage, n, METAL_TABLE | METAL_SPH_ALIAS, eng->stream);
+    d.mass = eng->s_mass.p;
+    d.hsml = r.hsml;
+    d.density = r.density;
+    if(A->hsml && n > 0) {
+        DevBuf<double> &up = eng->mt_stage[METAL_HSML_FIELD];
+        up.reserve((size_t)n + 1);
+        MPG_HIP(hipMemcpyAsync(up.p, A->hsml, (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        MetalsEngine::take_star_hsml(d.hsml, up.p, eng->s_type.p, n, eng->stream);
+    }
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    MPG_CALL(mpg_dev_metal_return(eng, &d, d_act, NumActiveParticle));
+    metal_unstage(*A, d, n, METAL_TABLE | METAL_SPH_ALIAS, eng->stream);
+    if(A->hsml && n > 0)
+        MPG_HIP(hipMemcpyAsync(A->hsml, d.hsml, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    if(eng->metals.ntargets > 0) {
+        eng->mt_mass.reserve((size_t)n + 1);
+        mass_to_records(*pv, eng->s_mass.p, eng->mt_mass.p, eng->stream);
+    }
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}
+

@@ -43,6 +43,7 @@ struct HydroCtl {
 };
 
 double sph_desnumngb(const mpg_density_params &P);
+int kernel_index(int enumtype); // enum DensityKernelType (1 cubic, 2 quintic, 4 quartic) -> KERNELS[] index; throws on anything else
 
 struct SphEngine {
     DevBuf<double> left, right, numngb, entvarpred, hsml_tree;

@@ -23,6 +23,7 @@
 // order with the reference's literal shrink; tests/test_veldisp_restated.py shows the restatement itself independent of the order.
 #include "veldisp.h"
 #include "ngb_walk.h"
+#include "ngb_narrow.h"
 #include <cmath>
 #include <type_traits>
 
@@ -49,78 +50,12 @@ __device__ __forceinline__ double vd_trial_radius(double left, double right, con
     return pow((1.0 * i + 1) / (1.0 * NWINDHSML + 1) * (rvol - lvol) + lvol, 1. / 3);
 }
 
-__device__ __forceinline__ double vd_pick(const double (&a)[NWINDHSML], const int k)
-{
-    return k == 0 ? a[0] : (k == 1 ? a[1] : (k == 2 ? a[2] : (k == 3 ? a[3] : a[4])));
-}
-
-// ngb_narrow_down, treewalk.c:1371-1434, for desnumngb = 40.  With maxcmpt == 1 the reference reads radius[1] and numNgb[1], which
-// nothing defines (:1418-1419), and then overwrites what it computed from them (:1421-1422): the defined outcome is
-// dngbdv = numNgb[0] / radius[0]^3.  The growth branch (:1400) uses the last two entries only when maxcmpt > 1.
+// ngb_narrow_down for the 5 radii and desnumngb = 40 of this loop: ngb_narrow.h
+__device__ __forceinline__ double vd_pick(const double (&a)[NWINDHSML], const int k) { return ngb_pick<NWINDHSML>(a, k); }
 __device__ __forceinline__ double vd_narrow_down(double &right, double &left, const double (&radius)[NWINDHSML], const double (&num)[NWINDHSML],
                                                  const int maxcmpt, const double box, int &closeidx)
 {
-    const double desnumngb = NUMDMNGB;
-    int close = 0;
-    double ngbdist = fabs(num[0] - desnumngb);
-#pragma unroll
-    for(int j = 1; j < NWINDHSML; j++) {
-        const double newdist = fabs(num[j] - desnumngb);
-        if(j < maxcmpt && newdist < ngbdist) {
-            ngbdist = newdist;
-            close = j;
-        }
-    }
-    closeidx = close;
-    bool stop = false;
-#pragma unroll
-    for(int j = 0; j < NWINDHSML; j++) {
-        if(j < maxcmpt && !stop) {
-            if(num[j] < desnumngb)
-                left = radius[j];
-            if(num[j] > desnumngb) {
-                right = radius[j];
-                stop = true;
-            }
-        }
-    }
-    double hsml = vd_pick(radius, close);
-    if(right > 0.99 * box) {
-        double dngbdv = 0;
-        const double nlast = vd_pick(num, maxcmpt - 1);
-        if(maxcmpt > 1) {
-            const double r1 = vd_pick(radius, maxcmpt - 1), r0 = vd_pick(radius, maxcmpt - 2);
-            if(r1 > r0)
-                dngbdv = (nlast - vd_pick(num, maxcmpt - 2)) / (pow(r1, 3) - pow(r0, 3));
-        }
-        double newhsml = 4 * hsml; // "Increase hsml by a maximum factor to avoid madness"
-        if(dngbdv > 0) {
-            const double dngb = desnumngb - nlast;
-            const double newvolume = pow(hsml, 3) + dngb / dngbdv;
-            if(pow(newvolume, 1. / 3) < newhsml)
-                newhsml = pow(newvolume, 1. / 3);
-        }
-        hsml = newhsml;
-    }
-    if(hsml > right)
-        hsml = right;
-    if(left == 0) { // extrapolate using volume, i.e. locally constant density
-        double dngbdv = 0;
-        if(maxcmpt > 1) {
-            if(radius[1] > radius[0])
-                dngbdv = (num[1] - num[0]) / (pow(radius[1], 3) - pow(radius[0], 3));
-        }
-        else if(radius[0] > 0)
-            dngbdv = num[0] / pow(radius[0], 3);
-        if(dngbdv > 0) {
-            const double dngb = desnumngb - num[0];
-            const double newvolume = pow(hsml, 3) + dngb / dngbdv;
-            hsml = pow(newvolume, 1. / 3);
-        }
-    }
-    if(hsml < left)
-        hsml = left;
-    return hsml;
+    return ngb_narrow_down<NWINDHSML>(right, left, radius, num, maxcmpt, NUMDMNGB, box, closeidx);
 }
 
 // DM_VelPred (density.c:106-112) of every particle of the DM tree, once per call, in tree order beside the positions

@@ -106,6 +106,20 @@ class VelDispParams(C.Structure):
     _fields_ = [("Time", C.c_double), ("hubble", C.c_double), ("ddrift", C.c_double), ("sfr_density_threshold", C.c_double)]
 
 
+METAL_ARRAY_FIELDS = ("massgenerated", "metalgenerated", "speciesgenerated", "stellarage", "mass", "hsml", "totalmassreturned", "lastenrichment",
+                      "density", "metallicity", "metals", "massreturned", "starvolume")
+
+
+class MetalArraysC(C.Structure):
+    """mpg_metal_arrays"""
+    _fields_ = [(k, C.c_void_p) for k in METAL_ARRAY_FIELDS]
+
+
+class MetalParams(C.Structure):
+    """mpg_metal_params"""
+    _fields_ = [("SPHWeighting", C.c_int), ("MaxNgbDeviation", C.c_double), ("MaxGasMass", C.c_double)]
+
+
 COOLING_ARRAY_FIELDS = ("density", "entropy", "ne", "sfr", "metallicity", "heiii_ionized", "tb_hydro")
 COOLING_BYTE_FIELDS = ("heiii_ionized", "tb_hydro")
 RECOMB_CEN92, RECOMB_VERNER96, RECOMB_BADNELL06 = 0, 1, 2      # enum RecombType, cooling_rates.h:10-14
@@ -1089,6 +1103,70 @@ class Engine:
         self._ck(self.lib.mpg_veldisp_export(self.h, C.c_int64(n), p(d["radius"]), p(d["iterations"]), p(d["numngb"]), p(d["maxcmpte"]),
                                              p(ql), C.c_int64(len(ql))))
         d["queue_lengths"] = [int(x) for x in ql[:self.veldisp_stats()["iterations"]]]
+        return d
+
+    # ------------------------------------------------------------------ stellar mass and metal return (metal_return, metal_return.c)
+    # `arrays` maps the field names of mpg_metal_arrays to device tensors (dev form) / contiguous numpy arrays (host forms); mass is float32,
+    # everything else float64.  The dev and resident forms run on the current tree, which must contain the gas.
+    def set_metal_params(self, SPHWeighting, MaxNgbDeviation, MaxGasMass):
+        p = MetalParams(int(SPHWeighting), MaxNgbDeviation, MaxGasMass)
+        self._ck(self.lib.mpg_set_metal_params(self.h, C.byref(p)))
+
+    def dev_metal_return(self, arrays, active=None):
+        a = MetalArraysC()
+        for k in METAL_ARRAY_FIELDS:
+            t = arrays.get(k)
+            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        nact = 0 if active is None else active.shape[0]
+        self._ck(self.lib.mpg_dev_metal_return(self.h, C.byref(a), _ptr(active), C.c_int64(nact)))
+
+    @staticmethod
+    def _metal_host_arrays(arrays, skip):
+        a = MetalArraysC()
+        for k in METAL_ARRAY_FIELDS:
+            t = None if k in skip else arrays.get(k)
+            if t is not None and (t.dtype != np.float64 or not t.flags["C_CONTIGUOUS"]):
+                raise EngineError("metal-return host array %s must be contiguous float64" % k)
+            setattr(a, k, None if t is None else t.ctypes.data)
+        return a
+
+    def metal_return(self, P, BoxSize, arrays, ActiveParticle=None):
+        """host form: Mass is the records' column (read from and written back into P)"""
+        v = self._view(P)
+        a = self._metal_host_arrays(arrays, ("mass",))
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_metal_return(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a),
+                                           None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+
+    def resident_sph_metal_return(self, P, arrays, ActiveParticle=None):
+        """on a resident gas run: Mass, Hsml and Density are resident columns; the other arrays (numpy float64) travel.  `hsml`, when
+        given, hands the stars' Hsml over and receives the resident column back"""
+        v = self._view(P)
+        a = self._metal_host_arrays(arrays, ("mass", "density"))
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_resident_sph_metal_return(self.h, C.byref(v), C.byref(a),
+                                                        None if act is None else act.ctypes.data_as(C.c_void_p),
+                                                        C.c_int64(0 if act is None else len(act))))
+
+    def metals_stats(self):
+        c = (C.c_int64 * 6)()
+        self._ck(self.lib.mpg_metals_get_stats(self.h, c))
+        return dict(iterations=c[0], targets=c[1], neighbours=c[2], candidates=c[3], refused=c[4], tight=c[5])
+
+    def metals_times(self):
+        """device time of the last call in ms: the radius loop, the return walk, the apply pass"""
+        c = (C.c_double * 3)()
+        self._ck(self.lib.mpg_metals_get_times(self.h, c))
+        return dict(loop_ms=c[0], scatter_ms=c[1], apply_ms=c[2])
+
+    def metals_export(self, n):
+        """per-particle results of the last call's radius loop (iterations -1: not a target) and the queue length of every iteration"""
+        d = dict(radius=np.zeros(n), iterations=np.zeros(n, np.int32), maxcmpte=np.zeros(n, np.int32), close=np.zeros(n, np.int32))
+        ql = np.zeros(max(self.metals_stats()["iterations"], 1), np.int64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.mpg_metals_export(self.h, C.c_int64(n), p(d["radius"]), p(d["iterations"]), p(d["maxcmpte"]), p(d["close"]),
+                                            p(ql), C.c_int64(len(ql))))
+        d["queue_lengths"] = [int(x) for x in ql[:self.metals_stats()["iterations"]]]
         return d
 
     # ------------------------------------------------------------------ radiative cooling (cooling_direct, sfr_eff.c:463-514)

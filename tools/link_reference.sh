@@ -13,7 +13,7 @@
 #   2. copy shim/*.c, shim/*.h and include/mpgadget_hip.h into <copy>/libgadget/;
 #   3. patch <copy>/libgadget/Makefile: drop gravpm.o gravshort-tree.o gravshort-pair.o gravity.o from GADGET_OBJS and add the shim
 #      objects; rename the five tree constructors in forcetree.o, the eight integrator entry points in timestep.o / drift.o and
-#      winds_find_vel_disp in veldisp.o and cooling_and_starformation in sfr_eff.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
+#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o and metal_return in metal_return.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
 #   4. add the two parameter hooks (set_densitypar, set_hydro_params), the accessors of mpg_shim.h and the
 #      mpg_shim_particles_changed() calls listed in INTEGRATION.md ("Where P[] is reordered") with sed;
 #   5. build the library of this repository, then `make` in the copy with LIBS += -L<repo>/mp-gadget_amd -lmpgadget_hip -lmpi.
@@ -22,12 +22,12 @@ REF=${1:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 WORK=${2:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 CHECK=${3:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
+SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
 SHIM_H="mpg_shim.h mpg_shim_epoch.h mpg_mpi_comm.h"
 REF_FILES="libgadget/Makefile libgadget/gravpm.c libgadget/gravshort-tree.c libgadget/gravshort-pair.c libgadget/gravity.c libgadget/forcetree.c
            libgadget/density.c libgadget/hydra.c libgadget/timestep.c libgadget/drift.c libgadget/timebinmgr.c libgadget/run.c libgadget/domain.c
            libgadget/exchange.c libgadget/fof.c libgadget/slotsmanager.c libgadget/veldisp.c libgadget/sfr_eff.c libgadget/cooling.c libgadget/cooling_rates.c
-           libgadget/cooling_uvfluc.c gadget/Makefile Makefile.rules Options.mk.example"
+           libgadget/cooling_uvfluc.c libgadget/metal_return.c gadget/Makefile Makefile.rules Options.mk.example"
 
 echo "== 0. inputs"
 for f in $REF_FILES; do test -f "$REF/$f" || { echo "missing in the reference checkout: $f"; exit 1; }; done
@@ -53,8 +53,13 @@ if [ "$CHECK" = "--check" ]; then
     MPIINC=${MPI_INCLUDE:-/opt/conda/include}
     printf '#include <stddef.h>\n#include <mpi.h>\ntypedef double pfft_complex[2];\ntypedef struct pfft_plan_s *pfft_plan;\n' > "$STUB/pfft.h"
     printf 'typedef struct gsl_interp gsl_interp;\ntypedef struct gsl_interp_accel gsl_interp_accel;\n' > "$STUB/gsl/gsl_interp.h"
+    # (metal_return.h, which metals-hip.c includes, names two more GSL types as pointer members: stand-ins for the shim files only - a
+    # reference file that includes <gsl/gsl_integration.h> calls GSL and is recognised below by the missing header)
+    mkdir -p "$STUB/shim/gsl"
+    printf 'typedef struct gsl_interp2d gsl_interp2d;\n' > "$STUB/shim/gsl/gsl_interp2d.h"
+    printf 'typedef struct gsl_integration_workspace gsl_integration_workspace;\n' > "$STUB/shim/gsl/gsl_integration.h"
     for f in $SHIM_C; do
-        gcc -std=gnu11 -fopenmp -fsyntax-only -Wall -Wextra -Werror -I "$STUB" -I "$MPIINC" -I "$T/libgadget" -I "$T" "$T/libgadget/$f" \
+        gcc -std=gnu11 -fopenmp -fsyntax-only -Wall -Wextra -Werror -I "$STUB" -I "$STUB/shim" -I "$MPIINC" -I "$T/libgadget" -I "$T" "$T/libgadget/$f" \
             || { echo "the shim file $f does not parse against this checkout"; exit 1; }
     done
 fi
@@ -63,7 +68,7 @@ echo "== 3. libgadget/Makefile"
 MK="$T/libgadget/Makefile"
 sed -i -e 's/\bgravshort-tree\.o gravshort-pair\.o hydra\.o/hydra.o/' -e 's/\bgravpm\.o powerspectrum\.o/powerspectrum.o/' \
        -e 's/\bpetapm\.o gravity\.o/petapm.o/' "$MK"
-sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
+sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
 cat >> "$MK" <<MKEOF
 
 # ---- MP-Gadget on libmpgadget_hip (tools/link_reference.sh)
@@ -73,6 +78,7 @@ CFLAGS += -DMPGADGET_HIP -I$ROOT/include
 .objs/drift.o: CFLAGS += -Ddrift_all_particles=cpu_drift_all_particles
 .objs/veldisp.o: CFLAGS += -Dwinds_find_vel_disp=cpu_winds_find_vel_disp
 .objs/sfr_eff.o: CFLAGS += -Dcooling_and_starformation=cpu_cooling_and_starformation
+.objs/metal_return.o: CFLAGS += -Dmetal_return=cpu_metal_return
 MKEOF
 
 echo "== 4. hooks in the reference sources (INTEGRATION.md lists them; each is one line)"
@@ -156,6 +162,10 @@ replace_once(T + "/libgadget/sfr_eff.c", "            else\n                cool
 replace_once(T + "/libgadget/sfr_eff.c", '    walltime_measure("/Cooling/Cooling");',
              '    { extern void mpg_shim_cooling_flush(double, double, const struct UVBG *); mpg_shim_cooling_flush(Time, hubble, &GlobalUVBG); }\n'
              '    walltime_measure("/Cooling/Cooling");')
+# the metal return (metals-hip.c): metal_yield is static and MetalParams file-static; a forwarding function and an accessor behind them
+append(T + "/libgadget/metal_return.c", "double mpg_shim_metal_yield(double dtmyrstart, double dtmyrend, double stellarmetal, struct MetalReturnPriv *priv, MyFloat *MetalYields, int tid, double masslow, double masshigh)\n"
+       "{\n    return metal_yield(dtmyrstart, dtmyrend, stellarmetal, priv->hub, &priv->interp, MetalYields, priv->imf_norm, priv->gsl_work[tid], masslow, masshigh);\n}\n"
+       "void mpg_shim_metal_params(int *SPHWeighting, double *MaxNgbDeviation)\n{\n    *SPHWeighting = MetalParams.SPHWeighting;\n    *MaxNgbDeviation = MetalParams.MaxNgbDeviation;\n}")
 # P[] is reordered / exchanged: the shim's upload cache must hear of it (the 64-record hash of mpg_shim_epoch.h is only a backstop)
 hook = "{ extern void mpg_shim_particles_changed(void); mpg_shim_particles_changed(); }"
 for path, func in (("/libgadget/domain.c", "domain_decompose_full"), ("/libgadget/domain.c", "domain_maintain"),
@@ -167,7 +177,8 @@ PYEOF
 
 if [ "$CHECK" = "--check" ]; then
     # the patched reference files and the renamed objects still parse (nothing is compiled to an object, linked or run); cooling_rates.c,
-    # which only gains one accessor line, calls GSL and cannot be parsed with the typedef-only stand-in
+    # which only gains one accessor line, and metal_return.c, which gains two functions, call GSL and cannot be parsed with the typedef-only
+    # stand-ins
     for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c sfr_eff.c cooling.c cooling_uvfluc.c; do
         extra=""
         case $f in
