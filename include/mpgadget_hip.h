@@ -527,6 +527,110 @@ int mpg_metals_get_times(mpg_engine *eng, double ms[3]);
 int mpg_metals_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iterations, int32_t *maxcmpte, int32_t *close, int64_t *queue_lengths,
                       int64_t queue_capacity);
 
+/* ---- black-hole accretion, mergers and feedback: blackhole(), libgadget/blackhole.c:215-370 (run.c:660) ----------------------------
+ * Everything of blackhole() between its dynamical-friction calls and its file output, for the active, not swallowed black holes
+ * (blackhole_haswork, :185-188), on the engine's CURRENT tree, which must hold gas AND black holes and carry the hmax moments of the Hsml
+ * passed here (the search is the symmetric one: a pair interacts inside max(Hsml_i, Hsml_j)):
+ *   the accretion walk (:471-649)  per target the kernel-weighted sums SmoothedEntropy, GasVel (SPH_VelPred), FeedbackWeightSum, MgasEnc
+ *       and `encounter`; every gas particle inside Hsml with table[ID_gas % size] < (BH_Mass - BHPartMass) wk / Density is marked for the
+ *       target, every black hole closer than 2 FORCE_SOFTENING / 2.8 that passes check_grav_bound (unless MergeGravBound == 0 or
+ *       repositioning is on) likewise when the target is eligible (larger ID than the marked one, or the marked one is inactive).  A mark
+ *       is the LARGEST ID + 1 over the candidates (64-bit atomic maximum), whatever the order of arrival.  For gas that is the
+ *       reference's result.  For black holes the reference compares the stored ID + 1 with the newcomer's ID (:548), so two candidate
+ *       swallowers with CONSECUTIVE IDs leave its result to the order its threads arrive in; the engine keeps the larger.
+ *   its post-process (:373-468)  Bondi Mdot with the Eddington cap, Mass += Mdot dtime, DragAccel (BH_DRAG 0 / 1 / 2), the bookkeeping of
+ *       the kinetic channel (KEflag, KineticFdbkEnergy).
+ *   the feedback walk (:746-902) for the targets that are not themselves marked: marked black holes and marked gas are swallowed
+ *       (Swallowed / IsGarbage in `flags`, SwallowID, SwallowTime, the swallower's sums of mass, momentum, BHP.Mass and CountProgs), the
+ *       unmarked gas inside Hsml gives minTimeBin and receives thermal energy or a kick.  Energy and kicks are summed per gas particle
+ *       with fp64 atomics; ONE apply pass per call turns the energy sum into entropy, u = min(u + sum e / Mass, u(5e8 K)) - in exact
+ *       arithmetic the reference's capped additions in any order, all additions being positive - and adds the velocity sum.
+ *   its post-process (:955-990)  BHP.Mass, the momentum-conserving velocity, the Mtrack / P.Mass rule, KineticFdbkEnergy reset.
+ * NOT CARRIED (an error return naming the setting; the shim keeps the CPU walks): BlackHoleFeedbackMethod with BH_FEEDBACK_OPTTHIN,
+ * BHFeedbackUseTcool == 2.  Dynamical friction and repositioning (bhdynfric.c) are not part of this call: DFAccel arrives as data.
+ * With no target nothing is read beyond the queue pass, nothing is written and no tree is demanded.  Garbage and swallowed rows carry
+ * type 7 (as in every dev call).  One rank only: there is no mpg_dist_* form. */
+typedef struct mpg_blackhole_params {
+    double BlackHoleAccretionFactor, BlackHoleFeedbackFactor, BlackHoleEddingtonFactor; /* struct BlackholeParams, blackhole.c:28-54 */
+    int BlackHoleFeedbackMethod; /* enum BlackHoleFeedbackMethod, blackhole.h:47-53: SPLINE 0x4, MASS 0x8, OPTTHIN 0x20 */
+    int BlackHoleKineticOn;
+    double BHKE_EddingtonThrFactor, BHKE_EddingtonMFactor, BHKE_EddingtonMPivot, BHKE_EddingtonMIndex, BHKE_EffRhoFactor, BHKE_EffCap,
+        BHKE_InjEnergyThr, BHKE_SfrCritOverDensity;
+    int MergeGravBound, BH_DRAG;
+    double SeedBHDynMass;
+    int BlackHoleRepositionEnabled; /* BHGetRepositionEnabled(): mergers skip check_grav_bound */
+    int WindDecouple;               /* HAS(wind_params.WindModel, WIND_DECOUPLE_SPH): gas with DelayTime > 0 is skipped */
+    int StarformationOn, BHFeedbackUseTcool;
+    double PhysDensThresh, OverDensThresh; /* sfr_params, for sfreff_on_eeqos (sfr_eff.c:535-551) */
+    double ForceSoftening;                 /* FORCE_SOFTENING(); <= 0: the engine's (mpg_force_softening) */
+    double GravInternal, HubbleParam, OmegaBaryon, Hubble; /* Cosmology */
+    double UnitTime_in_s, UnitVelocity_in_cm_per_s, uu_in_cgs; /* UnitSystem; uu_in_cgs = UnitEnergy_in_cgs / UnitMass_in_g */
+} mpg_blackhole_params;
+/* all arrays in particle order, n entries (x 3 where noted).  Slot members (SphP / BHP) are indexed by PARTICLE; entries of rows of other
+ * types are ignored.  Required unless marked optional. */
+typedef struct mpg_blackhole_arrays {
+    /* read */
+    const uint64_t *id;          /* P.ID */
+    const double *gacc;          /* [n][3] P.FullTreeGravAccel */
+    const double *gpm;           /* [n][3] P.GravPM */
+    const double *hydroacc;      /* [n][3] SphP.HydroAccel */
+    const uint8_t *tb_hydro;     /* P.TimeBinHydro */
+    const uint8_t *tb_grav;      /* P.TimeBinGravity */
+    const double *hsml;          /* P.Hsml of gas and black holes */
+    const double *density;       /* SphP.Density / BHP.Density */
+    const double *delaytime;     /* SphP.DelayTime */
+    const double *dfaccel;       /* [n][3] BHP.DFAccel */
+    const double *vdisp;         /* BHP.VDisp */
+    const uint8_t *active_hydro; /* optional: is_timebin_active(TimeBinHydro, Ti_drift) of the black holes; NULL: all active */
+    /* in / out */
+    float *mass;                 /* P.Mass (float, as in the reference) */
+    double *vel;                 /* [n][3] P.Vel */
+    double *entropy;             /* SphP.Entropy */
+    uint8_t *flags;              /* bit 0 IsGarbage, bit 1 Swallowed */
+    double *bh_mass;             /* BHP.Mass */
+    double *mtrack;              /* BHP.Mtrack */
+    double *kineticfdbkenergy;   /* BHP.KineticFdbkEnergy */
+    int32_t *countprogs;         /* BHP.CountProgs */
+    /* out: written for the targets (swallowid / swallowtime / encounter also for the black holes swallowed, bhheated for heated gas) */
+    double *mdot;                /* BHP.Mdot */
+    double *dragaccel;           /* [n][3] BHP.DragAccel */
+    int32_t *encounter;          /* BHP.encounter */
+    int32_t *mintimebin;         /* BHP.minTimeBin (targets of the feedback walk) */
+    uint64_t *swallowid;         /* BHP.SwallowID */
+    double *swallowtime;         /* BHP.SwallowTime */
+    uint8_t *bhheated;           /* P.BHHeated: set to 1, never cleared */
+    /* out, optional: the walks' private arrays (struct BHPriv), what collect_BH_info writes and the tests read */
+    double *feedbackweightsum, *bh_entropy, *gasvel /* [n][3] */, *mgasenc;
+    int32_t *keflag;
+    double *accreted_mass, *accreted_bhmass, *accreted_momentum /* [n][3] */;
+    uint64_t *sph_swallowid, *bh_swallowid; /* the marks of every gas particle / black hole of the tree (others 0) */
+} mpg_blackhole_arrays;
+/* the step's RandTable (set_random_numbers, run.c:582-584) as data: get_random_number(id) = table[id % size] (system.c:55-61).  Copied. */
+int mpg_set_random_table(mpg_engine *eng, const double *table, int64_t size);
+int mpg_set_blackhole_params(mpg_engine *eng, const mpg_blackhole_params *par);
+/* on the bound particles and the current tree; d_active NULL = all particles.  T supplies FgravkickB, gravkicks, hydrokicks, dloga_bin,
+ * atime and hubble.  An error when the tree lacks gas, black holes or hmax, and before mpg_set_random_table / mpg_set_blackhole_params. */
+int mpg_dev_blackhole(mpg_engine *eng, const mpg_blackhole_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive);
+/* host form: `pv` supplies Pos / Mass / Type / flags and receives the new Mass and flags (A->mass is not read); the members of `A` are
+ * HOST arrays in particle order, A->flags in / out like the records'.  The queue pass runs first: without a target no array travels; with
+ * one, the tree of gas and black holes and its hmax moments (from A->hsml) are built. */
+int mpg_blackhole(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_blackhole_arrays *A, const mpg_sph_times *T,
+                  const int *ActiveParticle, int64_t NumActiveParticle);
+/* on a resident gas run (mpg_resident_sph_begin): Pos, Mass, Vel, the accelerations (HydroAccel: the resident hydroacc_out), the time bins,
+ * Hsml, Density and Entropy are the resident columns and are updated in place (those members of `A` are not read); the type column takes 7
+ * for the rows swallowed; flags and the new Mass are also written into the records of `pv`.  Every other member of `A` (HOST arrays)
+ * travels, and only when the queue pass found a target.  When the call has a target and the current tree is not one of gas and black holes with hmax (find_vel_disp leaves the DM tree),
+ * that tree is built. */
+int mpg_resident_sph_blackhole(mpg_engine *eng, const mpg_particle_view *pv, const mpg_blackhole_arrays *A, const mpg_sph_times *T,
+                               const int *ActiveParticle, int64_t NumActiveParticle);
+/* statistics of the last call: [0] gas swallowed, [1] black holes swallowed, [2] candidates distance-tested and [3] neighbours found by the
+ * accretion walk, [4], [5] the same of the feedback walk, [6] targets of the accretion walk, [7] of the feedback walk */
+int mpg_blackhole_get_stats(mpg_engine *eng, int64_t stats[8]);
+/* device time of the last call (zeros when it had no target), in ms, from events on the engine's stream: [0] the accretion walk with its
+ * post-process, [1] the feedback walk with its post-process and the clearing of the accumulators, [2] the apply pass.  The queue pass of
+ * the feedback walk and the read-back of its length (a host round trip between [0] and [1]) are in none of the three. */
+int mpg_blackhole_get_times(mpg_engine *eng, double ms[3]);
+
 /* ---- introspection (tests, bench roofline accounting) ----------------------------------------- */
 typedef struct mpg_tree_stats {
     int64_t NumParticles; /* particles in the tree */

@@ -1877,6 +1877,106 @@ int mpg_metals_export(mpg_engine *eng, int64_t n, double *radius, int32_t *itera
     API_END
 }
 
+/* ------------------------------ black-hole accretion, mergers and feedback (blackhole.c) ------------------------------ */
+
+int mpg_set_random_table(mpg_engine *eng, const double *table, int64_t size)
+{
+    API_BEGIN
+    MPG_CHECK(eng && table && size > 0, "random table: a table of at least one entry is required");
+    MPG_HIP(hipSetDevice(eng->device));
+    eng->bh.set_random_table(table, size, eng->stream);
+    API_END
+}
+
+int mpg_set_blackhole_params(mpg_engine *eng, const mpg_blackhole_params *par)
+{
+    API_BEGIN
+    MPG_CHECK(eng && par, "null argument");
+    // what the engine does not carry is refused when it is set, so that a caller keeps its CPU path from the start
+    MPG_CHECK((par->BlackHoleFeedbackMethod & 0x20) == 0, "blackhole: BlackHoleFeedbackMethod with BH_FEEDBACK_OPTTHIN is not carried (get_neutral_fraction_sfreff)");
+    MPG_CHECK(par->BHFeedbackUseTcool != 2, "blackhole: BHFeedbackUseTcool == 2 is not carried (get_egyeff)");
+    MPG_CHECK(par->GravInternal > 0 && par->HubbleParam > 0 && par->UnitTime_in_s > 0 && par->UnitVelocity_in_cm_per_s > 0 && par->uu_in_cgs > 0,
+              "blackhole parameters: GravInternal, HubbleParam and the units must be positive");
+    eng->bhpar = *par;
+    eng->have_bhpar = true;
+    API_END
+}
+
+void blackhole_call(mpg_engine *eng, const mpg_blackhole_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive, int build)
+{
+    MPG_CHECK(eng && A && T, "null argument");
+    MPG_CHECK(nactive >= 0, "blackhole: negative list length");
+    MPG_CHECK(eng->have_bhpar, "blackhole: no parameters (mpg_set_blackhole_params first)");
+    MPG_CHECK(eng->bh.rndsize > 0, "blackhole: no random table (mpg_set_random_table first)");
+    MPG_CHECK(eng->d_pos || eng->n == 0, "blackhole: no particles bound");
+    for(int f = 0; f < BH_NFIELDS; f++)
+        MPG_CHECK(field_get(*A, BH_FIELDS[f].off) || (BH_FIELDS[f].role & BH_OPTIONAL) || eng->n == 0,
+                  std::string("blackhole: the array ") + BH_FIELDS[f].name + " is required");
+    MPG_HIP(hipSetDevice(eng->device));
+    const mpg_blackhole_params &P = eng->bhpar;
+    BhView v{eng->d_pos, eng->d_type, *A};
+    BhScalars S;
+    S.p = P;
+    S.merge_dist = 2 * (P.ForceSoftening > 0 ? P.ForceSoftening : 2.8 * eng->GravitySoftening) / 2.8; // blackhole.c:503
+    S.a3inv = 1. / (T->atime * T->atime * T->atime);
+    // blackhole.c:379-380, physconst.h
+    S.meddington_fac = (4 * M_PI * 6.672e-8 * 2.99792458e10 * 1.6726e-24 / (0.1 * 2.99792458e10 * 2.99792458e10 * 6.65245e-25)) * P.UnitTime_in_s / P.HubbleParam;
+    S.c2 = pow(2.99792458e10 / P.UnitVelocity_in_cm_per_s, 2);
+    S.rho_sfr = P.BHKE_SfrCritOverDensity * (P.OmegaBaryon * 3 * P.Hubble * P.Hubble / (8 * M_PI * P.GravInternal)); // :450-451
+    S.ucap = 5.0e8 / ((4 / (8 - 5 * (1 - 0.76))) * 1.6726e-24 / 1.38066e-16 * (5.0 / 3.0 - 1) * P.uu_in_cgs);           // :722-725
+    S.ktype = kernel_index(eng->denspar.DensityKernelType);
+    S.rnd = eng->bh.rnd.p;
+    S.rndsize = (uint64_t)eng->bh.rndsize;
+    const uint8_t *flags = eng->sph.mark_active(d_active, nactive, eng->n, eng->stream);
+    // no target: nothing further is read, nothing is written, no tree is demanded
+    if(eng->bh.make_queue(eng->d_type, flags, eng->n, eng->stream) > 0) {
+        const bool fits = eng->tree_allocated && (eng->tree_mask & 33) == 33 && eng->tree.has_hmax;
+        if(build == 2 || (!fits && build == 1)) {
+            MPG_CALL(mpg_dev_force_tree_rebuild_mask(eng, 33 /* GASMASK + BHMASK */, 0));
+            MPG_CALL(mpg_dev_force_update_hmax(eng, A->hsml));
+        }
+        // blackhole.c:237-238, treewalk.c:941-945
+        MPG_CHECK(eng->tree_allocated && (eng->tree_mask & 1) != 0, "blackhole: the current tree does not contain the gas (GASMASK)");
+        MPG_CHECK((eng->tree_mask & 32) != 0, "blackhole: the current tree does not contain the black holes (BHMASK)");
+        MPG_CHECK(eng->tree.has_hmax, "blackhole: symmetric search on a tree without hmax (force_tree_calc_moments first)");
+        MPG_CHECK(S.merge_dist > 0, "blackhole: no force softening");
+        eng->bh.run(eng->tree, v, *T, S, eng->n, eng->stream);
+    }
+}
+
+int64_t blackhole_targets(mpg_engine *eng, const int *d_active, int64_t nactive)
+{
+    MPG_CHECK(eng && nactive >= 0, "blackhole: null engine or negative list length");
+    MPG_HIP(hipSetDevice(eng->device));
+    const uint8_t *flags = eng->sph.mark_active(d_active, nactive, eng->n, eng->stream);
+    return eng->bh.make_queue(eng->d_type, flags, eng->n, eng->stream);
+}
+
+int mpg_dev_blackhole(mpg_engine *eng, const mpg_blackhole_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive)
+{
+    API_BEGIN
+    blackhole_call(eng, A, T, d_active, nactive, 0);
+    API_END
+}
+
+int mpg_blackhole_get_stats(mpg_engine *eng, int64_t stats[8])
+{
+    API_BEGIN
+    MPG_CHECK(eng && stats, "null argument");
+    for(int k = 0; k < BH_NSTATS; k++)
+        stats[k] = eng->bh.last_stats[k];
+    API_END
+}
+
+int mpg_blackhole_get_times(mpg_engine *eng, double ms[3])
+{
+    API_BEGIN
+    MPG_CHECK(eng && ms, "null argument");
+    for(int k = 0; k < 3; k++)
+        ms[k] = eng->bh.last_ms[k];
+    API_END
+}
+
 /* ------------------------------ introspection ------------------------------ */
 
 int mpg_tree_get_stats(mpg_engine *eng, mpg_tree_stats *st)

@@ -8,6 +8,7 @@
 #include "veldisp.h"
 #include "cooling.h"
 #include "metals.h"
+#include "blackhole.h"
 #include "timestep.h"
 #include "peano.h"
 #include "planes.h"
@@ -161,6 +162,13 @@ struct mpg_engine {
     MetalsEngine metals;
     DevBuf<double> mt_stage[13];
     HostBuf<float> mt_mass;
+    // black-hole accretion, mergers and feedback (blackhole.hip): parameters, the walks' state and the random table; the staging of its
+    // host forms (fields of mpg_blackhole_arrays)
+    mpg_blackhole_params bhpar{};
+    bool have_bhpar = false;
+    BlackholeEngine bh;
+    DevBuf<char> bh_stage[BH_NFIELDS];
+    HostBuf<float> bh_mass;
     void prefetch_join()
     {
         if(prefetch_thread.joinable())
@@ -180,6 +188,11 @@ extern "C" void wait_for_leaf_blocks(mpg_engine *eng, hipStream_t st);          
 // the host arrays of the SPH forms staged, `dev` filled with their device copies; the planes of a staged or resident table
 void stage_particles(mpg_engine *eng, const mpg_particle_view *P, double BoxSize);
 void stage_sph(mpg_engine *eng, const mpg_sph_arrays *host, mpg_sph_arrays *dev, int64_t n);
+// engine.hip, also used by host_forms.hip and resident.hip: the black-hole call on device arrays; when the call has a target, build == 1 builds
+// the tree of gas and black holes with hmax (from A->hsml) if the current tree is not one, build == 2 builds it in any case
+// ... and its queue pass alone: the number of targets the call would have (the host forms stage their arrays only when there is one)
+extern "C" int64_t blackhole_targets(mpg_engine *eng, const int *d_active, int64_t nactive);
+extern "C" void blackhole_call(mpg_engine *eng, const mpg_blackhole_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive, int build);
 void host_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *par, double *planes, int64_t *npart);
 
 // potential planes (planes.hip).  red: the sums over the ranks of the several-GPU form (dist.hip), or null; sum_device returns with the

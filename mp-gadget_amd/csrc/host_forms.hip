@@ -965,3 +965,36 @@ int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSiz
     API_END
 }
 
+// blackhole() for the listed particles of a host table: Mass is the records' column (staged with the table, written back into it with
+// the flags), the other arrays go through bh_stage / bh_unstage (host_table.h).  The tree of gas and black holes and its hmax are built
+// by the call itself once it knows that it has a target.
+int mpg_blackhole(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_blackhole_arrays *A, const mpg_sph_times *T,
+                  const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A && T, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    const int64_t n = pv->n;
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    // the queue pass first: without a target nothing travels, nothing is read and nothing is written
+    if(blackhole_targets(eng, d_act, NumActiveParticle) == 0) {
+        mpg_err_slot().clear();
+        return 0;
+    }
+    mpg_blackhole_arrays d{};
+    bh_stage(*A, d, eng->bh_stage, n, BH_TABLE, eng->stream);
+    d.mass = eng->s_mass.p;
+    // (a tree that a previous call left is one of another table or another step: always rebuilt when there is a target)
+    blackhole_call(eng, &d, T, d_act, NumActiveParticle, 2);
+    bh_unstage(*A, d, n, BH_TABLE, eng->stream);
+    if(eng->bh.ntargets > 0) {
+        BlackholeEngine::retype(eng->s_type.p, d.flags, n, eng->stream);
+        eng->bh_mass.reserve((size_t)n + 1);
+        mass_to_records(*pv, eng->s_mass.p, eng->bh_mass.p, eng->stream);
+        MPG_HIP(hipStreamSynchronize(eng->stream));
+        flags_to_records(*pv, A->flags);
+    }
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}

@@ -396,6 +396,105 @@ inline void metal_unstage(const mpg_metal_arrays &host, const mpg_metal_arrays &
             MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.width * sizeof(double), hipMemcpyDeviceToHost, st));
     }
 }
+// ... and of the black-hole call.  `mass` is the table's column in both host forms; on a resident gas run the SPH columns and the
+// table's Vel / accelerations are resident too; everything else travels.
+enum BhRole : unsigned {
+    BH_IN = 1,        // read by the call
+    BH_OUT = 2,       // comes back
+    BH_OPTIONAL = 4,  // may be NULL
+    BH_TABLE = 8,     // P.Mass: a column of the staged / resident table, never staged from `A`
+    BH_RES_ALIAS = 16 // resident gas run: aliases a resident column
+};
+struct BhField {
+    const char *name;
+    size_t off;  // of the member in mpg_blackhole_arrays
+    int bytes;   // per particle
+    unsigned role;
+};
+#define MPG_BH_FIELD(m, bytes, role) {#m, offsetof(mpg_blackhole_arrays, m), bytes, role}
+constexpr int BH_NFIELDS = 37;
+const BhField BH_FIELDS[BH_NFIELDS] = {
+    MPG_BH_FIELD(id, 8, BH_IN),
+    MPG_BH_FIELD(gacc, 24, BH_IN | BH_RES_ALIAS),
+    MPG_BH_FIELD(gpm, 24, BH_IN | BH_RES_ALIAS),
+    MPG_BH_FIELD(hydroacc, 24, BH_IN | BH_RES_ALIAS),
+    MPG_BH_FIELD(tb_hydro, 1, BH_IN | BH_RES_ALIAS),
+    MPG_BH_FIELD(tb_grav, 1, BH_IN | BH_RES_ALIAS),
+    MPG_BH_FIELD(hsml, 8, BH_IN | BH_RES_ALIAS),
+    MPG_BH_FIELD(density, 8, BH_IN | BH_RES_ALIAS),
+    MPG_BH_FIELD(delaytime, 8, BH_IN),
+    MPG_BH_FIELD(dfaccel, 24, BH_IN),
+    MPG_BH_FIELD(vdisp, 8, BH_IN),
+    MPG_BH_FIELD(active_hydro, 1, BH_IN | BH_OPTIONAL),
+    MPG_BH_FIELD(mass, 4, BH_TABLE),
+    MPG_BH_FIELD(vel, 24, BH_IN | BH_OUT | BH_RES_ALIAS),
+    MPG_BH_FIELD(entropy, 8, BH_IN | BH_OUT | BH_RES_ALIAS),
+    MPG_BH_FIELD(flags, 1, BH_IN | BH_OUT),
+    MPG_BH_FIELD(bh_mass, 8, BH_IN | BH_OUT),
+    MPG_BH_FIELD(mtrack, 8, BH_IN | BH_OUT),
+    MPG_BH_FIELD(kineticfdbkenergy, 8, BH_IN | BH_OUT),
+    MPG_BH_FIELD(countprogs, 4, BH_IN | BH_OUT),
+    MPG_BH_FIELD(mdot, 8, BH_OUT),
+    MPG_BH_FIELD(dragaccel, 24, BH_OUT),
+    MPG_BH_FIELD(encounter, 4, BH_OUT),
+    MPG_BH_FIELD(mintimebin, 4, BH_OUT),
+    MPG_BH_FIELD(swallowid, 8, BH_OUT),
+    MPG_BH_FIELD(swallowtime, 8, BH_OUT),
+    MPG_BH_FIELD(bhheated, 1, BH_OUT),
+    MPG_BH_FIELD(feedbackweightsum, 8, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(bh_entropy, 8, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(gasvel, 24, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(mgasenc, 8, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(keflag, 4, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(accreted_mass, 8, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(accreted_bhmass, 8, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(accreted_momentum, 24, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(sph_swallowid, 8, BH_OUT | BH_OPTIONAL),
+    MPG_BH_FIELD(bh_swallowid, 8, BH_OUT | BH_OPTIONAL),
+};
+#undef MPG_BH_FIELD
+static_assert(sizeof(mpg_blackhole_arrays) == BH_NFIELDS * sizeof(void *), "BH_FIELDS describes every member of mpg_blackhole_arrays");
+
+// The host arrays of `host` onto the device (stage[f], one buffer per field) and `dev` filled with the device pointers; fields with a
+// role in `skip` are left to the caller.  A required array that is missing is an error.
+inline void bh_stage(const mpg_blackhole_arrays &host, mpg_blackhole_arrays &dev, mpg::DevBuf<char> *stage, int64_t n, unsigned skip, hipStream_t st)
+{
+    for(int f = 0; f < BH_NFIELDS; f++) {
+        const BhField &F = BH_FIELDS[f];
+        if(F.role & skip)
+            continue;
+        void *h = field_get(host, F.off), *d = nullptr;
+        MPG_CHECK(h || (F.role & BH_OPTIONAL), std::string("blackhole: the array ") + F.name + " is required");
+        if(h) {
+            stage[f].reserve((size_t)n * F.bytes + 16);
+            d = stage[f].p;
+            // (the outputs go up too: the call writes the entries of its targets only, the others come back as they were)
+            MPG_HIP(hipMemcpyAsync(d, h, (size_t)n * F.bytes, hipMemcpyHostToDevice, st));
+        }
+        field_set(dev, F.off, d);
+    }
+}
+// ... and what the call wrote back into them (queued on st)
+inline void bh_unstage(const mpg_blackhole_arrays &host, const mpg_blackhole_arrays &dev, int64_t n, unsigned skip, hipStream_t st)
+{
+    for(int f = 0; f < BH_NFIELDS; f++) {
+        const BhField &F = BH_FIELDS[f];
+        void *h = field_get(host, F.off);
+        if(h && (F.role & BH_OUT) && !(F.role & skip))
+            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.bytes, hipMemcpyDeviceToHost, st));
+    }
+}
+// the flags byte of the records: IsGarbage and Swallowed as the call left them (`flags`: n host bytes)
+inline void flags_to_records(const mpg_particle_view &V, const uint8_t *flags)
+{
+    const HostTable T(V);
+    parallel_for(V.n, [=](int64_t lo, int64_t hi) {
+        for(int64_t i = lo; i < hi; i++) {
+            uint8_t *b = (uint8_t *)(T.rec(i) + T.V.off_flags);
+            *b = (uint8_t)((*b & ~3) | (flags[i] & 3));
+        }
+    });
+}
 // the table's Mass column from the device into the records (`pinned`: n floats of pinned staging)
 inline void mass_to_records(const mpg_particle_view &V, const float *d_mass, float *pinned, hipStream_t st)
 {

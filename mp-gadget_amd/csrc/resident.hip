@@ -543,3 +543,47 @@ int mpg_resident_sph_metal_return(mpg_engine *eng, const mpg_particle_view *pv, 
     API_END
 }
 
+// blackhole() on a resident gas run: the table's and the gas arrays' columns are the resident ones and are updated in place; the type
+// column and the integrator's flags take the rows swallowed; Mass and flags also go into the records, which the end of the resident
+// stretch does not fetch.  The per-black-hole members and ID / DelayTime travel.
+int mpg_resident_sph_blackhole(mpg_engine *eng, const mpg_particle_view *pv, const mpg_blackhole_arrays *A, const mpg_sph_times *T,
+                               const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A && T, "null argument");
+    resident_sph_check(eng, pv);
+    const int64_t n = pv->n;
+    const mpg_sph_arrays &r = eng->res_sph_dev;
+    MPG_CHECK(r.vel && r.gacc && r.gpm && r.hydroacc_out && r.tb_hydro && r.tb_grav && r.hsml && r.density && r.entropy,
+              "resident blackhole: the gas arrays lack one of vel, gacc, gpm, hydroacc_out, tb_hydro, tb_grav, hsml, density, entropy");
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    // the queue pass first: without a target nothing travels, nothing is read and nothing is written
+    if(blackhole_targets(eng, d_act, NumActiveParticle) == 0) {
+        mpg_err_slot().clear();
+        return 0;
+    }
+    mpg_blackhole_arrays d{};
+    bh_stage(*A, d, eng->bh_stage, n, BH_TABLE | BH_RES_ALIAS, eng->stream);
+    d.mass = eng->s_mass.p;
+    d.vel = (double *)r.vel;
+    d.gacc = r.gacc;
+    d.gpm = r.gpm;
+    d.hydroacc = r.hydroacc_out;
+    d.tb_hydro = r.tb_hydro;
+    d.tb_grav = r.tb_grav;
+    d.hsml = r.hsml;
+    d.density = r.density;
+    d.entropy = (double *)r.entropy;
+    blackhole_call(eng, &d, T, d_act, NumActiveParticle, 1);
+    bh_unstage(*A, d, n, BH_TABLE | BH_RES_ALIAS, eng->stream);
+    if(eng->bh.ntargets > 0) {
+        BlackholeEngine::retype(eng->s_type.p, d.flags, n, eng->stream);
+        resident_flags(eng, n);
+        eng->bh_mass.reserve((size_t)n + 1);
+        mass_to_records(*pv, eng->s_mass.p, eng->bh_mass.p, eng->stream);
+        MPG_HIP(hipStreamSynchronize(eng->stream));
+        flags_to_records(*pv, A->flags);
+    }
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}

@@ -120,6 +120,36 @@ class MetalParams(C.Structure):
     _fields_ = [("SPHWeighting", C.c_int), ("MaxNgbDeviation", C.c_double), ("MaxGasMass", C.c_double)]
 
 
+BLACKHOLE_ARRAY_FIELDS = ("id", "gacc", "gpm", "hydroacc", "tb_hydro", "tb_grav", "hsml", "density", "delaytime", "dfaccel", "vdisp", "active_hydro",
+                          "mass", "vel", "entropy", "flags", "bh_mass", "mtrack", "kineticfdbkenergy", "countprogs",
+                          "mdot", "dragaccel", "encounter", "mintimebin", "swallowid", "swallowtime", "bhheated",
+                          "feedbackweightsum", "bh_entropy", "gasvel", "mgasenc", "keflag", "accreted_mass", "accreted_bhmass", "accreted_momentum",
+                          "sph_swallowid", "bh_swallowid")
+# the element types of the members that are not float64 (numpy names; torch has no uint64: such tensors are int64 with the same bits)
+BLACKHOLE_ARRAY_DTYPES = dict(id="uint64", swallowid="uint64", sph_swallowid="uint64", bh_swallowid="uint64", tb_hydro="uint8", tb_grav="uint8",
+                              active_hydro="uint8", flags="uint8", bhheated="uint8", mass="float32", countprogs="int32", encounter="int32",
+                              mintimebin="int32", keflag="int32")
+BH_FEEDBACK_TOPHAT, BH_FEEDBACK_SPLINE, BH_FEEDBACK_MASS, BH_FEEDBACK_VOLUME, BH_FEEDBACK_OPTTHIN = 0x2, 0x4, 0x8, 0x10, 0x20   # blackhole.h:47-53
+
+
+class BlackholeArraysC(C.Structure):
+    """mpg_blackhole_arrays"""
+    _fields_ = [(k, C.c_void_p) for k in BLACKHOLE_ARRAY_FIELDS]
+
+
+class BlackholeParams(C.Structure):
+    """mpg_blackhole_params"""
+    _fields_ = [("BlackHoleAccretionFactor", C.c_double), ("BlackHoleFeedbackFactor", C.c_double), ("BlackHoleEddingtonFactor", C.c_double),
+                ("BlackHoleFeedbackMethod", C.c_int), ("BlackHoleKineticOn", C.c_int), ("BHKE_EddingtonThrFactor", C.c_double),
+                ("BHKE_EddingtonMFactor", C.c_double), ("BHKE_EddingtonMPivot", C.c_double), ("BHKE_EddingtonMIndex", C.c_double),
+                ("BHKE_EffRhoFactor", C.c_double), ("BHKE_EffCap", C.c_double), ("BHKE_InjEnergyThr", C.c_double),
+                ("BHKE_SfrCritOverDensity", C.c_double), ("MergeGravBound", C.c_int), ("BH_DRAG", C.c_int), ("SeedBHDynMass", C.c_double),
+                ("BlackHoleRepositionEnabled", C.c_int), ("WindDecouple", C.c_int), ("StarformationOn", C.c_int), ("BHFeedbackUseTcool", C.c_int),
+                ("PhysDensThresh", C.c_double), ("OverDensThresh", C.c_double), ("ForceSoftening", C.c_double), ("GravInternal", C.c_double),
+                ("HubbleParam", C.c_double), ("OmegaBaryon", C.c_double), ("Hubble", C.c_double), ("UnitTime_in_s", C.c_double),
+                ("UnitVelocity_in_cm_per_s", C.c_double), ("uu_in_cgs", C.c_double)]
+
+
 COOLING_ARRAY_FIELDS = ("density", "entropy", "ne", "sfr", "metallicity", "heiii_ionized", "tb_hydro")
 COOLING_BYTE_FIELDS = ("heiii_ionized", "tb_hydro")
 RECOMB_CEN92, RECOMB_VERNER96, RECOMB_BADNELL06 = 0, 1, 2      # enum RecombType, cooling_rates.h:10-14
@@ -1168,6 +1198,68 @@ class Engine:
                                             p(ql), C.c_int64(len(ql))))
         d["queue_lengths"] = [int(x) for x in ql[:self.metals_stats()["iterations"]]]
         return d
+
+    # ------------------------------------------------------------------ black-hole accretion, mergers and feedback (blackhole, blackhole.c)
+    # `arrays` maps the field names of mpg_blackhole_arrays to device tensors (dev form) / contiguous numpy arrays (host forms) of the
+    # element types in BLACKHOLE_ARRAY_DTYPES (float64 otherwise).  The dev form runs on the current tree: gas and black holes, with hmax.
+    def set_random_table(self, table):
+        t = np.ascontiguousarray(table, np.float64)
+        self._ck(self.lib.mpg_set_random_table(self.h, t.ctypes.data_as(C.c_void_p), C.c_int64(len(t))))
+
+    def set_blackhole_params(self, par):
+        if not isinstance(par, BlackholeParams):
+            par = BlackholeParams(**par)
+        self._ck(self.lib.mpg_set_blackhole_params(self.h, C.byref(par)))
+
+    def dev_blackhole(self, arrays, times, active=None):
+        a = BlackholeArraysC()
+        for k in BLACKHOLE_ARRAY_FIELDS:
+            t = arrays.get(k)
+            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        nact = 0 if active is None else active.shape[0]
+        self._ck(self.lib.mpg_dev_blackhole(self.h, C.byref(a), C.byref(times), _ptr(active), C.c_int64(nact)))
+
+    @staticmethod
+    def _blackhole_host_arrays(arrays, skip):
+        a = BlackholeArraysC()
+        for k in BLACKHOLE_ARRAY_FIELDS:
+            t = None if k in skip else arrays.get(k)
+            want = np.dtype(BLACKHOLE_ARRAY_DTYPES.get(k, "float64"))
+            if t is not None and (t.dtype != want or not t.flags["C_CONTIGUOUS"]):
+                raise EngineError("black-hole host array %s must be contiguous %s" % (k, want.name))
+            setattr(a, k, None if t is None else t.ctypes.data)
+        return a
+
+    def blackhole(self, P, BoxSize, arrays, times, ActiveParticle=None):
+        """host form: Mass is the records' column; Mass and the flags are written back into P"""
+        v = self._view(P)
+        a = self._blackhole_host_arrays(arrays, ("mass",))
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_blackhole(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times),
+                                        None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+
+    BLACKHOLE_RESIDENT_COLUMNS = ("mass", "vel", "gacc", "gpm", "hydroacc", "tb_hydro", "tb_grav", "hsml", "density", "entropy")
+
+    def resident_sph_blackhole(self, P, arrays, times, ActiveParticle=None):
+        """on a resident gas run: the columns in BLACKHOLE_RESIDENT_COLUMNS are resident; the other arrays (numpy) travel"""
+        v = self._view(P)
+        a = self._blackhole_host_arrays(arrays, self.BLACKHOLE_RESIDENT_COLUMNS)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_resident_sph_blackhole(self.h, C.byref(v), C.byref(a), C.byref(times),
+                                                     None if act is None else act.ctypes.data_as(C.c_void_p),
+                                                     C.c_int64(0 if act is None else len(act))))
+
+    def blackhole_stats(self):
+        c = (C.c_int64 * 8)()
+        self._ck(self.lib.mpg_blackhole_get_stats(self.h, c))
+        return dict(gas_swallowed=c[0], bh_swallowed=c[1], accretion_candidates=c[2], accretion_neighbours=c[3], feedback_candidates=c[4],
+                    feedback_neighbours=c[5], accretion_targets=c[6], feedback_targets=c[7])
+
+    def blackhole_times(self):
+        """device time of the last call in ms: the accretion walk, the feedback walk, the apply pass"""
+        c = (C.c_double * 3)()
+        self._ck(self.lib.mpg_blackhole_get_times(self.h, c))
+        return dict(accretion_ms=c[0], feedback_ms=c[1], apply_ms=c[2])
 
     # ------------------------------------------------------------------ radiative cooling (cooling_direct, sfr_eff.c:463-514)
     # `par` is a dict of the members of mpg_cooling_params (or a CoolingParams), `step` a dict with uvbg (dict of struct UVBG's members),

@@ -32,8 +32,9 @@ RENAMES = {
     "veldisp.c": ["winds_find_vel_disp"],
     "sfr_eff.c": ["cooling_and_starformation"],
     "metal_return.c": ["metal_return"],
+    "blackhole.c": ["blackhole"],
 }
-SHIM_C = ["gravity-hip.c", "sph-hip.c", "forcetree-hip.c", "timestep-hip.c", "veldisp-hip.c", "cooling-hip.c", "metals-hip.c", "mpg_mpi_comm.c", "mpg_rccl_mpi.c"]
+SHIM_C = ["gravity-hip.c", "sph-hip.c", "forcetree-hip.c", "timestep-hip.c", "veldisp-hip.c", "cooling-hip.c", "metals-hip.c", "blackhole-hip.c", "mpg_mpi_comm.c", "mpg_rccl_mpi.c"]
 EXTERNAL = [("pfft", r"^pfft_"), ("fftw", r"^fftw_"), ("gsl", r"^gsl_"), ("mpi", r"^P?MPI_"), ("openmp", r"^(GOMP_|omp_)"),
             ("hdf5", r"^H5")]
 

@@ -13,7 +13,7 @@
 #   2. copy shim/*.c, shim/*.h and include/mpgadget_hip.h into <copy>/libgadget/;
 #   3. patch <copy>/libgadget/Makefile: drop gravpm.o gravshort-tree.o gravshort-pair.o gravity.o from GADGET_OBJS and add the shim
 #      objects; rename the five tree constructors in forcetree.o, the eight integrator entry points in timestep.o / drift.o and
-#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o and metal_return in metal_return.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
+#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o, metal_return in metal_return.o and blackhole in blackhole.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
 #   4. add the two parameter hooks (set_densitypar, set_hydro_params), the accessors of mpg_shim.h and the
 #      mpg_shim_particles_changed() calls listed in INTEGRATION.md ("Where P[] is reordered") with sed;
 #   5. build the library of this repository, then `make` in the copy with LIBS += -L<repo>/mp-gadget_amd -lmpgadget_hip -lmpi.
@@ -22,12 +22,13 @@ REF=${1:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 WORK=${2:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 CHECK=${3:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
+SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c blackhole-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
 SHIM_H="mpg_shim.h mpg_shim_epoch.h mpg_mpi_comm.h"
 REF_FILES="libgadget/Makefile libgadget/gravpm.c libgadget/gravshort-tree.c libgadget/gravshort-pair.c libgadget/gravity.c libgadget/forcetree.c
            libgadget/density.c libgadget/hydra.c libgadget/timestep.c libgadget/drift.c libgadget/timebinmgr.c libgadget/run.c libgadget/domain.c
            libgadget/exchange.c libgadget/fof.c libgadget/slotsmanager.c libgadget/veldisp.c libgadget/sfr_eff.c libgadget/cooling.c libgadget/cooling_rates.c
-           libgadget/cooling_uvfluc.c libgadget/metal_return.c gadget/Makefile Makefile.rules Options.mk.example"
+           libgadget/cooling_uvfluc.c libgadget/metal_return.c libgadget/blackhole.c libgadget/bhdynfric.c
+           libgadget/winds.c gadget/Makefile Makefile.rules Options.mk.example"
 
 echo "== 0. inputs"
 for f in $REF_FILES; do test -f "$REF/$f" || { echo "missing in the reference checkout: $f"; exit 1; }; done
@@ -68,7 +69,7 @@ echo "== 3. libgadget/Makefile"
 MK="$T/libgadget/Makefile"
 sed -i -e 's/\bgravshort-tree\.o gravshort-pair\.o hydra\.o/hydra.o/' -e 's/\bgravpm\.o powerspectrum\.o/powerspectrum.o/' \
        -e 's/\bpetapm\.o gravity\.o/petapm.o/' "$MK"
-sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
+sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o blackhole-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
 cat >> "$MK" <<MKEOF
 
 # ---- MP-Gadget on libmpgadget_hip (tools/link_reference.sh)
@@ -79,6 +80,7 @@ CFLAGS += -DMPGADGET_HIP -I$ROOT/include
 .objs/veldisp.o: CFLAGS += -Dwinds_find_vel_disp=cpu_winds_find_vel_disp
 .objs/sfr_eff.o: CFLAGS += -Dcooling_and_starformation=cpu_cooling_and_starformation
 .objs/metal_return.o: CFLAGS += -Dmetal_return=cpu_metal_return
+.objs/blackhole.o: CFLAGS += -Dblackhole=cpu_blackhole
 MKEOF
 
 echo "== 4. hooks in the reference sources (INTEGRATION.md lists them; each is one line)"
@@ -166,6 +168,18 @@ replace_once(T + "/libgadget/sfr_eff.c", '    walltime_measure("/Cooling/Cooling
 append(T + "/libgadget/metal_return.c", "double mpg_shim_metal_yield(double dtmyrstart, double dtmyrend, double stellarmetal, struct MetalReturnPriv *priv, MyFloat *MetalYields, int tid, double masslow, double masshigh)\n"
        "{\n    return metal_yield(dtmyrstart, dtmyrend, stellarmetal, priv->hub, &priv->interp, MetalYields, priv->imf_norm, priv->gsl_work[tid], masslow, masshigh);\n}\n"
        "void mpg_shim_metal_params(int *SPHWeighting, double *MaxNgbDeviation)\n{\n    *SPHWeighting = MetalParams.SPHWeighting;\n    *MaxNgbDeviation = MetalParams.MaxNgbDeviation;\n}")
+# the black-hole step (blackhole-hip.c): accessors behind the file-static parameters of blackhole.c, bhdynfric.c, winds.c and sfr_eff.c
+append(T + "/libgadget/blackhole.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_blackhole_params(mpg_blackhole_params *p)\n{\n"
+       + "".join("    p->%s = blackhole_params.%s;\n" % (k, k) for k in (
+           "BlackHoleAccretionFactor", "BlackHoleFeedbackFactor", "BlackHoleEddingtonFactor", "BlackHoleKineticOn", "BHKE_EddingtonThrFactor",
+           "BHKE_EddingtonMFactor", "BHKE_EddingtonMPivot", "BHKE_EddingtonMIndex", "BHKE_EffRhoFactor", "BHKE_EffCap", "BHKE_InjEnergyThr",
+           "BHKE_SfrCritOverDensity", "MergeGravBound", "BH_DRAG", "SeedBHDynMass"))
+       + "    p->BlackHoleFeedbackMethod = (int)blackhole_params.BlackHoleFeedbackMethod;\n}")
+append(T + "/libgadget/bhdynfric.c", "int mpg_shim_bh_dynfric_method(void) { return blackhole_dynfric_params.BH_DynFrictionMethod; }")
+append(T + "/libgadget/winds.c", "int mpg_shim_wind_decouple(void) { return HAS(wind_params.WindModel, WIND_DECOUPLE_SPH) ? 1 : 0; }")
+append(T + "/libgadget/sfr_eff.c", "void mpg_shim_sfr_blackhole(int *StarformationOn, int *BHFeedbackUseTcool, double *PhysDensThresh, double *OverDensThresh)\n"
+       "{\n    *StarformationOn = sfr_params.StarformationOn;\n    *BHFeedbackUseTcool = sfr_params.BHFeedbackUseTcool;\n"
+       "    *PhysDensThresh = sfr_params.PhysDensThresh;\n    *OverDensThresh = sfr_params.OverDensThresh;\n}")
 # P[] is reordered / exchanged: the shim's upload cache must hear of it (the 64-record hash of mpg_shim_epoch.h is only a backstop)
 hook = "{ extern void mpg_shim_particles_changed(void); mpg_shim_particles_changed(); }"
 for path, func in (("/libgadget/domain.c", "domain_decompose_full"), ("/libgadget/domain.c", "domain_maintain"),
@@ -179,7 +193,7 @@ if [ "$CHECK" = "--check" ]; then
     # the patched reference files and the renamed objects still parse (nothing is compiled to an object, linked or run); cooling_rates.c,
     # which only gains one accessor line, and metal_return.c, which gains two functions, call GSL and cannot be parsed with the typedef-only
     # stand-ins
-    for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c sfr_eff.c cooling.c cooling_uvfluc.c; do
+    for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c sfr_eff.c cooling.c cooling_uvfluc.c blackhole.c bhdynfric.c winds.c; do
         extra=""
         case $f in
             forcetree.c) extra="-Dforce_tree_full=cpu_force_tree_full -Dforce_tree_rebuild_mask=cpu_force_tree_rebuild_mask -Dforce_tree_active_moments=cpu_force_tree_active_moments -Dforce_tree_calc_moments=cpu_force_tree_calc_moments -Dforce_tree_free=cpu_force_tree_free";;
@@ -187,6 +201,7 @@ if [ "$CHECK" = "--check" ]; then
             drift.c) extra="-Ddrift_all_particles=cpu_drift_all_particles";;
             veldisp.c) extra="-Dwinds_find_vel_disp=cpu_winds_find_vel_disp";;
             sfr_eff.c) extra="-Dcooling_and_starformation=cpu_cooling_and_starformation";;
+            blackhole.c) extra="-Dblackhole=cpu_blackhole";;
         esac
         if ! gcc -std=gnu11 -fopenmp -fsyntax-only -DMPGADGET_HIP $extra -I "$STUB" -I "$MPIINC" -I "$ROOT/include" -I "$T/libgadget" -I "$T" -I "$REF/depends/bigfile/src" "$T/libgadget/$f" 2> "$STUB/err"; then
             if grep -q 'gsl/.*No such file' "$STUB/err"; then
