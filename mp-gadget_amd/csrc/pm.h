@@ -27,7 +27,16 @@ struct PMesh {
     int nmesh = 0;
     bool have_plans = false;
     bool kspace_force = false; // true: forces by four inverse transforms as the reference does; false: by differencing the potential (pm.hip)
-    FftPlan plan_r2c, plan_c2r;
+    FftPlan plan_r2c, plan_c2r;   // 3-D, made on first use (ensure_3d)
+    // the fused x-pass form of the default step (pm.hip, k_xpass_solve): batched 2-D transforms over (y, z), one batch per x-plane, around
+    // one hand-written pass along x; made on first use (ensure_xpass).  xp_tw: exp(-2 pi i m / Nmesh), m < Nmesh
+    FftPlan plan2_r2c, plan2_c2r;
+    DevBuf<double> xp_tw;
+    int xp_blocks = 0;
+    bool xpass_usable() const; // this mesh and these settings take the fused x-pass unless MPG_PM_XPASS=0
+    void ensure_3d();
+    void ensure_xpass(hipStream_t st);
+    void xpass_solve(hipStream_t st);
     DevBuf<double> real;    // Nmesh^3
     DevBuf<double> rho_k;   // 2 * Nmesh^2 (Nmesh/2+1): potential in Fourier space after the transfer
     DevBuf<double> work_k;  // same size: per-component work array (Z2D overwrites its input)
@@ -94,7 +103,7 @@ struct PMesh {
 
     // gravpm_init_periodic -> petapm_init (gravpm.c:51-54, petapm.c:105-223)
     void init(double BoxSize, double Asmth, int Nmesh, double G, hipStream_t st);
-    void ensure_single(); // meshes + 3-D plans of the single-GPU form, made on first use
+    void ensure_single(); // meshes of the single-GPU form, made on first use (the plans when a step first needs them)
     // petapm_destroy (petapm.c:225-232)
     void destroy();
     // gravpm_force (gravpm.c:61-119): d_gravpm[n][3] is assigned, d_potential[n] (may be null) is incremented

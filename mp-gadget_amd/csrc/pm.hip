@@ -25,12 +25,19 @@ namespace mpg {
             ::mpg::fail(__FILE__, __LINE__, std::string("rocFFT error ") + std::to_string((int)_r) + " in " #expr); \
     } while(0)
 
-// put_particle_to_mesh through pm_iterate_one (petapm.c:955-1020, :1138-1144)
+// put_particle_to_mesh through pm_iterate_one (petapm.c:955-1020, :1138-1144).  Two lanes per particle: lane 2j + h adds the four corners
+// of particle j with z-bit h (c = 4h + 0 .. 3 in the corner order of pm_cic.h), so the lanes of a pair write z and z + 1, neighbours in
+// memory, in the SAME instruction.  The atomics run at the memory side as 64-byte requests and their number is what costs: in lattice
+// order at Nmesh = 2 N^(1/3) a wave of one particle per lane wrote every second double of 1 KiB per corner (16 half-used requests), a wave
+// of pairs writes 512 contiguous bytes (8 full ones).  Every addend is the expression of before, cic_weight(c, res, 1.0) * m; at
+// iz = Nmesh - 1 the pair's cells are a row apart and each lane's atomic goes its own way.
 __global__ void __launch_bounds__(256) k_cic_deposit(int64_t n, const double *__restrict__ pos, const float *__restrict__ mass,
                                                      const uint8_t *__restrict__ active, double cellsize, int nmesh,
                                                      double *__restrict__ mesh)
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = t >> 1;
+    const int h = (int)(t & 1);
     if(i >= n)
         return;
     if(active && !active[i])
@@ -40,8 +47,10 @@ __global__ void __launch_bounds__(256) k_cic_deposit(int64_t n, const double *__
     cic_cell3(pos + 3 * i, cellsize, nmesh, ic, res);
     const double m = (double)mass[i];
 #pragma unroll
-    for(int c = 0; c < 8; c++)
+    for(int q = 0; q < 4; q++) {
+        const int c = 4 * h + q;
         unsafeAtomicAdd(&mesh[cic_index(c, ic, nmesh)], cic_weight(c, res, 1.0) * m);
+    }
 }
 
 // the same onto the x-planes [x0, x0 + P) of a slab: the part of the particle's cloud that falls on them.  x is looked at first:
@@ -161,6 +170,13 @@ struct FourierCell {
     int ix, iy, iz;
     long long k2;
 };
+__device__ __forceinline__ long long fourier_k2(int ix, int iy, int iz, int nmesh)
+{
+    const int kx = ix <= nmesh / 2 ? ix : ix - nmesh;
+    const int ky = iy <= nmesh / 2 ? iy : iy - nmesh;
+    const int kz = iz;
+    return (long long)kx * kx + (long long)ky * ky + (long long)kz * kz;
+}
 template <bool XLAST>
 __device__ __forceinline__ FourierCell fourier_cell(size_t ip, int nmesh, int ny, int y0)
 {
@@ -178,10 +194,7 @@ __device__ __forceinline__ FourierCell fourier_cell(size_t ip, int nmesh, int ny
         c.iy = y0 + (int)(t % ny);
         c.ix = (int)(t / ny);
     }
-    const int kx = c.ix <= nmesh / 2 ? c.ix : c.ix - nmesh;
-    const int ky = c.iy <= nmesh / 2 ? c.iy : c.iy - nmesh;
-    const int kz = c.iz;
-    c.k2 = (long long)kx * kx + (long long)ky * ky + (long long)kz * kz;
+    c.k2 = fourier_k2(c.ix, c.iy, c.iz, nmesh);
     return c;
 }
 
@@ -261,6 +274,67 @@ __device__ __forceinline__ double nu_factor(double x, int kint, const double *s_
     return 1 + prefac * (y_lo + (x - x_lo) / (x_hi - x_lo) * (y_hi - y_lo));
 }
 
+// the LDS of a measuring block: the histograms Power[nbins], kk[nbins], Nmodes[nbins] and, NU, the response table
+struct PsLds {
+    double *pow, *kk;
+    unsigned long long *n;
+    const double *lk, *rt;
+    const int *gs;
+};
+
+__device__ __forceinline__ double ps_binsperunit(int nmesh) { return (nmesh - 1) / log(sqrt(3.0) * nmesh / 2.0); }
+
+// One mode of that pass, written once for the kernels that sweep rho_k (k_power_spectrum, k_xpass_solve): v is the mode fc as
+// transformed; it is measured into the block's histograms (the k = 0 mode into Norm) and comes back as what the mesh holds afterwards.
+// Returns whether that differs from what came in, i.e. has to be stored.
+template <bool FUSE, bool NU>
+__device__ __forceinline__ bool spectrum_mode(const FourierCell &fc, int nmesh, double binsperunit, const double *__restrict__ invsinc2, double2 &v,
+                                              const PsLds &s, double *__restrict__ acc, double asmth2, double pot_factor, const NuArgs &nu)
+{
+    const int nbins = nmesh;
+    const long long k2 = fc.k2;
+    if(k2 == 0) {
+        const double m0 = v.x * v.x + v.y * v.y;
+        acc[2 * nbins] = NU ? m0 * nu.normfac : m0; // Norm (gravpm.c:437-441: Norm *= MtotbyMcdm^2 with the response)
+        if(FUSE)
+            v = make_double2(0.0, 0.0);
+        return FUSE;
+    }
+    int kint = 0;
+    if(NU) { // the mode times nufac before it is measured (gravpm.c:418-436)
+        kint = logk_bin(k2, binsperunit);
+        const double nufac = nu_factor(log(sqrt((double)k2) * nu.kscale), kint < nbins ? kint : nbins - 1, s.lk, s.rt, s.gs, nu.nonzero, nu.prefac);
+        v.x *= nufac;
+        v.y *= nufac;
+    }
+    const double m = v.x * v.x + v.y * v.y;
+    const double f = invsinc2[fc.ix] * invsinc2[fc.iy] * invsinc2[fc.iz];
+    if(FUSE) { // (k_potential_transfer's factor)
+        const double fac = potential_fac(k2, asmth2, pot_factor, f);
+        v = make_double2(v.x * fac, v.y * fac);
+    }
+    if(!NU)
+        kint = logk_bin(k2, binsperunit);
+    if(kint < nbins) {
+        const int w = (fc.iz == 0 || fc.iz == nmesh / 2) ? 1 : 2;
+        __hip_atomic_fetch_add(&s.pow[kint], w * m * f * f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&s.kk[kint], w * sqrt((double)k2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&s.n[kint], (unsigned long long)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    return FUSE || NU;
+}
+
+// a block's histograms added to the mesh's accumulators
+__device__ __forceinline__ void spectrum_flush(int nbins, const PsLds &s, double *__restrict__ acc, unsigned long long *__restrict__ modes)
+{
+    for(int b = threadIdx.x; b < nbins; b += blockDim.x)
+        if(s.n[b]) {
+            unsafeAtomicAdd(&acc[b], s.pow[b]);
+            unsafeAtomicAdd(&acc[nbins + b], s.kk[b]);
+            atomicAdd(&modes[b], s.n[b]);
+        }
+}
+
 template <bool XLAST, bool FUSE = false, bool NU = false>
 __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y0, const double *__restrict__ invsinc2,
                                                         double2 *__restrict__ cplx, double *__restrict__ acc,
@@ -284,52 +358,235 @@ __global__ void __launch_bounds__(256) k_power_spectrum(int nmesh, int ny, int y
         }
     }
     __syncthreads();
+    const PsLds s{s_pow, s_kk, s_n, s_lk, s_rt, s_gs};
     const int nz = nmesh / 2 + 1;
     const size_t total = (size_t)nmesh * ny * nz;
-    const double binsperunit = (nbins - 1) / log(sqrt(3.0) * nmesh / 2.0);
+    const double binsperunit = ps_binsperunit(nbins);
     for(size_t ip = (size_t)blockIdx.x * blockDim.x + threadIdx.x; ip < total; ip += (size_t)gridDim.x * blockDim.x) {
-        const FourierCell fc = fourier_cell<XLAST>(ip, nmesh, ny, y0);
-        const long long k2 = fc.k2;
         double2 v = cplx[ip];
-        if(k2 == 0) {
-            const double m0 = v.x * v.x + v.y * v.y;
-            acc[2 * nbins] = NU ? m0 * nu.normfac : m0; // Norm (gravpm.c:437-441: Norm *= MtotbyMcdm^2 with the response)
-            if(FUSE)
-                cplx[ip] = make_double2(0.0, 0.0);
-            continue;
-        }
-        int kint = 0;
-        if(NU) { // the mode times nufac before it is measured (gravpm.c:418-436)
-            kint = logk_bin(k2, binsperunit);
-            const double nufac = nu_factor(log(sqrt((double)k2) * nu.kscale), kint < nbins ? kint : nbins - 1, s_lk, s_rt, s_gs, nu.nonzero,
-                                           nu.prefac);
-            v.x *= nufac;
-            v.y *= nufac;
-            if(!FUSE)
-                cplx[ip] = v;
-        }
-        const double m = v.x * v.x + v.y * v.y;
-        const double f = invsinc2[fc.ix] * invsinc2[fc.iy] * invsinc2[fc.iz];
-        if(FUSE) { // (k_potential_transfer's factor)
-            const double fac = potential_fac(k2, asmth2, pot_factor, f);
-            cplx[ip] = make_double2(v.x * fac, v.y * fac);
-        }
-        if(!NU)
-            kint = logk_bin(k2, binsperunit);
-        if(kint >= nbins)
-            continue;
-        const int w = (fc.iz == 0 || fc.iz == nmesh / 2) ? 1 : 2;
-        __hip_atomic_fetch_add(&s_pow[kint], w * m * f * f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&s_kk[kint], w * sqrt((double)k2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(&s_n[kint], (unsigned long long)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if(spectrum_mode<FUSE, NU>(fourier_cell<XLAST>(ip, nmesh, ny, y0), nmesh, binsperunit, invsinc2, v, s, acc, asmth2, pot_factor, nu))
+            cplx[ip] = v;
     }
     __syncthreads();
-    for(int b = threadIdx.x; b < nbins; b += blockDim.x)
-        if(s_n[b]) {
-            unsafeAtomicAdd(&acc[b], s_pow[b]);
-            unsafeAtomicAdd(&acc[nbins + b], s_kk[b]);
-            atomicAdd(&modes[b], s_n[b]);
+    spectrum_flush(nbins, s, acc, modes);
+}
+
+// The x-transform of the fused solve (k_xpass_solve): a Stockham transform of length N = 2^n in passes of radix 8 (and one of 4 or 2
+// first when n is no multiple of 3), written for N / 8 "threads" per column that hold 8 points each.  Thread j holds, before every pass
+// and after the last, the points j + q N / 8, q = 0 .. 7: in a pass of radix r it computes the 8 / r butterflies jb = j + u N / 8, whose
+// inputs jb + t N / r are its points q = u + t 8 / r, and whose outputs go to (jb - k) r + k + t Ns, k = jb mod Ns (Ns = the product of
+// the radices before) - after the last pass, Ns = N / r, those are the points it read.  So a column comes from memory into registers, is
+// exchanged through LDS between passes only, and leaves from registers.  DIR = -1: forward (exp(-2 pi i jk / N)), +1: backward; both
+// unnormalised as rocFFT's and PFFT's.  tw[m] = exp(-2 pi i m / N), m < N (fp64, rounded from extended precision on the host).
+__device__ __forceinline__ double2 xp_mul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+template <int DIR> __device__ __forceinline__ double2 xp_mul_i(double2 a) // a times DIR i
+{
+    return DIR < 0 ? make_double2(a.y, -a.x) : make_double2(-a.y, a.x);
+}
+__device__ __forceinline__ void xp_dft2(double2 &a, double2 &b)
+{
+    const double2 t = a;
+    a = make_double2(t.x + b.x, t.y + b.y);
+    b = make_double2(t.x - b.x, t.y - b.y);
+}
+template <int DIR> __device__ __forceinline__ void xp_dft4(double2 &v0, double2 &v1, double2 &v2, double2 &v3)
+{
+    xp_dft2(v0, v2);
+    xp_dft2(v1, v3);
+    v3 = xp_mul_i<DIR>(v3);
+    xp_dft2(v0, v1); // y0, y2
+    xp_dft2(v2, v3); // y1, y3
+    const double2 t = v1;
+    v1 = v2;
+    v2 = t;
+}
+template <int DIR> __device__ __forceinline__ void xp_dft8(double2 v[8], int s /* stride between the 8 points in v */)
+{
+    const double h = 0.70710678118654752440; // sqrt(1/2)
+#pragma unroll
+    for(int n = 0; n < 4; n++)
+        xp_dft2(v[n * s], v[(n + 4) * s]);
+    // times w8^n, w8 = exp(DIR 2 pi i / 8)
+    {
+        const double2 a = v[5 * s], b = v[7 * s];
+        v[5 * s] = DIR < 0 ? make_double2((a.x + a.y) * h, (a.y - a.x) * h) : make_double2((a.x - a.y) * h, (a.y + a.x) * h);
+        v[6 * s] = xp_mul_i<DIR>(v[6 * s]);
+        v[7 * s] = DIR < 0 ? make_double2((b.y - b.x) * h, -(b.x + b.y) * h) : make_double2(-(b.x + b.y) * h, (b.x - b.y) * h);
+    }
+    xp_dft4<DIR>(v[0], v[1 * s], v[2 * s], v[3 * s]); // y0, y2, y4, y6
+    xp_dft4<DIR>(v[4 * s], v[5 * s], v[6 * s], v[7 * s]); // y1, y3, y5, y7
+    const double2 e1 = v[1 * s], e2 = v[2 * s], e3 = v[3 * s], o0 = v[4 * s], o1 = v[5 * s], o2 = v[6 * s];
+    v[1 * s] = o0;
+    v[2 * s] = e1;
+    v[3 * s] = o1;
+    v[4 * s] = e2;
+    v[5 * s] = o2;
+    v[6 * s] = e3;
+}
+
+// radix of the pass that starts at Ns: the odd factor (2 or 4) first, then 8s
+template <int N> __device__ constexpr int xp_radix(int Ns)
+{
+    int n = 0;
+    for(int m = N; m > 1; m >>= 1)
+        n++;
+    return Ns == 1 && n % 3 ? 1 << (n % 3) : 8;
+}
+
+// one pass on the 8 points of thread j: twiddles, butterflies.  Leaves output t of butterfly u in v[u + t 8 / r].
+template <int N, int DIR, int Ns> __device__ __forceinline__ void xp_pass(double2 v[8], int j, const double2 *__restrict__ tw)
+{
+    constexpr int r = xp_radix<N>(Ns), nb = 8 / r;
+#pragma unroll
+    for(int u = 0; u < nb; u++) {
+        if(Ns > 1) {
+            const int k = (j + u * (N / 8)) % Ns;
+#pragma unroll
+            for(int t = 1; t < r; t++) {
+                double2 w = tw[t * k * (N / (Ns * r))];
+                if(DIR > 0)
+                    w.y = -w.y;
+                v[u + t * nb] = xp_mul(v[u + t * nb], w);
+            }
         }
+        if(r == 8)
+            xp_dft8<DIR>(v + u, nb);
+        else if(r == 4)
+            xp_dft4<DIR>(v[u], v[u + nb], v[u + 2 * nb], v[u + 3 * nb]);
+        else
+            xp_dft2(v[u], v[u + nb]);
+    }
+}
+
+// where output t of butterfly u of thread j goes in the pass that starts at Ns
+template <int N, int Ns> __device__ __forceinline__ int xp_out(int j, int u, int t)
+{
+    constexpr int r = xp_radix<N>(Ns);
+    const int jb = j + u * (N / 8), k = jb % Ns;
+    return (jb - k) * r + k + t * Ns;
+}
+
+// the exchange between two passes: buf[x * ld + c] is column c of the tile
+template <int N, int Ns> __device__ __forceinline__ void xp_scatter(const double2 v[8], int j, double2 *buf, int ld, int c)
+{
+    constexpr int r = xp_radix<N>(Ns), nb = 8 / r;
+#pragma unroll
+    for(int u = 0; u < nb; u++)
+#pragma unroll
+        for(int t = 0; t < r; t++)
+            buf[xp_out<N, Ns>(j, u, t) * ld + c] = v[u + t * nb];
+}
+template <int N> __device__ __forceinline__ void xp_gather(double2 v[8], int j, const double2 *buf, int ld, int c)
+{
+#pragma unroll
+    for(int q = 0; q < 8; q++)
+        v[q] = buf[(j + q * (N / 8)) * ld + c];
+}
+
+// the passes of one transform from Ns on, with the exchanges between them through `tile`
+template <int N, int DIR, int Ns> __device__ __forceinline__ void xp_transform(double2 v[8], int j, int c, int ld, double2 *tile, const double2 *__restrict__ tw)
+{
+    constexpr int r = xp_radix<N>(Ns);
+    xp_pass<N, DIR, Ns>(v, j, tw);
+    if constexpr(Ns * r < N) {
+        __syncthreads(); // (the tile may still be read: the exchange before this one)
+        xp_scatter<N, Ns>(v, j, tile, ld, c);
+        __syncthreads();
+        xp_gather<N>(v, j, tile, ld, c);
+        xp_transform<N, DIR, Ns * r>(v, j, c, ld, tile, tw);
+    }
+}
+
+// columns of kz per tile: 8 modes of 16 bytes are one 128-byte line per x; the tile N x columns stays within 64 KiB
+constexpr int xp_cols(int N) { return N <= 512 ? 8 : 4; }
+// waves per SIMD of the blocks a CU holds - two (one computes while the other waits for memory), or the one that its 160 KiB of LDS have
+// room for at N = 1024: the register budget of the kernel
+constexpr int xp_waves(int N)
+{
+    const int lds = N * xp_cols(N) * 16 + 3 * N * 8, blocks = 2 * lds <= 160 * 1024 ? 2 : 1, w = blocks * (N / 8 * xp_cols(N)) / 256;
+    return w > 1 ? w : 1;
+}
+constexpr bool xp_supported(int N) { return N == 64 || N == 128 || N == 256 || N == 512 || N == 1024; }
+
+// The x-part of the transfer stage in ONE pass over rho_k (layout [x][ky][kz], as the batched 2-D transforms over (y, z) leave and take
+// it): forward transform along x, the mode measured and multiplied by the potential factor (spectrum_mode<FUSE>: the arithmetic of
+// k_power_spectrum<false, true, false>), backward transform along x.  The 3-D plans sweep the same columns three times (forward x-pass,
+// k_power_spectrum, backward x-pass: 6 x 1.07 GB at Nmesh 512); this is one read and one write.  A work item is a tile of xp_cols(N)
+// consecutive kz at one ky (the first and the last tile of a row are ragged: their dead columns transform zeros and store nothing);
+// a block takes a contiguous share of them, ky-major, so that it walks along rows that are contiguous in memory, and keeps its P(k)
+// histograms in LDS across all of them.  N / 8 threads per column (xp_pass): a column comes from memory into registers, passes through
+// the LDS tile between the passes and for the mode arithmetic, and leaves from registers.
+template <int N>
+__global__ void __launch_bounds__(N / 8 * xp_cols(N), xp_waves(N)) k_xpass_solve(const double2 *__restrict__ tw, const double *__restrict__ invsinc2,
+                                                                    double2 *__restrict__ cplx, double *__restrict__ acc,
+                                                                    unsigned long long *__restrict__ modes, double asmth2, double pot_factor)
+{
+    constexpr int TC = xp_cols(N), nz = N / 2 + 1, ntile = N / 2 / TC + 1, nbins = N;
+    extern __shared__ __attribute__((aligned(16))) double2 s_xp[]; // the tile [N][TC], then Power[nbins], kk[nbins], modes[nbins] (u64)
+    double2 *tile = s_xp;
+    double *s_pow = (double *)(tile + N * TC);
+    const PsLds s{s_pow, s_pow + nbins, (unsigned long long *)(s_pow + 2 * nbins), nullptr, nullptr, nullptr};
+    for(int b = threadIdx.x; b < nbins; b += blockDim.x) {
+        s.pow[b] = 0;
+        s.kk[b] = 0;
+        s.n[b] = 0;
+    }
+    __syncthreads();
+    const int c = threadIdx.x % TC, j = threadIdx.x / TC;
+    // (the same for every thread: in scalar registers)
+    const double bpu = ps_binsperunit(nbins);
+    const double binsperunit = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(bpu)), __builtin_amdgcn_readfirstlane(__double2loint(bpu)));
+    const int items = N * ntile, per = (items + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int it0 = (int)blockIdx.x * per, it1 = it0 + per < items ? it0 + per : items;
+    for(int it = it0; it < it1; it++) {
+        FourierCell fc;
+        // tile t of row iy holds kz = t TC - s .. + TC - 1, s = iy mod TC: a row of nz = N / 2 + 1 modes starts s modes behind a
+        // boundary of TC modes in memory, the same s for every x, so each tile is ONE aligned line (128 bytes at TC = 8) per x - with
+        // tiles counted from kz = 0 every line was fetched and written by two tiles
+        fc.iy = it / ntile;
+        const int kz0 = (it % ntile) * TC - fc.iy % TC;
+        fc.iz = kz0 + c;
+        const bool live = fc.iz >= 0 && fc.iz < nz;
+        // mode (x, iy, iz) is cplx[(x N + iy) nz + iz].  Of x = j + q N / 8 the part q goes into a base that is the same for the whole
+        // block and the rest into ONE 32-bit byte offset per thread (j N nz 16 < 2^31 up to N = 1024): eight 64-bit addresses per thread
+        // would cost the registers that the second block per CU needs
+        char *base = (char *)(cplx + ((ptrdiff_t)fc.iy * nz + kz0)); // (never in front of the mesh: kz0 < 0 only for iy > 0)
+        const unsigned off = ((unsigned)j * (N * nz) + c) * (unsigned)sizeof(double2);
+        double2 v[8];
+#pragma unroll
+        for(int q = 0; q < 8; q++)
+            v[q] = live ? *(const double2 *)(base + (size_t)q * (N / 8) * (N * nz) * sizeof(double2) + off) : make_double2(0.0, 0.0);
+        // (jt is j, but not to the compiler: the twiddles and window factors of a thread are the same for every item, and kept in
+        // registers across the loop - 70 of them - they leave no room for two blocks per CU)
+        int jt = j;
+        asm volatile("" : "+v"(jt));
+        xp_transform<N, -1, 1>(v, jt, c, TC, tile, tw);
+        // the modes, one at a time from the thread's own slots of the tile: with the 8 points in registers beside the polynomials of exp
+        // and log there is no room for two blocks per CU
+        __syncthreads(); // (the tile may still be read: the last exchange)
+#pragma unroll
+        for(int q = 0; q < 8; q++)
+            tile[(jt + q * (N / 8)) * TC + c] = v[q];
+        if(live) {
+#pragma unroll 1
+            for(int q = 0; q < 8; q++) {
+                fc.ix = jt + q * (N / 8);
+                fc.k2 = fourier_k2(fc.ix, fc.iy, fc.iz, N);
+                double2 m = tile[fc.ix * TC + c];
+                spectrum_mode<true, false>(fc, N, binsperunit, invsinc2, m, s, acc, asmth2, pot_factor, NuArgs{});
+                tile[fc.ix * TC + c] = m;
+            }
+        }
+        xp_gather<N>(v, jt, tile, TC, c);
+        xp_transform<N, 1, 1>(v, jt, c, TC, tile, tw);
+        if(live) {
+#pragma unroll
+            for(int q = 0; q < 8; q++)
+                *(double2 *)(base + (size_t)q * (N / 8) * (N * nz) * sizeof(double2) + off) = v[q];
+        }
+    }
+    __syncthreads();
+    spectrum_flush(nbins, s, acc, modes);
 }
 
 // plane_neutrino_correction_transfer, plane.c:291-311: every mode times nufac - 1 (the same table, clamps and interpolation as NU above,
@@ -562,11 +819,66 @@ void PMesh::ensure_single()
     real.reserve(nreal);
     rho_k.reserve(2 * ncplx);
     work_k.reserve(2 * ncplx);
+    have_plans = true;
+}
+
+void PMesh::ensure_3d()
+{
+    if(plan_r2c.ready())
+        return;
     // x slowest, z fastest: rocFFT takes the lengths fastest first; contiguous real mesh <-> Nmesh^2 (Nmesh/2 + 1) Hermitian half
     const size_t len3[3] = {(size_t)nmesh, (size_t)nmesh, (size_t)nmesh};
     plan_r2c.create(rocfft_placement_notinplace, rocfft_transform_type_real_forward, 3, len3, 1);
     plan_c2r.create(rocfft_placement_notinplace, rocfft_transform_type_real_inverse, 3, len3, 1);
-    have_plans = true;
+}
+
+bool PMesh::xpass_usable() const { return xp_supported(nmesh) && !kspace_force && !nu_fn && measure_power; }
+
+using XpKernel = void (*)(const double2 *, const double *, double2 *, double *, unsigned long long *, double, double);
+static XpKernel xp_kernel(int nmesh)
+{
+    switch(nmesh) {
+    case 64: return k_xpass_solve<64>;
+    case 128: return k_xpass_solve<128>;
+    case 256: return k_xpass_solve<256>;
+    case 512: return k_xpass_solve<512>;
+    case 1024: return k_xpass_solve<1024>;
+    }
+    return nullptr;
+}
+static size_t xp_lds_bytes(int nmesh) { return (size_t)nmesh * xp_cols(nmesh) * sizeof(double2) + (size_t)nmesh * 3 * sizeof(double); }
+
+void PMesh::ensure_xpass(hipStream_t st)
+{
+    if(plan2_r2c.ready())
+        return;
+    const size_t len2[2] = {(size_t)nmesh, (size_t)nmesh};
+    plan2_r2c.create(rocfft_placement_notinplace, rocfft_transform_type_real_forward, 2, len2, (size_t)nmesh);
+    plan2_c2r.create(rocfft_placement_notinplace, rocfft_transform_type_real_inverse, 2, len2, (size_t)nmesh);
+    std::vector<double> tw(2 * (size_t)nmesh);
+    for(int m = 0; m < nmesh; m++) { // in extended precision, rounded once
+        const long double a = -2 * M_PIl * m / nmesh;
+        tw[2 * m] = (double)cosl(a);
+        tw[2 * m + 1] = (double)sinl(a);
+    }
+    xp_tw.reserve(tw.size());
+    MPG_HIP(hipMemcpyAsync(xp_tw.p, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    MPG_HIP(hipStreamSynchronize(st));
+    // (the tile and the histograms are more than the 64 KiB a launch may ask for unannounced)
+    MPG_HIP(hipFuncSetAttribute((const void *)xp_kernel(nmesh), hipFuncAttributeMaxDynamicSharedMemorySize, (int)xp_lds_bytes(nmesh)));
+    // two blocks per CU hold a tile each, and a block's share is whole work items
+    int dev = 0, cus = 0;
+    MPG_HIP(hipGetDevice(&dev));
+    MPG_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const int items = nmesh * (nmesh / 2 / xp_cols(nmesh) + 1);
+    xp_blocks = std::max(1, std::min(items, 2 * cus));
+}
+
+void PMesh::xpass_solve(hipStream_t st)
+{
+    ps_zero(st);
+    hipLaunchKernelGGL(xp_kernel(nmesh), dim3(xp_blocks), dim3(nmesh / 8 * xp_cols(nmesh)), xp_lds_bytes(nmesh), st, (const double2 *)xp_tw.p,
+                       (const double *)invsinc2.p, (double2 *)rho_k.p, ps_acc.p, ps_modes.p, asmth2(), pot_factor());
 }
 
 void PMesh::ps_zero(hipStream_t st)
@@ -663,11 +975,11 @@ const float *PMesh::tracer_mass(int64_t n, const float *d_mass, const uint8_t *d
 
 void PMesh::destroy()
 {
-    if(have_plans) {
-        plan_r2c.destroy();
-        plan_c2r.destroy();
-        have_plans = false;
-    }
+    plan_r2c.destroy();
+    plan_c2r.destroy();
+    plan2_r2c.destroy();
+    plan2_c2r.destroy();
+    have_plans = false;
     slab_destroy();
     real.release();
     rho_k.release();
@@ -688,7 +1000,7 @@ void PMesh::deposit(int64_t n, const double *d_pos, const float *d_mass, const u
     const bool whole = x0 == 0 && P == nmesh;
     auto plain = [&]() {
         if(whole)
-            hipLaunchKernelGGL(k_cic_deposit, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_mass, d_active, cellsize, nmesh, mesh);
+            hipLaunchKernelGGL(k_cic_deposit, dim3(nblk(2 * n)), dim3(256), 0, st, n, d_pos, d_mass, d_active, cellsize, nmesh, mesh);
         else
             hipLaunchKernelGGL(k_cic_deposit_slab, dim3(nblk(n)), dim3(256), 0, st, n, d_pos, d_mass, d_active, cellsize, nmesh, x0, P, mesh);
     };
@@ -790,6 +1102,7 @@ double PMesh::plane_nu_correction(int64_t n, const double *d_pos, const float *d
     MPG_CHECK(!slab.ready, "potential planes: the massive-neutrino correction is not available while the mesh is in its slab-decomposed form");
     MPG_CHECK(fn && box_mpc > 0, "potential planes: the massive-neutrino correction needs a callback and BoxSize_in_MPC > 0");
     ensure_single();
+    ensure_3d();
     const size_t nreal = (size_t)nmesh * nmesh * nmesh, nb = (size_t)nmesh;
     // what the last PM step left for mpg_gravpm_get_powerspectrum is set aside
     // (ps_valid survives gravpm_init_periodic: after a change of Nmesh without a PM step the accumulators are still the old mesh's and
@@ -872,19 +1185,35 @@ void PMesh::force(int64_t n, const double *d_pos, const float *d_mass, const uin
         deposit(n, d_pos, d_mass, d_active, real.p, 0, nmesh, dep_single, st, tm);
     if(tm)
         tm->lap(st, &tm->t.pm_deposit);
-    plan_r2c.exec(real.p, rho_k.p, st);
-    lap(t_fft);
     static const bool fuse_ps = !(getenv("MPG_PM_FUSE_PS") && getenv("MPG_PM_FUSE_PS")[0] == '0');
-    if(fuse_ps) // P(k) and the potential transfer in one pass over rho_k (round 6)
-        transfer_stage<false, true>(TR_BOTH, rho_k.p, nmesh, 0, 2048, st);
-    else
-        transfer_stage<false, false>(TR_BOTH, rho_k.p, nmesh, 0, 2048, st);
-    lap(t_tr);
+    // the default step on a mesh the kernel is built for: 2-D transforms over (y, z) and the x-transforms fused with the transfer stage
+    // (k_xpass_solve); MPG_PM_XPASS=0 (read on every call) keeps the 3-D plans
+    const char *xe = getenv("MPG_PM_XPASS");
+    const bool xpass = fuse_ps && xpass_usable() && !(xe && xe[0] == '0');
+    if(xpass) {
+        ensure_xpass(st);
+        plan2_r2c.exec(real.p, rho_k.p, st);
+        lap(t_fft);
+        xpass_solve(st);
+        lap(t_tr);
+        plan2_c2r.exec(rho_k.p, real.p, st);
+    }
+    else {
+        ensure_3d();
+        plan_r2c.exec(real.p, rho_k.p, st);
+        lap(t_fft);
+        if(fuse_ps) // P(k) and the potential transfer in one pass over rho_k (round 6)
+            transfer_stage<false, true>(TR_BOTH, rho_k.p, nmesh, 0, 2048, st);
+        else
+            transfer_stage<false, false>(TR_BOTH, rho_k.p, nmesh, 0, 2048, st);
+        lap(t_tr);
+    }
     // functions[] = Potential, ForceX, ForceY, ForceZ (gravpm.c:32-39).  Default: one inverse transform (the potential), the
     // forces by differencing it in real space (k_cic_readout_stencil: the same operator as force_transfer); kspace_force restores
     // the reference's four inverse transforms.
     if(!kspace_force) {
-        plan_c2r.exec(rho_k.p, real.p, st); // rho_k is consumed: it is not needed again
+        if(!xpass)
+            plan_c2r.exec(rho_k.p, real.p, st); // rho_k is consumed: it is not needed again
         lap(t_fft);
         // potential and forces in one read-out pass straight from the potential mesh (k_cic_readout_stencil)
         if(n > 0)
@@ -1025,11 +1354,11 @@ void PMesh::slab_init(int rank, int world)
     slab.C.reserve(2 * (size_t)slab.P * nmesh * nz);
     slab.rho_k.reserve(2 * (size_t)nmesh * S);
     // the single-GPU meshes and plans are not needed in this form
-    if(have_plans) {
-        plan_r2c.destroy();
-        plan_c2r.destroy();
-        have_plans = false;
-    }
+    plan_r2c.destroy();
+    plan_c2r.destroy();
+    plan2_r2c.destroy();
+    plan2_c2r.destroy();
+    have_plans = false;
     real.release();
     rho_k.release();
     work_k.release();
