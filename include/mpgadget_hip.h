@@ -547,7 +547,8 @@ int mpg_metals_export(mpg_engine *eng, int64_t n, double *radius, int32_t *itera
  *       arithmetic the reference's capped additions in any order, all additions being positive - and adds the velocity sum.
  *   its post-process (:955-990)  BHP.Mass, the momentum-conserving velocity, the Mtrack / P.Mass rule, KineticFdbkEnergy reset.
  * NOT CARRIED (an error return naming the setting; the shim keeps the CPU walks): BlackHoleFeedbackMethod with BH_FEEDBACK_OPTTHIN,
- * BHFeedbackUseTcool == 2.  Dynamical friction and repositioning (bhdynfric.c) are not part of this call: DFAccel arrives as data.
+ * BHFeedbackUseTcool == 2.  Dynamical friction and repositioning (bhdynfric.c) are not part of this call: DFAccel arrives as data, from
+ * mpg_dev_blackhole_dynfric (below), which blackhole() calls first.
  * With no target nothing is read beyond the queue pass, nothing is written and no tree is demanded.  Garbage and swallowed rows carry
  * type 7 (as in every dev call).  One rank only: there is no mpg_dist_* form. */
 typedef struct mpg_blackhole_params {
@@ -631,6 +632,79 @@ int mpg_blackhole_get_stats(mpg_engine *eng, int64_t stats[8]);
  * the feedback walk and the read-back of its length (a host round trip between [0] and [1]) are in none of the three. */
 int mpg_blackhole_get_times(mpg_engine *eng, double ms[3]);
 
+/* ---- black-hole dynamical friction and the potential minimum: blackhole_dynfric + blackhole_dfaccel, libgadget/bhdynfric.c
+ * (blackhole.c:254-256, the first two calls of blackhole()) -----------------------------------------------------------------------------
+ * THE TREE: the call builds the tree of its type mask itself, without moments - stars and black holes, with the DM when
+ * BH_DynFrictionMethod > 1, with the gas when it is 3, every type when BlackHoleRepositionEnabled (blackhole_dynfric_treemask, :66-81) -
+ * and that tree is the engine's current tree when the call returns, as after find_vel_disp.  With method 0 and no repositioning nothing is
+ * read or written and no tree is built; with no target no tree is built either.
+ * Targets: the listed, not swallowed black holes; with method > 0 those whose active_dynfric byte is set (the caller's
+ * is_timebin_active(BHP.TimeBinDynFric, Ti_Current); NULL: all); with method 0 and repositioning every listed black hole, and only the
+ * potential minimum is searched (blackhole_minpot).  One pass per target over every particle of the tree with r^2 < Hsml^2 (asymmetric):
+ *   the potential minimum   the particle of smallest Potential, starting from the target's own Potential and position; a neighbour wins
+ *       only when strictly lower.  minpot / minpotpos are always written for a target; minpotvel (the neighbour's raw Vel) and
+ *       jumptominpot = BlackHoleRepositionEnabled only when a lower neighbour exists.  THE ONE DEFINED DIFFERENCE: among neighbours of
+ *       EQUAL lowest potential the reference keeps the one it visits first; the engine keeps the one of smaller particle index.
+ *   the friction sums (method > 0) over the stars, the DM (method > 1) and the gas (method 3): sum m wk, sum m wk v[k], sum m wk v[k]^2
+ *       with wk = density_kernel_wk(r / Hsml) and v = DM_VelPred / SPH_VelPred (gas); then rms = sqrt(rms / density), vel /= density, or,
+ *       for density == 0, the target is counted in ZeroDF.  df_density / df_vel / df_rmsvel are overwritten for targets and untouched
+ *       for every other row.
+ * Then, with method > 0, blackhole_compute_dfaccel (:86-145) for EVERY listed black hole, target or not, from the stored sums; a
+ * non-finite relative velocity (the reference's endrun(6)) is an error return.  One rank only: there is no mpg_dist_* form. */
+typedef struct mpg_bh_dynfric_params {
+    int BH_DynFrictionMethod; /* 0 off, 1 stars, 2 + DM, 3 + gas */
+    int BH_DFBoostFactor;
+    double BH_DFbmax;
+    int BlackHoleRepositionEnabled;
+    double GravInternal;
+    int DensityKernelType;    /* GetDensityKernelType() */
+} mpg_bh_dynfric_params;
+/* all arrays in particle order, n entries (x 3 where noted); entries of rows that are no black holes are ignored in the BHP members */
+typedef struct mpg_bh_dynfric_arrays {
+    /* read */
+    const double *vel;             /* [n][3] P.Vel */
+    const double *gacc;            /* [n][3] P.FullTreeGravAccel (method > 0) */
+    const double *gpm;             /* [n][3] P.GravPM (method > 0) */
+    const double *hydroacc;        /* [n][3] SphP.HydroAccel (method 3) */
+    const uint8_t *tb_grav;        /* P.TimeBinGravity (method > 0) */
+    const uint8_t *tb_hydro;       /* P.TimeBinHydro (method 3) */
+    const double *hsml;            /* P.Hsml of the black holes */
+    const double *potential;       /* P.Potential */
+    const double *bh_mass;         /* BHP.Mass (method > 0: ZeroDFMass) */
+    const uint8_t *active_dynfric; /* optional: is_timebin_active(BHP.TimeBinDynFric, Ti_Current); NULL: all */
+    /* in / out (method > 0; jumptominpot always) */
+    double *df_density;            /* BHP.DF_SurroundingDensity */
+    double *df_vel;                /* [n][3] BHP.DF_SurroundingVel */
+    double *df_rmsvel;             /* BHP.DF_SurroundingRmsVel */
+    int32_t *jumptominpot;         /* BHP.JumpToMinPot */
+    /* out */
+    double *minpot;                /* BHP.MinPot */
+    double *minpotpos;             /* [n][3] BHP.MinPotPos */
+    double *minpotvel;             /* [n][3] BHP.MinPotVel */
+    double *dfaccel;               /* [n][3] BHP.DFAccel (method > 0) */
+} mpg_bh_dynfric_arrays;
+int mpg_set_bh_dynfric_params(mpg_engine *eng, const mpg_bh_dynfric_params *par);
+/* on the bound particles; d_active NULL = all particles.  T supplies FgravkickB, gravkicks, hydrokicks and atime. */
+int mpg_dev_blackhole_dynfric(mpg_engine *eng, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive);
+/* host form: `pv` supplies Pos / Mass / Type; the members of `A` are HOST arrays.  The queue pass runs first: without a target (and, for
+ * method > 0, without a listed black hole) no array travels. */
+int mpg_blackhole_dynfric(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T,
+                          const int *ActiveParticle, int64_t NumActiveParticle);
+/* on a resident gas run: Pos, Mass, Vel, the accelerations (HydroAccel: the resident hydroacc_out), the time bins, Hsml and Potential are
+ * the resident columns (those members of `A` are not read); the per-black-hole members (HOST arrays) travel.  mpg_resident_sph_blackhole
+ * after this call finds another tree than its own and builds it. */
+int mpg_resident_sph_blackhole_dynfric(mpg_engine *eng, const mpg_particle_view *pv, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T,
+                                       const int *ActiveParticle, int64_t NumActiveParticle);
+/* statistics of the last call: [0] targets, [1] candidates distance-tested, [2] neighbours found, [3] ZeroDF (targets with no density),
+ * [4] listed black holes; *zerodfmass their summed BHP.Mass (may be NULL) */
+int mpg_bh_dynfric_get_stats(mpg_engine *eng, int64_t stats[5], double *zerodfmass);
+/* device time of the last call in ms from events on the engine's stream: [0] the walk with its post-process, [1] the DFAccel pass */
+int mpg_bh_dynfric_get_times(mpg_engine *eng, double ms[2]);
+/* the walk's per-target state of the last call, n entries each (any may be NULL): the raw sums before the post-process ([n][5]: sum m wk,
+ * sum m wk v[3], sum m wk v^2), the particle of the potential minimum (-1: none lower than the target), the tree particles inside Hsml.
+ * Rows that were no targets hold -1 in minidx and numngb. */
+int mpg_bh_dynfric_export(mpg_engine *eng, int64_t n, double *rawsums, int32_t *minidx, int32_t *numngb);
+
 /* ---- introspection (tests, bench roofline accounting) ----------------------------------------- */
 typedef struct mpg_tree_stats {
     int64_t NumParticles; /* particles in the tree */
@@ -684,7 +758,8 @@ int mpg_dev_grav_short_pair(mpg_engine *eng, const int *d_active, int64_t nactiv
 /* ---- time integration on device-resident arrays: the streaming loops the reference runs between force
  * steps.  Arrays are in particle order with n entries; flags[i] is the bit-field byte of struct particle_data (bit 0 IsGarbage,
  * bit 1 Swallowed; may be NULL).  Results are bit-identical to the reference's loops (no FMA contraction).
- * Not carried: black-hole repositioning (drift.c:33-55) and the dynamic-friction / drag kicks of type 5 (timestep.c:1003-1010). */
+ * Black-hole repositioning (drift.c:31-53) and the dynamic-friction / drag kicks of type 5 (timestep.c:1007-1013) are calls of their own:
+ * mpg_dev_reposition_blackholes before the drift, mpg_dev_apply_bh_subgrid_kick after a half kick. */
 #define MPG_TIMEBINS 46 /* timebinmgr.h:8 */
 typedef struct mpg_kick_factors_s {
     double gravkick[MPG_TIMEBINS + 1];  /* get_exact_gravkick_factor(Ti_kick[bin], Ti_kick[bin] + dti/2); 0 for inactive bins */
@@ -714,6 +789,19 @@ int mpg_dev_apply_half_kick(mpg_engine *eng, int64_t n, const int *d_active, int
 int mpg_dev_apply_hydro_half_kick(mpg_engine *eng, int64_t n, const int *d_active, int64_t nactive, double *d_vel, const unsigned char *d_type,
                                   const unsigned char *d_flags, const unsigned char *d_tb_hydro, const double *d_hydroaccel, double *d_entropy,
                                   const double *d_dtentropy, const mpg_kick_factors *K);
+/* the kicks of do_hydro_kick for black holes (timestep.c:1007-1013): for the live type-5 rows among the listed particles (d_active == NULL:
+ * all n) Vel += DFAccel * K->gravkick[TimeBinHydro], then Vel += DragAccel * K->gravkick[TimeBinHydro] - two additions per component, in that
+ * order.  Called after mpg_dev_apply_half_kick or mpg_dev_apply_hydro_half_kick (which leave type 5 alone), a black hole's velocity is
+ * bit-identical to the reference's.  d_tb_hydro NULL: bin 0.  A hydro bin above MPG_TIMEBINS is an error. */
+int mpg_dev_apply_bh_subgrid_kick(mpg_engine *eng, int64_t n, const int *d_active, int64_t nactive, double *d_vel, const unsigned char *d_type,
+                                  const unsigned char *d_flags, const unsigned char *d_tb_hydro, const double *d_dfaccel, const double *d_dragaccel,
+                                  const mpg_kick_factors *K);
+/* the jump of the black holes to their potential minimum (real_drift_particle, drift.c:31-53), to be called BEFORE
+ * mpg_dev_drift_all_particles when BlackHoleRepositionEnabled: a live black hole whose JumpToMinPot is set takes MinPotPos / MinPotVel; the
+ * flag of every live black hole is cleared.  Returns non-zero (the reference's endrun(1)) when NEAREST(Pos - MinPotPos) exceeds
+ * 0.1 BoxSize along an axis - the reference's signed test - and leaves that black hole where it is. */
+int mpg_dev_reposition_blackholes(mpg_engine *eng, int64_t n, double *d_pos, double *d_vel, const unsigned char *d_type, const unsigned char *d_flags,
+                                  int32_t *d_jumptominpot, const double *d_minpotpos, const double *d_minpotvel, double BoxSize);
 
 /* get_timestep_gravity_dloga (timestep.c:1039-1074) for every particle: dloga = H * sqrt(2 ErrTolIntAccuracy a (FORCE_SOFTENING/2.8)
  * / |a_phys|), a_phys = (FullTreeGravAccel + GravPM) / a^2.  Uses the softening set by mpg_gravshort_set_softenings. */
@@ -776,8 +864,8 @@ int mpg_dev_hierarchical_gravity_accelerations(mpg_engine *eng, const mpg_hiergr
 /* find_hydro_timesteps (timestep.c:617-733), the assignment of the hydro time bins of the active gas / black-hole particles, in its two
  * halves: the particle loop on the device (new bin from get_timestep_hydro_dloga through convert_timestep_to_ti and get_timebin_from_dti,
  * never above the particle's gravity bin, written to TimeBinHydro when old and new bin are active), and - after the caller's MPI_Allreduce of
- * the smallest bin and the counts, where it has ranks - the update of times->mintimebin (host).  Not carried: the dynamic-friction bins of the
- * black holes (timestep.c:676-695).  Uses the particles bound with mpg_dev_bind_particles for n. */
+ * the smallest bin and the counts, where it has ranks - the update of times->mintimebin (host).  The dynamic-friction bins of the
+ * black holes (timestep.c:676-695) are mpg_dev_find_dynfric_timesteps, called after this.  Uses the particles bound with mpg_dev_bind_particles for n. */
 typedef struct {
     const unsigned char *d_type;          /* P[].Type; NULL: no gas */
     const unsigned char *d_flags;         /* bit 0 IsGarbage, bit 1 Swallowed; may be NULL */
@@ -796,6 +884,28 @@ typedef struct {
 int mpg_dev_find_hydro_timesteps(mpg_engine *eng, const mpg_hydrostep_arrays *A, const int *d_active, int64_t NumActiveParticle,
                                  const mpg_drift_kick_times *times, const mpg_timeline *timeline, const mpg_timestep_params *par, double CourantFac,
                                  double atime, double hubble, mpg_hydrostep_result *out);
+/* the dynamic-friction bins of the black holes (timestep.c:676-691): get_timestep_dynfric_dloga (timestep.c:1119-1145) through
+ * convert_timestep_to_ti and get_timebin_from_dti (with BHP.TimeBinDynFric as the old bin), clamped into [TimeBinHydro, TimeBinGravity] and
+ * written to d_tb_dynfric, for the live black holes among the listed particles.  Call it AFTER mpg_dev_find_hydro_timesteps: it reads the
+ * new hydro bin.  Returns the sum and the maximum of bin - TimeBinHydro and the number of black holes (the reference's message). */
+typedef struct {
+    const unsigned char *d_type;
+    const unsigned char *d_flags;     /* bit 0 IsGarbage, bit 1 Swallowed; may be NULL */
+    const double *d_vel;              /* [n][3] P[].Vel */
+    const double *d_df_vel;           /* [n][3] BHP().DF_SurroundingVel */
+    const double *d_hsml, *d_dthsml;  /* P[].Hsml, P[].DtHsml (may be NULL: zero) */
+    const unsigned char *d_tb_grav;   /* P[].TimeBinGravity; NULL: no cap */
+    const unsigned char *d_tb_hydro;  /* P[].TimeBinHydro, as mpg_dev_find_hydro_timesteps left it */
+    unsigned char *d_tb_dynfric;      /* BHP().TimeBinDynFric per particle, updated */
+} mpg_dynfricstep_arrays;
+typedef struct {
+    int64_t dynratio; /* sum of bin_dynfric - TimeBinHydro (MPI_SUM) */
+    int maxdyndiff;   /* its maximum */
+    int64_t nbh;      /* black holes (MPI_SUM) */
+} mpg_dynfricstep_result;
+int mpg_dev_find_dynfric_timesteps(mpg_engine *eng, const mpg_dynfricstep_arrays *A, const int *d_active, int64_t NumActiveParticle,
+                                   const mpg_drift_kick_times *times, const mpg_timeline *timeline, const mpg_timestep_params *par, double CourantFac,
+                                   double atime, double hubble, mpg_dynfricstep_result *out);
 /* the tail of find_hydro_timesteps (timestep.c:709-733) with the all-reduced smallest bin: the rule for a bin without active particles,
  * set_bh_first_timestep on the first step (d_type / d_tb_hydro of n particles; may be NULL when isFirstTimeStep == 0), times->mintimebin */
 int mpg_dev_hydro_timesteps_finish(mpg_engine *eng, int mTimeBin_global, int isFirstTimeStep, int64_t n, const unsigned char *d_type,

@@ -705,6 +705,34 @@ int mpg_dev_apply_hydro_half_kick(mpg_engine *eng, int64_t n, const int *d_activ
     API_END
 }
 
+int mpg_dev_apply_bh_subgrid_kick(mpg_engine *eng, int64_t n, const int *d_active, int64_t nactive, double *d_vel, const unsigned char *d_type,
+                                  const unsigned char *d_flags, const unsigned char *d_tb_hydro, const double *d_dfaccel, const double *d_dragaccel,
+                                  const mpg_kick_factors *K)
+{
+    API_BEGIN
+    MPG_CHECK(eng && d_vel && d_type && d_dfaccel && d_dragaccel && K && n >= 0 && nactive >= 0, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    eng->ts_flag.reserve(4);
+    MPG_HIP(hipMemsetAsync(eng->ts_flag.p, 0, sizeof(unsigned), eng->stream));
+    launch_bh_subgrid_kick(n, d_active, nactive, d_vel, d_type, d_flags, d_tb_hydro, d_dfaccel, d_dragaccel, *K, eng->ts_flag.p, eng->stream);
+    MPG_CHECK(read_flag(eng, eng->ts_flag.p) == 0, "black-hole sub-grid kick: a black hole has an unexpected hydro time bin (> TIMEBINS)");
+    API_END
+}
+
+int mpg_dev_reposition_blackholes(mpg_engine *eng, int64_t n, double *d_pos, double *d_vel, const unsigned char *d_type, const unsigned char *d_flags,
+                                  int32_t *d_jumptominpot, const double *d_minpotpos, const double *d_minpotvel, double BoxSize)
+{
+    API_BEGIN
+    MPG_CHECK(eng && d_pos && d_vel && d_type && d_jumptominpot && d_minpotpos && d_minpotvel && n >= 0 && BoxSize > 0, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    eng->ts_flag.reserve(4);
+    MPG_HIP(hipMemsetAsync(eng->ts_flag.p, 0, sizeof(unsigned), eng->stream));
+    launch_reposition_blackholes(n, d_pos, d_vel, d_type, d_flags, d_jumptominpot, d_minpotpos, d_minpotvel, BoxSize, eng->ts_flag.p, eng->stream);
+    MPG_CHECK(read_flag(eng, eng->ts_flag.p) == 0,
+              "reposition: drifting a black hole very far (more than 0.1 BoxSize to its potential minimum): the time step is too sparse");
+    API_END
+}
+
 int mpg_dev_timestep_gravity_dloga(mpg_engine *eng, int64_t n, const double *d_gravaccel, const double *d_gravpm, double atime, double hubble,
                                    double ErrTolIntAccuracy, double *d_dloga)
 {
@@ -1212,6 +1240,40 @@ int mpg_dev_find_hydro_timesteps(mpg_engine *eng, const mpg_hydrostep_arrays *A,
     out->badstepsizecount = (int64_t)h[5];
     out->badtimebins = (int64_t)h[6];
     out->mTimeBin = (int)h[7];
+    API_END
+}
+
+// the dynamic-friction bins of the black holes (timestep.c:676-691), after mpg_dev_find_hydro_timesteps: it reads the new hydro bin
+int mpg_dev_find_dynfric_timesteps(mpg_engine *eng, const mpg_dynfricstep_arrays *A, const int *d_active, int64_t NumActiveParticle,
+                                   const mpg_drift_kick_times *times, const mpg_timeline *timeline, const mpg_timestep_params *par, double CourantFac,
+                                   double atime, double hubble, mpg_dynfricstep_result *out)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A && times && timeline && par && out, "null argument");
+    MPG_CHECK(A->d_type && A->d_vel && A->d_df_vel && A->d_hsml && A->d_tb_hydro && A->d_tb_dynfric,
+              "find_dynfric_timesteps: the arrays type, vel, df_vel, hsml, tb_hydro and tb_dynfric are needed");
+    MPG_CHECK(timeline->nsync >= 2 && timeline->loga, "find_dynfric_timesteps: the timeline needs at least two sync points");
+    MPG_HIP(hipSetDevice(eng->device));
+    const int64_t nact = d_active ? NumActiveParticle : eng->n;
+    eng->hier_sp.reserve((size_t)timeline->nsync + MPG_TIMEBINS + 2);
+    MPG_HIP(hipMemcpyAsync(eng->hier_sp.p, timeline->loga, (size_t)timeline->nsync * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+    HierTimeline T;
+    T.sp = eng->hier_sp.p;
+    T.nsync = (int)timeline->nsync;
+    T.loga_cur = host_loga_from_ti(timeline, times->Ti_Current);
+    T.ti0 = host_ti_from_loga(timeline, T.loga_cur);
+    T.MinSizeTimestep = par->MinSizeTimestep;
+    eng->hier_cnt.reserve(64);
+    unsigned long long h[3] = {0, 0, 0};
+    MPG_HIP(hipMemcpyAsync(eng->hier_cnt.p, h, sizeof(h), hipMemcpyHostToDevice, eng->stream));
+    launch_find_dynfric_timesteps(d_active, nact, A->d_type, A->d_flags, A->d_vel, A->d_df_vel, A->d_hsml, A->d_dthsml, A->d_tb_grav, A->d_tb_hydro,
+                                  A->d_tb_dynfric, atime, hubble, par->ErrTolIntAccuracy, CourantFac, T, times->PM_length, times->Ti_Current,
+                                  eng->hier_cnt.p, eng->stream);
+    MPG_HIP(hipMemcpyAsync(h, eng->hier_cnt.p, sizeof(h), hipMemcpyDeviceToHost, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    out->dynratio = (int64_t)h[0];
+    out->maxdyndiff = (int)h[1];
+    out->nbh = (int64_t)h[2];
     API_END
 }
 
@@ -1974,6 +2036,128 @@ int mpg_blackhole_get_times(mpg_engine *eng, double ms[3])
     MPG_CHECK(eng && ms, "null argument");
     for(int k = 0; k < 3; k++)
         ms[k] = eng->bh.last_ms[k];
+    API_END
+}
+
+/* ------------------------------ black-hole dynamical friction and the potential minimum (bhdynfric.c) ------------------------------ */
+
+int mpg_set_bh_dynfric_params(mpg_engine *eng, const mpg_bh_dynfric_params *par)
+{
+    API_BEGIN
+    MPG_CHECK(eng && par, "null argument");
+    MPG_CHECK(par->BH_DynFrictionMethod >= 0 && par->BH_DynFrictionMethod <= 3, "dynamical friction parameters: BH_DynFrictionMethod is 0, 1, 2 or 3");
+    MPG_CHECK(par->BH_DynFrictionMethod == 0 || par->GravInternal > 0, "dynamical friction parameters: GravInternal must be positive");
+    (void)kernel_index(par->DensityKernelType); // (an unknown kernel type is an error here, not at the first call)
+    eng->dfpar = *par;
+    eng->have_dfpar = true;
+    API_END
+}
+
+// blackhole_dynfric_treemask, bhdynfric.c:66-81
+static int dynfric_treemask(const mpg_bh_dynfric_params &P)
+{
+    int mask = 16 + 32; // STARMASK + BHMASK
+    if(P.BH_DynFrictionMethod > 1)
+        mask += 2; // DMMASK
+    if(P.BH_DynFrictionMethod > 2)
+        mask += 1; // GASMASK
+    if(P.BlackHoleRepositionEnabled)
+        mask = 63; // ALLMASK
+    return mask;
+}
+
+int64_t dynfric_listed(mpg_engine *eng, const int *d_active, int64_t nactive)
+{
+    MPG_CHECK(eng && nactive >= 0, "blackhole_dynfric: null engine or negative list length");
+    MPG_CHECK(eng->have_dfpar, "blackhole_dynfric: no parameters (mpg_set_bh_dynfric_params first)");
+    MPG_HIP(hipSetDevice(eng->device));
+    eng->df.reset();
+    if(eng->dfpar.BH_DynFrictionMethod == 0 && !eng->dfpar.BlackHoleRepositionEnabled)
+        return 0;
+    const uint8_t *flags = eng->sph.mark_active(d_active, nactive, eng->n, eng->stream);
+    eng->df.make_queues(eng->d_type, flags, nullptr, 0, eng->n, eng->stream);
+    return eng->df.nlisted;
+}
+
+void dynfric_call(mpg_engine *eng, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive)
+{
+    MPG_CHECK(eng && A && T, "null argument");
+    MPG_CHECK(nactive >= 0, "blackhole_dynfric: negative list length");
+    MPG_CHECK(eng->have_dfpar, "blackhole_dynfric: no parameters (mpg_set_bh_dynfric_params first)");
+    MPG_CHECK(eng->d_pos || eng->n == 0, "blackhole_dynfric: no particles bound");
+    MPG_HIP(hipSetDevice(eng->device));
+    const mpg_bh_dynfric_params &P = eng->dfpar;
+    const int method = P.BH_DynFrictionMethod;
+    eng->df.reset();
+    if(method == 0 && !P.BlackHoleRepositionEnabled) // bhdynfric.c:356-362: nothing is read, nothing is written, no tree is built
+        return;
+    DfView v{eng->d_pos, eng->d_mass, eng->d_type, *A};
+    DfScalars S;
+    S.p = P;
+    S.ktype = kernel_index(P.DensityKernelType);
+    const uint8_t *flags = eng->sph.mark_active(d_active, nactive, eng->n, eng->stream);
+    const int64_t ntargets = eng->df.make_queues(eng->d_type, flags, method > 0 ? A->active_dynfric : nullptr, method, eng->n, eng->stream);
+    if(eng->df.nlisted == 0)
+        return;
+    // what this method reads and writes
+    MPG_CHECK(A->vel && A->hsml && A->potential && A->jumptominpot && A->minpot && A->minpotpos && A->minpotvel,
+              "blackhole_dynfric: the arrays vel, hsml, potential, jumptominpot, minpot, minpotpos and minpotvel are required");
+    if(method > 0) {
+        MPG_CHECK(A->gacc && A->gpm && A->tb_grav && A->bh_mass && A->df_density && A->df_vel && A->df_rmsvel && A->dfaccel,
+                  "blackhole_dynfric: dynamical friction needs the arrays gacc, gpm, tb_grav, bh_mass, df_density, df_vel, df_rmsvel and dfaccel");
+        MPG_CHECK(method < 3 || (A->hydroacc && A->tb_hydro), "blackhole_dynfric: BH_DynFrictionMethod 3 needs the arrays hydroacc and tb_hydro");
+    }
+    if(ntargets > 0) {
+        // force_tree_rebuild_mask(tree, ddecomp, treemask, NULL), bhdynfric.c:295 / :372: the engine's current tree is, from here on, the
+        // tree of this mask without moments
+        MPG_CALL(mpg_dev_force_tree_rebuild_mask(eng, dynfric_treemask(P), 0));
+        eng->df.walk(eng->tree, v, *T, S, eng->n, eng->stream);
+    }
+    if(method > 0) // blackhole_dfaccel: every listed black hole, target or not
+        eng->df.dfaccel(v, *T, S, eng->stream);
+}
+
+int mpg_dev_blackhole_dynfric(mpg_engine *eng, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive)
+{
+    API_BEGIN
+    dynfric_call(eng, A, T, d_active, nactive);
+    API_END
+}
+
+int mpg_bh_dynfric_get_stats(mpg_engine *eng, int64_t stats[5], double *zerodfmass)
+{
+    API_BEGIN
+    MPG_CHECK(eng && stats, "null argument");
+    for(int k = 0; k < DF_NSTATS; k++)
+        stats[k] = eng->df.last_stats[k];
+    if(zerodfmass)
+        *zerodfmass = eng->df.last_zeromass;
+    API_END
+}
+
+int mpg_bh_dynfric_get_times(mpg_engine *eng, double ms[2])
+{
+    API_BEGIN
+    MPG_CHECK(eng && ms, "null argument");
+    ms[0] = eng->df.last_ms[0];
+    ms[1] = eng->df.last_ms[1];
+    API_END
+}
+
+int mpg_bh_dynfric_export(mpg_engine *eng, int64_t n, double *rawsums, int32_t *minidx, int32_t *numngb)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    DynfricEngine &D = eng->df;
+    MPG_CHECK(n == D.n_state, "mpg_bh_dynfric_export: n is not the particle number of the last blackhole_dynfric walk");
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    if(rawsums && n > 0)
+        MPG_HIP(hipMemcpy(rawsums, D.raw.p, (size_t)DF_NRAW * n * sizeof(double), hipMemcpyDeviceToHost));
+    if(minidx && n > 0)
+        MPG_HIP(hipMemcpy(minidx, D.minidx.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(numngb && n > 0)
+        MPG_HIP(hipMemcpy(numngb, D.numngb.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     API_END
 }
 

@@ -9,6 +9,7 @@
 #include "cooling.h"
 #include "metals.h"
 #include "blackhole.h"
+#include "dynfric.h"
 #include "timestep.h"
 #include "peano.h"
 #include "planes.h"
@@ -169,6 +170,11 @@ struct mpg_engine {
     BlackholeEngine bh;
     DevBuf<char> bh_stage[BH_NFIELDS];
     HostBuf<float> bh_mass;
+    // black-hole dynamical friction and the potential minimum (dynfric.hip): parameters, the walk's state; the staging of its host forms
+    mpg_bh_dynfric_params dfpar{};
+    bool have_dfpar = false;
+    DynfricEngine df;
+    DevBuf<char> df_stage[DF_NFIELDS];
     void prefetch_join()
     {
         if(prefetch_thread.joinable())
@@ -193,6 +199,11 @@ void stage_sph(mpg_engine *eng, const mpg_sph_arrays *host, mpg_sph_arrays *dev,
 // ... and its queue pass alone: the number of targets the call would have (the host forms stage their arrays only when there is one)
 extern "C" int64_t blackhole_targets(mpg_engine *eng, const int *d_active, int64_t nactive);
 extern "C" void blackhole_call(mpg_engine *eng, const mpg_blackhole_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive, int build);
+// ... the same of the dynamical-friction call: its queue pass without the dynfric bins (returns the number of listed black holes, 0 when
+// the parameters switch the call off: then nothing would be read or written) and the call on device arrays, which builds the tree of its
+// mask when it has a target
+extern "C" int64_t dynfric_listed(mpg_engine *eng, const int *d_active, int64_t nactive);
+extern "C" void dynfric_call(mpg_engine *eng, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive);
 void host_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *par, double *planes, int64_t *npart);
 
 // potential planes (planes.hip).  red: the sums over the ranks of the several-GPU form (dist.hip), or null; sum_device returns with the

@@ -965,6 +965,30 @@ int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSiz
     API_END
 }
 
+// blackhole_dynfric + blackhole_dfaccel for the listed particles of a host table: the arrays go through df_stage / df_unstage
+// (host_table.h); nothing of the records is written.  The tree of the call's mask is built by the call itself once it has a target.
+int mpg_blackhole_dynfric(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T,
+                          const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A && T, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    const int64_t n = pv->n;
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    // the queue pass first: without a listed black hole nothing travels, nothing is read and nothing is written
+    if(dynfric_listed(eng, d_act, NumActiveParticle) == 0) {
+        mpg_err_slot().clear();
+        return 0;
+    }
+    mpg_bh_dynfric_arrays d{};
+    df_stage(*A, d, eng->df_stage, n, 0, eng->stream);
+    dynfric_call(eng, &d, T, d_act, NumActiveParticle);
+    df_unstage(*A, d, n, 0, eng->stream);
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}
+
 // blackhole() for the listed particles of a host table: Mass is the records' column (staged with the table, written back into it with
 // the flags), the other arrays go through bh_stage / bh_unstage (host_table.h).  The tree of gas and black holes and its hmax are built
 // by the call itself once it knows that it has a target.

@@ -484,6 +484,58 @@ inline void bh_unstage(const mpg_blackhole_arrays &host, const mpg_blackhole_arr
             MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.bytes, hipMemcpyDeviceToHost, st));
     }
 }
+// ... and of the dynamical-friction call (roles as above; BH_OPTIONAL here: not read by every method, checked by the call itself).  On a
+// resident gas run the table's Vel / accelerations / Potential and the SPH columns are resident; the per-black-hole members travel.
+#define MPG_DF_FIELD(m, bytes, role) {#m, offsetof(mpg_bh_dynfric_arrays, m), bytes, role}
+constexpr int DF_NFIELDS = 18;
+const BhField DF_FIELDS[DF_NFIELDS] = {
+    MPG_DF_FIELD(vel, 24, BH_IN | BH_RES_ALIAS),
+    MPG_DF_FIELD(gacc, 24, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
+    MPG_DF_FIELD(gpm, 24, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
+    MPG_DF_FIELD(hydroacc, 24, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
+    MPG_DF_FIELD(tb_grav, 1, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
+    MPG_DF_FIELD(tb_hydro, 1, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
+    MPG_DF_FIELD(hsml, 8, BH_IN | BH_RES_ALIAS),
+    MPG_DF_FIELD(potential, 8, BH_IN | BH_RES_ALIAS),
+    MPG_DF_FIELD(bh_mass, 8, BH_IN | BH_OPTIONAL),
+    MPG_DF_FIELD(active_dynfric, 1, BH_IN | BH_OPTIONAL),
+    MPG_DF_FIELD(df_density, 8, BH_IN | BH_OUT | BH_OPTIONAL),
+    MPG_DF_FIELD(df_vel, 24, BH_IN | BH_OUT | BH_OPTIONAL),
+    MPG_DF_FIELD(df_rmsvel, 8, BH_IN | BH_OUT | BH_OPTIONAL),
+    MPG_DF_FIELD(jumptominpot, 4, BH_IN | BH_OUT),
+    MPG_DF_FIELD(minpot, 8, BH_OUT),
+    MPG_DF_FIELD(minpotpos, 24, BH_OUT),
+    MPG_DF_FIELD(minpotvel, 24, BH_OUT),
+    MPG_DF_FIELD(dfaccel, 24, BH_OUT | BH_OPTIONAL),
+};
+#undef MPG_DF_FIELD
+static_assert(sizeof(mpg_bh_dynfric_arrays) == DF_NFIELDS * sizeof(void *), "DF_FIELDS describes every member of mpg_bh_dynfric_arrays");
+inline void df_stage(const mpg_bh_dynfric_arrays &host, mpg_bh_dynfric_arrays &dev, mpg::DevBuf<char> *stage, int64_t n, unsigned skip, hipStream_t st)
+{
+    for(int f = 0; f < DF_NFIELDS; f++) {
+        const BhField &F = DF_FIELDS[f];
+        if(F.role & skip)
+            continue;
+        void *h = field_get(host, F.off), *d = nullptr;
+        MPG_CHECK(h || (F.role & BH_OPTIONAL), std::string("blackhole_dynfric: the array ") + F.name + " is required");
+        if(h) {
+            stage[f].reserve((size_t)n * F.bytes + 16);
+            d = stage[f].p;
+            // (the outputs go up too: the call writes the entries of its targets only, the others come back as they were)
+            MPG_HIP(hipMemcpyAsync(d, h, (size_t)n * F.bytes, hipMemcpyHostToDevice, st));
+        }
+        field_set(dev, F.off, d);
+    }
+}
+inline void df_unstage(const mpg_bh_dynfric_arrays &host, const mpg_bh_dynfric_arrays &dev, int64_t n, unsigned skip, hipStream_t st)
+{
+    for(int f = 0; f < DF_NFIELDS; f++) {
+        const BhField &F = DF_FIELDS[f];
+        void *h = field_get(host, F.off);
+        if(h && (F.role & BH_OUT) && !(F.role & skip))
+            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.bytes, hipMemcpyDeviceToHost, st));
+    }
+}
 // the flags byte of the records: IsGarbage and Swallowed as the call left them (`flags`: n host bytes)
 inline void flags_to_records(const mpg_particle_view &V, const uint8_t *flags)
 {

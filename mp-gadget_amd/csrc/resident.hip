@@ -543,6 +543,40 @@ int mpg_resident_sph_metal_return(mpg_engine *eng, const mpg_particle_view *pv, 
     API_END
 }
 
+// blackhole_dynfric + blackhole_dfaccel on a resident gas run: Pos, Mass, Vel, the accelerations, the bins, Hsml and Potential are the
+// resident columns; the per-black-hole members travel, and only when the list holds a black hole.  Nothing resident is written.  The call
+// leaves the tree of its own mask: mpg_resident_sph_blackhole, next in blackhole(), builds the tree of gas and black holes again.
+int mpg_resident_sph_blackhole_dynfric(mpg_engine *eng, const mpg_particle_view *pv, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T,
+                                       const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A && T, "null argument");
+    resident_sph_check(eng, pv);
+    const int64_t n = pv->n;
+    const mpg_sph_arrays &r = eng->res_sph_dev;
+    MPG_CHECK(r.vel && r.gacc && r.gpm && r.hydroacc_out && r.tb_hydro && r.tb_grav && r.hsml,
+              "resident blackhole_dynfric: the gas arrays lack one of vel, gacc, gpm, hydroacc_out, tb_hydro, tb_grav, hsml");
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    if(dynfric_listed(eng, d_act, NumActiveParticle) == 0) {
+        mpg_err_slot().clear();
+        return 0;
+    }
+    mpg_bh_dynfric_arrays d{};
+    df_stage(*A, d, eng->df_stage, n, BH_RES_ALIAS, eng->stream);
+    d.vel = r.vel;
+    d.gacc = r.gacc;
+    d.gpm = r.gpm;
+    d.hydroacc = r.hydroacc_out;
+    d.tb_hydro = r.tb_hydro;
+    d.tb_grav = r.tb_grav;
+    d.hsml = r.hsml;
+    d.potential = eng->r_pot.p;
+    dynfric_call(eng, &d, T, d_act, NumActiveParticle);
+    df_unstage(*A, d, n, BH_RES_ALIAS, eng->stream);
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}
+
 // blackhole() on a resident gas run: the table's and the gas arrays' columns are the resident ones and are updated in place; the type
 // column and the integrator's flags take the rows swallowed; Mass and flags also go into the records, which the end of the resident
 // stretch does not fetch.  The per-black-hole members and ID / DelayTime travel.

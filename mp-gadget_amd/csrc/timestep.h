@@ -43,6 +43,14 @@ void launch_half_kick(int64_t n, const int *active, int64_t nactive, double *vel
                       const mpg_kick_factors &K, unsigned *err, hipStream_t st);
 void launch_hydro_half_kick(int64_t n, const int *active, int64_t nactive, double *vel, const uint8_t *type, const uint8_t *flags, const uint8_t *tbh,
                             const double *hacc, double *entropy, const double *dtentropy, const mpg_kick_factors &K, unsigned *err, hipStream_t st);
+void launch_bh_subgrid_kick(int64_t n, const int *active, int64_t nactive, double *vel, const uint8_t *type, const uint8_t *flags, const uint8_t *tbh,
+                            const double *dfaccel, const double *dragaccel, const mpg_kick_factors &K, unsigned *err, hipStream_t st);
+void launch_find_dynfric_timesteps(const int *list, int64_t nlist, const uint8_t *type, const uint8_t *flags, const double *vel, const double *df_vel,
+                                   const double *hsml, const double *dthsml, const uint8_t *tb_grav, const uint8_t *tb_hydro, uint8_t *tb_dynfric,
+                                   double atime, double hubble, double errtol, double courant, const HierTimeline &T, int64_t dti_max,
+                                   int64_t Ti_Current, unsigned long long *out, hipStream_t st);
+void launch_reposition_blackholes(int64_t n, double *pos, double *vel, const uint8_t *type, const uint8_t *flags, int *jump, const double *minpotpos,
+                                  const double *minpotvel, double box, unsigned *err, hipStream_t st);
 void launch_timestep_gravity(int64_t n, const double *gacc, const double *gpm, double atime, double hubble, double errtol, double soft,
                              double *dloga, hipStream_t st);
 } // namespace mpg

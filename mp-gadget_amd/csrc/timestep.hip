@@ -9,8 +9,11 @@
 //   k_assign_gravity_bins, k_level_gravity_bins, k_push_down_bins, k_kick_list, k_sublist_flags
 //                    the per-particle loops of the hierarchical gravity level loop             timestep.c:239-599, 1435-1478
 // The per-bin factors (get_exact_drift/gravkick/hydrokick_factor, dloga_from_dti) are computed by the caller with the
-// reference's own functions and passed in (mpg_kick_factors), as for the SPH loops.  Not carried: black-hole repositioning
-// and the dynamic-friction / drag kicks of type-5 particles (sub-grid physics, out of scope).
+// reference's own functions and passed in (mpg_kick_factors), as for the SPH loops.
+//   k_bh_subgrid_kick         the DFAccel / DragAccel kicks of type 5 in do_hydro_kick               timestep.c:1007-1013
+//   k_find_dynfric_timesteps  get_timestep_dynfric_dloga and the dynamic-friction bin                timestep.c:676-691, 1119-1145
+//   k_reposition_blackholes   the jump to the potential minimum in real_drift_particle               drift.c:31-53
+// are kernels of their own, called beside the loops above (k_half_kick and k_drift themselves leave type 5 to them).
 // Pure HBM streaming: per particle 73 B read + 32 B written (drift), 48 + 24 B (PM kick), up to 98 + 32 B (half kick), about 90 + 32 B
 // per gas particle (hydro half kick).
 // Floating-point contraction is off in this file: the reference's loops are compiled without FMA, and these results are
@@ -129,7 +132,7 @@ __global__ void __launch_bounds__(256) k_half_kick(int64_t n, const int *__restr
 // apply_hydro_half_kick (timestep.c:930-968): the hydro part of do_hydro_kick (timestep.c:1004-1036) for the gas among the listed
 // particles, in the reference's order - velocity kick, gas velocity limit, entropy - and applied whatever the factor (0 for a bin that is
 // not active or lies below mintimebin), as the reference does.  No gravity kick: FullTreeGravAccel is not read.  Other types are left
-// alone; black holes (the dynamic-friction / drag kicks of type 5) never get here, mpg_shim_resident_begin refuses them.
+// alone; the dynamic-friction / drag kicks of type 5 are k_bh_subgrid_kick's.
 __global__ void __launch_bounds__(256) k_hydro_half_kick(int64_t n, const int *__restrict__ active, int64_t nactive, double *__restrict__ vel,
                                                          const uint8_t *__restrict__ type, const uint8_t *__restrict__ flags,
                                                          const uint8_t *__restrict__ tbh, const double *__restrict__ hacc,
@@ -433,6 +436,118 @@ __global__ void __launch_bounds__(256) k_find_timesteps(const int *__restrict__ 
     }
 }
 
+// The kicks of do_hydro_kick for black holes (timestep.c:1007-1013): Vel += DFAccel * Fgravkick, then Vel += DragAccel * Fgravkick - two
+// additions per component, in that order - with Fgravkick = gravkick[TimeBinHydro], for the live type-5 rows among the listed particles
+__global__ void __launch_bounds__(256) k_bh_subgrid_kick(int64_t n, const int *__restrict__ active, int64_t nactive, double *__restrict__ vel,
+                                                         const uint8_t *__restrict__ type, const uint8_t *__restrict__ flags,
+                                                         const uint8_t *__restrict__ tbh, const double *__restrict__ dfaccel,
+                                                         const double *__restrict__ dragaccel, const mpg_kick_factors K, unsigned *__restrict__ err)
+{
+    const int64_t pa = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(pa >= (active ? nactive : n))
+        return;
+    const int64_t i = active ? active[pa] : pa;
+    if((flags && (flags[i] & 3)) || type[i] != 5)
+        return;
+    const int bh = tbh ? tbh[i] : 0;
+    if(bh > MPG_TIMEBINS) {
+        atomicExch(err, 4u);
+        return;
+    }
+    const double F = K.gravkick[bh];
+#pragma unroll
+    for(int j = 0; j < 3; j++) {
+        double v = vel[3 * i + j];
+        v += dfaccel[3 * i + j] * F;
+        v += dragaccel[3 * i + j] * F;
+        vel[3 * i + j] = v;
+    }
+}
+
+// get_timestep_dynfric_dloga (timestep.c:1119-1145) and the dynamic-friction bin of find_hydro_timesteps (timestep.c:676-691) for the live
+// black holes of the list, after their new hydro bin has been written: the bin of the crossing time of the kernel at the velocity relative
+// to the surroundings (or the total velocity when larger), or of the Hsml criterion when shorter, clamped into [TimeBinHydro,
+// TimeBinGravity].  out[0]: the sum of bin - TimeBinHydro, out[1]: its maximum, out[2]: the black holes.
+__global__ void __launch_bounds__(256) k_find_dynfric_timesteps(const int *__restrict__ list, int64_t nlist, const uint8_t *__restrict__ type,
+                                                                const uint8_t *__restrict__ flags, const double *__restrict__ vel,
+                                                                const double *__restrict__ df_vel, const double *__restrict__ hsml,
+                                                                const double *__restrict__ dthsml, const uint8_t *__restrict__ tb_grav,
+                                                                const uint8_t *__restrict__ tb_hydro, uint8_t *__restrict__ tb_dynfric, double atime,
+                                                                double hubble, double errtol, double courant, HierTimeline T, int64_t dti_max,
+                                                                int64_t Ti_Current, unsigned long long *__restrict__ out)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(k >= nlist)
+        return;
+    const int64_t i = list ? list[k] : k;
+    if((flags && (flags[i] & 3)) || (type[i] & 7) != 5)
+        return;
+    double bhvel = 0, bhvel2 = 0;
+#pragma unroll
+    for(int j = 0; j < 3; j++) {
+        const double d = vel[3 * i + j] - df_vel[3 * i + j];
+        bhvel += d * d;
+        bhvel2 += vel[3 * i + j] * vel[3 * i + j];
+    }
+    if(bhvel2 > bhvel)
+        bhvel = bhvel2;
+    bhvel = sqrt(bhvel);
+    double dt = 2 * errtol * atime * atime * hsml[i] / (bhvel + 1e-20);
+    const double dt_hsml = courant * atime * atime * fabs(hsml[i] / ((dthsml ? dthsml[i] : 0.0) + 1e-20));
+    if(dt_hsml < dt)
+        dt = dt_hsml;
+    const double dloga = dt * hubble;
+    const int64_t dti = convert_timestep_to_ti_dev(dloga, dti_max, T);
+    int bin = timebin_from_dti_dev(dti, tb_dynfric[i], Ti_Current);
+    const int bg = tb_grav ? tb_grav[i] : MPG_TIMEBINS, bh = tb_hydro[i];
+    if(bin > bg)
+        bin = bg;
+    if(bin < bh)
+        bin = bh;
+    tb_dynfric[i] = (uint8_t)bin;
+    const int diff = bin - bh;
+    atomicAdd(&out[0], (unsigned long long)(long long)diff);
+    if(diff > 0)
+        atomicMax(&out[1], (unsigned long long)diff);
+    atomicAdd(&out[2], 1ull);
+}
+
+// The jump of a black hole to the potential minimum (real_drift_particle, drift.c:31-53), before the drift: a flagged black hole takes
+// MinPotPos / MinPotVel, the flag of every live black hole is cleared.  A jump farther than 0.1 BoxSize along an axis (the reference's signed
+// test on NEAREST(Pos - MinPotPos), its endrun(1)) raises err and moves nothing.
+__global__ void __launch_bounds__(256) k_reposition_blackholes(int64_t n, double *__restrict__ pos, double *__restrict__ vel,
+                                                               const uint8_t *__restrict__ type, const uint8_t *__restrict__ flags,
+                                                               int *__restrict__ jump, const double *__restrict__ minpotpos,
+                                                               const double *__restrict__ minpotvel, double box, unsigned *__restrict__ err)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n || (flags && (flags[i] & 3)) || (type[i] & 7) != 5)
+        return;
+    if(jump[i]) {
+        bool far = false;
+#pragma unroll
+        for(int k = 0; k < 3; k++) {
+            double dx = pos[3 * i + k] - minpotpos[3 * i + k]; // NEAREST, partmanager.h:99
+            if(dx > 0.5 * box)
+                dx -= box;
+            if(dx < -0.5 * box)
+                dx += box;
+            if(dx > 0.1 * box)
+                far = true;
+        }
+        if(far) {
+            atomicExch(err, 1u);
+            return;
+        }
+#pragma unroll
+        for(int k = 0; k < 3; k++) {
+            pos[3 * i + k] = minpotpos[3 * i + k];
+            vel[3 * i + k] = minpotvel[3 * i + k];
+        }
+    }
+    jump[i] = 0;
+}
+
 // The first loop of hierarchical_gravity_and_timesteps (timestep.c:345-370): new gravity bin of every particle of the list from
 // the stored acceleration; counts[bin] += 1; bad += 1 for dti <= 1 or > TIMEBASE (print_bad_timebin).
 __global__ void __launch_bounds__(256) k_assign_gravity_bins(const int *__restrict__ list, int64_t nlist, const double *__restrict__ gacc,
@@ -541,6 +656,34 @@ __global__ void __launch_bounds__(256) k_sublist_flags(const int *__restrict__ l
         ok = (Ti_Current % ((int64_t)1 << bin)) == 0;
     value[k] = (int)pa;
     keep[k] = ok ? 1 : 0;
+}
+
+void launch_bh_subgrid_kick(int64_t n, const int *active, int64_t nactive, double *vel, const uint8_t *type, const uint8_t *flags, const uint8_t *tbh,
+                            const double *dfaccel, const double *dragaccel, const mpg_kick_factors &K, unsigned *err, hipStream_t st)
+{
+    const int64_t na = active ? nactive : n;
+    if(na > 0)
+        hipLaunchKernelGGL(k_bh_subgrid_kick, dim3(nblk(na)), dim3(256), 0, st, n, active, nactive, vel, type, flags, tbh, dfaccel, dragaccel, K, err);
+    MPG_HIP(hipGetLastError());
+}
+
+void launch_find_dynfric_timesteps(const int *list, int64_t nlist, const uint8_t *type, const uint8_t *flags, const double *vel, const double *df_vel,
+                                   const double *hsml, const double *dthsml, const uint8_t *tb_grav, const uint8_t *tb_hydro, uint8_t *tb_dynfric,
+                                   double atime, double hubble, double errtol, double courant, const HierTimeline &T, int64_t dti_max,
+                                   int64_t Ti_Current, unsigned long long *out, hipStream_t st)
+{
+    if(nlist > 0)
+        hipLaunchKernelGGL(k_find_dynfric_timesteps, dim3(nblk(nlist)), dim3(256), 0, st, list, nlist, type, flags, vel, df_vel, hsml, dthsml, tb_grav,
+                           tb_hydro, tb_dynfric, atime, hubble, errtol, courant, T, dti_max, Ti_Current, out);
+    MPG_HIP(hipGetLastError());
+}
+
+void launch_reposition_blackholes(int64_t n, double *pos, double *vel, const uint8_t *type, const uint8_t *flags, int *jump, const double *minpotpos,
+                                  const double *minpotvel, double box, unsigned *err, hipStream_t st)
+{
+    if(n > 0)
+        hipLaunchKernelGGL(k_reposition_blackholes, dim3(nblk(n)), dim3(256), 0, st, n, pos, vel, type, flags, jump, minpotpos, minpotvel, box, err);
+    MPG_HIP(hipGetLastError());
 }
 
 void launch_timestep_gravity(int64_t n, const double *gacc, const double *gpm, double atime, double hubble, double errtol, double soft,

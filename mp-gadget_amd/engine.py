@@ -137,6 +137,22 @@ class BlackholeArraysC(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in BLACKHOLE_ARRAY_FIELDS]
 
 
+BH_DYNFRIC_ARRAY_FIELDS = ("vel", "gacc", "gpm", "hydroacc", "tb_grav", "tb_hydro", "hsml", "potential", "bh_mass", "active_dynfric",
+                           "df_density", "df_vel", "df_rmsvel", "jumptominpot", "minpot", "minpotpos", "minpotvel", "dfaccel")
+BH_DYNFRIC_ARRAY_DTYPES = dict(tb_grav="uint8", tb_hydro="uint8", active_dynfric="uint8", jumptominpot="int32")
+
+
+class BhDynfricArraysC(C.Structure):
+    """mpg_bh_dynfric_arrays"""
+    _fields_ = [(k, C.c_void_p) for k in BH_DYNFRIC_ARRAY_FIELDS]
+
+
+class BhDynfricParams(C.Structure):
+    """mpg_bh_dynfric_params"""
+    _fields_ = [("BH_DynFrictionMethod", C.c_int), ("BH_DFBoostFactor", C.c_int), ("BH_DFbmax", C.c_double), ("BlackHoleRepositionEnabled", C.c_int),
+                ("GravInternal", C.c_double), ("DensityKernelType", C.c_int)]
+
+
 class BlackholeParams(C.Structure):
     """mpg_blackhole_params"""
     _fields_ = [("BlackHoleAccretionFactor", C.c_double), ("BlackHoleFeedbackFactor", C.c_double), ("BlackHoleEddingtonFactor", C.c_double),
@@ -269,6 +285,16 @@ class HydroStepArrays(C.Structure):
 class HydroStepResult(C.Structure):
     """mpg_hydrostep_result"""
     _fields_ = [("mTimeBin", C.c_int), ("ntitype", C.c_int64 * 5), ("badstepsizecount", C.c_int64), ("badtimebins", C.c_int64)]
+
+
+class DynfricStepArrays(C.Structure):
+    """mpg_dynfricstep_arrays: device arrays of the dynamic-friction bins"""
+    _fields_ = [(k, C.c_void_p) for k in ("d_type", "d_flags", "d_vel", "d_df_vel", "d_hsml", "d_dthsml", "d_tb_grav", "d_tb_hydro", "d_tb_dynfric")]
+
+
+class DynfricStepResult(C.Structure):
+    """mpg_dynfricstep_result"""
+    _fields_ = [("dynratio", C.c_int64), ("maxdyndiff", C.c_int), ("nbh", C.c_int64)]
 
 
 class TimestepResult(C.Structure):
@@ -839,6 +865,30 @@ class Engine:
                                                         C.c_int64(0 if active is None else active.shape[0]), _ptr(vel), _ptr(type), _ptr(flags),
                                                         _ptr(tb_hydro), _ptr(hydroaccel), _ptr(entropy), _ptr(dtentropy), C.byref(K)))
 
+    def dev_apply_bh_subgrid_kick(self, vel, K, type, dfaccel, dragaccel, active=None, flags=None, tb_hydro=None):
+        """the DFAccel and DragAccel kicks of the black holes (timestep.c:1007-1013), after a half kick"""
+        self._ck(self.lib.mpg_dev_apply_bh_subgrid_kick(self.h, C.c_int64(vel.shape[0]), _ptr(active),
+                                                        C.c_int64(0 if active is None else active.shape[0]), _ptr(vel), _ptr(type), _ptr(flags),
+                                                        _ptr(tb_hydro), _ptr(dfaccel), _ptr(dragaccel), C.byref(K)))
+
+    def dev_reposition_blackholes(self, pos, vel, type, jumptominpot, minpotpos, minpotvel, BoxSize, flags=None):
+        """the jump of the flagged black holes to their potential minimum (drift.c:31-53), before the drift"""
+        self._ck(self.lib.mpg_dev_reposition_blackholes(self.h, C.c_int64(pos.shape[0]), _ptr(pos), _ptr(vel), _ptr(type), _ptr(flags),
+                                                        _ptr(jumptominpot), _ptr(minpotpos), _ptr(minpotvel), C.c_double(BoxSize)))
+
+    def dev_find_dynfric_timesteps(self, arrays, active, times, sync_loga, ErrTolIntAccuracy, MinSizeTimestep, CourantFac, atime, hubble):
+        """the dynamic-friction bins of the black holes (timestep.c:676-691), after dev_find_hydro_timesteps.  arrays: dict of device tensors
+        type, flags, vel, df_vel, hsml, dthsml, tb_grav, tb_hydro, tb_dynfric (missing: NULL)."""
+        A = DynfricStepArrays(*[_ptr(arrays.get(k)) for k in ("type", "flags", "vel", "df_vel", "hsml", "dthsml", "tb_grav", "tb_hydro", "tb_dynfric")])
+        loga = (C.c_double * len(sync_loga))(*[float(x) for x in sync_loga])
+        tl = Timeline(len(sync_loga), C.cast(loga, C.POINTER(C.c_double)))
+        par = TimestepParams(ErrTolIntAccuracy, MinSizeTimestep)
+        res = DynfricStepResult()
+        na = active.shape[0] if active is not None else 0
+        self._ck(self.lib.mpg_dev_find_dynfric_timesteps(self.h, C.byref(A), _ptr(active), C.c_int64(na), C.byref(times), C.byref(tl), C.byref(par),
+                                                         C.c_double(CourantFac), C.c_double(atime), C.c_double(hubble), C.byref(res)))
+        return dict(dynratio=res.dynratio, maxdyndiff=res.maxdyndiff, nbh=res.nbh)
+
     def dev_timestep_gravity_dloga(self, gravaccel, gravpm, atime, hubble, ErrTolIntAccuracy, dloga):
         self._ck(self.lib.mpg_dev_timestep_gravity_dloga(self.h, C.c_int64(gravaccel.shape[0]), _ptr(gravaccel), _ptr(gravpm), C.c_double(atime),
                                                          C.c_double(hubble), C.c_double(ErrTolIntAccuracy), _ptr(dloga)))
@@ -1260,6 +1310,72 @@ class Engine:
         c = (C.c_double * 3)()
         self._ck(self.lib.mpg_blackhole_get_times(self.h, c))
         return dict(accretion_ms=c[0], feedback_ms=c[1], apply_ms=c[2])
+
+    # ------------------------------------------------------------------ black-hole dynamical friction and the potential minimum (bhdynfric.c)
+    # `arrays` maps the field names of mpg_bh_dynfric_arrays to device tensors (dev form) / contiguous numpy arrays (host forms) of the
+    # element types in BH_DYNFRIC_ARRAY_DTYPES (float64 otherwise).  The call builds the tree of its type mask itself and leaves it current.
+    def set_bh_dynfric_params(self, BH_DynFrictionMethod, BH_DFBoostFactor=1, BH_DFbmax=20.0, BlackHoleRepositionEnabled=0, GravInternal=1.0,
+                              DensityKernelType=DENSITY_KERNEL_QUINTIC_SPLINE):
+        p = BhDynfricParams(int(BH_DynFrictionMethod), int(BH_DFBoostFactor), float(BH_DFbmax), int(BlackHoleRepositionEnabled), float(GravInternal),
+                            int(DensityKernelType))
+        self._ck(self.lib.mpg_set_bh_dynfric_params(self.h, C.byref(p)))
+
+    def dev_blackhole_dynfric(self, arrays, times, active=None):
+        a = BhDynfricArraysC()
+        for k in BH_DYNFRIC_ARRAY_FIELDS:
+            t = arrays.get(k)
+            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        nact = 0 if active is None else active.shape[0]
+        self._ck(self.lib.mpg_dev_blackhole_dynfric(self.h, C.byref(a), C.byref(times), _ptr(active), C.c_int64(nact)))
+
+    @staticmethod
+    def _bh_dynfric_host_arrays(arrays, skip):
+        a = BhDynfricArraysC()
+        for k in BH_DYNFRIC_ARRAY_FIELDS:
+            t = None if k in skip else arrays.get(k)
+            want = np.dtype(BH_DYNFRIC_ARRAY_DTYPES.get(k, "float64"))
+            if t is not None and (t.dtype != want or not t.flags["C_CONTIGUOUS"]):
+                raise EngineError("dynamical-friction host array %s must be contiguous %s" % (k, want.name))
+            setattr(a, k, None if t is None else t.ctypes.data)
+        return a
+
+    def blackhole_dynfric(self, P, BoxSize, arrays, times, ActiveParticle=None):
+        """host form: P supplies Pos / Mass / Type; the arrays (numpy) travel when the list holds a black hole"""
+        v = self._view(P)
+        a = self._bh_dynfric_host_arrays(arrays, ())
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_blackhole_dynfric(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times),
+                                                None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+
+    BH_DYNFRIC_RESIDENT_COLUMNS = ("vel", "gacc", "gpm", "hydroacc", "tb_grav", "tb_hydro", "hsml", "potential")
+
+    def resident_sph_blackhole_dynfric(self, P, arrays, times, ActiveParticle=None):
+        """on a resident gas run: the columns in BH_DYNFRIC_RESIDENT_COLUMNS are resident; the per-black-hole arrays (numpy) travel"""
+        v = self._view(P)
+        a = self._bh_dynfric_host_arrays(arrays, self.BH_DYNFRIC_RESIDENT_COLUMNS)
+        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        self._ck(self.lib.mpg_resident_sph_blackhole_dynfric(self.h, C.byref(v), C.byref(a), C.byref(times),
+                                                             None if act is None else act.ctypes.data_as(C.c_void_p),
+                                                             C.c_int64(0 if act is None else len(act))))
+
+    def bh_dynfric_stats(self):
+        c = (C.c_int64 * 5)()
+        m = C.c_double(0.0)
+        self._ck(self.lib.mpg_bh_dynfric_get_stats(self.h, c, C.byref(m)))
+        return dict(targets=c[0], candidates=c[1], neighbours=c[2], zerodf=c[3], listed=c[4], zerodfmass=m.value)
+
+    def bh_dynfric_times(self):
+        """device time of the last call in ms: the walk, the DFAccel pass"""
+        c = (C.c_double * 2)()
+        self._ck(self.lib.mpg_bh_dynfric_get_times(self.h, c))
+        return dict(walk_ms=c[0], dfaccel_ms=c[1])
+
+    def bh_dynfric_export(self, n):
+        """the walk's per-target state of the last call: raw sums [n][5], index of the potential minimum, tree particles inside Hsml"""
+        d = dict(rawsums=np.zeros((n, 5)), minidx=np.zeros(n, np.int32), numngb=np.zeros(n, np.int32))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.mpg_bh_dynfric_export(self.h, C.c_int64(n), p(d["rawsums"]), p(d["minidx"]), p(d["numngb"])))
+        return d
 
     # ------------------------------------------------------------------ radiative cooling (cooling_direct, sfr_eff.c:463-514)
     # `par` is a dict of the members of mpg_cooling_params (or a CoolingParams), `step` a dict with uvbg (dict of struct UVBG's members),

@@ -4,18 +4,19 @@
  * The reference's own definition stays in the link under another name (blackhole.o is compiled with -Dblackhole=cpu_blackhole,
  * tools/link_reference.sh).  This file calls it with several ranks (the library has no several-rank form of these walks, DESIGN.md section
  * 3.11) and with the two settings the engine does not carry: BH_FEEDBACK_OPTTHIN and BHFeedbackUseTcool == 2.
- * With one rank the two tree walks - accretion and feedback - and their post-processes run on the device.  What stays on the host, in the
- * reference's own code: the queue (blackholes_active), dynamical friction and the potential minimum (blackhole_dynfric, blackhole_dfaccel:
- * DFAccel goes over as data) and the two file writers (collect_BH_info, write_blackhole_txt), which are fed from the optional outputs of
- * mpg_blackhole_arrays through a struct BHPriv filled by slot.  The step's random table goes over on every call (mpg_set_random_table).
+ * With one rank everything between the queue and the file writers runs on the device: dynamical friction and the potential minimum
+ * (mpg_blackhole_dynfric / mpg_resident_sph_blackhole_dynfric in place of the reference's blackhole_dynfric and blackhole_dfaccel, which are
+ * not called), then the two tree walks - accretion and feedback - and their post-processes.  What stays on the host, in the reference's
+ * own code: the queue (blackholes_active) and the two file writers (collect_BH_info, write_blackhole_txt), which are fed from the optional
+ * outputs of mpg_blackhole_arrays through a struct BHPriv filled by slot.  The step's random table goes over on every call
+ * (mpg_set_random_table).
  * The file-static parameters are read through accessors that tools/link_reference.sh appends to its working copies of blackhole.c,
  * bhdynfric.c, winds.c and sfr_eff.c.  Gas that the call swallowed comes back with IsGarbage in the flags array; slots_mark_garbage is
  * then called here for its counter side effects.  P[].Mass and the flags byte are read from and written into the records by the library.
- * Inside a resident stretch (timestep-hip.c) the table's and the gas arrays' columns are the resident ones; ID, DelayTime and the
- * per-black-hole members travel.  The host's dynamical-friction walk reads P[] and is refused there: with BH_DynFrictionMethod > 0 or
- * repositioning the caller ends the resident stretch first; with neither, DFAccel is zeroed by blackhole_dfaccel from BhP alone.
- * The tree argument is not read on one rank: the library walks its own tree of gas and black holes, which it builds when the current one
- * is another (after winds_find_vel_disp: the DM tree).
+ * Inside a resident stretch (timestep-hip.c) the table's and the gas arrays' columns are the resident ones - Potential among them, so the
+ * dynamical-friction walk needs nothing of P[] there; ID, DelayTime and the per-black-hole members travel.
+ * The tree argument is not read on one rank: the dynamical-friction call builds the tree of its own type mask, and the black-hole call then
+ * builds its tree of gas and black holes because the current one is another (as after winds_find_vel_disp: the DM tree).
  * Clocks: /BH/DynFric, /BH/Accretion and /BH/Feedback from the device times (mpg_blackhole_get_times), /BH/Info as the reference.
  * Compiled inside the reference tree (see gravity-hip.c). */
 #include <mpi.h>
@@ -24,6 +25,7 @@
 #include <omp.h>
 #include "blackhole.h"
 #include "bhdynfric.h"
+#include "density.h"
 #include "bhinfo.h"
 #include "partmanager.h"
 #include "slotsmanager.h"
@@ -43,7 +45,7 @@ void cpu_blackhole(const ActiveParticles *act, double atime, Cosmology *CP, Forc
 int blackholes_active(const ActiveParticles *act, int **ActiveBlackHoles, int64_t *NumActiveBlackHoles); /* blackhole.c:191 */
 /* appended to the working copies of blackhole.c, bhdynfric.c, winds.c and sfr_eff.c (tools/link_reference.sh, step 4) */
 void mpg_shim_blackhole_params(mpg_blackhole_params *p);
-int mpg_shim_bh_dynfric_method(void);
+void mpg_shim_bh_dynfric_params(int *BH_DynFrictionMethod, int *BH_DFBoostFactor, double *BH_DFbmax);
 int mpg_shim_wind_decouple(void);
 void mpg_shim_sfr_blackhole(int *StarformationOn, int *BHFeedbackUseTcool, double *PhysDensThresh, double *OverDensThresh);
 
@@ -78,19 +80,14 @@ void blackhole(const ActiveParticles *act, double atime, Cosmology *CP, ForceTre
     par.UnitTime_in_s = units.UnitTime_in_s;
     par.UnitVelocity_in_cm_per_s = units.UnitVelocity_in_cm_per_s;
     par.uu_in_cgs = units.UnitEnergy_in_cgs / units.UnitMass_in_g;
-    /* dynamical friction and the potential minimum: the reference's own walks on the host (blackhole.c:246-256) */
     struct kick_factor_data kf;
     init_kick_factor_data(&kf, times, CP);
-    if(resident && (mpg_shim_bh_dynfric_method() > 0 || par.BlackHoleRepositionEnabled))
-        endrun(5, "blackhole(): dynamical friction / repositioning read P[] on the host (mpg_shim_resident_end first)\n");
-    if(!resident) {
-        struct BHDynFricPriv dynpriv[1] = {{0}};
-        dynpriv->kf = &kf;
-        dynpriv->Ti_Current = times->Ti_Current;
-        blackhole_dynfric(ActiveBlackHoles, NumActiveBlackHoles, ddecomp, dynpriv);
-    }
-    blackhole_dfaccel(ActiveBlackHoles, NumActiveBlackHoles, atime, CP->GravInternal);
-    walltime_measure("/BH/DynFric");
+    mpg_bh_dynfric_params dfpar;
+    memset(&dfpar, 0, sizeof(dfpar));
+    mpg_shim_bh_dynfric_params(&dfpar.BH_DynFrictionMethod, &dfpar.BH_DFBoostFactor, &dfpar.BH_DFbmax);
+    dfpar.BlackHoleRepositionEnabled = par.BlackHoleRepositionEnabled;
+    dfpar.GravInternal = CP->GravInternal;
+    dfpar.DensityKernelType = (int)GetDensityKernelType();
 
     const int64_t n = PartManager->NumPart;
     int64_t i;
@@ -106,23 +103,25 @@ void blackhole(const ActiveParticles *act, double atime, Cosmology *CP, ForceTre
     t.atime = atime;
     t.hubble = hubble_function(CP, atime);
     /* columns in particle order, from the arena (freed in reverse order) */
-    double *block = (double *)mymalloc("mpg_bh", (size_t)n * 39 * sizeof(double));
+    double *block = (double *)mymalloc("mpg_bh", (size_t)n * 52 * sizeof(double));
     uint64_t *ids = (uint64_t *)mymalloc("mpg_bh_id", (size_t)n * 4 * sizeof(uint64_t));
-    int32_t *ints = (int32_t *)mymalloc("mpg_bh_int", (size_t)n * 4 * sizeof(int32_t));
-    uint8_t *bytes = (uint8_t *)mymalloc("mpg_bh_u8", (size_t)n * 5);
+    int32_t *ints = (int32_t *)mymalloc("mpg_bh_int", (size_t)n * 5 * sizeof(int32_t));
+    uint8_t *bytes = (uint8_t *)mymalloc("mpg_bh_u8", (size_t)n * 6);
     double *q = block;
 #define COL(w) (q += (size_t)n * (w), q - (size_t)n * (w))
     double *gacc = COL(3), *gpm = COL(3), *hydroacc = COL(3), *hsml = COL(1), *density = COL(1), *delaytime = COL(1), *dfaccel = COL(3),
            *vdisp = COL(1), *vel = COL(3), *entropy = COL(1), *bhmass = COL(1), *mtrack = COL(1), *ke = COL(1), *mdot = COL(1), *drag = COL(3),
            *swallowtime = COL(1), *fws = COL(1), *bhent = COL(1), *gasvel = COL(3), *mgas = COL(1), *accm = COL(1), *accbh = COL(1),
-           *accmom = COL(3);
+           *accmom = COL(3), *potential = COL(1), *dfdens = COL(1), *dfvel = COL(3), *dfrms = COL(1), *minpot = COL(1), *minpotpos = COL(3),
+           *minpotvel = COL(3);
 #undef COL
     uint64_t *id = ids, *swallowid = ids + n, *sphswal = ids + 2 * n, *bhswal = ids + 3 * n;
-    int32_t *countprogs = ints, *encounter = ints + n, *mintimebin = ints + 2 * n, *keflag = ints + 3 * n;
-    uint8_t *tbh = bytes, *tbg = bytes + n, *active_hydro = bytes + 2 * n, *flags = bytes + 3 * n, *heated = bytes + 4 * n;
-    memset(block, 0, (size_t)n * 39 * sizeof(double));
+    int32_t *countprogs = ints, *encounter = ints + n, *mintimebin = ints + 2 * n, *keflag = ints + 3 * n, *jump = ints + 4 * n;
+    uint8_t *tbh = bytes, *tbg = bytes + n, *active_hydro = bytes + 2 * n, *flags = bytes + 3 * n, *heated = bytes + 4 * n,
+            *active_dynfric = bytes + 5 * n;
+    memset(block, 0, (size_t)n * 52 * sizeof(double));
     memset(ids, 0, (size_t)n * 4 * sizeof(uint64_t));
-    memset(ints, 0, (size_t)n * 4 * sizeof(int32_t));
+    memset(ints, 0, (size_t)n * 5 * sizeof(int32_t));
     #pragma omp parallel for
     for(i = 0; i < n; i++) {
         int k;
@@ -133,6 +132,8 @@ void blackhole(const ActiveParticles *act, double atime, Cosmology *CP, ForceTre
         flags[i] = (P[i].IsGarbage ? 1 : 0) | (P[i].Swallowed ? 2 : 0);
         heated[i] = P[i].BHHeated;
         hsml[i] = P[i].Hsml;
+        potential[i] = P[i].Potential;
+        active_dynfric[i] = 0;
         for(k = 0; k < 3; k++) {
             vel[3 * i + k] = P[i].Vel[k];
             gacc[3 * i + k] = P[i].FullTreeGravAccel[k];
@@ -159,12 +160,78 @@ void blackhole(const ActiveParticles *act, double atime, Cosmology *CP, ForceTre
             swallowtime[i] = BHP(i).SwallowTime;
             encounter[i] = BHP(i).encounter;
             mintimebin[i] = BHP(i).minTimeBin;
+            active_dynfric[i] = is_timebin_active(BHP(i).TimeBinDynFric, times->Ti_Current) ? 1 : 0;
+            dfdens[i] = BHP(i).DF_SurroundingDensity;
+            dfrms[i] = BHP(i).DF_SurroundingRmsVel;
+            jump[i] = BHP(i).JumpToMinPot;
+            minpot[i] = BHP(i).MinPot;
             for(k = 0; k < 3; k++) {
                 dfaccel[3 * i + k] = BHP(i).DFAccel[k];
                 drag[3 * i + k] = BHP(i).DragAccel[k];
+                dfvel[3 * i + k] = BHP(i).DF_SurroundingVel[k];
+                minpotpos[3 * i + k] = BHP(i).MinPotPos[k];
+                minpotvel[3 * i + k] = BHP(i).MinPotVel[k];
             }
         }
     }
+    /* dynamical friction and the potential minimum (blackhole.c:246-256) on the device; the rows of black holes that were no targets come
+     * back as they went */
+    mpg_bh_dynfric_arrays D;
+    memset(&D, 0, sizeof(D));
+    D.vel = vel;
+    D.gacc = gacc;
+    D.gpm = gpm;
+    D.hydroacc = hydroacc;
+    D.tb_grav = tbg;
+    D.tb_hydro = tbh;
+    D.hsml = hsml;
+    D.potential = potential;
+    D.bh_mass = bhmass;
+    D.active_dynfric = active_dynfric;
+    D.df_density = dfdens;
+    D.df_vel = dfvel;
+    D.df_rmsvel = dfrms;
+    D.jumptominpot = jump;
+    D.minpot = minpot;
+    D.minpotpos = minpotpos;
+    D.minpotvel = minpotvel;
+    D.dfaccel = dfaccel;
+    ck(mpg_set_bh_dynfric_params(mpg_shim_engine(), &dfpar));
+    if(resident) {
+        mpg_particle_view rv = mpg_shim_view();
+        ck(mpg_resident_sph_blackhole_dynfric(mpg_shim_engine(), &rv, &D, &t, act->ActiveParticle, act->NumActiveParticle));
+    }
+    else {
+        mpg_shim_set_domain(ddecomp);
+        mpg_shim_sync(times->Ti_Current, atime, PartManager->BoxSize, 0);
+        mpg_particle_view v = mpg_shim_view();
+        ck(mpg_blackhole_dynfric(mpg_shim_engine(), &v, PartManager->BoxSize, &D, &t, act->ActiveParticle, act->NumActiveParticle));
+    }
+    if(dfpar.BH_DynFrictionMethod > 0 || dfpar.BlackHoleRepositionEnabled) {
+        #pragma omp parallel for
+        for(i = 0; i < n; i++) {
+            int k;
+            if(P[i].IsGarbage || P[i].Type != 5)
+                continue;
+            BHP(i).DF_SurroundingDensity = dfdens[i];
+            BHP(i).DF_SurroundingRmsVel = dfrms[i];
+            BHP(i).JumpToMinPot = (char)jump[i];
+            BHP(i).MinPot = minpot[i];
+            for(k = 0; k < 3; k++) {
+                BHP(i).DFAccel[k] = dfaccel[3 * i + k];
+                BHP(i).DF_SurroundingVel[k] = dfvel[3 * i + k];
+                BHP(i).MinPotPos[k] = minpotpos[3 * i + k];
+                BHP(i).MinPotVel[k] = minpotvel[3 * i + k];
+            }
+        }
+        int64_t dstats[5];
+        double zeromass = 0;
+        ck(mpg_bh_dynfric_get_stats(mpg_shim_engine(), dstats, &zeromass));
+        if(dstats[3] > 0)
+            message(0, "Dynamic Friction density is zero for %ld BHs avg mass %g.\n", (long)dstats[3], zeromass / dstats[3]);
+    }
+    walltime_measure("/BH/DynFric");
+
     mpg_blackhole_arrays A;
     memset(&A, 0, sizeof(A));
     A.id = id;

@@ -29,8 +29,9 @@
  * before.  Inside one, the factors come from the reference's own get_exact_*_factor / dloga_from_dti (host arithmetic on the integer
  * timeline) and the per-particle loops run as mpg_resident_* on the device (include/mpgadget_hip.h).  One rank per GPU; NTask > 1 keeps the
  * host path (the resident calls are one-rank forms: mpg_dist_* owns the multi-rank choreography).
- * Not covered (the shim stops with a message): black-hole particles inside a resident stretch (drift.c:33-55 repositioning, the
- * dynamic-friction kicks, timestep.c:1003-1010), ForceEqualTimesteps; star particles created inside a stretch get no stored acceleration
+ * Not covered (the shim stops with a message): black-hole particles inside a resident stretch - the library has the three kernels
+ * (mpg_dev_reposition_blackholes for drift.c:31-53, mpg_dev_apply_bh_subgrid_kick for timestep.c:1007-1013, mpg_dev_find_dynfric_timesteps
+ * for timestep.c:676-691) but this file does not call them yet -, ForceEqualTimesteps; star particles created inside a stretch get no stored acceleration
  * (only NumPart rows of StoredGravAccel are kept).  With NTask > 1 mpg_shim_resident_begin returns at once and both branches keep the
  * host path. */
 #include <mpi.h>

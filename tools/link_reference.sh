@@ -175,7 +175,9 @@ append(T + "/libgadget/blackhole.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_b
            "BHKE_EddingtonMFactor", "BHKE_EddingtonMPivot", "BHKE_EddingtonMIndex", "BHKE_EffRhoFactor", "BHKE_EffCap", "BHKE_InjEnergyThr",
            "BHKE_SfrCritOverDensity", "MergeGravBound", "BH_DRAG", "SeedBHDynMass"))
        + "    p->BlackHoleFeedbackMethod = (int)blackhole_params.BlackHoleFeedbackMethod;\n}")
-append(T + "/libgadget/bhdynfric.c", "int mpg_shim_bh_dynfric_method(void) { return blackhole_dynfric_params.BH_DynFrictionMethod; }")
+append(T + "/libgadget/bhdynfric.c", "void mpg_shim_bh_dynfric_params(int *BH_DynFrictionMethod, int *BH_DFBoostFactor, double *BH_DFbmax)\n"
+       "{\n    *BH_DynFrictionMethod = blackhole_dynfric_params.BH_DynFrictionMethod;\n    *BH_DFBoostFactor = blackhole_dynfric_params.BH_DFBoostFactor;\n"
+       "    *BH_DFbmax = blackhole_dynfric_params.BH_DFbmax;\n}")
 append(T + "/libgadget/winds.c", "int mpg_shim_wind_decouple(void) { return HAS(wind_params.WindModel, WIND_DECOUPLE_SPH) ? 1 : 0; }")
 append(T + "/libgadget/sfr_eff.c", "void mpg_shim_sfr_blackhole(int *StarformationOn, int *BHFeedbackUseTcool, double *PhysDensThresh, double *OverDensThresh)\n"
        "{\n    *StarformationOn = sfr_params.StarformationOn;\n    *BHFeedbackUseTcool = sfr_params.BHFeedbackUseTcool;\n"
