@@ -289,14 +289,42 @@ __device__ __forceinline__ void node_test_masks(const GravParams &gp, const Node
 // reference's two tests to ITS node for target t (gravshort-tree.c:198-241; node_test_masks above), and the outcomes are lane
 // masks: the entries of target t are appended by all lanes at once (position = count + v_mbcnt of the mask), the counts advance by
 // s_bcnt1, the push mask of a lane collects the targets that open its node.  After the 8 targets the opened internal nodes' children
-// go back to the frontier (one entry per child: a prefix sum over the lanes by four ballots).
+// go back to the frontier (one entry per child, at positions from a prefix sum over the lanes: push_children).
 // Per target the set of nodes tested and the outcome of every test are exactly those of its own walk (a node reaches the frontier
 // with bit t set iff target t opened its parent); the ORDER of a target's list entries depends on its 7 wave-mates.
-constexpr int QCAP = 1024; // frontier entries per wave (node index 4 B + target mask 1 B); a wave that would exceed it hands its targets to the fallback
+constexpr int QCAP = 1024; // frontier entries per wave; a wave that would exceed it hands its targets to the fallback
+// A frontier entry is ONE word, target mask << 24 | node index, wherever the tree has at most 2^24 nodes (PACKQ; decided on the host: 256^3
+// particles make a few million nodes); otherwise a 4-byte node index and a 1-byte mask in two arrays.  The packed frontier of a wave has one
+// word in front of it that holds 0 (no target: what the idle lanes of a pop read) and QSLACK words behind it that are written and never
+// read: push_children writes up to 7 words beyond the entries it adds, and lane l without children to push writes words QCAP + l ... + 7.
+constexpr int QSLACK = 64 + 7;
+constexpr int QSTRIDE_PACKED = 1 + QCAP + QSLACK;
 
 __device__ __forceinline__ unsigned mbcnt64(const unsigned long long b)
 {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+}
+
+// p[C] = v for a pointer into LDS, as one ds_write_b32 of its own that hipcc neither pairs with a neighbour nor moves over another access.
+// (The wave's own later LDS operations see it: those of one wave complete in order.)
+template <int C>
+__device__ __forceinline__ void lds_store32(unsigned *p, const unsigned v)
+{
+    const unsigned a = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)p;
+    asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(a), "v"(v), "n"(4 * C) : "memory");
+}
+
+// inclusive prefix sum over the 64 lanes of a wave, ALL of them active: four row shifts (a row = 16 lanes; a lane without a source keeps the
+// 0 of `old`), then lane 15 of rows 0 and 2 added to rows 1 and 3, then lane 31 to rows 2 and 3.  Six v_add_u32 with a DPP operand.
+__device__ __forceinline__ int wave_prefix_sum(int x)
+{
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false); // row_shr:1
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false); // row_shr:2
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false); // row_shr:4
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false); // row_shr:8
+    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false); // row_bcast:15
+    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false); // row_bcast:31
+    return x;
 }
 
 
@@ -336,8 +364,8 @@ struct WaveTargets {
     unsigned c_vis[8], c_used[8];
 };
 
-// returns false on an internal error (loop guard)
-template <bool COUNT, int MODE, bool O32, bool F32 = false>
+// returns false on an internal error (loop guard).  PACKQ: q_node holds packed entries and q_mask is unused (see QCAP)
+template <bool COUNT, int MODE, bool O32, bool PACKQ, bool F32 = false>
 __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams &gp, unsigned *__restrict__ Lw, unsigned *__restrict__ q_node,
                                            unsigned char *__restrict__ q_mask, const double *__restrict__ s_tgt, const int cap, const int lane,
                                            const unsigned live0, WaveTargets &T, unsigned &overflowed, bool &wrapped, unsigned (&c_pp)[8],
@@ -353,21 +381,46 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
 
     // the children of the nodes a pass opened: one frontier entry per child, mask = the targets that opened the parent.  Returns false
     // if the frontier would overflow (a pathological tree): every target still walking goes to the fallback.
+    // A pushing lane has 1 to 8 children; all 64 lanes are active here.
     auto push_children = [&](const bool pushing, const NodeLinkB &lk, const unsigned openmask) -> bool {
-        const unsigned long long bp = __builtin_amdgcn_ballot_w64(pushing);
-        if(bp == 0ull)
+        if(!any_lane(pushing))
             return true;
-        const unsigned nm1 = (unsigned)(lk.nchild - 1); // 0..7
-        const unsigned long long b0 = __builtin_amdgcn_ballot_w64(pushing && (nm1 & 1u)), b1 = __builtin_amdgcn_ballot_w64(pushing && (nm1 & 2u)),
-                                 b2 = __builtin_amdgcn_ballot_w64(pushing && (nm1 & 4u));
-        const int total = __builtin_popcountll(bp) + __builtin_popcountll(b0) + 2 * __builtin_popcountll(b1) + 4 * __builtin_popcountll(b2);
+        // the lane's entries start behind those of the pushing lanes below it: one prefix sum over the wave (rounds 3-6: four ballots, three of
+        // them over the bits of nchild - 1, and eight v_mbcnt)
+        const int mine = pushing ? lk.nchild : 0;
+        const int upto = wave_prefix_sum(mine);
+        const int total = __builtin_amdgcn_readlane(upto, 63);
         if(sp + total > QCAP) {
             overflowed |= live;
             live = 0;
             return false;
         }
-        if(pushing) {
-            const unsigned at = (unsigned)sp + mbcnt64(bp) + mbcnt64(b0) + 2u * mbcnt64(b1) + 4u * mbcnt64(b2);
+        const unsigned at = (unsigned)(sp + upto - mine);
+        if constexpr(PACKQ) {
+            // Every pushing lane writes ALL 8 slots at + 7 ... at + 0, in this order, one LDS instruction each, without looking at nchild
+            // (a test per child costs a compare and an exec save / restore each).  A slot at + c with c >= nchild is dead for this lane: it
+            // lies in the entries of pushing lanes ABOVE this one (their `at` is larger by at least nchild), or behind the last entry
+            // pushed, in the frontier's unused part and its QSLACK words.  The lane that owns a slot x writes it as ITS child c' = x - at'
+            // < c: in a LATER instruction of this sequence, and the LDS operations of a wave complete in order, so the owner's value is
+            // the one that stays.  Two lanes never write one address in the SAME instruction: that needs equal `at`, and every pushing
+            // lane has at least one child.  For the same reason the writes must stay 8 instructions: paired into ds_write2_b32, the dead
+            // slot c + 1 of a lane with one child and the live slot c of the next lane would meet inside one instruction.  hipcc pairs
+            // plain stores, across empty asm statements too, and turns volatile ones into flat stores with a wait each: lds_store32.
+            // A lane with nothing to push writes too, 8 words of its own among the QSLACK words (sp + total <= QCAP: behind every entry):
+            // one select of the address instead of an exec save / restore around the writes.
+            const unsigned first = (openmask << 24) | (unsigned)lk.firstchild; // (firstchild + 7 < 2^24: no carry into the mask)
+            unsigned *qa = q_node + (pushing ? at : (unsigned)(QCAP + lane));
+            lds_store32<7>(qa, first + 7u);
+            lds_store32<6>(qa, first + 6u);
+            lds_store32<5>(qa, first + 5u);
+            lds_store32<4>(qa, first + 4u);
+            lds_store32<3>(qa, first + 3u);
+            lds_store32<2>(qa, first + 2u);
+            lds_store32<1>(qa, first + 1u);
+            lds_store32<0>(qa, first);
+        }
+        else if(pushing) {
+            const unsigned nm1 = (unsigned)(lk.nchild - 1); // 0..7
 #pragma unroll
             for(unsigned c = 0; c < 8; c++)
                 if(c <= nm1) {
@@ -475,11 +528,22 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
         }
         __builtin_amdgcn_wave_barrier();
         const int n = sp < 64 ? sp : 64;
-        const bool valid = lane < n;
-        // (idle lanes read entry 0, which always holds a node index: no exec-mask regions around the two reads)
-        const int qi = valid ? sp - 1 - lane : 0;
-        const unsigned my = q_node[qi];
-        const unsigned mask = valid ? ((unsigned)q_mask[qi] & live) : 0u;
+        // my: the lane's node; mask: the targets that reached it and still walk, in bits 24-31 as the packed entry holds them (bit 24 + t
+        // for target t: the passes below test them where they stand)
+        unsigned my, mask;
+        if constexpr(PACKQ) {
+            // (idle lanes read the word in front of the frontier: node 0 for the loads, no target)
+            const unsigned w = q_node[max(sp - 1 - lane, -1)];
+            my = w & 0xffffffu;
+            mask = w & (live << 24);
+        }
+        else {
+            const bool valid = lane < n;
+            // (idle lanes read entry 0, which always holds a node index: no exec-mask regions around the two reads)
+            const int qi = valid ? sp - 1 - lane : 0;
+            my = q_node[qi];
+            mask = valid ? (((unsigned)q_mask[qi] & live) << 24) : 0u;
+        }
         sp -= n;
         const NodeGeo g = ld<O32>(tv.geoB, my);
         const Src4 mom = ld<O32>(tv.momB, my);
@@ -515,7 +579,7 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
             ml2 = mom.m * l2;
         }
         const unsigned ent_val = my; // a leaf entry = the leaf's level-order node number (its block of 8 source records: tv.srcL)
-        unsigned openmask = 0;
+        unsigned openmask = 0; // the targets that open the lane's node
         if(COUNT) {
             st_a++;
             st_al += (unsigned)n;
@@ -536,11 +600,15 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
         const unsigned long long m_single = __builtin_amdgcn_ballot_w64(lk.pcount == 1);
         auto pass = [&](auto checked_tag) {
             constexpr bool CHECKED = decltype(checked_tag)::value;
+            // (From target 7 down, as measured; every target has lists of its own, so the order of a pop's passes shows in none of them.
+            // Taking the lanes of target t as the carry of mask + mask - one v_add_co_u32 in place of v_and + v_cmp - made the kernel 0.2 ms
+            // SLOWER: the eight sums depend on each other and every pass then waits for its own carry; profiles/lists_pop_cost.)
+            unsigned om = 0u;
 #pragma unroll
-            for(int t = 0; t < 8; t++) {
+            for(int t = 7; t >= 0; t--) {
+                const unsigned long long m_act = __builtin_amdgcn_ballot_w64((mask & (0x01000000u << t)) != 0u);
                 // (no lane for a target that overflowed, is absent or did not open the parent; measured: 28 % of the passes over a
                 // target find no lane with its bit - the entries popped late in a walk belong to few of the 8 targets)
-                const unsigned long long m_act = __builtin_amdgcn_ballot_w64((mask & (1u << t)) != 0u);
                 if(m_act == 0ull)
                     continue;
                 // (one address for the wave: a broadcast read.  The empty asm hides from hipcc that the 8 reads are the same in every
@@ -609,7 +677,7 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
                 T.nleaf[t] += kl;
                 T.nnode[t] += kn;
                 maxused = max(maxused, T.nleaf[t] + T.nnode[t]);
-                openmask |= __builtin_amdgcn_inverse_ballot_w64(bpush) ? (1u << t) : 0u;
+                om |= __builtin_amdgcn_inverse_ballot_w64(bpush) ? (1u << t) : 0u;
                 // an entry on a wrapped periodic image: MODE 2 can meet one only among the root and its children (the top passes above)
                 if(MODE == 1)
                     wmask |= m_wrap & (bl | bn);
@@ -621,6 +689,7 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
                 // (the 8 targets' tests are independent: left alone, hipcc interleaves them and runs out of registers)
                 __builtin_amdgcn_sched_barrier(0);
             }
+            openmask = om;
         };
         if(maxused + 64 > cap)
             pass(std::true_type{});
@@ -634,19 +703,28 @@ __device__ __forceinline__ bool walk_wave8(const TreeView &tv, const GravParams 
 }
 
 // one wave = one chunk of k_walk_eval (8 consecutive targets)
-template <bool COUNT, bool FASTWRAP, bool O32, bool F32>
+template <bool COUNT, bool FASTWRAP, bool O32, bool F32, bool PACKQ>
 __global__ void __launch_bounds__(256, LIST_BLOCKS) k_walk_lists8(const TreeView tv, const GravParams gp, const WalkIO io, unsigned *__restrict__ lists,
                                                       int2 *__restrict__ counts, const int cap, const int64_t slot0, const int64_t nslots,
                                                       unsigned *__restrict__ ctl, int *__restrict__ ovf)
 {
-    __shared__ unsigned s_qnode[4 * QCAP];
-    __shared__ unsigned char s_qmask[4 * QCAP];
+    constexpr int QSTRIDE = PACKQ ? QSTRIDE_PACKED : QCAP;
+    __shared__ unsigned s_qnode[4 * QSTRIDE];
     __shared__ __attribute__((aligned(32))) double s_tgt4[4 * 8 * 4];
     __shared__ __attribute__((aligned(16))) float s_tgtf4[F32 ? 4 * 8 * 4 : 4];
     set_wave_prio(io.list_prio);
     const int lane = threadIdx.x & 63;
-    unsigned *q_node = s_qnode + (threadIdx.x >> 6) * QCAP;
-    unsigned char *q_mask = s_qmask + (threadIdx.x >> 6) * QCAP;
+    unsigned *q_node = s_qnode + (threadIdx.x >> 6) * QSTRIDE;
+    unsigned char *q_mask = nullptr;
+    if constexpr(PACKQ) {
+        if(lane == 0)
+            q_node[0] = 0u; // the word in front of the wave's frontier, never written again (see QCAP)
+        q_node++;
+    }
+    else {
+        __shared__ unsigned char s_qmask[4 * QCAP];
+        q_mask = s_qmask + (threadIdx.x >> 6) * QCAP;
+    }
     double *s_tgt = s_tgt4 + (threadIdx.x >> 6) * 32;
     const unsigned nchunks = (unsigned)((nslots + 7) / 8);
     const ChunkIter it(nchunks);
@@ -728,17 +806,17 @@ __global__ void __launch_bounds__(256, LIST_BLOCKS) k_walk_lists8(const TreeView
                         *(float4 *)(s_tgtf + 4 * lane) = make_float4((float)(vx - W.ox), (float)(vy - W.oy), (float)(vz - W.oz), (float)sqrt(vaold));
                     __builtin_amdgcn_wave_barrier();
                     n_f32w++;
-                    ok = walk_wave8<COUNT, 2, O32, true>(tv, gp, L, q_node, q_mask, s_tgt, cap, lane, live0, T, overflowed, wrapped, c_pp, guard_max, ctl, st_a,
+                    ok = walk_wave8<COUNT, 2, O32, PACKQ, true>(tv, gp, L, q_node, q_mask, s_tgt, cap, lane, live0, T, overflowed, wrapped, c_pp, guard_max, ctl, st_a,
                                                          st_al, W, &n_amb);
                 }
                 else
-                    ok = walk_wave8<COUNT, 2, O32>(tv, gp, L, q_node, q_mask, s_tgt, cap, lane, live0, T, overflowed, wrapped, c_pp, guard_max, ctl, st_a, st_al);
+                    ok = walk_wave8<COUNT, 2, O32, PACKQ>(tv, gp, L, q_node, q_mask, s_tgt, cap, lane, live0, T, overflowed, wrapped, c_pp, guard_max, ctl, st_a, st_al);
             }
             else
-                ok = walk_wave8<COUNT, 1, O32>(tv, gp, L, q_node, q_mask, s_tgt, cap, lane, live0, T, overflowed, wrapped, c_pp, guard_max, ctl, st_a, st_al);
+                ok = walk_wave8<COUNT, 1, O32, PACKQ>(tv, gp, L, q_node, q_mask, s_tgt, cap, lane, live0, T, overflowed, wrapped, c_pp, guard_max, ctl, st_a, st_al);
         }
         else
-            ok = walk_wave8<COUNT, 0, O32>(tv, gp, L, q_node, q_mask, s_tgt, cap, lane, live0, T, overflowed, wrapped, c_pp, guard_max, ctl, st_a, st_al);
+            ok = walk_wave8<COUNT, 0, O32, PACKQ>(tv, gp, L, q_node, q_mask, s_tgt, cap, lane, live0, T, overflowed, wrapped, c_pp, guard_max, ctl, st_a, st_al);
         if(!ok)
             return;
         int nl = 0, nn = 0;
@@ -1059,7 +1137,12 @@ void launch_split_t(const TreeView &tv, const GravParams &gp, const WalkIO &io, 
     const char *f32_e = getenv("MPG_LISTS_F32");
     const bool f32_env = f32_e && f32_e[0] == '1';
     const bool f32 = FASTWRAP && f32_env && gp.bhangle2 > 1e-6 && gp.bhangle2 < 1e6 && gp.rcut > 1e-12 && gp.rcut < 1e12 && gp.box < 1e12;
-    auto kl = (FASTWRAP && f32) ? k_walk_lists8<COUNT, FASTWRAP, O32, FASTWRAP> : k_walk_lists8<COUNT, FASTWRAP, O32, false>;
+    // one word per frontier entry where a node index fits 24 bits (see QCAP); MPG_LISTS_PACKQ=0 (experiment knob, read per launch: the tests
+    // switch it) forces the two arrays that larger trees take
+    const char *pq_e = getenv("MPG_LISTS_PACKQ");
+    const bool packq = tv.nnodes + 1 <= (1ll << 24) && !(pq_e && pq_e[0] == '0');
+    auto kl = (FASTWRAP && f32) ? (packq ? k_walk_lists8<COUNT, FASTWRAP, O32, FASTWRAP, true> : k_walk_lists8<COUNT, FASTWRAP, O32, FASTWRAP, false>)
+                                : (packq ? k_walk_lists8<COUNT, FASTWRAP, O32, false, true> : k_walk_lists8<COUNT, FASTWRAP, O32, false, false>);
     auto ke = k_walk_eval<POT, FASTWRAP, O32>;
     if(const char *e = getenv("MPG_LIST_CAP")) // experiment knob
         ws.split_cap = atoi(e) / 8 * 8;
