@@ -705,6 +705,100 @@ int mpg_bh_dynfric_get_times(mpg_engine *eng, double ms[2]);
  * Rows that were no targets hold -1 in minidx and numngb. */
 int mpg_bh_dynfric_export(mpg_engine *eng, int64_t n, double *rawsums, int32_t *minidx, int32_t *numngb);
 
+/* ---- the wind model: winds_and_feedback, winds_subgrid, winds_evolve, libgadget/winds.c (sfr_eff.c:235, 283, 391-392) --------------
+ * winds_and_feedback (:298-371) for the NEW STARS of a step, given as a list of rows, on the engine's CURRENT tree, which must contain the
+ * gas.  No hmax is needed: both searches are asymmetric inside the star's Hsml.  With WIND_SUBGRID set or an empty list nothing is read,
+ * nothing is written and no tree is demanded.
+ *   the weight walk (:414-450)    TotalWeight = sum of P.Mass over the gas with r <= Hsml and DelayTime <= 0.  A candidate is a row of the
+ *       tree whose CURRENT type is 0: black holes in the tree, type-7 rows and gas converted since the tree was built are skipped.  Mass is
+ *       the column bound with mpg_dev_bind_particles as it is NOW, not the tree-order copy of the last build.  The walk counts the eligible
+ *       neighbours (the reference's nvisited), which sizes the list of potential kicks.
+ *   the feedback walk (:513-569)  same search, same eligibility; no candidate when TotalWeight == 0 or Vdisp <= 0.  get_wind_params
+ *       (:493-511) once per star; p = windeff Mass_star / TotalWeight; a pair is a potential kick iff
+ *       table[(ID_star + ID_gas) % size] < p and v > 0 (the sum wraps as unsigned 64-bit; the table of mpg_set_random_table).
+ *   the nearest-star rule (:207-224, :338-356)  a gas particle takes the kick of the candidate of smallest r = sqrt(r2); ties go to the
+ *       smaller star ID.  Taken with two 64-bit atomic minima (the bits of r, then the star ID among the entries at that r) and one apply
+ *       pass over the list: the result does not depend on the order of arrival and no lane waits for another.
+ *   the kick (:453-490)  Vel += v dir with theta = acos(2 t[(ID_gas + 3) % size] - 1), phi = 2 pi t[(ID_gas + 4) % size];
+ *       Entropy += therm / enttou, enttou = pow(Density / atime^3, GAMMA_MINUS1) / GAMMA_MINUS1; with MaxWindFreeTravelTime > 0
+ *       DelayTime = min(WindFreeTravelLength / (v / atime), MaxWindFreeTravelTime).
+ * ERRORS: a listed row outside the table or not of type 4 (endrun(5), :406-407), no random table, no parameters, a tree without the gas, a
+ * search that overflowed its stack, a kick list without room (endrun(5), :559-561): all of these are found before Vel, Entropy or
+ * DelayTime is written.  A non-finite kick velocity or DelayTime ("Odd v", endrun(5), :350-355) is found AFTER the kicks have been
+ * applied, as in the reference, which then ends the run: Vel, Entropy and DelayTime are undefined after this error.
+ * One rank only: there is no mpg_dist_* form, and no form on a resident gas run. */
+typedef struct mpg_wind_params {
+    int WindModel;               /* enum WindModel, winds.h:13-20: SUBGRID 1, DECOUPLE_SPH 2, USE_HALO 4, FIXED_EFFICIENCY 8, ISOTROPIC 512 */
+    double WindEfficiency, WindSigma0, WindSpeedFactor, MinWindVelocity, WindThermalFactor, WindFreeTravelLength;
+    double WindSpeed;            /* after init_winds: already divided by sqrt(WindEfficiency) for WIND_FIXED_EFFICIENCY */
+    double MaxWindFreeTravelTime;/* in internal units (after init_winds) */
+    double WindFreeTravelDensThresh;
+} mpg_wind_params;
+/* all arrays in particle order, n entries (x 3 where noted).  Slot members are indexed by PARTICLE. */
+typedef struct mpg_wind_arrays {
+    /* read */
+    const uint64_t *id;      /* P.ID */
+    const double *hsml;      /* P.Hsml of the stars (winds_and_feedback only) */
+    const double *vdisp;     /* STARP.VDisp of the stars (winds_and_feedback); SPHP.VDisp of the gas (winds_subgrid) */
+    const double *density;   /* SPHP.Density */
+    const uint8_t *tb_hydro; /* P.TimeBinHydro (winds_evolve only) */
+    /* in / out */
+    double *vel;             /* [n][3] P.Vel */
+    double *entropy;         /* SPHP.Entropy */
+    double *delaytime;       /* SPHP.DelayTime */
+    /* out, optional (winds_and_feedback) */
+    double *totalweight;     /* TotalWeight of every listed star */
+    uint64_t *kick_star;     /* ID + 1 of the star whose kick a gas particle received, 0 for every other row (all n are written) */
+} mpg_wind_arrays;
+/* an error (the reference's endrun(1)) for a model with neither WIND_FIXED_EFFICIENCY nor WIND_USE_HALO */
+int mpg_set_wind_params(mpg_engine *eng, const mpg_wind_params *par);
+/* on the bound particles and the current tree; d_newstars: nnew rows (device).  Required: id, hsml, vdisp, density, vel, entropy, delaytime */
+int mpg_dev_winds_and_feedback(mpg_engine *eng, const mpg_wind_arrays *A, const int *d_newstars, int64_t nnew, double atime);
+/* host form: `pv` supplies Pos / Mass / Type / flags, the members of `A` and NewStars are HOST arrays.  The gas tree is built as
+ * mpg_density builds it unless the list is empty or WIND_SUBGRID is set: then nothing travels. */
+int mpg_winds_and_feedback(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_wind_arrays *A, const int *NewStars,
+                           int64_t NumNewStars, double atime);
+/* winds_subgrid / winds_make_after_sf (:275-295, :571-589): one lane per listed gas particle (d_maybewind NULL: rows 0 .. n - 1, as the
+ * reference's NULL list); prob = 1 - exp(-windeff sm / Mass), sm = d_stellarmass[row] (by PARTICLE, not by slot); kicked when
+ * table[(ID + 2) % size] < prob, with the kick above and the particle's own vdisp.  Nothing unless WIND_SUBGRID is set.  Required: id,
+ * vdisp, density, vel, entropy, delaytime. */
+int mpg_dev_winds_subgrid(mpg_engine *eng, const mpg_wind_arrays *A, const int *d_maybewind, int64_t n, const double *d_stellarmass, double atime);
+/* winds_evolve (:374-391) for the listed rows of type 0 (d_active NULL: every row): DelayTime = 0 when DelayTime > 0 and
+ * Density / atime^3 < WindFreeTravelDensThresh; else the clamp to MaxWindFreeTravelTime and
+ * DelayTime = max(DelayTime - dloga_bin[TimeBinHydro] / hubble, 0).  T supplies atime, hubble and dloga_bin.  Required: density,
+ * tb_hydro, delaytime. */
+int mpg_dev_winds_evolve(mpg_engine *eng, const mpg_wind_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive);
+/* statistics of the last mpg_dev_winds_and_feedback: [0] stars, [1] candidates distance-tested by the weight walk, [2] eligible neighbours
+ * (nvisited), [3] potential kicks, [4] kicks applied, [5] kicks discarded; *maxvel (may be NULL) the velocity of the kick applied to the
+ * lowest particle index, which is what the reference prints as "Vel" (0 without a kick).  After mpg_dev_winds_subgrid: [0] listed rows,
+ * [4] kicks applied. */
+int mpg_winds_get_stats(mpg_engine *eng, int64_t stats[6], double *maxvel);
+/* DECOUPLED WIND GAS IN hydro_force.  With WIND_DECOUPLE_SPH in the WindModel of mpg_set_wind_params AND a DelayTime column, gas with
+ * DelayTime > 0 (winds_is_particle_decoupled, :113-120) takes no part in the hydro forces:
+ *   as a source (hydra.c:360-363) it contributes nothing to any target: no acceleration, no DtEntropy, no MaxSignalVel;
+ *   as a target (hydro_postprocess -> winds_decoupled_hydro, :122-136) its walk still runs; it then gets HydroAccel = 0, DtEntropy = 0 and
+ *       MaxSignalVel = hsml_c max(2 windspeed, MaxSignalVel), windspeed = WindSpeed atime fac_mu, fac_mu = atime^(3 (GAMMA - 1) / 2) / atime,
+ *       hsml_c = cbrt(WindFreeTravelDensThresh / Density) atime.
+ * Without the bit or without a column hydro_force launches the kernels it launched before there was such a rule.  The column (SphP.DelayTime
+ * by particle, n entries) arrives through one of three setters; NULL unbinds:
+ *   mpg_dev_set_delaytime           a device array, read by mpg_dev_hydro_force (the caller keeps it alive)
+ *   mpg_set_delaytime               a host array, uploaded by every mpg_hydro_force (staged or resident) and in effect for that call
+ *   mpg_resident_sph_set_delaytime  a host array, uploaded NOW into the engine and in effect for the mpg_hydro_force calls of the resident gas
+ *                                   run until the next such call or mpg_resident_sph_end (the kicks of winds_and_feedback change DelayTime
+ *                                   on the host: the caller hands the column over again after them)
+ * The density loop's rule for black-hole targets (density.c:455) is not carried. */
+int mpg_dev_set_delaytime(mpg_engine *eng, const double *d_delaytime);
+int mpg_set_delaytime(mpg_engine *eng, const double *delaytime);
+int mpg_resident_sph_set_delaytime(mpg_engine *eng, const double *delaytime);
+/* the potential kicks of the last mpg_dev_winds_and_feedback, star by star in list order, while the tree of that call is
+ * still the engine's: the rows of the star and of the gas particle of the first `capacity` entries into host arrays (either may be NULL),
+ * *count the length of the list */
+int mpg_winds_export(mpg_engine *eng, int64_t capacity, int32_t *star, int32_t *gas, int64_t *count);
+/* device time of the last mpg_dev_winds_and_feedback in ms (zeros when it had nothing to do), from events on the engine's stream: [0] the
+ * weight walk, [1] the feedback walk with the clearing of its per-particle words, [2] the resolve and apply passes.  The read-back of
+ * the neighbour count that sizes the list (a host round trip between [0] and [1]) is in none of the three. */
+int mpg_winds_get_times(mpg_engine *eng, double ms[3]);
+
 /* ---- introspection (tests, bench roofline accounting) ----------------------------------------- */
 typedef struct mpg_tree_stats {
     int64_t NumParticles; /* particles in the tree */

@@ -1681,7 +1681,26 @@ int mpg_dev_hydro_force(mpg_engine *eng, const mpg_sph_arrays *A, const mpg_sph_
     MPG_CHECK(!eng->hydropar.DensityIndependentSphOn || A->egywtdensity, "hydro_force: pressure-entropy SPH needs egywtdensity");
     MPG_HIP(hipSetDevice(eng->device));
     const SphView v = make_sph_view(eng, A);
-    eng->sph.hydro_force(eng->tree, v, *T, eng->denspar, eng->hydropar, d_active, nactive, eng->n, eng->stream);
+    // decoupled wind gas: only with the model's bit AND a DelayTime column; otherwise the loop without the rule, as before there was one
+    const bool decouple = eng->d_delaytime && eng->have_windpar && (eng->windpar.WindModel & WIND_DECOUPLE_SPH) != 0;
+    const HydroWind W{eng->d_delaytime, eng->windpar.WindSpeed, eng->windpar.WindFreeTravelDensThresh, T->atime};
+    eng->sph.hydro_force(eng->tree, v, *T, eng->denspar, eng->hydropar, d_active, nactive, eng->n, eng->stream, decouple ? &W : nullptr);
+    API_END
+}
+
+int mpg_dev_set_delaytime(mpg_engine *eng, const double *d_delaytime)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    eng->d_delaytime = d_delaytime;
+    API_END
+}
+
+int mpg_set_delaytime(mpg_engine *eng, const double *delaytime)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    eng->h_delaytime = delaytime;
     API_END
 }
 
@@ -2036,6 +2055,139 @@ int mpg_blackhole_get_times(mpg_engine *eng, double ms[3])
     MPG_CHECK(eng && ms, "null argument");
     for(int k = 0; k < 3; k++)
         ms[k] = eng->bh.last_ms[k];
+    API_END
+}
+
+/* ------------------------------ the wind model (winds.c) ------------------------------ */
+
+int mpg_set_wind_params(mpg_engine *eng, const mpg_wind_params *par)
+{
+    API_BEGIN
+    MPG_CHECK(eng && par, "null argument");
+    char model[32];
+    snprintf(model, sizeof(model), "0x%X", (unsigned)par->WindModel);
+    // init_winds, winds.c:98-101
+    MPG_CHECK((par->WindModel & (WIND_FIXED_EFFICIENCY | WIND_USE_HALO)) != 0, std::string("WindModel = ") + model + " is strange. This shall not happen.");
+    eng->windpar = *par;
+    eng->have_windpar = true;
+    API_END
+}
+
+// the view and the scalars of a wind call on the bound particles
+static void winds_setup(mpg_engine *eng, const mpg_wind_arrays *A, double atime, const char *who, WindView &v, WindScalars &S)
+{
+    MPG_CHECK(eng->have_windpar, std::string(who) + ": no parameters (mpg_set_wind_params first)");
+    MPG_CHECK(eng->d_pos || eng->n == 0, std::string(who) + ": no particles bound");
+    MPG_HIP(hipSetDevice(eng->device));
+    v = WindView{eng->d_pos, eng->d_mass, eng->d_type, eng->n, *A};
+    S.p = eng->windpar;
+    S.atime = atime;
+    S.rnd = eng->bh.rnd.p;
+    S.rndsize = (uint64_t)eng->bh.rndsize;
+}
+
+int mpg_dev_winds_and_feedback(mpg_engine *eng, const mpg_wind_arrays *A, const int *d_newstars, int64_t nnew, double atime)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A, "null argument");
+    MPG_CHECK(nnew >= 0, "winds_and_feedback: negative list length");
+    WindView v;
+    WindScalars S;
+    winds_setup(eng, A, atime, "winds_and_feedback", v, S);
+    eng->winds.reset();
+    // winds.c:302-306: the subgrid model does nothing here; without a new star nothing is read, nothing is written, no tree is demanded
+    if((eng->windpar.WindModel & WIND_SUBGRID) == 0 && nnew > 0) {
+        MPG_CHECK(d_newstars, "winds_and_feedback: no list of new stars");
+        MPG_CHECK(eng->bh.rndsize > 0, "winds_and_feedback: no random table (mpg_set_random_table first)");
+        MPG_CHECK(A->id && A->hsml && A->vdisp && A->density && A->vel && A->entropy && A->delaytime,
+                  "winds_and_feedback: the arrays id, hsml, vdisp, density, vel, entropy and delaytime are required");
+        eng->winds.check_stars(v, d_newstars, nnew, eng->stream);
+        MPG_CHECK(eng->tree_allocated && (eng->tree_mask & 1) != 0, "winds_and_feedback: the current tree does not contain the gas (GASMASK)");
+        eng->winds.run(eng->tree, v, S, d_newstars, nnew, eng->stream);
+    }
+    API_END
+}
+
+int mpg_dev_winds_subgrid(mpg_engine *eng, const mpg_wind_arrays *A, const int *d_maybewind, int64_t n, const double *d_stellarmass, double atime)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A, "null argument");
+    MPG_CHECK(n >= 0, "winds_subgrid: negative list length");
+    WindView v;
+    WindScalars S;
+    winds_setup(eng, A, atime, "winds_subgrid", v, S);
+    eng->winds.reset();
+    if((eng->windpar.WindModel & WIND_SUBGRID) != 0 && n > 0) { // winds.c:279-283
+        MPG_CHECK(eng->bh.rndsize > 0, "winds_subgrid: no random table (mpg_set_random_table first)");
+        MPG_CHECK(d_stellarmass && A->id && A->vdisp && A->density && A->vel && A->entropy && A->delaytime && eng->d_mass,
+                  "winds_subgrid: the stellar masses and the arrays id, vdisp, density, vel, entropy and delaytime are required");
+        eng->winds.subgrid(v, S, d_maybewind, n, d_stellarmass, eng->stream);
+    }
+    API_END
+}
+
+int mpg_dev_winds_evolve(mpg_engine *eng, const mpg_wind_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A && T, "null argument");
+    MPG_CHECK(nactive >= 0, "winds_evolve: negative list length");
+    WindView v;
+    WindScalars S;
+    winds_setup(eng, A, T->atime, "winds_evolve", v, S);
+    const int64_t nlist = d_active ? nactive : eng->n;
+    if(nlist > 0) {
+        MPG_CHECK(A->density && A->tb_hydro && A->delaytime, "winds_evolve: the arrays density, tb_hydro and delaytime are required");
+        eng->winds.evolve(v, S, *T, d_active, nlist, eng->stream);
+    }
+    API_END
+}
+
+int mpg_winds_get_stats(mpg_engine *eng, int64_t stats[6], double *maxvel)
+{
+    API_BEGIN
+    MPG_CHECK(eng && stats, "null argument");
+    for(int k = 0; k < WD_NSTATS; k++)
+        stats[k] = eng->winds.last_stats[k];
+    if(maxvel)
+        *maxvel = eng->winds.last_maxvel;
+    API_END
+}
+
+int mpg_winds_export(mpg_engine *eng, int64_t capacity, int32_t *star, int32_t *gas, int64_t *count)
+{
+    API_BEGIN
+    MPG_CHECK(eng && count && capacity >= 0, "null argument");
+    const int64_t nk = eng->winds.last_stats[3], m = eng->winds.last_capacity;
+    *count = nk;
+    if(m > 0 && (star || gas)) {
+        MPG_HIP(hipSetDevice(eng->device));
+        MPG_HIP(hipStreamSynchronize(eng->stream));
+        const TreeView tv = eng->tree.view();
+        std::vector<WindKick> k((size_t)m);
+        std::vector<int> order((size_t)tv.npart);
+        MPG_HIP(hipMemcpy(k.data(), eng->winds.kicks.p, (size_t)m * sizeof(WindKick), hipMemcpyDeviceToHost));
+        MPG_HIP(hipMemcpy(order.data(), tv.order, (size_t)tv.npart * sizeof(int), hipMemcpyDeviceToHost));
+        int64_t out = 0;
+        for(int64_t e = 0; e < m && out < capacity; e++) {
+            if(k[e].star < 0) // an unused entry of a star's segment
+                continue;
+            MPG_CHECK(k[e].slot >= 0 && k[e].slot < tv.npart, "mpg_winds_export: the tree of the last call is gone");
+            if(star)
+                star[out] = k[e].star;
+            if(gas)
+                gas[out] = order[k[e].slot];
+            out++;
+        }
+    }
+    API_END
+}
+
+int mpg_winds_get_times(mpg_engine *eng, double ms[3])
+{
+    API_BEGIN
+    MPG_CHECK(eng && ms, "null argument");
+    for(int k = 0; k < 3; k++)
+        ms[k] = eng->winds.last_ms[k];
     API_END
 }
 

@@ -8,6 +8,7 @@
 #include "veldisp.h"
 #include "cooling.h"
 #include "metals.h"
+#include "winds.h"
 #include "blackhole.h"
 #include "dynfric.h"
 #include "timestep.h"
@@ -175,6 +176,17 @@ struct mpg_engine {
     bool have_dfpar = false;
     DynfricEngine df;
     DevBuf<char> df_stage[DF_NFIELDS];
+    // the wind model (winds.hip): parameters, the walks' state (the random table is the black holes'); the staging of its host form
+    mpg_wind_params windpar{};
+    bool have_windpar = false;
+    WindsEngine winds;
+    DevBuf<char> wd_stage[WD_NFIELDS];
+    // ... and SphP.DelayTime for hydro_force's decoupling (WIND_DECOUPLE_SPH): the device column in effect (mpg_dev_set_delaytime, or
+    // s_delaytime after mpg_resident_sph_set_delaytime), the host column mpg_hydro_force uploads per call (mpg_set_delaytime) into
+    // s_delaytime_call
+    const double *d_delaytime = nullptr;
+    const double *h_delaytime = nullptr;
+    DevBuf<double> s_delaytime, s_delaytime_call;
     void prefetch_join()
     {
         if(prefetch_thread.joinable())

@@ -862,7 +862,18 @@ int mpg_hydro_force(mpg_engine *eng, const mpg_particle_view *P, const mpg_sph_a
     else
         stage_sph(eng, A, &d, P->n);
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
-    MPG_CALL(mpg_dev_hydro_force(eng, &d, T, d_act, NumActiveParticle));
+    // the host DelayTime column of mpg_set_delaytime travels with the call and is the column in effect for it
+    const double *const bound = eng->d_delaytime;
+    if(eng->h_delaytime && P->n > 0) {
+        // (a buffer of its own: s_delaytime may hold the column of mpg_resident_sph_set_delaytime, which comes back into effect below)
+        eng->s_delaytime_call.reserve((size_t)P->n + 1);
+        MPG_HIP(hipMemcpyAsync(eng->s_delaytime_call.p, eng->h_delaytime, (size_t)P->n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        eng->d_delaytime = eng->s_delaytime_call.p;
+    }
+    const int rc = mpg_dev_hydro_force(eng, &d, T, d_act, NumActiveParticle);
+    if(eng->h_delaytime)
+        eng->d_delaytime = bound;
+    MPG_CHECK(rc == 0, mpg_last_error());
     if(!res)
         unstage_sph(eng, A, &d, P->n, true);
     API_END
@@ -1019,6 +1030,34 @@ int mpg_blackhole(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, 
         MPG_HIP(hipStreamSynchronize(eng->stream));
         flags_to_records(*pv, A->flags);
     }
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}
+
+// winds_and_feedback for the new stars of a host table: the arrays go through wd_stage / wd_unstage (host_table.h); nothing of the records
+// is written.  Without a new star, or with the subgrid model, nothing travels and no tree is built (winds.c:302-306).
+int mpg_winds_and_feedback(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_wind_arrays *A, const int *NewStars,
+                           int64_t NumNewStars, double atime)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A, "null argument");
+    MPG_CHECK(NumNewStars >= 0, "winds_and_feedback: negative list length");
+    MPG_CHECK(eng->have_windpar, "winds_and_feedback: no parameters (mpg_set_wind_params first)");
+    if((eng->windpar.WindModel & WIND_SUBGRID) != 0 || NumNewStars == 0) {
+        mpg_err_slot().clear();
+        return 0;
+    }
+    MPG_CHECK(NewStars, "winds_and_feedback: no list of new stars");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    const int64_t n = pv->n;
+    mpg_wind_arrays d{};
+    wd_stage(*A, d, eng->wd_stage, n, BH_OTHER_CALL, eng->stream);
+    const int *d_new = upload_active(eng->s_active, NewStars, NumNewStars, eng->stream);
+    // the tree of the call: the gas tree as mpg_density builds it (winds_find_weights, winds.c:235-240)
+    MPG_CALL(mpg_dev_force_tree_rebuild_mask(eng, 1 /* GASMASK */, 0));
+    MPG_CALL(mpg_dev_winds_and_feedback(eng, &d, d_new, NumNewStars, atime));
+    wd_unstage(*A, d, n, BH_OTHER_CALL, eng->stream);
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }

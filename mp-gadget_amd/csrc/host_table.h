@@ -403,7 +403,8 @@ enum BhRole : unsigned {
     BH_OUT = 2,       // comes back
     BH_OPTIONAL = 4,  // may be NULL
     BH_TABLE = 8,     // P.Mass: a column of the staged / resident table, never staged from `A`
-    BH_RES_ALIAS = 16 // resident gas run: aliases a resident column
+    BH_RES_ALIAS = 16, // resident gas run: aliases a resident column
+    BH_OTHER_CALL = 32 // read by another call that takes the same struct: never staged by this one
 };
 struct BhField {
     const char *name;
@@ -531,6 +532,49 @@ inline void df_unstage(const mpg_bh_dynfric_arrays &host, const mpg_bh_dynfric_a
 {
     for(int f = 0; f < DF_NFIELDS; f++) {
         const BhField &F = DF_FIELDS[f];
+        void *h = field_get(host, F.off);
+        if(h && (F.role & BH_OUT) && !(F.role & skip))
+            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.bytes, hipMemcpyDeviceToHost, st));
+    }
+}
+// ... and of winds_and_feedback (roles as above).  tb_hydro is winds_evolve's alone and does not travel.
+#define MPG_WD_FIELD(m, bytes, role) {#m, offsetof(mpg_wind_arrays, m), bytes, role}
+constexpr int WD_NFIELDS = 10;
+const BhField WD_FIELDS[WD_NFIELDS] = {
+    MPG_WD_FIELD(id, 8, BH_IN),
+    MPG_WD_FIELD(hsml, 8, BH_IN),
+    MPG_WD_FIELD(vdisp, 8, BH_IN),
+    MPG_WD_FIELD(density, 8, BH_IN),
+    MPG_WD_FIELD(tb_hydro, 1, BH_OTHER_CALL),
+    MPG_WD_FIELD(vel, 24, BH_IN | BH_OUT),
+    MPG_WD_FIELD(entropy, 8, BH_IN | BH_OUT),
+    MPG_WD_FIELD(delaytime, 8, BH_IN | BH_OUT),
+    MPG_WD_FIELD(totalweight, 8, BH_OUT | BH_OPTIONAL),
+    MPG_WD_FIELD(kick_star, 8, BH_OUT | BH_OPTIONAL),
+};
+#undef MPG_WD_FIELD
+static_assert(sizeof(mpg_wind_arrays) == WD_NFIELDS * sizeof(void *), "WD_FIELDS describes every member of mpg_wind_arrays");
+inline void wd_stage(const mpg_wind_arrays &host, mpg_wind_arrays &dev, mpg::DevBuf<char> *stage, int64_t n, unsigned skip, hipStream_t st)
+{
+    for(int f = 0; f < WD_NFIELDS; f++) {
+        const BhField &F = WD_FIELDS[f];
+        if(F.role & skip)
+            continue;
+        void *h = field_get(host, F.off), *d = nullptr;
+        MPG_CHECK(h || (F.role & BH_OPTIONAL), std::string("winds_and_feedback: the array ") + F.name + " is required");
+        if(h) {
+            stage[f].reserve((size_t)n * F.bytes + 16);
+            d = stage[f].p;
+            // (the outputs go up too: the call writes the entries of its stars and of the kicked gas only, the others come back as they were)
+            MPG_HIP(hipMemcpyAsync(d, h, (size_t)n * F.bytes, hipMemcpyHostToDevice, st));
+        }
+        field_set(dev, F.off, d);
+    }
+}
+inline void wd_unstage(const mpg_wind_arrays &host, const mpg_wind_arrays &dev, int64_t n, unsigned skip, hipStream_t st)
+{
+    for(int f = 0; f < WD_NFIELDS; f++) {
+        const BhField &F = WD_FIELDS[f];
         void *h = field_get(host, F.off);
         if(h && (F.role & BH_OUT) && !(F.role & skip))
             MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.bytes, hipMemcpyDeviceToHost, st));

@@ -259,6 +259,28 @@ int mpg_resident_sph_end(mpg_engine *eng, const mpg_sph_arrays *A)
     }
     MPG_HIP(hipStreamSynchronize(eng->stream));
     eng->sph_resident = false;
+    if(eng->d_delaytime == eng->s_delaytime.p) // the column of mpg_resident_sph_set_delaytime ends with the stretch
+        eng->d_delaytime = nullptr;
+    API_END
+}
+
+// SphP.DelayTime of a resident gas run for hydro_force's decoupling: uploaded now, in effect until the next call or the end of the stretch
+int mpg_resident_sph_set_delaytime(mpg_engine *eng, const double *delaytime)
+{
+    API_BEGIN
+    MPG_CHECK(eng && eng->sph_resident, "mpg_resident_sph_set_delaytime: no resident gas arrays");
+    MPG_HIP(hipSetDevice(eng->device));
+    const int64_t n = eng->res_n;
+    if(!delaytime || n <= 0) {
+        if(eng->d_delaytime == eng->s_delaytime.p)
+            eng->d_delaytime = nullptr;
+    }
+    else {
+        eng->s_delaytime.reserve((size_t)n + 1);
+        MPG_HIP(hipMemcpyAsync(eng->s_delaytime.p, delaytime, (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        MPG_HIP(hipStreamSynchronize(eng->stream));
+        eng->d_delaytime = eng->s_delaytime.p;
+    }
     API_END
 }
 

@@ -37,6 +37,14 @@ struct DensityCtl {
     const double *entvarpred;
 };
 
+// the wind model's decoupling in hydro_force (winds_is_particle_decoupled, winds_decoupled_hydro, winds.c:113-136)
+struct HydroWind {
+    const double *delaytime; // SphP.DelayTime by particle
+    double windspeed2;       // the caller: WindSpeed; the kernel: 2 * WindSpeed * atime * fac_mu
+    double densthresh;       // WindFreeTravelDensThresh
+    double atime;
+};
+
 struct HydroCtl {
     int ktype;
     double fac_mu, fac_vsic_fix, hubble_a2;
@@ -69,7 +77,7 @@ struct SphEngine {
     void calc_hmax(TreeBuilder &tree, hipStream_t st);
     // hydro_force(), hydra.c:153-245
     void hydro_force(TreeBuilder &tree, const SphView &A, const mpg_sph_times &T, const mpg_density_params &P, const mpg_hydro_params &HP,
-                     const int *d_active, int64_t nactive, int64_t n, hipStream_t st);
+                     const int *d_active, int64_t nactive, int64_t n, hipStream_t st, const HydroWind *wind = nullptr);
 };
 
 } // namespace mpg

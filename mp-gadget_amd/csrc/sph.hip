@@ -459,10 +459,13 @@ __device__ __forceinline__ double pressure_pred(double eom, double entvar) // Pr
     return exp(SPH_GAMMA * log(entvar * eom));
 }
 
-// per-source record of the hydro loop (tree order); every field is a function of the source particle alone
-__global__ void __launch_bounds__(256) k_hydro_prepare(int64_t npart, const int *__restrict__ order, const SphView A, const mpg_sph_times T,
-                                                       const mpg_hydro_params HP, const double *__restrict__ entvarpred, double fac_mu,
-                                                       HydroSrc *__restrict__ hs, double *__restrict__ hsml_t)
+// per-source record of the hydro loop (tree order); every field is a function of the source particle alone.  DEC: with the wind model's
+// WIND_DECOUPLE_SPH, a source with DelayTime > 0 (winds_is_particle_decoupled, winds.c:113-120) takes its smoothing length NEGATED into
+// hsml_t: no pair test keeps it (hydro_test) and no node's search radius counts it (k_hsmax_leaf) - hydra.c:360-363 without a new load.
+template <bool DEC>
+__device__ __forceinline__ void hydro_prepare(int64_t npart, const int *__restrict__ order, const SphView &A, const mpg_sph_times &T,
+                                              const mpg_hydro_params &HP, const double *__restrict__ entvarpred, double fac_mu,
+                                              HydroSrc *__restrict__ hs, double *__restrict__ hsml_t, const double *__restrict__ delaytime)
 {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(k >= npart)
@@ -485,7 +488,21 @@ __global__ void __launch_bounds__(256) k_hydro_prepare(int64_t npart, const int 
     o.dhsml = A.dhsmlegyfac[ci];
     o.dloga = T.dloga_bin[bin];
     hs[k] = o;
-    hsml_t[k] = o.hsml; // (the distance tests read the smoothing lengths alone: 8 bytes per candidate instead of a line of the 96-byte records)
+    // (the distance tests read the smoothing lengths alone: 8 bytes per candidate instead of a line of the 96-byte records)
+    hsml_t[k] = (DEC && delaytime[ci] > 0) ? -o.hsml : o.hsml;
+}
+__global__ void __launch_bounds__(256) k_hydro_prepare(int64_t npart, const int *__restrict__ order, const SphView A, const mpg_sph_times T,
+                                                       const mpg_hydro_params HP, const double *__restrict__ entvarpred, double fac_mu,
+                                                       HydroSrc *__restrict__ hs, double *__restrict__ hsml_t)
+{
+    hydro_prepare<false>(npart, order, A, T, HP, entvarpred, fac_mu, hs, hsml_t, nullptr);
+}
+__global__ void __launch_bounds__(256) k_hydro_prepare_decoupled(int64_t npart, const int *__restrict__ order, const SphView A, const mpg_sph_times T,
+                                                                 const mpg_hydro_params HP, const double *__restrict__ entvarpred, double fac_mu,
+                                                                 HydroSrc *__restrict__ hs, double *__restrict__ hsml_t,
+                                                                 const double *__restrict__ delaytime)
+{
+    hydro_prepare<true>(npart, order, A, T, HP, entvarpred, fac_mu, hs, hsml_t, delaytime);
 }
 
 // the target-side constants of hydro_ngbiter
@@ -498,10 +515,13 @@ struct HydroAcc {
 };
 
 // symmetric distance test (treewalk.c:1218-1232) and the pair condition of hydro_ngbiter (hydra.c:330-338): is this a pair?
-template <bool WRAP>
+// DEC: a negative hsml_j is a decoupled wind particle, which is no source (hydro_prepare)
+template <bool WRAP, bool DEC>
 __device__ __forceinline__ bool hydro_test(const Src4 s, const double hsml_j, const HydroTarget &t, const DKernel &kernel_i, const HydroCtl &C,
                                            const double box)
 {
+    if(DEC && hsml_j < 0)
+        return false;
     const double hh = fmax(hsml_j, t.me.hsml);
     const double d0 = near_img<WRAP>(t.px - s.x, box, 1.0 / box);
     const double d1 = near_img<WRAP>(t.py - s.y, box, 1.0 / box);
@@ -587,9 +607,11 @@ __device__ __forceinline__ void hydro_eval(const Src4 s, const HydroSrc &o, cons
 }
 
 // The end of the hydro loop for one target: hydro_reduce (assign) + hydro_postprocess (hydra.c:279-294, 514-528) and the statistics.
+// DEC: a target with DelayTime > 0 keeps what its walk found of MaxSignalVel and nothing else (winds_decoupled_hydro, winds.c:122-136).
+template <bool DEC>
 __device__ __forceinline__ void hydro_finish(const SphView &A, const HydroCtl &C, HydroAcc &a, const HydroTarget &t, const bool valid, const int s,
                                              const int i, unsigned long long *__restrict__ stats, const unsigned n_cand,
-                                             const unsigned n_pair)
+                                             const unsigned n_pair, const HydroWind *__restrict__ W)
 {
     a.Acc0 = group_sum(a.Acc0);
     a.Acc1 = group_sum(a.Acc1);
@@ -604,16 +626,29 @@ __device__ __forceinline__ void hydro_finish(const SphView &A, const HydroCtl &C
         A.hydroacc_out[3 * (int64_t)i + 2] = a.Acc2;
         A.maxsignalvel[i] = a.MaxSignalVel;
         A.dtentropy_out[i] = a.DtEntropy * (SPH_GAMMA_MINUS1 / (C.hubble_a2 * pow(t.IDensity, SPH_GAMMA_MINUS1)));
+        if(DEC && W->delaytime[i] > 0) {
+            A.hydroacc_out[3 * (int64_t)i] = 0;
+            A.hydroacc_out[3 * (int64_t)i + 1] = 0;
+            A.hydroacc_out[3 * (int64_t)i + 2] = 0;
+            A.dtentropy_out[i] = 0;
+            const double hsml_c = cbrt(W->densthresh / t.IDensity) * W->atime;
+            A.maxsignalvel[i] = hsml_c * (W->windspeed2 > a.MaxSignalVel ? W->windspeed2 : a.MaxSignalVel); // DMAX
+        }
     }
     wave_stats(stats, n_cand, n_pair);
 }
 
-// hydro_force loop: the group-cooperative search of ngb_walk.h with the symmetric cull
+// hydro_force loop: the group-cooperative search of ngb_walk.h with the symmetric cull.  DEC = false (no trailing argument) is the loop
+// without the wind model's decoupling, with the arguments and the code it had before there was such a rule, and the only form a run
+// without a DelayTime column launches; DEC = true takes one HydroWind behind the others.
+__device__ __forceinline__ const HydroWind *hydro_wind() { return nullptr; }
+__device__ __forceinline__ const HydroWind *hydro_wind(const HydroWind &W) { return &W; }
+template <bool DEC, class... Wind>
 __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphView A, const mpg_sph_times T, const mpg_hydro_params HP,
                                                const HydroCtl C, const HydroSrc *__restrict__ hs, const double *__restrict__ hsml_t,
                                                const int *__restrict__ slot_of,
                                                const int *__restrict__ targets, int64_t ntargets, unsigned long long *__restrict__ stats,
-                                               unsigned *__restrict__ err)
+                                               unsigned *__restrict__ err, const Wind... W)
 {
     __shared__ unsigned s_stack[4 * 8 * SPH_STK];
     __shared__ int s_cbuf[4 * 8 * SPH_CBUF];
@@ -672,7 +707,7 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
             bool keep = false;
             if(live) {
                 n_cand++;
-                keep = hydro_test<WRAP>(cand.p, cand.hsml, t, kernel_i, C, tv.box);
+                keep = hydro_test<WRAP, DEC>(cand.p, cand.hsml, t, kernel_i, C, tv.box);
                 n_pair += keep ? 1u : 0u;
             }
             cnt = cbuf_push(cbuf, head, cnt, keep, slot, s, gshift);
@@ -704,7 +739,7 @@ __global__ void __launch_bounds__(256, 4) k_hydro(const TreeView tv, const SphVi
         loops(std::true_type{});
     if(ngb_overflowed(g, err))
         return;
-    hydro_finish(A, C, a, t, valid, s, i, stats, n_cand, n_pair);
+    hydro_finish<DEC>(A, C, a, t, valid, s, i, stats, n_cand, n_pair, hydro_wind(W...));
 }
 
 __global__ void __launch_bounds__(256) k_slot_of(int64_t npart, const int *__restrict__ order, int *__restrict__ slot_of)
@@ -840,7 +875,7 @@ void SphEngine::calc_hmax(TreeBuilder &tree, hipStream_t st)
 }
 
 void SphEngine::hydro_force(TreeBuilder &tree, const SphView &A, const mpg_sph_times &T, const mpg_density_params &P, const mpg_hydro_params &HP,
-                            const int *d_active, int64_t nactive, int64_t n, hipStream_t st)
+                            const int *d_active, int64_t nactive, int64_t n, hipStream_t st, const HydroWind *wind)
 {
     tree.ensure_level_order(st);
     TreeView tv = tree.view();
@@ -859,7 +894,11 @@ void SphEngine::hydro_force(TreeBuilder &tree, const SphView &A, const mpg_sph_t
     MPG_HIP(hipMemsetAsync(stats.p, 0, 8 * sizeof(unsigned long long), st));
     if(tv.npart > 0) {
         hipLaunchKernelGGL(k_slot_of, dim3(nblk(tv.npart)), dim3(256), 0, st, tv.npart, tv.order, slot_of.p);
-        hipLaunchKernelGGL(k_hydro_prepare, dim3(nblk(tv.npart)), dim3(256), 0, st, tv.npart, tv.order, A, T, HP, entvarpred.p, C.fac_mu, hsrc.p, hsml_t.p);
+        if(wind)
+            hipLaunchKernelGGL(k_hydro_prepare_decoupled, dim3(nblk(tv.npart)), dim3(256), 0, st, tv.npart, tv.order, A, T, HP, entvarpred.p, C.fac_mu,
+                               hsrc.p, hsml_t.p, wind->delaytime);
+        else
+            hipLaunchKernelGGL(k_hydro_prepare, dim3(nblk(tv.npart)), dim3(256), 0, st, tv.npart, tv.order, A, T, HP, entvarpred.p, C.fac_mu, hsrc.p, hsml_t.p);
         // the symmetric search runs on the cubes around the nodes' particles; its radius per node is the largest of the smoothing lengths
         // the pair tests below read (hsml_t), where the reference has the reach beyond the cell's faces (hmax)
         static const bool cell_cull = getenv("MPG_SPH_CELL_CULL") != nullptr;
@@ -882,8 +921,18 @@ void SphEngine::hydro_force(TreeBuilder &tree, const SphView &A, const mpg_sph_t
         MPG_HIP(hipMemcpyAsync(&nt, ctr.p + CTR_QUEUE, sizeof(unsigned), hipMemcpyDeviceToHost, st));
         MPG_HIP(hipStreamSynchronize(st));
     }
-    if(nt > 0)
-        hipLaunchKernelGGL(k_hydro, dim3(nblk(nt, 32)), dim3(256), 0, st, tv, A, T, HP, C, hsrc.p, hsml_t.p, slot_of.p, queue_a.p, (int64_t)nt, stats.p,
+    if(nt > 0 && wind) {
+        // winds_decoupled_hydro, winds.c:131-133, with the wind model's WindSpeed in wind->windspeed2
+        HydroWind W = *wind;
+        double windspeed = W.windspeed2 * atime;
+        windspeed *= C.fac_mu;
+        W.windspeed2 = 2 * windspeed;
+        W.atime = atime;
+        hipLaunchKernelGGL((k_hydro<true, HydroWind>), dim3(nblk(nt, 32)), dim3(256), 0, st, tv, A, T, HP, C, hsrc.p, hsml_t.p, slot_of.p, queue_a.p, (int64_t)nt,
+                           stats.p, ctr.p + CTR_ERR, W);
+    }
+    else if(nt > 0)
+        hipLaunchKernelGGL((k_hydro<false>), dim3(nblk(nt, 32)), dim3(256), 0, st, tv, A, T, HP, C, hsrc.p, hsml_t.p, slot_of.p, queue_a.p, (int64_t)nt, stats.p,
                            ctr.p + CTR_ERR);
     MPG_HIP(hipGetLastError());
     unsigned long long hs[2] = {0, 0};

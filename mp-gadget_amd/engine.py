@@ -166,6 +166,23 @@ class BlackholeParams(C.Structure):
                 ("UnitVelocity_in_cm_per_s", C.c_double), ("uu_in_cgs", C.c_double)]
 
 
+WIND_ARRAY_FIELDS = ("id", "hsml", "vdisp", "density", "tb_hydro", "vel", "entropy", "delaytime", "totalweight", "kick_star")
+WIND_ARRAY_DTYPES = dict(id="uint64", kick_star="uint64", tb_hydro="uint8")
+WIND_SUBGRID, WIND_DECOUPLE_SPH, WIND_USE_HALO, WIND_FIXED_EFFICIENCY, WIND_ISOTROPIC = 1, 2, 4, 8, 512   # enum WindModel, winds.h:13-20
+
+
+class WindArraysC(C.Structure):
+    """mpg_wind_arrays"""
+    _fields_ = [(k, C.c_void_p) for k in WIND_ARRAY_FIELDS]
+
+
+class WindParams(C.Structure):
+    """mpg_wind_params"""
+    _fields_ = [("WindModel", C.c_int), ("WindEfficiency", C.c_double), ("WindSigma0", C.c_double), ("WindSpeedFactor", C.c_double),
+                ("MinWindVelocity", C.c_double), ("WindThermalFactor", C.c_double), ("WindFreeTravelLength", C.c_double),
+                ("WindSpeed", C.c_double), ("MaxWindFreeTravelTime", C.c_double), ("WindFreeTravelDensThresh", C.c_double)]
+
+
 COOLING_ARRAY_FIELDS = ("density", "entropy", "ne", "sfr", "metallicity", "heiii_ionized", "tb_hydro")
 COOLING_BYTE_FIELDS = ("heiii_ionized", "tb_hydro")
 RECOMB_CEN92, RECOMB_VERNER96, RECOMB_BADNELL06 = 0, 1, 2      # enum RecombType, cooling_rates.h:10-14
@@ -1310,6 +1327,90 @@ class Engine:
         c = (C.c_double * 3)()
         self._ck(self.lib.mpg_blackhole_get_times(self.h, c))
         return dict(accretion_ms=c[0], feedback_ms=c[1], apply_ms=c[2])
+
+    # ------------------------------------------------------------------ the wind model (winds.c)
+    # `arrays` maps the field names of mpg_wind_arrays to device tensors (dev forms) / contiguous numpy arrays (host form) of the element
+    # types in WIND_ARRAY_DTYPES (float64 otherwise).  The random table is the one of set_random_table.
+    def set_wind_params(self, par):
+        if not isinstance(par, WindParams):
+            par = WindParams(**par)
+        self._ck(self.lib.mpg_set_wind_params(self.h, C.byref(par)))
+
+    @staticmethod
+    def _wind_dev_arrays(arrays):
+        a = WindArraysC()
+        for k in WIND_ARRAY_FIELDS:
+            t = arrays.get(k)
+            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        return a
+
+    def dev_set_delaytime(self, delaytime):
+        """SphP.DelayTime (float64 device tensor by particle, or None) for the decoupling of dev_hydro_force"""
+        self._keep["delaytime"] = delaytime
+        self._ck(self.lib.mpg_dev_set_delaytime(self.h, _ptr(delaytime)))
+
+    def set_delaytime(self, delaytime):
+        """the host column (contiguous float64 numpy, or None) every hydro_force uploads"""
+        if delaytime is not None and (delaytime.dtype != np.float64 or not delaytime.flags["C_CONTIGUOUS"]):
+            raise EngineError("delaytime must be contiguous float64")
+        self._keep["h_delaytime"] = delaytime
+        self._ck(self.lib.mpg_set_delaytime(self.h, None if delaytime is None else delaytime.ctypes.data_as(C.c_void_p)))
+
+    def resident_sph_set_delaytime(self, delaytime):
+        """the host column of a resident gas run, uploaded now"""
+        if delaytime is not None and (delaytime.dtype != np.float64 or not delaytime.flags["C_CONTIGUOUS"]):
+            raise EngineError("delaytime must be contiguous float64")
+        self._ck(self.lib.mpg_resident_sph_set_delaytime(self.h, None if delaytime is None else delaytime.ctypes.data_as(C.c_void_p)))
+
+    def dev_winds_and_feedback(self, arrays, newstars, atime):
+        """newstars: int32 device tensor of rows (or None: no new star)"""
+        a = self._wind_dev_arrays(arrays)
+        nnew = 0 if newstars is None else newstars.shape[0]
+        self._ck(self.lib.mpg_dev_winds_and_feedback(self.h, C.byref(a), _ptr(newstars), C.c_int64(nnew), C.c_double(atime)))
+
+    def winds_and_feedback(self, P, BoxSize, arrays, NewStars, atime):
+        """host form: P supplies Pos / Mass / Type / flags; the arrays are numpy"""
+        v = self._view(P)
+        a = WindArraysC()
+        for k in WIND_ARRAY_FIELDS:
+            t = arrays.get(k)
+            want = np.dtype(WIND_ARRAY_DTYPES.get(k, "float64"))
+            if t is not None and (t.dtype != want or not t.flags["C_CONTIGUOUS"]):
+                raise EngineError("wind host array %s must be contiguous %s" % (k, want.name))
+            setattr(a, k, None if t is None else t.ctypes.data)
+        new = np.ascontiguousarray(NewStars if NewStars is not None else [], np.int32)
+        self._ck(self.lib.mpg_winds_and_feedback(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), new.ctypes.data_as(C.c_void_p),
+                                                 C.c_int64(len(new)), C.c_double(atime)))
+
+    def dev_winds_subgrid(self, arrays, maybewind, stellarmass, atime, n=None):
+        """maybewind: int32 device tensor of rows, or None with n: rows 0 .. n - 1; stellarmass: float64 device tensor by particle"""
+        a = self._wind_dev_arrays(arrays)
+        nl = int(n) if maybewind is None else maybewind.shape[0]
+        self._ck(self.lib.mpg_dev_winds_subgrid(self.h, C.byref(a), _ptr(maybewind), C.c_int64(nl), _ptr(stellarmass), C.c_double(atime)))
+
+    def dev_winds_evolve(self, arrays, times, active=None):
+        a = self._wind_dev_arrays(arrays)
+        nact = 0 if active is None else active.shape[0]
+        self._ck(self.lib.mpg_dev_winds_evolve(self.h, C.byref(a), C.byref(times), _ptr(active), C.c_int64(nact)))
+
+    def winds_stats(self):
+        c = (C.c_int64 * 6)()
+        v = C.c_double(0.0)
+        self._ck(self.lib.mpg_winds_get_stats(self.h, c, C.byref(v)))
+        return dict(stars=c[0], candidates=c[1], neighbours=c[2], potential_kicks=c[3], applied=c[4], discarded=c[5], maxvel=v.value)
+
+    def winds_export(self):
+        """the potential kicks of the last dev_winds_and_feedback as (star rows, gas rows), while its tree is still current"""
+        nk = self.winds_stats()["potential_kicks"]
+        star, gas, cnt = np.zeros(max(nk, 1), np.int32), np.zeros(max(nk, 1), np.int32), C.c_int64(0)
+        self._ck(self.lib.mpg_winds_export(self.h, C.c_int64(nk), star.ctypes.data_as(C.c_void_p), gas.ctypes.data_as(C.c_void_p), C.byref(cnt)))
+        return star[:nk], gas[:nk]
+
+    def winds_times(self):
+        """device time of the last winds_and_feedback in ms: the weight walk, the feedback walk, the resolve and apply passes"""
+        c = (C.c_double * 3)()
+        self._ck(self.lib.mpg_winds_get_times(self.h, c))
+        return dict(weight_ms=c[0], feedback_ms=c[1], apply_ms=c[2])
 
     # ------------------------------------------------------------------ black-hole dynamical friction and the potential minimum (bhdynfric.c)
     # `arrays` maps the field names of mpg_bh_dynfric_arrays to device tensors (dev form) / contiguous numpy arrays (host forms) of the

@@ -249,6 +249,27 @@ void density(const ActiveParticles *act, int update_hsml, int DoEgyDensity, int 
     walltime_add("/SPH/Density/Misc", 0);
 }
 
+/* Decoupled wind gas (winds_is_particle_decoupled, hydra.c:360-363, 522-526): when the model decouples, the model's parameters go to the
+ * library and SphP.DelayTime by particle is returned (mymalloc; the caller frees it), else NULL.  One rank only: mpg_dist_hydro_force
+ * does not carry the rule.  The two accessors are appended to the working copy of winds.c (tools/link_reference.sh, step 4). */
+int mpg_shim_wind_decouple(void);
+void mpg_shim_wind_params(mpg_wind_params *p);
+static double *gather_delaytime(void)
+{
+    if(!mpg_shim_wind_decouple())
+        return NULL;
+    mpg_wind_params par;
+    mpg_shim_wind_params(&par);
+    ck(mpg_set_wind_params(mpg_shim_engine(), &par));
+    const int64_t n = PartManager->NumPart;
+    int64_t i;
+    double *dt = (double *)mymalloc("mpg_delaytime", (size_t)(n > 0 ? n : 1) * sizeof(double));
+    #pragma omp parallel for
+    for(i = 0; i < n; i++)
+        dt[i] = (P[i].Type == 0 && !P[i].IsGarbage) ? SPHP(i).DelayTime : 0;
+    return dt;
+}
+
 void hydro_force(const ActiveParticles *act, const double atime, struct sph_pred_data *SPH_predicted, const DriftKickTimes times,
                  Cosmology *CP, const ForceTree *const tree)
 {
@@ -262,6 +283,11 @@ void hydro_force(const ActiveParticles *act, const double atime, struct sph_pred
     if(mpg_shim_resident()) { /* (see density()) */
         mpg_particle_view rv = view();
         fill_times(&t, &times, CP, atime);
+        /* (DelayTime is no resident column: winds_evolve and the kicks change it on the host, outside the stretch) */
+        double *dt = gather_delaytime();
+        ck(mpg_resident_sph_set_delaytime(mpg_shim_engine(), dt));
+        if(dt)
+            myfree(dt);
         ck(mpg_hydro_force(mpg_shim_engine(), &rv, mpg_shim_resident_sph(), &t, act->ActiveParticle, act->NumActiveParticle));
         walltime_add("/SPH/Hydro/WalkPrim", walltime_measure(WALLTIME_IGNORE));
         return;
@@ -274,8 +300,14 @@ void hydro_force(const ActiveParticles *act, const double atime, struct sph_pred
     if(mpg_shim_dist()) {
         ck(mpg_dist_hydro_force(mpg_shim_dist(), &v, &H.A, &t, act->ActiveParticle, act->NumActiveParticle));
     }
-    else
+    else {
+        double *dt = gather_delaytime();
+        ck(mpg_set_delaytime(mpg_shim_engine(), dt));
         ck(mpg_hydro_force(mpg_shim_engine(), &v, &H.A, &t, act->ActiveParticle, act->NumActiveParticle));
+        ck(mpg_set_delaytime(mpg_shim_engine(), NULL));
+        if(dt)
+            myfree(dt);
+    }
     #pragma omp parallel for
     for(i = 0; i < PartManager->NumPart; i++) {
         int k;

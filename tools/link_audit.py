@@ -33,8 +33,9 @@ RENAMES = {
     "sfr_eff.c": ["cooling_and_starformation"],
     "metal_return.c": ["metal_return"],
     "blackhole.c": ["blackhole"],
+    "winds.c": ["winds_and_feedback"],
 }
-SHIM_C = ["gravity-hip.c", "sph-hip.c", "forcetree-hip.c", "timestep-hip.c", "veldisp-hip.c", "cooling-hip.c", "metals-hip.c", "blackhole-hip.c", "mpg_mpi_comm.c", "mpg_rccl_mpi.c"]
+SHIM_C = ["gravity-hip.c", "sph-hip.c", "forcetree-hip.c", "timestep-hip.c", "veldisp-hip.c", "cooling-hip.c", "metals-hip.c", "blackhole-hip.c", "winds-hip.c", "mpg_mpi_comm.c", "mpg_rccl_mpi.c"]
 EXTERNAL = [("pfft", r"^pfft_"), ("fftw", r"^fftw_"), ("gsl", r"^gsl_"), ("mpi", r"^P?MPI_"), ("openmp", r"^(GOMP_|omp_)"),
             ("hdf5", r"^H5")]
 

@@ -13,7 +13,7 @@
 #   2. copy shim/*.c, shim/*.h and include/mpgadget_hip.h into <copy>/libgadget/;
 #   3. patch <copy>/libgadget/Makefile: drop gravpm.o gravshort-tree.o gravshort-pair.o gravity.o from GADGET_OBJS and add the shim
 #      objects; rename the five tree constructors in forcetree.o, the eight integrator entry points in timestep.o / drift.o and
-#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o, metal_return in metal_return.o and blackhole in blackhole.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
+#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o, metal_return in metal_return.o, blackhole in blackhole.o and winds_and_feedback in winds.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
 #   4. add the two parameter hooks (set_densitypar, set_hydro_params), the accessors of mpg_shim.h and the
 #      mpg_shim_particles_changed() calls listed in INTEGRATION.md ("Where P[] is reordered") with sed;
 #   5. build the library of this repository, then `make` in the copy with LIBS += -L<repo>/mp-gadget_amd -lmpgadget_hip -lmpi.
@@ -22,7 +22,7 @@ REF=${1:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 WORK=${2:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 CHECK=${3:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c blackhole-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
+SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c blackhole-hip.c winds-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
 SHIM_H="mpg_shim.h mpg_shim_epoch.h mpg_mpi_comm.h"
 REF_FILES="libgadget/Makefile libgadget/gravpm.c libgadget/gravshort-tree.c libgadget/gravshort-pair.c libgadget/gravity.c libgadget/forcetree.c
            libgadget/density.c libgadget/hydra.c libgadget/timestep.c libgadget/drift.c libgadget/timebinmgr.c libgadget/run.c libgadget/domain.c
@@ -69,7 +69,7 @@ echo "== 3. libgadget/Makefile"
 MK="$T/libgadget/Makefile"
 sed -i -e 's/\bgravshort-tree\.o gravshort-pair\.o hydra\.o/hydra.o/' -e 's/\bgravpm\.o powerspectrum\.o/powerspectrum.o/' \
        -e 's/\bpetapm\.o gravity\.o/petapm.o/' "$MK"
-sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o blackhole-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
+sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o blackhole-hip.o winds-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
 cat >> "$MK" <<MKEOF
 
 # ---- MP-Gadget on libmpgadget_hip (tools/link_reference.sh)
@@ -81,6 +81,7 @@ CFLAGS += -DMPGADGET_HIP -I$ROOT/include
 .objs/sfr_eff.o: CFLAGS += -Dcooling_and_starformation=cpu_cooling_and_starformation
 .objs/metal_return.o: CFLAGS += -Dmetal_return=cpu_metal_return
 .objs/blackhole.o: CFLAGS += -Dblackhole=cpu_blackhole
+.objs/winds.o: CFLAGS += -Dwinds_and_feedback=cpu_winds_and_feedback
 MKEOF
 
 echo "== 4. hooks in the reference sources (INTEGRATION.md lists them; each is one line)"
@@ -179,6 +180,12 @@ append(T + "/libgadget/bhdynfric.c", "void mpg_shim_bh_dynfric_params(int *BH_Dy
        "{\n    *BH_DynFrictionMethod = blackhole_dynfric_params.BH_DynFrictionMethod;\n    *BH_DFBoostFactor = blackhole_dynfric_params.BH_DFBoostFactor;\n"
        "    *BH_DFbmax = blackhole_dynfric_params.BH_DFbmax;\n}")
 append(T + "/libgadget/winds.c", "int mpg_shim_wind_decouple(void) { return HAS(wind_params.WindModel, WIND_DECOUPLE_SPH) ? 1 : 0; }")
+# the wind model (winds-hip.c, sph-hip.c): struct WindParams after init_winds
+append(T + "/libgadget/winds.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_wind_params(mpg_wind_params *p)\n{\n    p->WindModel = (int)wind_params.WindModel;\n"
+       + "".join("    p->%s = wind_params.%s;\n" % (k, k) for k in (
+           "WindEfficiency", "WindSigma0", "WindSpeedFactor", "MinWindVelocity", "WindThermalFactor", "WindFreeTravelLength", "WindSpeed",
+           "MaxWindFreeTravelTime", "WindFreeTravelDensThresh"))
+       + "}")
 append(T + "/libgadget/sfr_eff.c", "void mpg_shim_sfr_blackhole(int *StarformationOn, int *BHFeedbackUseTcool, double *PhysDensThresh, double *OverDensThresh)\n"
        "{\n    *StarformationOn = sfr_params.StarformationOn;\n    *BHFeedbackUseTcool = sfr_params.BHFeedbackUseTcool;\n"
        "    *PhysDensThresh = sfr_params.PhysDensThresh;\n    *OverDensThresh = sfr_params.OverDensThresh;\n}")
@@ -204,6 +211,7 @@ if [ "$CHECK" = "--check" ]; then
             veldisp.c) extra="-Dwinds_find_vel_disp=cpu_winds_find_vel_disp";;
             sfr_eff.c) extra="-Dcooling_and_starformation=cpu_cooling_and_starformation";;
             blackhole.c) extra="-Dblackhole=cpu_blackhole";;
+            winds.c) extra="-Dwinds_and_feedback=cpu_winds_and_feedback";;
         esac
         if ! gcc -std=gnu11 -fopenmp -fsyntax-only -DMPGADGET_HIP $extra -I "$STUB" -I "$MPIINC" -I "$ROOT/include" -I "$T/libgadget" -I "$T" -I "$REF/depends/bigfile/src" "$T/libgadget/$f" 2> "$STUB/err"; then
             if grep -q 'gsl/.*No such file' "$STUB/err"; then
