@@ -1990,9 +1990,8 @@ void blackhole_call(mpg_engine *eng, const mpg_blackhole_arrays *A, const mpg_sp
     MPG_CHECK(eng->have_bhpar, "blackhole: no parameters (mpg_set_blackhole_params first)");
     MPG_CHECK(eng->bh.rndsize > 0, "blackhole: no random table (mpg_set_random_table first)");
     MPG_CHECK(eng->d_pos || eng->n == 0, "blackhole: no particles bound");
-    for(int f = 0; f < BH_NFIELDS; f++)
-        MPG_CHECK(field_get(*A, BH_FIELDS[f].off) || (BH_FIELDS[f].role & BH_OPTIONAL) || eng->n == 0,
-                  std::string("blackhole: the array ") + BH_FIELDS[f].name + " is required");
+    for(const ArrayField &F : BH_FIELDS)
+        MPG_CHECK(field_get(*A, F.off) || (F.role & ARR_OPTIONAL) || eng->n == 0, std::string("blackhole: the array ") + F.name + " is required");
     MPG_HIP(hipSetDevice(eng->device));
     const mpg_blackhole_params &P = eng->bhpar;
     BhView v{eng->d_pos, eng->d_type, *A};

@@ -153,34 +153,32 @@ struct mpg_engine {
     std::string prefetch_error;
     mpg_particle_view prefetch_view{};
     // the staging of the velocity dispersion's host form (fields of mpg_veldisp_arrays)
-    DevBuf<double> vd_stage[8];
-    DevBuf<uint8_t> vd_stage_tb;
+    DevBuf<char> vd_stage[std::size(VDISP_FIELDS)];
     // radiative cooling (cooling.hip): parameters, tables and counters; the staging of its host forms (fields of mpg_cooling_arrays)
     CoolingEngine cooling;
-    DevBuf<double> cl_stage[5];
-    DevBuf<uint8_t> cl_stage_u8[2];
+    DevBuf<char> cl_stage[std::size(COOL_FIELDS)];
     // stellar mass and metal return (metals.hip): parameters and the loop's state; the staging of its host forms (fields of mpg_metal_arrays)
     mpg_metal_params metalpar{1, 2.0, 0.0};
     MetalsEngine metals;
-    DevBuf<double> mt_stage[13];
+    DevBuf<char> mt_stage[std::size(METAL_FIELDS)];
     HostBuf<float> mt_mass;
     // black-hole accretion, mergers and feedback (blackhole.hip): parameters, the walks' state and the random table; the staging of its
     // host forms (fields of mpg_blackhole_arrays)
     mpg_blackhole_params bhpar{};
     bool have_bhpar = false;
     BlackholeEngine bh;
-    DevBuf<char> bh_stage[BH_NFIELDS];
+    DevBuf<char> bh_stage[std::size(BH_FIELDS)];
     HostBuf<float> bh_mass;
     // black-hole dynamical friction and the potential minimum (dynfric.hip): parameters, the walk's state; the staging of its host forms
     mpg_bh_dynfric_params dfpar{};
     bool have_dfpar = false;
     DynfricEngine df;
-    DevBuf<char> df_stage[DF_NFIELDS];
+    DevBuf<char> df_stage[std::size(DF_FIELDS)];
     // the wind model (winds.hip): parameters, the walks' state (the random table is the black holes'); the staging of its host form
     mpg_wind_params windpar{};
     bool have_windpar = false;
     WindsEngine winds;
-    DevBuf<char> wd_stage[WD_NFIELDS];
+    DevBuf<char> wd_stage[std::size(WD_FIELDS)];
     // ... and SphP.DelayTime for hydro_force's decoupling (WIND_DECOUPLE_SPH): the device column in effect (mpg_dev_set_delaytime, or
     // s_delaytime after mpg_resident_sph_set_delaytime), the host column mpg_hydro_force uploads per call (mpg_set_delaytime) into
     // s_delaytime_call

@@ -887,26 +887,11 @@ int mpg_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, double BoxSi
     MPG_CHECK(A->vel && A->hsml && A->density && A->vdisp, "find_vel_disp: the arrays vel, hsml, density and vdisp are required");
     MPG_HIP(hipSetDevice(eng->device));
     stage_particles(eng, pv, BoxSize);
-    const size_t n = (size_t)pv->n;
-    mpg_veldisp_arrays d;
-    for(int f = 0; f < VDISP_NFIELDS; f++) { // every given array goes up
-        const VdispField &F = VDISP_FIELDS[f];
-        void *h = field_get(*A, F.off), *dv = nullptr;
-        if(h && F.width == 0) {
-            eng->vd_stage_tb.reserve(n + 1);
-            dv = eng->vd_stage_tb.p;
-            MPG_HIP(hipMemcpyAsync(dv, h, n, hipMemcpyHostToDevice, eng->stream));
-        }
-        else if(h) {
-            eng->vd_stage[f].reserve(n * F.width + 1);
-            dv = eng->vd_stage[f].p;
-            MPG_HIP(hipMemcpyAsync(dv, h, n * F.width * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-        }
-        field_set(d, F.off, dv);
-    }
+    mpg_veldisp_arrays d{};
+    stage_fields(VDISP_FIELDS, *A, d, eng->vd_stage, pv->n, 0, "find_vel_disp", eng->stream);
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
     MPG_CALL(mpg_dev_find_vel_disp(eng, &d, T, par, d_act, NumActiveParticle));
-    MPG_HIP(hipMemcpyAsync(A->vdisp, d.vdisp, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    unstage_fields(VDISP_FIELDS, *A, d, pv->n, 0, eng->stream); // (vdisp alone)
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }
@@ -921,36 +906,20 @@ int mpg_cooling(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, co
     MPG_CHECK(pv->n == 0 || (A->density && A->entropy && A->ne && A->sfr), "cooling: the arrays density, entropy, ne and sfr are required");
     MPG_HIP(hipSetDevice(eng->device));
     stage_particles(eng, pv, BoxSize);
-    const size_t n = (size_t)pv->n;
-    mpg_cooling_arrays d;
-    for(int f = 0; f < COOL_NFIELDS; f++) { // every given array goes up
-        const CoolField &F = COOL_FIELDS[f];
-        void *h = field_get(*A, F.off), *dv = nullptr;
-        if(h && F.width == 0) {
-            eng->cl_stage_u8[F.slot].reserve(n + 1);
-            dv = eng->cl_stage_u8[F.slot].p;
-            MPG_HIP(hipMemcpyAsync(dv, h, n, hipMemcpyHostToDevice, eng->stream));
-        }
-        else if(h) {
-            eng->cl_stage[F.slot].reserve(n + 1);
-            dv = eng->cl_stage[F.slot].p;
-            MPG_HIP(hipMemcpyAsync(dv, h, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-        }
-        field_set(d, F.off, dv);
-    }
+    mpg_cooling_arrays d{};
+    stage_fields(COOL_FIELDS, *A, d, eng->cl_stage, pv->n, 0, "cooling", eng->stream);
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
     const int rc = mpg_dev_cooling(eng, &d, T, step, d_act, NumActiveParticle);
     const std::string err = rc ? mpg_last_error() : "";
-    for(int f = 0; f < COOL_NFIELDS; f++)
-        if(COOL_FIELDS[f].out && n > 0)
-            MPG_HIP(hipMemcpyAsync(field_get(*A, COOL_FIELDS[f].off), field_get(d, COOL_FIELDS[f].off), n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+    if(pv->n > 0)
+        unstage_fields(COOL_FIELDS, *A, d, pv->n, 0, eng->stream);
     MPG_HIP(hipStreamSynchronize(eng->stream));
     MPG_CHECK(rc == 0, err);
     API_END
 }
 
 // metal_return for the listed particles of a host table: Mass is the records' column (staged with the table, written back into it), the
-// other arrays go through metal_stage / metal_unstage (host_table.h)
+// other arrays go through stage_fields / unstage_fields (host_table.h)
 int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_metal_arrays *A, const int *ActiveParticle,
                      int64_t NumActiveParticle)
 {
@@ -960,14 +929,14 @@ int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSiz
     stage_particles(eng, pv, BoxSize);
     const int64_t n = pv->n;
     mpg_metal_arrays d{};
-    metal_stage(*A, d, eng->mt_stage, n, METAL_TABLE, eng->stream);
+    stage_fields(METAL_FIELDS, *A, d, eng->mt_stage, n, ARR_TABLE, "metal_return", eng->stream);
     d.mass = eng->s_mass.p;
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
     // the tree of the call: the gas tree as mpg_density builds it.  (Built before the dev call, which demands it only when it has a target;
     // whether it has one is the device's knowledge, and a second queue pass here would cost what the build of a small tree costs.)
     MPG_CALL(mpg_dev_force_tree_rebuild_mask(eng, 1 /* GASMASK */, 0));
     MPG_CALL(mpg_dev_metal_return(eng, &d, d_act, NumActiveParticle));
-    metal_unstage(*A, d, n, METAL_TABLE, eng->stream);
+    unstage_fields(METAL_FIELDS, *A, d, n, ARR_TABLE, eng->stream);
     if(eng->metals.ntargets > 0) {
         eng->mt_mass.reserve((size_t)n + 1);
         mass_to_records(*pv, eng->s_mass.p, eng->mt_mass.p, eng->stream);
@@ -976,7 +945,7 @@ int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSiz
     API_END
 }
 
-// blackhole_dynfric + blackhole_dfaccel for the listed particles of a host table: the arrays go through df_stage / df_unstage
+// blackhole_dynfric + blackhole_dfaccel for the listed particles of a host table: the arrays go through stage_fields / unstage_fields
 // (host_table.h); nothing of the records is written.  The tree of the call's mask is built by the call itself once it has a target.
 int mpg_blackhole_dynfric(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T,
                           const int *ActiveParticle, int64_t NumActiveParticle)
@@ -993,15 +962,15 @@ int mpg_blackhole_dynfric(mpg_engine *eng, const mpg_particle_view *pv, double B
         return 0;
     }
     mpg_bh_dynfric_arrays d{};
-    df_stage(*A, d, eng->df_stage, n, 0, eng->stream);
+    stage_fields(DF_FIELDS, *A, d, eng->df_stage, n, 0, "blackhole_dynfric", eng->stream);
     dynfric_call(eng, &d, T, d_act, NumActiveParticle);
-    df_unstage(*A, d, n, 0, eng->stream);
+    unstage_fields(DF_FIELDS, *A, d, n, 0, eng->stream);
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }
 
 // blackhole() for the listed particles of a host table: Mass is the records' column (staged with the table, written back into it with
-// the flags), the other arrays go through bh_stage / bh_unstage (host_table.h).  The tree of gas and black holes and its hmax are built
+// the flags), the other arrays go through stage_fields / unstage_fields (host_table.h).  The tree of gas and black holes and its hmax are built
 // by the call itself once it knows that it has a target.
 int mpg_blackhole(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_blackhole_arrays *A, const mpg_sph_times *T,
                   const int *ActiveParticle, int64_t NumActiveParticle)
@@ -1018,11 +987,11 @@ int mpg_blackhole(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, 
         return 0;
     }
     mpg_blackhole_arrays d{};
-    bh_stage(*A, d, eng->bh_stage, n, BH_TABLE, eng->stream);
+    stage_fields(BH_FIELDS, *A, d, eng->bh_stage, n, ARR_TABLE, "blackhole", eng->stream);
     d.mass = eng->s_mass.p;
     // (a tree that a previous call left is one of another table or another step: always rebuilt when there is a target)
     blackhole_call(eng, &d, T, d_act, NumActiveParticle, 2);
-    bh_unstage(*A, d, n, BH_TABLE, eng->stream);
+    unstage_fields(BH_FIELDS, *A, d, n, ARR_TABLE, eng->stream);
     if(eng->bh.ntargets > 0) {
         BlackholeEngine::retype(eng->s_type.p, d.flags, n, eng->stream);
         eng->bh_mass.reserve((size_t)n + 1);
@@ -1034,7 +1003,7 @@ int mpg_blackhole(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, 
     API_END
 }
 
-// winds_and_feedback for the new stars of a host table: the arrays go through wd_stage / wd_unstage (host_table.h); nothing of the records
+// winds_and_feedback for the new stars of a host table: the arrays go through stage_fields / unstage_fields (host_table.h); nothing of the records
 // is written.  Without a new star, or with the subgrid model, nothing travels and no tree is built (winds.c:302-306).
 int mpg_winds_and_feedback(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_wind_arrays *A, const int *NewStars,
                            int64_t NumNewStars, double atime)
@@ -1052,12 +1021,12 @@ int mpg_winds_and_feedback(mpg_engine *eng, const mpg_particle_view *pv, double 
     stage_particles(eng, pv, BoxSize);
     const int64_t n = pv->n;
     mpg_wind_arrays d{};
-    wd_stage(*A, d, eng->wd_stage, n, BH_OTHER_CALL, eng->stream);
+    stage_fields(WD_FIELDS, *A, d, eng->wd_stage, n, ARR_OTHER_CALL, "winds_and_feedback", eng->stream);
     const int *d_new = upload_active(eng->s_active, NewStars, NumNewStars, eng->stream);
     // the tree of the call: the gas tree as mpg_density builds it (winds_find_weights, winds.c:235-240)
     MPG_CALL(mpg_dev_force_tree_rebuild_mask(eng, 1 /* GASMASK */, 0));
     MPG_CALL(mpg_dev_winds_and_feedback(eng, &d, d_new, NumNewStars, atime));
-    wd_unstage(*A, d, n, BH_OTHER_CALL, eng->stream);
+    unstage_fields(WD_FIELDS, *A, d, n, ARR_OTHER_CALL, eng->stream);
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }

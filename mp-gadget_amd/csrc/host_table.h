@@ -1,6 +1,7 @@
 // host_table.h -- the marshalling layer of the host-pointer ("drop-in") forms: everything that reads or writes the caller's records
-// (mpg_particle_view) and host arrays (mpg_sph_arrays, mpg_veldisp_arrays, mpg_cooling_arrays, mpg_metal_arrays).  Used by host_forms.hip, resident.hip and dist.hip; no
-// engine state lives here.
+// (mpg_particle_view) and host arrays: mpg_sph_arrays through SPH_FIELDS, whose staging has rules of its own (host_forms.hip), and the
+// structs of the velocity dispersion, cooling, metal return, black holes, dynamical friction and winds through one ArrayField table each
+// and stage_fields / unstage_fields.  Used by host_forms.hip, resident.hip and dist.hip; no engine state lives here.
 #pragma once
 #include "../../include/mpgadget_hip.h"
 #include "mpg_common.h"
@@ -8,6 +9,7 @@
 #include <cstddef>
 #include <cstring>
 #include <functional>
+#include <iterator>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -303,281 +305,205 @@ const SphField SPH_FIELDS[SPH_NFIELDS] = {
 static_assert(sizeof(mpg_sph_arrays) == SPH_NFIELDS * sizeof(void *), "SPH_FIELDS describes every member of mpg_sph_arrays");
 inline size_t sph_field_bytes(const SphField &F, int64_t n) { return F.width == 0 ? (size_t)n : (size_t)n * F.width * sizeof(double); }
 
-// ... and of the velocity dispersion: every member is an input, vdisp is also the output
-struct VdispField {
-    size_t off; // of the member in mpg_veldisp_arrays
-    int width;  // doubles per particle; 0: one byte per particle
+// ---- the host arrays of the other calls ------------------------------------------------------------------------------------------
+// One table per struct of array pointers, in the struct's member order, and one pair of functions that moves what a table describes.
+// A new module's host arrays: (1) a table X_FIELDS here, with its static_assert; (2) `DevBuf<char> x_stage[std::size(X_FIELDS)]` in
+// engine_internal.h; (3) stage_fields / the dev call / unstage_fields in its host form; (4) the tuple X_ARRAY_FIELDS, the dict
+// X_ARRAY_DTYPES and the class XArraysC in engine.py, bound with _dev_arrays / _host_arrays; (5) the struct's name in STRUCTS of
+// tests/test_array_structs.py, which holds the tuple and the dict against the header.
+enum ArrayRole : unsigned {
+    ARR_IN = 1,         // read by the call
+    ARR_OUT = 2,        // comes back
+    ARR_OPTIONAL = 4,   // may be NULL
+    ARR_TABLE = 8,      // P.Mass: a column of the staged / resident table, never staged from the struct
+    ARR_RES_ALIAS = 16, // resident gas run: aliases a resident column
+    ARR_OTHER_CALL = 32 // read by another call that takes the same struct: never staged by this one
 };
-constexpr int VDISP_NFIELDS = 8;
-const VdispField VDISP_FIELDS[VDISP_NFIELDS] = {
-    {offsetof(mpg_veldisp_arrays, vel), 3},  {offsetof(mpg_veldisp_arrays, gacc), 3},   {offsetof(mpg_veldisp_arrays, gpm), 3},
-    {offsetof(mpg_veldisp_arrays, tb_grav), 0}, {offsetof(mpg_veldisp_arrays, hsml), 1}, {offsetof(mpg_veldisp_arrays, dthsml), 1},
-    {offsetof(mpg_veldisp_arrays, density), 1}, {offsetof(mpg_veldisp_arrays, vdisp), 1}};
-static_assert(sizeof(mpg_veldisp_arrays) == VDISP_NFIELDS * sizeof(void *), "VDISP_FIELDS describes every member of mpg_veldisp_arrays");
-
-// ... and of the cooling: density, metallicity and the two byte columns are inputs, entropy / ne / sfr go up and come back
-struct CoolField {
-    size_t off; // of the member in mpg_cooling_arrays
-    int width;  // doubles per particle; 0: one byte per particle
-    int slot;   // ordinal among the double (or the byte) members: the staging buffer
-    bool out;
-};
-constexpr int COOL_NFIELDS = 7;
-const CoolField COOL_FIELDS[COOL_NFIELDS] = {
-    {offsetof(mpg_cooling_arrays, density), 1, 0, false},     {offsetof(mpg_cooling_arrays, entropy), 1, 1, true},
-    {offsetof(mpg_cooling_arrays, ne), 1, 2, true},           {offsetof(mpg_cooling_arrays, sfr), 1, 3, true},
-    {offsetof(mpg_cooling_arrays, metallicity), 1, 4, false}, {offsetof(mpg_cooling_arrays, heiii_ionized), 0, 0, false},
-    {offsetof(mpg_cooling_arrays, tb_hydro), 0, 1, false}};
-static_assert(sizeof(mpg_cooling_arrays) == COOL_NFIELDS * sizeof(void *), "COOL_FIELDS describes every member of mpg_cooling_arrays");
-
-// ... and of the stellar mass and metal return.  `mass` is the table's column in both host forms (P.Mass of the records), `hsml` and
-// `density` are resident columns on a resident gas run; everything else travels.
-enum MetalRole : unsigned {
-    METAL_IN = 1,        // read by the call
-    METAL_OUT = 2,       // comes back
-    METAL_OPTIONAL = 4,  // may be NULL
-    METAL_TABLE = 8,     // P.Mass: a column of the staged / resident table, never staged from `A`
-    METAL_SPH_ALIAS = 16 // resident gas run: aliases a column of the resident SPH arrays
-};
-struct MetalField {
+struct ArrayField {
     const char *name;
-    size_t off; // of the member in mpg_metal_arrays
-    int width;  // doubles per particle
-    unsigned role;
+    size_t off;    // of the member in its struct
+    size_t elem;   // bytes of one element: the sizeof of the member's pointee, as the header declares it
+    int width;     // elements per particle
+    unsigned role; // ArrayRole bits
 };
-#define MPG_METAL_FIELD(m, width, role) {#m, offsetof(mpg_metal_arrays, m), width, role}
-constexpr int METAL_NFIELDS = 13;
-constexpr int METAL_HSML_FIELD = 5; // index of `hsml` below (its staging buffer)
-const MetalField METAL_FIELDS[METAL_NFIELDS] = {
-    MPG_METAL_FIELD(massgenerated, 1, METAL_IN),
-    MPG_METAL_FIELD(metalgenerated, 1, METAL_IN),
-    MPG_METAL_FIELD(speciesgenerated, 9, METAL_IN),
-    MPG_METAL_FIELD(stellarage, 1, METAL_IN),
-    MPG_METAL_FIELD(mass, 0, METAL_TABLE),
-    MPG_METAL_FIELD(hsml, 1, METAL_IN | METAL_OUT | METAL_SPH_ALIAS),
-    MPG_METAL_FIELD(totalmassreturned, 1, METAL_IN | METAL_OUT),
-    MPG_METAL_FIELD(lastenrichment, 1, METAL_IN | METAL_OUT),
-    MPG_METAL_FIELD(density, 1, METAL_IN | METAL_OUT | METAL_SPH_ALIAS),
-    MPG_METAL_FIELD(metallicity, 1, METAL_IN | METAL_OUT),
-    MPG_METAL_FIELD(metals, 9, METAL_IN | METAL_OUT),
-    MPG_METAL_FIELD(massreturned, 1, METAL_OUT | METAL_OPTIONAL),
-    MPG_METAL_FIELD(starvolume, 1, METAL_OUT | METAL_OPTIONAL),
-};
-#undef MPG_METAL_FIELD
-static_assert(sizeof(mpg_metal_arrays) == METAL_NFIELDS * sizeof(void *), "METAL_FIELDS describes every member of mpg_metal_arrays");
-
-// The host arrays of `host` onto the device (stage[f], one buffer per field) and `dev` filled with the device pointers; fields with a
-// role in `skip` are left to the caller (dev keeps what it holds there).  A required array that is missing is an error.
-inline void metal_stage(const mpg_metal_arrays &host, mpg_metal_arrays &dev, mpg::DevBuf<double> *stage, int64_t n, unsigned skip, hipStream_t st)
+#define MPG_ARRAY_FIELD(S, m, width, role) {#m, offsetof(S, m), sizeof(*S().m), width, role}
+// the table names every member of S once and in S's order: entry f is the f-th pointer of the struct
+template <class S, size_t N> constexpr bool describes_every_member(const ArrayField (&T)[N])
 {
-    for(int f = 0; f < METAL_NFIELDS; f++) {
-        const MetalField &F = METAL_FIELDS[f];
+    for(size_t f = 0; f < N; f++)
+        if(T[f].off != f * sizeof(void *))
+            return false;
+    return sizeof(S) == N * sizeof(void *);
+}
+// the index of the member at `off` (its entry, and its staging buffer); asked for a constant, a member the table lacks does not compile
+template <size_t N> constexpr int field_index(const ArrayField (&T)[N], size_t off)
+{
+    for(size_t f = 0; f < N; f++)
+        if(T[f].off == off)
+            return (int)f;
+    throw mpg::Error("field_index: no such member");
+}
+
+// the velocity dispersion: vdisp is in / out (mpg_find_vel_disp checks the required arrays itself, with a text of its own)
+constexpr ArrayField VDISP_FIELDS[] = {
+    MPG_ARRAY_FIELD(mpg_veldisp_arrays, vel, 3, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_veldisp_arrays, gacc, 3, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_veldisp_arrays, gpm, 3, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_veldisp_arrays, tb_grav, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_veldisp_arrays, hsml, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_veldisp_arrays, dthsml, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_veldisp_arrays, density, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_veldisp_arrays, vdisp, 1, ARR_IN | ARR_OUT),
+};
+static_assert(describes_every_member<mpg_veldisp_arrays>(VDISP_FIELDS), "VDISP_FIELDS follows mpg_veldisp_arrays");
+
+// the cooling: entropy, ne and sfr go up and come back.  (ARR_OPTIONAL throughout: mpg_cooling checks density, entropy, ne and sfr itself,
+// with a text of its own, and asks for none of them when the table is empty.)
+constexpr ArrayField COOL_FIELDS[] = {
+    MPG_ARRAY_FIELD(mpg_cooling_arrays, density, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_cooling_arrays, entropy, 1, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_cooling_arrays, ne, 1, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_cooling_arrays, sfr, 1, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_cooling_arrays, metallicity, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_cooling_arrays, heiii_ionized, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_cooling_arrays, tb_hydro, 1, ARR_IN | ARR_OPTIONAL),
+};
+static_assert(describes_every_member<mpg_cooling_arrays>(COOL_FIELDS), "COOL_FIELDS follows mpg_cooling_arrays");
+
+// the stellar mass and metal return.  `mass` is the table's column in both host forms (P.Mass of the records), `hsml` and `density` are
+// resident columns on a resident gas run; everything else travels.
+constexpr ArrayField METAL_FIELDS[] = {
+    MPG_ARRAY_FIELD(mpg_metal_arrays, massgenerated, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, metalgenerated, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, speciesgenerated, 9, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, stellarage, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, mass, 1, ARR_TABLE),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, hsml, 1, ARR_IN | ARR_OUT | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, totalmassreturned, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, lastenrichment, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, density, 1, ARR_IN | ARR_OUT | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, metallicity, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, metals, 9, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, massreturned, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_metal_arrays, starvolume, 1, ARR_OUT | ARR_OPTIONAL),
+};
+static_assert(describes_every_member<mpg_metal_arrays>(METAL_FIELDS), "METAL_FIELDS follows mpg_metal_arrays");
+
+// the black-hole call.  `mass` is the table's column in both host forms; on a resident gas run the SPH columns and the table's Vel /
+// accelerations are resident too; everything else travels.
+constexpr ArrayField BH_FIELDS[] = {
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, id, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, gacc, 3, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, gpm, 3, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, hydroacc, 3, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, tb_hydro, 1, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, tb_grav, 1, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, hsml, 1, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, density, 1, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, delaytime, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, dfaccel, 3, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, vdisp, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, active_hydro, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, mass, 1, ARR_TABLE),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, vel, 3, ARR_IN | ARR_OUT | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, entropy, 1, ARR_IN | ARR_OUT | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, flags, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, bh_mass, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, mtrack, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, kineticfdbkenergy, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, countprogs, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, mdot, 1, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, dragaccel, 3, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, encounter, 1, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, mintimebin, 1, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, swallowid, 1, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, swallowtime, 1, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, bhheated, 1, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, feedbackweightsum, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, bh_entropy, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, gasvel, 3, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, mgasenc, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, keflag, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, accreted_mass, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, accreted_bhmass, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, accreted_momentum, 3, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, sph_swallowid, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_blackhole_arrays, bh_swallowid, 1, ARR_OUT | ARR_OPTIONAL),
+};
+static_assert(describes_every_member<mpg_blackhole_arrays>(BH_FIELDS), "BH_FIELDS follows mpg_blackhole_arrays");
+
+// the dynamical-friction call (ARR_OPTIONAL here: not read by every method, checked by the call itself).  On a resident gas run the
+// table's Vel / accelerations / Potential and the SPH columns are resident; the per-black-hole members travel.
+constexpr ArrayField DF_FIELDS[] = {
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, vel, 3, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, gacc, 3, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, gpm, 3, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, hydroacc, 3, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, tb_grav, 1, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, tb_hydro, 1, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, hsml, 1, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, potential, 1, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, bh_mass, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, active_dynfric, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, df_density, 1, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, df_vel, 3, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, df_rmsvel, 1, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, jumptominpot, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, minpot, 1, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, minpotpos, 3, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, minpotvel, 3, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_bh_dynfric_arrays, dfaccel, 3, ARR_OUT | ARR_OPTIONAL),
+};
+static_assert(describes_every_member<mpg_bh_dynfric_arrays>(DF_FIELDS), "DF_FIELDS follows mpg_bh_dynfric_arrays");
+
+// winds_and_feedback.  tb_hydro is winds_evolve's alone and does not travel.
+constexpr ArrayField WD_FIELDS[] = {
+    MPG_ARRAY_FIELD(mpg_wind_arrays, id, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, hsml, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, vdisp, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, density, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, tb_hydro, 1, ARR_OTHER_CALL),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, vel, 3, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, entropy, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, delaytime, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, totalweight, 1, ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_wind_arrays, kick_star, 1, ARR_OUT | ARR_OPTIONAL),
+};
+static_assert(describes_every_member<mpg_wind_arrays>(WD_FIELDS), "WD_FIELDS follows mpg_wind_arrays");
+
+// Room for n particles of field F in its staging buffer and, when the host array `h` is given, its n entries on the way up (queued on
+// st): the device pointer.  (512 bytes of slack: 64 spare elements of the widest type, and never an empty allocation.)
+inline void *stage_field(const ArrayField &F, mpg::DevBuf<char> &buf, const void *h, int64_t n, hipStream_t st)
+{
+    const size_t bytes = (size_t)n * F.elem * F.width;
+    buf.reserve(bytes + 512);
+    if(h)
+        MPG_HIP(hipMemcpyAsync(buf.p, h, bytes, hipMemcpyHostToDevice, st));
+    return buf.p;
+}
+// The host arrays of `host` onto the device (bufs[f], one buffer per field) and `dev` filled with the device pointers; fields with a
+// role in `skip` are left to the caller (dev keeps what it holds there).  A required array that is missing is an error in `who`'s name.
+template <class S, size_t N>
+inline void stage_fields(const ArrayField (&T)[N], const S &host, S &dev, mpg::DevBuf<char> *bufs, int64_t n, unsigned skip, const char *who,
+                         hipStream_t st)
+{
+    for(size_t f = 0; f < N; f++) {
+        const ArrayField &F = T[f];
         if(F.role & skip)
             continue;
-        void *h = field_get(host, F.off), *d = nullptr;
-        MPG_CHECK(h || (F.role & METAL_OPTIONAL), std::string("metal_return: the array ") + F.name + " is required");
-        if(h) {
-            const size_t bytes = (size_t)n * F.width * sizeof(double);
-            stage[f].reserve((size_t)n * F.width + 1);
-            d = stage[f].p;
-            // (the outputs go up too: the call writes the entries of its targets only, the others come back as they were)
-            MPG_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
-        }
-        field_set(dev, F.off, d);
+        const void *h = field_get(host, F.off);
+        MPG_CHECK(h || (F.role & ARR_OPTIONAL), std::string(who) + ": the array " + F.name + " is required");
+        // (the outputs go up too: the call writes the entries of its targets only, the others come back as they were)
+        field_set(dev, F.off, h ? stage_field(F, bufs[f], h, n, st) : nullptr);
     }
 }
 // ... and what the call wrote back into them (queued on st)
-inline void metal_unstage(const mpg_metal_arrays &host, const mpg_metal_arrays &dev, int64_t n, unsigned skip, hipStream_t st)
+template <class S, size_t N> inline void unstage_fields(const ArrayField (&T)[N], const S &host, const S &dev, int64_t n, unsigned skip, hipStream_t st)
 {
-    for(int f = 0; f < METAL_NFIELDS; f++) {
-        const MetalField &F = METAL_FIELDS[f];
+    for(const ArrayField &F : T) {
         void *h = field_get(host, F.off);
-        if(h && (F.role & METAL_OUT) && !(F.role & skip))
-            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.width * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-}
-// ... and of the black-hole call.  `mass` is the table's column in both host forms; on a resident gas run the SPH columns and the
-// table's Vel / accelerations are resident too; everything else travels.
-enum BhRole : unsigned {
-    BH_IN = 1,        // read by the call
-    BH_OUT = 2,       // comes back
-    BH_OPTIONAL = 4,  // may be NULL
-    BH_TABLE = 8,     // P.Mass: a column of the staged / resident table, never staged from `A`
-    BH_RES_ALIAS = 16, // resident gas run: aliases a resident column
-    BH_OTHER_CALL = 32 // read by another call that takes the same struct: never staged by this one
-};
-struct BhField {
-    const char *name;
-    size_t off;  // of the member in mpg_blackhole_arrays
-    int bytes;   // per particle
-    unsigned role;
-};
-#define MPG_BH_FIELD(m, bytes, role) {#m, offsetof(mpg_blackhole_arrays, m), bytes, role}
-constexpr int BH_NFIELDS = 37;
-const BhField BH_FIELDS[BH_NFIELDS] = {
-    MPG_BH_FIELD(id, 8, BH_IN),
-    MPG_BH_FIELD(gacc, 24, BH_IN | BH_RES_ALIAS),
-    MPG_BH_FIELD(gpm, 24, BH_IN | BH_RES_ALIAS),
-    MPG_BH_FIELD(hydroacc, 24, BH_IN | BH_RES_ALIAS),
-    MPG_BH_FIELD(tb_hydro, 1, BH_IN | BH_RES_ALIAS),
-    MPG_BH_FIELD(tb_grav, 1, BH_IN | BH_RES_ALIAS),
-    MPG_BH_FIELD(hsml, 8, BH_IN | BH_RES_ALIAS),
-    MPG_BH_FIELD(density, 8, BH_IN | BH_RES_ALIAS),
-    MPG_BH_FIELD(delaytime, 8, BH_IN),
-    MPG_BH_FIELD(dfaccel, 24, BH_IN),
-    MPG_BH_FIELD(vdisp, 8, BH_IN),
-    MPG_BH_FIELD(active_hydro, 1, BH_IN | BH_OPTIONAL),
-    MPG_BH_FIELD(mass, 4, BH_TABLE),
-    MPG_BH_FIELD(vel, 24, BH_IN | BH_OUT | BH_RES_ALIAS),
-    MPG_BH_FIELD(entropy, 8, BH_IN | BH_OUT | BH_RES_ALIAS),
-    MPG_BH_FIELD(flags, 1, BH_IN | BH_OUT),
-    MPG_BH_FIELD(bh_mass, 8, BH_IN | BH_OUT),
-    MPG_BH_FIELD(mtrack, 8, BH_IN | BH_OUT),
-    MPG_BH_FIELD(kineticfdbkenergy, 8, BH_IN | BH_OUT),
-    MPG_BH_FIELD(countprogs, 4, BH_IN | BH_OUT),
-    MPG_BH_FIELD(mdot, 8, BH_OUT),
-    MPG_BH_FIELD(dragaccel, 24, BH_OUT),
-    MPG_BH_FIELD(encounter, 4, BH_OUT),
-    MPG_BH_FIELD(mintimebin, 4, BH_OUT),
-    MPG_BH_FIELD(swallowid, 8, BH_OUT),
-    MPG_BH_FIELD(swallowtime, 8, BH_OUT),
-    MPG_BH_FIELD(bhheated, 1, BH_OUT),
-    MPG_BH_FIELD(feedbackweightsum, 8, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(bh_entropy, 8, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(gasvel, 24, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(mgasenc, 8, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(keflag, 4, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(accreted_mass, 8, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(accreted_bhmass, 8, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(accreted_momentum, 24, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(sph_swallowid, 8, BH_OUT | BH_OPTIONAL),
-    MPG_BH_FIELD(bh_swallowid, 8, BH_OUT | BH_OPTIONAL),
-};
-#undef MPG_BH_FIELD
-static_assert(sizeof(mpg_blackhole_arrays) == BH_NFIELDS * sizeof(void *), "BH_FIELDS describes every member of mpg_blackhole_arrays");
-
-// The host arrays of `host` onto the device (stage[f], one buffer per field) and `dev` filled with the device pointers; fields with a
-// role in `skip` are left to the caller.  A required array that is missing is an error.
-inline void bh_stage(const mpg_blackhole_arrays &host, mpg_blackhole_arrays &dev, mpg::DevBuf<char> *stage, int64_t n, unsigned skip, hipStream_t st)
-{
-    for(int f = 0; f < BH_NFIELDS; f++) {
-        const BhField &F = BH_FIELDS[f];
-        if(F.role & skip)
-            continue;
-        void *h = field_get(host, F.off), *d = nullptr;
-        MPG_CHECK(h || (F.role & BH_OPTIONAL), std::string("blackhole: the array ") + F.name + " is required");
-        if(h) {
-            stage[f].reserve((size_t)n * F.bytes + 16);
-            d = stage[f].p;
-            // (the outputs go up too: the call writes the entries of its targets only, the others come back as they were)
-            MPG_HIP(hipMemcpyAsync(d, h, (size_t)n * F.bytes, hipMemcpyHostToDevice, st));
-        }
-        field_set(dev, F.off, d);
-    }
-}
-// ... and what the call wrote back into them (queued on st)
-inline void bh_unstage(const mpg_blackhole_arrays &host, const mpg_blackhole_arrays &dev, int64_t n, unsigned skip, hipStream_t st)
-{
-    for(int f = 0; f < BH_NFIELDS; f++) {
-        const BhField &F = BH_FIELDS[f];
-        void *h = field_get(host, F.off);
-        if(h && (F.role & BH_OUT) && !(F.role & skip))
-            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.bytes, hipMemcpyDeviceToHost, st));
-    }
-}
-// ... and of the dynamical-friction call (roles as above; BH_OPTIONAL here: not read by every method, checked by the call itself).  On a
-// resident gas run the table's Vel / accelerations / Potential and the SPH columns are resident; the per-black-hole members travel.
-#define MPG_DF_FIELD(m, bytes, role) {#m, offsetof(mpg_bh_dynfric_arrays, m), bytes, role}
-constexpr int DF_NFIELDS = 18;
-const BhField DF_FIELDS[DF_NFIELDS] = {
-    MPG_DF_FIELD(vel, 24, BH_IN | BH_RES_ALIAS),
-    MPG_DF_FIELD(gacc, 24, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
-    MPG_DF_FIELD(gpm, 24, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
-    MPG_DF_FIELD(hydroacc, 24, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
-    MPG_DF_FIELD(tb_grav, 1, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
-    MPG_DF_FIELD(tb_hydro, 1, BH_IN | BH_OPTIONAL | BH_RES_ALIAS),
-    MPG_DF_FIELD(hsml, 8, BH_IN | BH_RES_ALIAS),
-    MPG_DF_FIELD(potential, 8, BH_IN | BH_RES_ALIAS),
-    MPG_DF_FIELD(bh_mass, 8, BH_IN | BH_OPTIONAL),
-    MPG_DF_FIELD(active_dynfric, 1, BH_IN | BH_OPTIONAL),
-    MPG_DF_FIELD(df_density, 8, BH_IN | BH_OUT | BH_OPTIONAL),
-    MPG_DF_FIELD(df_vel, 24, BH_IN | BH_OUT | BH_OPTIONAL),
-    MPG_DF_FIELD(df_rmsvel, 8, BH_IN | BH_OUT | BH_OPTIONAL),
-    MPG_DF_FIELD(jumptominpot, 4, BH_IN | BH_OUT),
-    MPG_DF_FIELD(minpot, 8, BH_OUT),
-    MPG_DF_FIELD(minpotpos, 24, BH_OUT),
-    MPG_DF_FIELD(minpotvel, 24, BH_OUT),
-    MPG_DF_FIELD(dfaccel, 24, BH_OUT | BH_OPTIONAL),
-};
-#undef MPG_DF_FIELD
-static_assert(sizeof(mpg_bh_dynfric_arrays) == DF_NFIELDS * sizeof(void *), "DF_FIELDS describes every member of mpg_bh_dynfric_arrays");
-inline void df_stage(const mpg_bh_dynfric_arrays &host, mpg_bh_dynfric_arrays &dev, mpg::DevBuf<char> *stage, int64_t n, unsigned skip, hipStream_t st)
-{
-    for(int f = 0; f < DF_NFIELDS; f++) {
-        const BhField &F = DF_FIELDS[f];
-        if(F.role & skip)
-            continue;
-        void *h = field_get(host, F.off), *d = nullptr;
-        MPG_CHECK(h || (F.role & BH_OPTIONAL), std::string("blackhole_dynfric: the array ") + F.name + " is required");
-        if(h) {
-            stage[f].reserve((size_t)n * F.bytes + 16);
-            d = stage[f].p;
-            // (the outputs go up too: the call writes the entries of its targets only, the others come back as they were)
-            MPG_HIP(hipMemcpyAsync(d, h, (size_t)n * F.bytes, hipMemcpyHostToDevice, st));
-        }
-        field_set(dev, F.off, d);
-    }
-}
-inline void df_unstage(const mpg_bh_dynfric_arrays &host, const mpg_bh_dynfric_arrays &dev, int64_t n, unsigned skip, hipStream_t st)
-{
-    for(int f = 0; f < DF_NFIELDS; f++) {
-        const BhField &F = DF_FIELDS[f];
-        void *h = field_get(host, F.off);
-        if(h && (F.role & BH_OUT) && !(F.role & skip))
-            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.bytes, hipMemcpyDeviceToHost, st));
-    }
-}
-// ... and of winds_and_feedback (roles as above).  tb_hydro is winds_evolve's alone and does not travel.
-#define MPG_WD_FIELD(m, bytes, role) {#m, offsetof(mpg_wind_arrays, m), bytes, role}
-constexpr int WD_NFIELDS = 10;
-const BhField WD_FIELDS[WD_NFIELDS] = {
-    MPG_WD_FIELD(id, 8, BH_IN),
-    MPG_WD_FIELD(hsml, 8, BH_IN),
-    MPG_WD_FIELD(vdisp, 8, BH_IN),
-    MPG_WD_FIELD(density, 8, BH_IN),
-    MPG_WD_FIELD(tb_hydro, 1, BH_OTHER_CALL),
-    MPG_WD_FIELD(vel, 24, BH_IN | BH_OUT),
-    MPG_WD_FIELD(entropy, 8, BH_IN | BH_OUT),
-    MPG_WD_FIELD(delaytime, 8, BH_IN | BH_OUT),
-    MPG_WD_FIELD(totalweight, 8, BH_OUT | BH_OPTIONAL),
-    MPG_WD_FIELD(kick_star, 8, BH_OUT | BH_OPTIONAL),
-};
-#undef MPG_WD_FIELD
-static_assert(sizeof(mpg_wind_arrays) == WD_NFIELDS * sizeof(void *), "WD_FIELDS describes every member of mpg_wind_arrays");
-inline void wd_stage(const mpg_wind_arrays &host, mpg_wind_arrays &dev, mpg::DevBuf<char> *stage, int64_t n, unsigned skip, hipStream_t st)
-{
-    for(int f = 0; f < WD_NFIELDS; f++) {
-        const BhField &F = WD_FIELDS[f];
-        if(F.role & skip)
-            continue;
-        void *h = field_get(host, F.off), *d = nullptr;
-        MPG_CHECK(h || (F.role & BH_OPTIONAL), std::string("winds_and_feedback: the array ") + F.name + " is required");
-        if(h) {
-            stage[f].reserve((size_t)n * F.bytes + 16);
-            d = stage[f].p;
-            // (the outputs go up too: the call writes the entries of its stars and of the kicked gas only, the others come back as they were)
-            MPG_HIP(hipMemcpyAsync(d, h, (size_t)n * F.bytes, hipMemcpyHostToDevice, st));
-        }
-        field_set(dev, F.off, d);
-    }
-}
-inline void wd_unstage(const mpg_wind_arrays &host, const mpg_wind_arrays &dev, int64_t n, unsigned skip, hipStream_t st)
-{
-    for(int f = 0; f < WD_NFIELDS; f++) {
-        const BhField &F = WD_FIELDS[f];
-        void *h = field_get(host, F.off);
-        if(h && (F.role & BH_OUT) && !(F.role & skip))
-            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.bytes, hipMemcpyDeviceToHost, st));
+        if(h && (F.role & ARR_OUT) && !(F.role & skip))
+            MPG_HIP(hipMemcpyAsync(h, field_get(dev, F.off), (size_t)n * F.elem * F.width, hipMemcpyDeviceToHost, st));
     }
 }
 // the flags byte of the records: IsGarbage and Swallowed as the call left them (`flags`: n host bytes)

@@ -479,9 +479,8 @@ int mpg_resident_sph_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv,
     d.hsml = r.hsml;
     d.dthsml = r.dthsml;
     d.density = r.density;
-    eng->vd_stage[7].reserve(n + 1);
-    d.vdisp = eng->vd_stage[7].p;
-    MPG_HIP(hipMemcpyAsync(d.vdisp, vdisp, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+    constexpr int VDISP = field_index(VDISP_FIELDS, offsetof(mpg_veldisp_arrays, vdisp));
+    d.vdisp = (double *)stage_field(VDISP_FIELDS[VDISP], eng->vd_stage[VDISP], vdisp, pv->n, eng->stream);
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
     MPG_CALL(mpg_dev_find_vel_disp(eng, &d, T, par, d_act, NumActiveParticle));
     MPG_HIP(hipMemcpyAsync(vdisp, d.vdisp, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
@@ -505,21 +504,16 @@ int mpg_resident_sph_cooling(mpg_engine *eng, const mpg_particle_view *pv, const
     d.density = r.density;
     d.entropy = (double *)r.entropy;
     d.tb_hydro = r.tb_hydro;
-    eng->cl_stage[2].reserve(n + 1);
-    d.ne = eng->cl_stage[2].p;
-    MPG_HIP(hipMemcpyAsync(d.ne, ne, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-    eng->cl_stage[3].reserve(n + 1); // Sfr is no resident column: a scratch column takes the zeros
-    d.sfr = eng->cl_stage[3].p;
-    if(metallicity) {
-        eng->cl_stage[4].reserve(n + 1);
-        MPG_HIP(hipMemcpyAsync(eng->cl_stage[4].p, metallicity, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-        d.metallicity = eng->cl_stage[4].p;
-    }
-    if(heiii_ionized) {
-        eng->cl_stage_u8[0].reserve(n + 1);
-        MPG_HIP(hipMemcpyAsync(eng->cl_stage_u8[0].p, heiii_ionized, n, hipMemcpyHostToDevice, eng->stream));
-        d.heiii_ionized = eng->cl_stage_u8[0].p;
-    }
+    constexpr int NE = field_index(COOL_FIELDS, offsetof(mpg_cooling_arrays, ne)), SFR = field_index(COOL_FIELDS, offsetof(mpg_cooling_arrays, sfr)),
+                  METALLICITY = field_index(COOL_FIELDS, offsetof(mpg_cooling_arrays, metallicity)),
+                  HEIII = field_index(COOL_FIELDS, offsetof(mpg_cooling_arrays, heiii_ionized));
+    d.ne = (double *)stage_field(COOL_FIELDS[NE], eng->cl_stage[NE], ne, pv->n, eng->stream);
+    // Sfr is no resident column: a scratch column, reserved and not uploaded, takes the zeros
+    d.sfr = (double *)stage_field(COOL_FIELDS[SFR], eng->cl_stage[SFR], nullptr, pv->n, eng->stream);
+    if(metallicity)
+        d.metallicity = (const double *)stage_field(COOL_FIELDS[METALLICITY], eng->cl_stage[METALLICITY], metallicity, pv->n, eng->stream);
+    if(heiii_ionized)
+        d.heiii_ionized = (const uint8_t *)stage_field(COOL_FIELDS[HEIII], eng->cl_stage[HEIII], heiii_ionized, pv->n, eng->stream);
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
     const int rc = mpg_dev_cooling(eng, &d, T, step, d_act, NumActiveParticle);
     const std::string err = rc ? mpg_last_error() : "";
@@ -542,19 +536,18 @@ int mpg_resident_sph_metal_return(mpg_engine *eng, const mpg_particle_view *pv, 
     const int64_t n = pv->n;
     const mpg_sph_arrays &r = eng->res_sph_dev;
     mpg_metal_arrays d{};
-    metal_stage(*A, d, eng->mt_stage, n, METAL_TABLE | METAL_SPH_ALIAS, eng->stream);
+    stage_fields(METAL_FIELDS, *A, d, eng->mt_stage, n, ARR_TABLE | ARR_RES_ALIAS, "metal_return", eng->stream);
     d.mass = eng->s_mass.p;
     d.hsml = r.hsml;
     d.density = r.density;
     if(A->hsml && n > 0) {
-        DevBuf<double> &up = eng->mt_stage[METAL_HSML_FIELD];
-        up.reserve((size_t)n + 1);
-        MPG_HIP(hipMemcpyAsync(up.p, A->hsml, (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
-        MetalsEngine::take_star_hsml(d.hsml, up.p, eng->s_type.p, n, eng->stream);
+        constexpr int HSML = field_index(METAL_FIELDS, offsetof(mpg_metal_arrays, hsml));
+        const double *up = (const double *)stage_field(METAL_FIELDS[HSML], eng->mt_stage[HSML], A->hsml, n, eng->stream);
+        MetalsEngine::take_star_hsml(d.hsml, up, eng->s_type.p, n, eng->stream);
     }
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
     MPG_CALL(mpg_dev_metal_return(eng, &d, d_act, NumActiveParticle));
-    metal_unstage(*A, d, n, METAL_TABLE | METAL_SPH_ALIAS, eng->stream);
+    unstage_fields(METAL_FIELDS, *A, d, n, ARR_TABLE | ARR_RES_ALIAS, eng->stream);
     if(A->hsml && n > 0)
         MPG_HIP(hipMemcpyAsync(A->hsml, d.hsml, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
     if(eng->metals.ntargets > 0) {
@@ -584,7 +577,7 @@ int mpg_resident_sph_blackhole_dynfric(mpg_engine *eng, const mpg_particle_view 
         return 0;
     }
     mpg_bh_dynfric_arrays d{};
-    df_stage(*A, d, eng->df_stage, n, BH_RES_ALIAS, eng->stream);
+    stage_fields(DF_FIELDS, *A, d, eng->df_stage, n, ARR_RES_ALIAS, "blackhole_dynfric", eng->stream);
     d.vel = r.vel;
     d.gacc = r.gacc;
     d.gpm = r.gpm;
@@ -594,7 +587,7 @@ int mpg_resident_sph_blackhole_dynfric(mpg_engine *eng, const mpg_particle_view 
     d.hsml = r.hsml;
     d.potential = eng->r_pot.p;
     dynfric_call(eng, &d, T, d_act, NumActiveParticle);
-    df_unstage(*A, d, n, BH_RES_ALIAS, eng->stream);
+    unstage_fields(DF_FIELDS, *A, d, n, ARR_RES_ALIAS, eng->stream);
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }
@@ -619,7 +612,7 @@ int mpg_resident_sph_blackhole(mpg_engine *eng, const mpg_particle_view *pv, con
         return 0;
     }
     mpg_blackhole_arrays d{};
-    bh_stage(*A, d, eng->bh_stage, n, BH_TABLE | BH_RES_ALIAS, eng->stream);
+    stage_fields(BH_FIELDS, *A, d, eng->bh_stage, n, ARR_TABLE | ARR_RES_ALIAS, "blackhole", eng->stream);
     d.mass = eng->s_mass.p;
     d.vel = (double *)r.vel;
     d.gacc = r.gacc;
@@ -631,7 +624,7 @@ int mpg_resident_sph_blackhole(mpg_engine *eng, const mpg_particle_view *pv, con
     d.density = r.density;
     d.entropy = (double *)r.entropy;
     blackhole_call(eng, &d, T, d_act, NumActiveParticle, 1);
-    bh_unstage(*A, d, n, BH_TABLE | BH_RES_ALIAS, eng->stream);
+    unstage_fields(BH_FIELDS, *A, d, n, ARR_TABLE | ARR_RES_ALIAS, eng->stream);
     if(eng->bh.ntargets > 0) {
         BlackholeEngine::retype(eng->s_type.p, d.flags, n, eng->stream);
         resident_flags(eng, n);

@@ -87,6 +87,8 @@ class SphTimes(C.Structure):
 SPH_ARRAY_FIELDS = ("hsml", "dthsml", "vel", "gacc", "gpm", "hydroacc_in", "tb_hydro", "tb_grav", "entropy", "dtentropy_in",
                     "density", "egywtdensity", "dhsmlegyfac", "divvel", "curlvel", "gradrho", "hydroacc_out", "dtentropy_out",
                     "maxsignalvel")
+# the element types of the members that are not float64 (numpy names), here and in the *_ARRAY_DTYPES below
+SPH_ARRAY_DTYPES = dict(tb_hydro="uint8", tb_grav="uint8")
 
 
 class SphArraysC(C.Structure):
@@ -94,6 +96,7 @@ class SphArraysC(C.Structure):
 
 
 VELDISP_ARRAY_FIELDS = ("vel", "gacc", "gpm", "tb_grav", "hsml", "dthsml", "density", "vdisp")
+VELDISP_ARRAY_DTYPES = dict(tb_grav="uint8")
 
 
 class VelDispArraysC(C.Structure):
@@ -108,6 +111,7 @@ class VelDispParams(C.Structure):
 
 METAL_ARRAY_FIELDS = ("massgenerated", "metalgenerated", "speciesgenerated", "stellarage", "mass", "hsml", "totalmassreturned", "lastenrichment",
                       "density", "metallicity", "metals", "massreturned", "starvolume")
+METAL_ARRAY_DTYPES = dict(mass="float32")
 
 
 class MetalArraysC(C.Structure):
@@ -125,7 +129,7 @@ BLACKHOLE_ARRAY_FIELDS = ("id", "gacc", "gpm", "hydroacc", "tb_hydro", "tb_grav"
                           "mdot", "dragaccel", "encounter", "mintimebin", "swallowid", "swallowtime", "bhheated",
                           "feedbackweightsum", "bh_entropy", "gasvel", "mgasenc", "keflag", "accreted_mass", "accreted_bhmass", "accreted_momentum",
                           "sph_swallowid", "bh_swallowid")
-# the element types of the members that are not float64 (numpy names; torch has no uint64: such tensors are int64 with the same bits)
+# (torch has no uint64: such tensors are int64 with the same bits)
 BLACKHOLE_ARRAY_DTYPES = dict(id="uint64", swallowid="uint64", sph_swallowid="uint64", bh_swallowid="uint64", tb_hydro="uint8", tb_grav="uint8",
                               active_hydro="uint8", flags="uint8", bhheated="uint8", mass="float32", countprogs="int32", encounter="int32",
                               mintimebin="int32", keflag="int32")
@@ -185,6 +189,7 @@ class WindParams(C.Structure):
 
 COOLING_ARRAY_FIELDS = ("density", "entropy", "ne", "sfr", "metallicity", "heiii_ionized", "tb_hydro")
 COOLING_BYTE_FIELDS = ("heiii_ionized", "tb_hydro")
+COOLING_ARRAY_DTYPES = dict.fromkeys(COOLING_BYTE_FIELDS, "uint8")
 RECOMB_CEN92, RECOMB_VERNER96, RECOMB_BADNELL06 = 0, 1, 2      # enum RecombType, cooling_rates.h:10-14
 COOLING_KWH92, COOLING_ENZO2NYX, COOLING_SHERWOOD = 0, 1, 2    # enum CoolingType, cooling_rates.h:16-20
 
@@ -261,6 +266,38 @@ def _ptr(t):
     if isinstance(t, int):
         return C.c_void_p(t)
     return C.c_void_p(t.data_ptr())
+
+
+def _dev_arrays(cls, arrays):
+    """The struct `cls` of array pointers from `arrays`: member name -> device tensor (torch) / raw pointer (int) / None."""
+    a = cls()
+    for k, _ in cls._fields_:
+        t = arrays.get(k)
+        setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+    return a
+
+
+def _host_arrays(cls, dtypes, arrays, who, skip=(), n=None):
+    """The struct `cls` from `arrays`: member name -> contiguous numpy array of the element type in `dtypes` (float64 otherwise) and,
+    when `n` is given, of that length.  The members in `skip` stay NULL; `who` names the module in the error text."""
+    a = cls()
+    for k, _ in cls._fields_:
+        t = None if k in skip else arrays.get(k)
+        if t is None:
+            continue
+        want = np.dtype(dtypes.get(k, "float64"))
+        if t.dtype != want or not t.flags["C_CONTIGUOUS"] or (n is not None and len(t) != n):
+            raise EngineError("%s host array %s must be contiguous %s%s" % (who, k, want.name, "" if n is None else " of len(P)"))
+        setattr(a, k, t.ctypes.data)
+    return a
+
+
+def _active(ActiveParticle):
+    """(pointer or None, count) of a host index list (None: all particles).  The pointer holds the int32 array it points into."""
+    if ActiveParticle is None:
+        return None, 0
+    act = np.ascontiguousarray(ActiveParticle, np.int32)
+    return act.ctypes.data_as(C.c_void_p), len(act)
 
 
 TIMEBINS = 46
@@ -607,19 +644,17 @@ class Engine:
 
     def resident_apply_half_kick(self, P, K, ActiveParticle=None):
         v = self._view(P)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_resident_apply_half_kick(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                       C.c_int64(0 if act is None else len(act)), C.byref(K)))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_resident_apply_half_kick(self.h, C.byref(v), act, C.c_int64(nact), C.byref(K)))
 
     def resident_find_hydro_timesteps(self, P, times, sync_loga, MinSizeTimestep, CourantFac, atime, hubble, ActiveParticle=None, isFirstTimeStep=False):
         v = self._view(P)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        act, nact = _active(ActiveParticle)
         loga = (C.c_double * len(sync_loga))(*[float(x) for x in sync_loga])
         tl = Timeline(len(sync_loga), C.cast(loga, C.POINTER(C.c_double)))
         par = TimestepParams(0.0, MinSizeTimestep)
         res = HydroStepResult()
-        self._ck(self.lib.mpg_resident_find_hydro_timesteps(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                            C.c_int64(0 if act is None else len(act)), C.byref(times), C.byref(tl), C.byref(par),
+        self._ck(self.lib.mpg_resident_find_hydro_timesteps(self.h, C.byref(v), act, C.c_int64(nact), C.byref(times), C.byref(tl), C.byref(par),
                                                             C.c_double(CourantFac), C.c_double(atime), C.c_double(hubble), int(bool(isFirstTimeStep)),
                                                             C.byref(res)))
         return dict(mTimeBin=res.mTimeBin, ntitype=list(res.ntitype), badstepsizecount=res.badstepsizecount, badtimebins=res.badtimebins)
@@ -629,13 +664,12 @@ class Engine:
         """find_timesteps (timestep.c:739-849) on a resident gas run: both time bins of the active particles, times.PM_length on a PM step
         (dti_max_pm = the caller's get_PM_timestep_ti), times.mintimebin / maxtimebin"""
         v = self._view(P)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        act, nact = _active(ActiveParticle)
         loga = (C.c_double * len(sync_loga))(*[float(x) for x in sync_loga])
         tl = Timeline(len(sync_loga), C.cast(loga, C.POINTER(C.c_double)))
         par = TimestepParams(ErrTolIntAccuracy, MinSizeTimestep)
         res = TimestepResult()
-        self._ck(self.lib.mpg_resident_find_timesteps(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                      C.c_int64(0 if act is None else len(act)), C.byref(times), C.byref(tl), C.byref(par),
+        self._ck(self.lib.mpg_resident_find_timesteps(self.h, C.byref(v), act, C.c_int64(nact), C.byref(times), C.byref(tl), C.byref(par),
                                                       C.c_double(CourantFac), C.c_double(atime), C.c_double(hubble), C.c_int64(dti_max_pm), C.byref(res)))
         return dict(mTimeBin=res.mTimeBin, maxTimeBin=res.maxTimeBin, isPM=res.isPM, ntitype=list(res.ntitype),
                     badstepsizecount=res.badstepsizecount, badtimebins=res.badtimebins)
@@ -643,9 +677,8 @@ class Engine:
     def resident_apply_hydro_half_kick(self, P, K, ActiveParticle=None):
         """apply_hydro_half_kick (timestep.c:930-968) on a resident gas run: the hydro kick of the gas alone (SplitGravityTimestepsOn)"""
         v = self._view(P)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_resident_apply_hydro_half_kick(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                             C.c_int64(0 if act is None else len(act)), C.byref(K)))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_resident_apply_hydro_half_kick(self.h, C.byref(v), act, C.c_int64(nact), C.byref(K)))
 
     def _stored_accel(self, P, StoredGravAccel):
         """the host StoredGravAccel of a resident split-gravity step: the engine keeps its pointer until _and_timesteps or resident_end"""
@@ -664,14 +697,13 @@ class Engine:
         active level and their kicks on the resident table.  StoredGravAccel: None or a NumPy (n, 3) array (include/mpgadget_hip.h: the
         engine holds a device copy for it, written back by resident_end).  gravkick(ti0, ti1) -> get_exact_gravkick_factor."""
         v = self._view(P)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        na = len(P) if act is None else len(act)
+        act, nact = _active(ActiveParticle)
+        na = len(P) if act is None else nact
         nag = na if NumActiveGravity is None else int(NumActiveGravity)
         sga = self._stored_accel(P, StoredGravAccel)
         fn = GRAVKICK_FN(lambda ctx, a, b: float(gravkick(a, b)))
-        self._ck(self.lib.mpg_resident_hierarchical_gravity_accelerations(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                                          C.c_int64(na), C.c_int64(nag), C.byref(times), C.c_double(rho0),
-                                                                          int(HybridNuGrav), fn, None, sga))
+        self._ck(self.lib.mpg_resident_hierarchical_gravity_accelerations(self.h, C.byref(v), act, C.c_int64(na), C.c_int64(nag), C.byref(times),
+                                                                          C.c_double(rho0), int(HybridNuGrav), fn, None, sga))
 
     def resident_hierarchical_gravity_and_timesteps(self, P, times, sync_loga, ErrTolIntAccuracy, MinSizeTimestep, atime, hubble, dti_max_pm, rho0,
                                                     gravkick, ActiveParticle=None, NumActiveGravity=None, StoredGravAccel=None, HybridNuGrav=0):
@@ -679,8 +711,8 @@ class Engine:
         levels and the kicks; times updated in place (dti_max_pm = the caller's get_PM_timestep_ti on a PM step).  Returns
         badstepsizecount.  The engine releases StoredGravAccel afterwards (the reference frees it there)."""
         v = self._view(P)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        na = len(P) if act is None else len(act)
+        act, nact = _active(ActiveParticle)
+        na = len(P) if act is None else nact
         nag = na if NumActiveGravity is None else int(NumActiveGravity)
         sga = self._stored_accel(P, StoredGravAccel)
         loga = (C.c_double * len(sync_loga))(*[float(x) for x in sync_loga])
@@ -688,10 +720,10 @@ class Engine:
         par = TimestepParams(ErrTolIntAccuracy, MinSizeTimestep)
         fn = GRAVKICK_FN(lambda ctx, a, b: float(gravkick(a, b)))
         bad = C.c_int64(0)
-        self._ck(self.lib.mpg_resident_hierarchical_gravity_and_timesteps(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                                          C.c_int64(na), C.c_int64(nag), C.byref(times), C.byref(tl), C.byref(par),
-                                                                          C.c_double(atime), C.c_double(hubble), C.c_int64(dti_max_pm),
-                                                                          C.c_double(rho0), int(HybridNuGrav), fn, None, sga, C.byref(bad)))
+        self._ck(self.lib.mpg_resident_hierarchical_gravity_and_timesteps(self.h, C.byref(v), act, C.c_int64(na), C.c_int64(nag), C.byref(times),
+                                                                          C.byref(tl), C.byref(par), C.c_double(atime), C.c_double(hubble),
+                                                                          C.c_int64(dti_max_pm), C.c_double(rho0), int(HybridNuGrav), fn, None, sga,
+                                                                          C.byref(bad)))
         return bad.value
 
     def host_prefetch(self, P, box):
@@ -731,9 +763,8 @@ class Engine:
 
     def force_tree_active_moments(self, P, BoxSize, ActiveParticle=None, HybridNuTracer=0):
         v = self._view(P)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_force_tree_active_moments(self.h, C.byref(v), C.c_double(BoxSize), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                        C.c_int64(0 if act is None else len(act)), int(HybridNuTracer)))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_force_tree_active_moments(self.h, C.byref(v), C.c_double(BoxSize), act, C.c_int64(nact), int(HybridNuTracer)))
 
     def dev_force_tree_active_moments(self, active=None, HybridNuTracer=0):
         self._ck(self.lib.mpg_dev_force_tree_active_moments(self.h, _ptr(active), C.c_int64(0 if active is None else active.shape[0]),
@@ -741,16 +772,11 @@ class Engine:
 
     def grav_short_tree(self, P, ActiveParticle=None, AccelStore=None, rho0=0.0):
         v = self._view(P)
-        act = None
-        nact = 0
-        if ActiveParticle is not None:
-            act = np.ascontiguousarray(ActiveParticle, np.int32)
-            nact = len(act)
+        act, nact = _active(ActiveParticle)
         if AccelStore is not None and (AccelStore.dtype != np.float64 or AccelStore.shape != (len(P), 3)
                                        or not AccelStore.flags["C_CONTIGUOUS"]):
             raise EngineError("AccelStore must be a contiguous float64 [NumPart,3] array")
-        self._ck(self.lib.mpg_grav_short_tree(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                              C.c_int64(nact),
+        self._ck(self.lib.mpg_grav_short_tree(self.h, C.byref(v), act, C.c_int64(nact),
                                               None if AccelStore is None else AccelStore.ctypes.data_as(C.c_void_p),
                                               C.c_double(rho0)))
 
@@ -857,9 +883,8 @@ class Engine:
 
     def grav_short_pair(self, P, Rcut, ActiveParticle=None, rho0=0.0):
         v = self._view(P)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_grav_short_pair(self.h, C.byref(v), None if act is None else act.ctypes.data_as(C.c_void_p),
-                                              C.c_int64(0 if act is None else len(act)), C.c_double(Rcut), C.c_double(rho0)))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_grav_short_pair(self.h, C.byref(v), act, C.c_int64(nact), C.c_double(Rcut), C.c_double(rho0)))
 
     # time integration on device-resident arrays (drift.c / timestep.c loops)
     def dev_drift_all_particles(self, pos, vel, ddrift, BoxSize, random_shift=(0.0, 0.0, 0.0), type=None, flags=None, hsml=None, dthsml=None):
@@ -1078,11 +1103,7 @@ class Engine:
     @staticmethod
     def _sph_arrays(arrays):
         """arrays: dict name -> device tensor (torch) / raw pointer / None for the fields of mpg_sph_arrays."""
-        a = SphArraysC()
-        for k in SPH_ARRAY_FIELDS:
-            t = arrays.get(k)
-            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
-        return a
+        return _dev_arrays(SphArraysC, arrays)
 
     def dev_force_tree_rebuild_mask(self, mask, with_moments=False):
         self._ck(self.lib.mpg_dev_force_tree_rebuild_mask(self.h, int(mask), int(bool(with_moments))))
@@ -1114,15 +1135,7 @@ class Engine:
     # host-pointer SPH path: `arrays` maps field names of mpg_sph_arrays to contiguous numpy arrays in particle order
     @staticmethod
     def _sph_host_arrays(arrays):
-        a = SphArraysC()
-        for k in SPH_ARRAY_FIELDS:
-            t = arrays.get(k)
-            if t is not None:
-                want = np.uint8 if k.startswith("tb_") else np.float64
-                if t.dtype != want or not t.flags["C_CONTIGUOUS"]:
-                    raise EngineError("SPH host array %s must be contiguous %s" % (k, want.__name__))
-            setattr(a, k, None if t is None else t.ctypes.data)
-        return a
+        return _host_arrays(SphArraysC, SPH_ARRAY_DTYPES, arrays, "SPH")
 
     def set_init_hsml(self, P, BoxSize, arrays, MeanGasSeparation):
         v = self._view(P)
@@ -1132,17 +1145,15 @@ class Engine:
     def density(self, P, BoxSize, arrays, times, ActiveParticle=None, update_hsml=1, DoEgyDensity=0, BlackHoleOn=0):
         v = self._view(P)
         a = self._sph_host_arrays(arrays)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_density(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times),
-                                      None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act)),
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_density(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), act, C.c_int64(nact),
                                       int(update_hsml), int(DoEgyDensity), int(BlackHoleOn)))
 
     def hydro_force(self, P, arrays, times, ActiveParticle=None):
         v = self._view(P)
         a = self._sph_host_arrays(arrays)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_hydro_force(self.h, C.byref(v), C.byref(a), C.byref(times),
-                                          None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_hydro_force(self.h, C.byref(v), C.byref(a), C.byref(times), act, C.c_int64(nact)))
 
     def sph_stats(self):
         c = (C.c_int64 * 4)()
@@ -1153,28 +1164,17 @@ class Engine:
     # `arrays` maps the field names of mpg_veldisp_arrays to device tensors (dev form) / contiguous numpy arrays (host form); vdisp is
     # in/out.  After a call that found work the engine's current tree is the DM tree (include/mpgadget_hip.h).
     def dev_find_vel_disp(self, arrays, times, Time, hubble, ddrift, sfr_density_threshold, active=None):
-        a = VelDispArraysC()
-        for k in VELDISP_ARRAY_FIELDS:
-            t = arrays.get(k)
-            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        a = _dev_arrays(VelDispArraysC, arrays)
         p = VelDispParams(Time, hubble, ddrift, sfr_density_threshold)
         nact = 0 if active is None else active.shape[0]
         self._ck(self.lib.mpg_dev_find_vel_disp(self.h, C.byref(a), C.byref(times), C.byref(p), _ptr(active), C.c_int64(nact)))
 
     def find_vel_disp(self, P, BoxSize, arrays, times, Time, hubble, ddrift, sfr_density_threshold, ActiveParticle=None):
         v = self._view(P)
-        a = VelDispArraysC()
-        for k in VELDISP_ARRAY_FIELDS:
-            t = arrays.get(k)
-            if t is not None:
-                want = np.uint8 if k == "tb_grav" else np.float64
-                if t.dtype != want or not t.flags["C_CONTIGUOUS"]:
-                    raise EngineError("velocity-dispersion host array %s must be contiguous %s" % (k, want.__name__))
-            setattr(a, k, None if t is None else t.ctypes.data)
+        a = _host_arrays(VelDispArraysC, VELDISP_ARRAY_DTYPES, arrays, "velocity-dispersion")
         p = VelDispParams(Time, hubble, ddrift, sfr_density_threshold)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_find_vel_disp(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), C.byref(p),
-                                            None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_find_vel_disp(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), C.byref(p), act, C.c_int64(nact)))
 
     def resident_sph_find_vel_disp(self, P, times, Time, hubble, ddrift, sfr_density_threshold, vdisp, ActiveParticle=None):
         """on a resident gas run: only `vdisp` (numpy float64 [n], in/out) travels"""
@@ -1182,10 +1182,8 @@ class Engine:
         if vdisp.dtype != np.float64 or not vdisp.flags["C_CONTIGUOUS"] or len(vdisp) != len(P):
             raise EngineError("vdisp must be a contiguous float64 array of len(P)")
         p = VelDispParams(Time, hubble, ddrift, sfr_density_threshold)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_resident_sph_find_vel_disp(self.h, C.byref(v), C.byref(times), C.byref(p),
-                                                         None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                         C.c_int64(0 if act is None else len(act)), C.c_void_p(vdisp.ctypes.data)))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_resident_sph_find_vel_disp(self.h, C.byref(v), C.byref(times), C.byref(p), act, C.c_int64(nact), C.c_void_p(vdisp.ctypes.data)))
 
     def veldisp_stats(self):
         c = (C.c_int64 * 5)()
@@ -1210,40 +1208,28 @@ class Engine:
         self._ck(self.lib.mpg_set_metal_params(self.h, C.byref(p)))
 
     def dev_metal_return(self, arrays, active=None):
-        a = MetalArraysC()
-        for k in METAL_ARRAY_FIELDS:
-            t = arrays.get(k)
-            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        a = _dev_arrays(MetalArraysC, arrays)
         nact = 0 if active is None else active.shape[0]
         self._ck(self.lib.mpg_dev_metal_return(self.h, C.byref(a), _ptr(active), C.c_int64(nact)))
 
     @staticmethod
     def _metal_host_arrays(arrays, skip):
-        a = MetalArraysC()
-        for k in METAL_ARRAY_FIELDS:
-            t = None if k in skip else arrays.get(k)
-            if t is not None and (t.dtype != np.float64 or not t.flags["C_CONTIGUOUS"]):
-                raise EngineError("metal-return host array %s must be contiguous float64" % k)
-            setattr(a, k, None if t is None else t.ctypes.data)
-        return a
+        return _host_arrays(MetalArraysC, METAL_ARRAY_DTYPES, arrays, "metal-return", skip)
 
     def metal_return(self, P, BoxSize, arrays, ActiveParticle=None):
         """host form: Mass is the records' column (read from and written back into P)"""
         v = self._view(P)
         a = self._metal_host_arrays(arrays, ("mass",))
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_metal_return(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a),
-                                           None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_metal_return(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), act, C.c_int64(nact)))
 
     def resident_sph_metal_return(self, P, arrays, ActiveParticle=None):
         """on a resident gas run: Mass, Hsml and Density are resident columns; the other arrays (numpy float64) travel.  `hsml`, when
         given, hands the stars' Hsml over and receives the resident column back"""
         v = self._view(P)
         a = self._metal_host_arrays(arrays, ("mass", "density"))
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_resident_sph_metal_return(self.h, C.byref(v), C.byref(a),
-                                                        None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                        C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_resident_sph_metal_return(self.h, C.byref(v), C.byref(a), act, C.c_int64(nact)))
 
     def metals_stats(self):
         c = (C.c_int64 * 6)()
@@ -1279,31 +1265,20 @@ class Engine:
         self._ck(self.lib.mpg_set_blackhole_params(self.h, C.byref(par)))
 
     def dev_blackhole(self, arrays, times, active=None):
-        a = BlackholeArraysC()
-        for k in BLACKHOLE_ARRAY_FIELDS:
-            t = arrays.get(k)
-            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        a = _dev_arrays(BlackholeArraysC, arrays)
         nact = 0 if active is None else active.shape[0]
         self._ck(self.lib.mpg_dev_blackhole(self.h, C.byref(a), C.byref(times), _ptr(active), C.c_int64(nact)))
 
     @staticmethod
     def _blackhole_host_arrays(arrays, skip):
-        a = BlackholeArraysC()
-        for k in BLACKHOLE_ARRAY_FIELDS:
-            t = None if k in skip else arrays.get(k)
-            want = np.dtype(BLACKHOLE_ARRAY_DTYPES.get(k, "float64"))
-            if t is not None and (t.dtype != want or not t.flags["C_CONTIGUOUS"]):
-                raise EngineError("black-hole host array %s must be contiguous %s" % (k, want.name))
-            setattr(a, k, None if t is None else t.ctypes.data)
-        return a
+        return _host_arrays(BlackholeArraysC, BLACKHOLE_ARRAY_DTYPES, arrays, "black-hole", skip)
 
     def blackhole(self, P, BoxSize, arrays, times, ActiveParticle=None):
         """host form: Mass is the records' column; Mass and the flags are written back into P"""
         v = self._view(P)
         a = self._blackhole_host_arrays(arrays, ("mass",))
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_blackhole(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times),
-                                        None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_blackhole(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), act, C.c_int64(nact)))
 
     BLACKHOLE_RESIDENT_COLUMNS = ("mass", "vel", "gacc", "gpm", "hydroacc", "tb_hydro", "tb_grav", "hsml", "density", "entropy")
 
@@ -1311,10 +1286,8 @@ class Engine:
         """on a resident gas run: the columns in BLACKHOLE_RESIDENT_COLUMNS are resident; the other arrays (numpy) travel"""
         v = self._view(P)
         a = self._blackhole_host_arrays(arrays, self.BLACKHOLE_RESIDENT_COLUMNS)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_resident_sph_blackhole(self.h, C.byref(v), C.byref(a), C.byref(times),
-                                                     None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                     C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_resident_sph_blackhole(self.h, C.byref(v), C.byref(a), C.byref(times), act, C.c_int64(nact)))
 
     def blackhole_stats(self):
         c = (C.c_int64 * 8)()
@@ -1338,11 +1311,7 @@ class Engine:
 
     @staticmethod
     def _wind_dev_arrays(arrays):
-        a = WindArraysC()
-        for k in WIND_ARRAY_FIELDS:
-            t = arrays.get(k)
-            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
-        return a
+        return _dev_arrays(WindArraysC, arrays)
 
     def dev_set_delaytime(self, delaytime):
         """SphP.DelayTime (float64 device tensor by particle, or None) for the decoupling of dev_hydro_force"""
@@ -1371,16 +1340,9 @@ class Engine:
     def winds_and_feedback(self, P, BoxSize, arrays, NewStars, atime):
         """host form: P supplies Pos / Mass / Type / flags; the arrays are numpy"""
         v = self._view(P)
-        a = WindArraysC()
-        for k in WIND_ARRAY_FIELDS:
-            t = arrays.get(k)
-            want = np.dtype(WIND_ARRAY_DTYPES.get(k, "float64"))
-            if t is not None and (t.dtype != want or not t.flags["C_CONTIGUOUS"]):
-                raise EngineError("wind host array %s must be contiguous %s" % (k, want.name))
-            setattr(a, k, None if t is None else t.ctypes.data)
-        new = np.ascontiguousarray(NewStars if NewStars is not None else [], np.int32)
-        self._ck(self.lib.mpg_winds_and_feedback(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), new.ctypes.data_as(C.c_void_p),
-                                                 C.c_int64(len(new)), C.c_double(atime)))
+        a = _host_arrays(WindArraysC, WIND_ARRAY_DTYPES, arrays, "wind")
+        new, nnew = _active(NewStars if NewStars is not None else [])
+        self._ck(self.lib.mpg_winds_and_feedback(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), new, C.c_int64(nnew), C.c_double(atime)))
 
     def dev_winds_subgrid(self, arrays, maybewind, stellarmass, atime, n=None):
         """maybewind: int32 device tensor of rows, or None with n: rows 0 .. n - 1; stellarmass: float64 device tensor by particle"""
@@ -1422,31 +1384,20 @@ class Engine:
         self._ck(self.lib.mpg_set_bh_dynfric_params(self.h, C.byref(p)))
 
     def dev_blackhole_dynfric(self, arrays, times, active=None):
-        a = BhDynfricArraysC()
-        for k in BH_DYNFRIC_ARRAY_FIELDS:
-            t = arrays.get(k)
-            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        a = _dev_arrays(BhDynfricArraysC, arrays)
         nact = 0 if active is None else active.shape[0]
         self._ck(self.lib.mpg_dev_blackhole_dynfric(self.h, C.byref(a), C.byref(times), _ptr(active), C.c_int64(nact)))
 
     @staticmethod
     def _bh_dynfric_host_arrays(arrays, skip):
-        a = BhDynfricArraysC()
-        for k in BH_DYNFRIC_ARRAY_FIELDS:
-            t = None if k in skip else arrays.get(k)
-            want = np.dtype(BH_DYNFRIC_ARRAY_DTYPES.get(k, "float64"))
-            if t is not None and (t.dtype != want or not t.flags["C_CONTIGUOUS"]):
-                raise EngineError("dynamical-friction host array %s must be contiguous %s" % (k, want.name))
-            setattr(a, k, None if t is None else t.ctypes.data)
-        return a
+        return _host_arrays(BhDynfricArraysC, BH_DYNFRIC_ARRAY_DTYPES, arrays, "dynamical-friction", skip)
 
     def blackhole_dynfric(self, P, BoxSize, arrays, times, ActiveParticle=None):
         """host form: P supplies Pos / Mass / Type; the arrays (numpy) travel when the list holds a black hole"""
         v = self._view(P)
         a = self._bh_dynfric_host_arrays(arrays, ())
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_blackhole_dynfric(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times),
-                                                None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_blackhole_dynfric(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), act, C.c_int64(nact)))
 
     BH_DYNFRIC_RESIDENT_COLUMNS = ("vel", "gacc", "gpm", "hydroacc", "tb_grav", "tb_hydro", "hsml", "potential")
 
@@ -1454,10 +1405,8 @@ class Engine:
         """on a resident gas run: the columns in BH_DYNFRIC_RESIDENT_COLUMNS are resident; the per-black-hole arrays (numpy) travel"""
         v = self._view(P)
         a = self._bh_dynfric_host_arrays(arrays, self.BH_DYNFRIC_RESIDENT_COLUMNS)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_resident_sph_blackhole_dynfric(self.h, C.byref(v), C.byref(a), C.byref(times),
-                                                             None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                             C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_resident_sph_blackhole_dynfric(self.h, C.byref(v), C.byref(a), C.byref(times), act, C.c_int64(nact)))
 
     def bh_dynfric_stats(self):
         c = (C.c_int64 * 5)()
@@ -1516,28 +1465,17 @@ class Engine:
 
     def dev_cooling(self, arrays, times, step, active=None, nactive=None):
         """active: int32 device tensor of caller indices, or a raw device pointer (int) with `nactive` entries"""
-        a = CoolingArraysC()
-        for k in COOLING_ARRAY_FIELDS:
-            t = arrays.get(k)
-            setattr(a, k, None if t is None else (t if isinstance(t, int) else t.data_ptr()))
+        a = _dev_arrays(CoolingArraysC, arrays)
         s = self.cooling_step(step)
         nact = 0 if active is None else (int(nactive) if nactive is not None else active.shape[0])
         self._ck(self.lib.mpg_dev_cooling(self.h, C.byref(a), C.byref(times), C.byref(s), _ptr(active), C.c_int64(nact)))
 
     def cooling(self, P, BoxSize, arrays, times, step, ActiveParticle=None):
         v = self._view(P)
-        a = CoolingArraysC()
-        for k in COOLING_ARRAY_FIELDS:
-            t = arrays.get(k)
-            if t is not None:
-                want = np.uint8 if k in COOLING_BYTE_FIELDS else np.float64
-                if t.dtype != want or not t.flags["C_CONTIGUOUS"] or len(t) != len(P):
-                    raise EngineError("cooling host array %s must be contiguous %s of len(P)" % (k, want.__name__))
-            setattr(a, k, None if t is None else t.ctypes.data)
+        a = _host_arrays(CoolingArraysC, COOLING_ARRAY_DTYPES, arrays, "cooling", n=len(P))
         s = self.cooling_step(step)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
-        self._ck(self.lib.mpg_cooling(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), C.byref(s),
-                                      None if act is None else act.ctypes.data_as(C.c_void_p), C.c_int64(0 if act is None else len(act))))
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_cooling(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), C.byref(s), act, C.c_int64(nact)))
 
     def resident_sph_cooling(self, P, times, step, ne, metallicity=None, heiii_ionized=None, ActiveParticle=None):
         """on a resident gas run: `ne` (numpy float64 [n], in/out) travels, with the optional inputs metallicity (float64) and heiii_ionized (uint8)"""
@@ -1546,11 +1484,10 @@ class Engine:
             if t is not None and (t.dtype != want or not t.flags["C_CONTIGUOUS"] or len(t) != len(P)):
                 raise EngineError("%s must be a contiguous %s array of len(P)" % (name, want.__name__))
         s = self.cooling_step(step)
-        act = None if ActiveParticle is None else np.ascontiguousarray(ActiveParticle, np.int32)
+        act, nact = _active(ActiveParticle)
         hp = lambda t: None if t is None else C.c_void_p(t.ctypes.data)
-        self._ck(self.lib.mpg_resident_sph_cooling(self.h, C.byref(v), C.byref(times), C.byref(s),
-                                                   None if act is None else act.ctypes.data_as(C.c_void_p),
-                                                   C.c_int64(0 if act is None else len(act)), hp(ne), hp(metallicity), hp(heiii_ionized)))
+        self._ck(self.lib.mpg_resident_sph_cooling(self.h, C.byref(v), C.byref(times), C.byref(s), act, C.c_int64(nact), hp(ne), hp(metallicity),
+                                                   hp(heiii_ionized)))
 
     def dev_cooling_state(self, rho, u, ne, step, lambdanet=None, temp=None, nh0=None):
         """the network alone on device tensors (float64 [n]) in physical cgs units; ne is in/out, the three outputs are optional"""

@@ -267,6 +267,7 @@ def test_host_form(pkg):
     ntree = eng.tree_stats().NumParticles
     eng.close()
     assert ntree == int(((d["type"] == 0) | (d["type"] == 5)).sum())
+    assert a["id"].tobytes() == d["id"].tobytes()                     # an input goes up and does not come back
     got = dict(a, mass=P["Mass"].copy(), id=d["id"])
     compare(d, par, T, out, info, got, stats, "host / zel")
     assert np.array_equal(P["Flags"] & 3, got["flags"] & 3)

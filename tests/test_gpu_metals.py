@@ -278,6 +278,7 @@ def test_host_form_equals_the_dev_form(pkg):
     exp, stats = eng.metals_export(d["n"]), eng.metals_stats()
     assert eng.tree_stats().NumParticles == len(info["gas"])             # the gas tree, built by the call
     eng.close()
+    assert a["massgenerated"].tobytes() == d["massgenerated"].tobytes()  # an input goes up and does not come back
     compare(d, sphw, out, res, info, got, exp, stats, "host / clustered")
     dev, exp_d, stats_d, _ = run_dev(pkg, torch, d, sphw, active, pkg.engine.GASMASK)
     for key in ("hsml", "starvolume", "lastenrichment", "massreturned", "totalmassreturned"):     # per-target sums in a fixed lane order

@@ -173,6 +173,7 @@ def test_host_form_active_sublist(pkg):
     a = dict(vel=d["vel"].copy(), gacc=d["gacc"].copy(), gpm=d["gpm"].copy(), tb_grav=d["tb_grav"].copy(), hsml=d["hsml"].copy(),
              dthsml=d["dthsml"].copy(), density=d["density"].copy(), vdisp=vd)
     eng.find_vel_disp(P, d["box"], a, sph_times(pkg, t), t["Time"], t["hubble"], t["ddrift"], thr, ActiveParticle=act)
+    assert a["vel"].tobytes() == d["vel"].tobytes()                   # an input goes up and does not come back
     compare(d, res, vd_ref, vd, eng.veldisp_export(d["n"]), eng.veldisp_stats(), "host / zel / sublist")
     eng.close()
 

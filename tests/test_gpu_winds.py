@@ -174,6 +174,7 @@ def test_host_form(pkg, name, kind, dec):
     s, g = eng.winds_export()
     eng.close()
     assert np.array_equal(P["Mass"], d["mass"]) and np.array_equal(P["Type"], table_type)
+    assert a["vdisp"].tobytes() == d["vdisp"].tobytes()              # an input goes up and does not come back
     compare(d, par, out, info, a, stats, set(zip(s.tolist(), g.tolist())), "host / %s / %s%s" % (name, kind, " / decoupling" if dec else ""))
 
 
