@@ -799,6 +799,83 @@ int mpg_winds_export(mpg_engine *eng, int64_t capacity, int32_t *star, int32_t *
  * the neighbour count that sizes the list (a host round trip between [0] and [1]) is in none of the three. */
 int mpg_winds_get_times(mpg_engine *eng, double ms[3]);
 
+/* ---- helium reionisation by quasar bubbles: do_heiii_reionization, libgadget/cooling_qso_lightup.c (run.c:622, 632-635) -------------
+ * turn_on_quasars (:523-638) for ONE rank, after the caller's guards of :641-659.  The engine reads no file: the caller interpolates the
+ * history table (desired_ion_frac), evaluates Q_inst and the rhobar arithmetic of :550-554 (non_overlapping_bubble_number).
+ *   flash (:539-548)   with desired_ion_frac > heIIIreion_finish_frac every row of type 0 goes through ionize_single_particle (:388-408):
+ *       a row with the flag is left alone; otherwise flag = 1 and Entropy += deltau / uu_in_cgs / entropytou,
+ *       deltau = qso_inst_heating (1 - HYDROGEN_MASSFRAC) / (PROTONMASS HEMASS), entropytou = pow(Density / atime^3, GAMMA_MINUS1) / GAMMA_MINUS1.
+ *   the fraction (:367-382)  initionfrac = curionfrac = (rows of type 0 with the flag) / n_gas_tot.
+ *   the candidates (:290-311)  the groups with min <= Mass <= max in the order of the group table; only with curionfrac < desired.
+ *   the loop (:575-628), iteration = 0, 1, ... while curionfrac < desired:
+ *       choice   qso = (int64)(table[(TotNgroups + iteration) % size] * ncand_tot), ncand_tot--; position = qso, or -1 outside the list;
+ *                when ncand_tot <= 0 now the loop ends BEFORE the bubble: the last remaining candidate is never lit.
+ *       bubble   only for position > 0 (:505): the candidate at list position 0 ionises nothing and is consumed all the same.  Centre =
+ *                CM of the group, radius = mean_bubble + sqrt(var_bubble) sqrt(-2 log u1) cos(2 pi u2), u1 = table[MinID % size],
+ *                u2 = table[(MinID + 1) % size], computed on the host in double.  Every row of CURRENT type 0 without the flag whose
+ *                nearest image lies within r2 <= radius^2 is ionised as above; count = the rows newly ionised.
+ *       then     curionfrac += count / n_gas_tot; the loop ends when count < 0.01 non_overlapping_bubble_number and iteration > 10;
+ *                otherwise the candidate leaves the list.
+ * The device scans the gas once per BATCH of iterations and keeps, per row, the first bubble that covers it; the host replays the loop on
+ * the counts (same doubles, same order) and an apply pass ionises the rows of the bubbles before the stop: flags, counts and curionfrac
+ * are those of the sequential loop for every batch size.  No tree is read, built or changed.  Garbage rows carry type 7 in
+ * the bound type column.
+ * ERRORS (returned; the reference would endrun or divide by zero): no parameters, no random table (mpg_set_random_table), n_gas_tot <= 0,
+ * no type column; and, found when the candidate list is drawn, before any bubble is scanned (a flash has been applied by then): a radius
+ * that is not positive and finite, a table value of exactly 0 at a seed used as u1. */
+typedef struct mpg_heiii_params {
+    double qso_candidate_min_mass, qso_candidate_max_mass; /* QSOMinMass, QSOMaxMass */
+    double mean_bubble, var_bubble;                        /* QSOMeanBubble, QSOVarBubble */
+    double heIIIreion_finish_frac;                         /* QSOHeIIIReionFinishFrac */
+} mpg_heiii_params;
+typedef struct mpg_heiii_step {
+    double atime;
+    double desired_ion_frac;   /* XHeIII(atime), :530 */
+    double qso_inst_heating;   /* Q_inst of the table's header, in erg */
+    double uu_in_cgs;          /* UnitInternalEnergy_in_cgs */
+    int64_t n_gas_tot;         /* SlotsManager->info[0].size */
+    int64_t non_overlapping_bubble_number; /* :550-554 */
+    int64_t TotNgroups;        /* fof.TotNgroups: the seed of the choices */
+} mpg_heiii_step;
+enum { MPG_HEIII_NOTHING_TO_DO = 0, MPG_HEIII_NO_CANDIDATES = 1, MPG_HEIII_REACHED = 2, MPG_HEIII_EXHAUSTED = 3, MPG_HEIII_INSUFFICIENT = 4 };
+typedef struct mpg_heiii_result {
+    int64_t n_ionized_before;  /* rows of type 0 with the flag on entry */
+    int64_t flash_ionized;     /* rows the flash branch ionised (0 without it) */
+    int64_t iterations;        /* iterations that reached the bookkeeping of :587-621 (the entries of mpg_heiii_export) */
+    int64_t tot_n_ionized;     /* summed counts of the bubbles */
+    double initionfrac, curionfrac;
+    int stop_reason;           /* MPG_HEIII_*: curionfrac >= desired on entry; no group in the mass window; desired reached; the list
+                                * ran out (:581-585); insufficient ionisation (:618-621) */
+} mpg_heiii_result;
+int mpg_set_heiii_params(mpg_engine *eng, const mpg_heiii_params *par);
+/* gas_ionization_fraction on the bound particles: *n_ionized = rows of type 0 with the flag, *fraction = n_ionized / n_gas_tot (either may be
+ * NULL).  need_change_helium_ionization_fraction (:661-669) is fraction < desired. */
+int mpg_dev_heiii_ionization_fraction(mpg_engine *eng, const uint8_t *d_heiii_ionized, int64_t n_gas_tot, int64_t *n_ionized, double *fraction);
+/* on the bound particles (Pos and Type; Type is required).  Device columns of n entries: density (read), entropy and heiii_ionized (in / out);
+ * device group columns of ngroups entries as mpg_dev_fof_groups fills them: d_group_mass, d_group_cm [ngroups][3], d_group_minid.  Mass is
+ * read back whole, CM and MinID for the candidates only.  The group columns may be NULL with ngroups == 0. */
+int mpg_dev_heiii_reionization(mpg_engine *eng, const mpg_heiii_step *step, const double *d_density, double *d_entropy, uint8_t *d_heiii_ionized,
+                               const double *d_group_mass, const double *d_group_cm, const uint64_t *d_group_minid, int64_t ngroups,
+                               mpg_heiii_result *result);
+/* host form: `pv` supplies Pos / Type / flags; all arrays are HOST arrays.  entropy and heiii_ionized come back. */
+int mpg_heiii_reionization(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_heiii_step *step, const double *density,
+                           double *entropy, uint8_t *heiii_ionized, const double *group_mass, const double *group_cm,
+                           const uint64_t *group_minid, int64_t ngroups, mpg_heiii_result *result);
+/* on a resident gas run: Density and Entropy are the resident columns; the flag (HOST array) travels in and out, the groups are HOST arrays */
+int mpg_resident_sph_heiii_reionization(mpg_engine *eng, const mpg_particle_view *pv, const mpg_heiii_step *step, uint8_t *heiii_ionized,
+                                        const double *group_mass, const double *group_cm, const uint64_t *group_minid, int64_t ngroups,
+                                        mpg_heiii_result *result);
+/* the iterations of the last call, `capacity` entries at most into host arrays (any may be NULL); *count their number.  position: new_qso,
+ * the position in the candidate list as it stood; group: the index into the group table, or -1 when position <= 0 (nothing was lit; radius
+ * is 0 then); count: rows newly ionised; curionfrac after the iteration.  The shim writes FdHelium from these. */
+int mpg_heiii_export(mpg_engine *eng, int64_t capacity, int64_t *position, int64_t *group, double *radius, int64_t *count, double *curionfrac,
+                     int64_t *n);
+/* bubbles per scan, 1 .. 64; 0: the default (64).  The result does not depend on it. */
+int mpg_heiii_set_batch(mpg_engine *eng, int batch);
+/* device time of the last call in ms, from events on the engine's stream, summed over its batches: [0] the scan kernels, [1] the copies of
+ * the counts, [2] the apply passes.  The host's replay between [1] and [2], the fraction count and the flash are in none. */
+int mpg_heiii_get_times(mpg_engine *eng, double ms[3]);
+
 /* ---- introspection (tests, bench roofline accounting) ----------------------------------------- */
 typedef struct mpg_tree_stats {
     int64_t NumParticles; /* particles in the tree */

@@ -1966,6 +1966,7 @@ int mpg_set_random_table(mpg_engine *eng, const double *table, int64_t size)
     MPG_CHECK(eng && table && size > 0, "random table: a table of at least one entry is required");
     MPG_HIP(hipSetDevice(eng->device));
     eng->bh.set_random_table(table, size, eng->stream);
+    eng->heiii.rnd.assign(table, table + size); // the choices and radii of the helium reionisation are the host's
     API_END
 }
 
@@ -2187,6 +2188,124 @@ int mpg_winds_get_times(mpg_engine *eng, double ms[3])
     MPG_CHECK(eng && ms, "null argument");
     for(int k = 0; k < 3; k++)
         ms[k] = eng->winds.last_ms[k];
+    API_END
+}
+
+/* ------------------------------ helium reionisation by quasar bubbles (cooling_qso_lightup.c) ------------------------------ */
+
+int mpg_set_heiii_params(mpg_engine *eng, const mpg_heiii_params *par)
+{
+    API_BEGIN
+    MPG_CHECK(eng && par, "null argument");
+    MPG_CHECK(par->var_bubble >= 0, "heiii parameters: var_bubble is a variance");
+    eng->heiii.par = *par;
+    eng->heiii.have_par = true;
+    API_END
+}
+
+int mpg_heiii_set_batch(mpg_engine *eng, int batch)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    MPG_CHECK(batch >= 0 && batch <= HEIII_MAXB, "mpg_heiii_set_batch: 0 (the default) or 1 .. 64 bubbles per scan");
+    eng->heiii.batch = batch;
+    API_END
+}
+
+static HeiiiView heiii_view(mpg_engine *eng, const char *who, const double *d_density, double *d_entropy, uint8_t *d_flag)
+{
+    MPG_CHECK(eng->d_pos || eng->n == 0, std::string(who) + ": no particles bound");
+    MPG_CHECK(eng->d_type || eng->n == 0, std::string(who) + ": the bound particles have no type column");
+    MPG_CHECK(d_flag || eng->n == 0, std::string(who) + ": the array heiii_ionized is required");
+    return HeiiiView{eng->d_pos, eng->d_type, eng->n, d_density, d_entropy, d_flag};
+}
+
+int mpg_dev_heiii_ionization_fraction(mpg_engine *eng, const uint8_t *d_heiii_ionized, int64_t n_gas_tot, int64_t *n_ionized, double *fraction)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    MPG_CHECK(n_gas_tot > 0, "heiii_ionization_fraction: n_gas_tot must be positive");
+    MPG_HIP(hipSetDevice(eng->device));
+    const HeiiiView v = heiii_view(eng, "heiii_ionization_fraction", nullptr, nullptr, (uint8_t *)d_heiii_ionized);
+    const int64_t c = eng->heiii.count_ionized(v, eng->stream);
+    if(n_ionized)
+        *n_ionized = c;
+    if(fraction)
+        *fraction = (double)c / (double)n_gas_tot; // :381
+    API_END
+}
+
+void heiii_call(mpg_engine *eng, const mpg_heiii_step *step, const double *d_density, double *d_entropy, uint8_t *d_flag, const HeiiiGroups &groups,
+                mpg_heiii_result *result)
+{
+    MPG_CHECK(eng && step, "null argument");
+    MPG_CHECK(eng->heiii.have_par, "heiii_reionization: no parameters (mpg_set_heiii_params first)");
+    MPG_CHECK(!eng->heiii.rnd.empty(), "heiii_reionization: no random table (mpg_set_random_table first)");
+    MPG_CHECK(step->n_gas_tot > 0, "heiii_reionization: n_gas_tot must be positive");
+    MPG_CHECK(step->atime > 0 && step->uu_in_cgs > 0, "heiii_reionization: atime and uu_in_cgs must be positive");
+    MPG_HIP(hipSetDevice(eng->device));
+    const HeiiiView v = heiii_view(eng, "heiii_reionization", d_density, d_entropy, d_flag);
+    MPG_CHECK((d_density && d_entropy) || eng->n == 0, "heiii_reionization: the arrays density and entropy are required");
+    try {
+        eng->heiii.run(v, eng->box, *step, groups, eng->stream);
+    } catch(...) {
+        if(result)
+            *result = eng->heiii.last;
+        throw;
+    }
+    if(result)
+        *result = eng->heiii.last;
+}
+
+int mpg_dev_heiii_reionization(mpg_engine *eng, const mpg_heiii_step *step, const double *d_density, double *d_entropy, uint8_t *d_heiii_ionized,
+                               const double *d_group_mass, const double *d_group_cm, const uint64_t *d_group_minid, int64_t ngroups,
+                               mpg_heiii_result *result)
+{
+    API_BEGIN
+    MPG_CHECK(eng && ngroups >= 0, "heiii_reionization: null engine or negative group number");
+    // the groups when the loop asks for them: Mass whole, CM and MinID of the candidates
+    const HeiiiGroups groups = [=](const mpg_heiii_params &par, std::vector<int64_t> &cand, std::vector<double> &ccm, std::vector<uint64_t> &cid) {
+        MPG_CHECK(ngroups == 0 || (d_group_mass && d_group_cm && d_group_minid), "heiii_reionization: the group columns mass, cm and minid are required");
+        std::vector<double> mass((size_t)ngroups);
+        if(ngroups > 0) {
+            MPG_HIP(hipMemcpyAsync(mass.data(), d_group_mass, (size_t)ngroups * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+            MPG_HIP(hipStreamSynchronize(eng->stream));
+        }
+        heiii_candidates(par, mass.data(), ngroups, cand);
+        eng->heiii.gather_groups(cand, d_group_cm, d_group_minid, ccm, cid, eng->stream);
+    };
+    heiii_call(eng, step, d_density, d_entropy, d_heiii_ionized, groups, result);
+    API_END
+}
+
+int mpg_heiii_export(mpg_engine *eng, int64_t capacity, int64_t *position, int64_t *group, double *radius, int64_t *count, double *curionfrac,
+                     int64_t *n)
+{
+    API_BEGIN
+    MPG_CHECK(eng && n && capacity >= 0, "null argument");
+    const std::vector<HeiiiRecord> &R = eng->heiii.records;
+    *n = (int64_t)R.size();
+    for(int64_t k = 0; k < (int64_t)R.size() && k < capacity; k++) {
+        if(position)
+            position[k] = R[k].position;
+        if(group)
+            group[k] = R[k].group;
+        if(radius)
+            radius[k] = R[k].radius;
+        if(count)
+            count[k] = R[k].count;
+        if(curionfrac)
+            curionfrac[k] = R[k].curionfrac;
+    }
+    API_END
+}
+
+int mpg_heiii_get_times(mpg_engine *eng, double ms[3])
+{
+    API_BEGIN
+    MPG_CHECK(eng && ms, "null argument");
+    for(int k = 0; k < 3; k++)
+        ms[k] = eng->heiii.last_ms[k];
     API_END
 }
 

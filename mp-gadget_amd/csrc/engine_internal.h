@@ -9,6 +9,7 @@
 #include "cooling.h"
 #include "metals.h"
 #include "winds.h"
+#include "heiii.h"
 #include "blackhole.h"
 #include "dynfric.h"
 #include "timestep.h"
@@ -185,6 +186,10 @@ struct mpg_engine {
     const double *d_delaytime = nullptr;
     const double *h_delaytime = nullptr;
     DevBuf<double> s_delaytime, s_delaytime_call;
+    // helium reionisation by quasar bubbles (heiii.hip): parameters, the host's random table, the loop's state; the staging of its host forms
+    HeiiiEngine heiii;
+    DevBuf<double> he_density, he_entropy;
+    DevBuf<uint8_t> he_flag;
     void prefetch_join()
     {
         if(prefetch_thread.joinable())
@@ -214,6 +219,11 @@ extern "C" void blackhole_call(mpg_engine *eng, const mpg_blackhole_arrays *A, c
 // mask when it has a target
 extern "C" int64_t dynfric_listed(mpg_engine *eng, const int *d_active, int64_t nactive);
 extern "C" void dynfric_call(mpg_engine *eng, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive);
+// ... and the helium reionisation call on device particle columns with the groups wherever `groups` finds them (engine.hip)
+extern "C" void heiii_call(mpg_engine *eng, const mpg_heiii_step *step, const double *d_density, double *d_entropy, uint8_t *d_flag, const HeiiiGroups &groups,
+                mpg_heiii_result *result);
+// ... the groups from HOST columns (host_forms.hip)
+HeiiiGroups heiii_host_groups(const double *mass, const double *cm, const uint64_t *minid, int64_t ngroups);
 void host_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *par, double *planes, int64_t *npart);
 
 // potential planes (planes.hip).  red: the sums over the ranks of the several-GPU form (dist.hip), or null; sum_device returns with the

@@ -1030,3 +1030,47 @@ int mpg_winds_and_feedback(mpg_engine *eng, const mpg_particle_view *pv, double 
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }
+
+// the candidate groups of the helium reionisation from HOST group columns (the dev form gathers them from the device table)
+HeiiiGroups heiii_host_groups(const double *mass, const double *cm, const uint64_t *minid, int64_t ngroups)
+{
+    return [=](const mpg_heiii_params &par, std::vector<int64_t> &cand, std::vector<double> &ccm, std::vector<uint64_t> &cid) {
+        MPG_CHECK(ngroups == 0 || (mass && cm && minid), "heiii_reionization: the group columns mass, cm and minid are required");
+        heiii_candidates(par, mass, ngroups, cand);
+        for(int64_t g : cand) {
+            for(int j = 0; j < 3; j++)
+                ccm.push_back(cm[3 * g + j]);
+            cid.push_back(minid[g]);
+        }
+    };
+}
+
+// do_heiii_reionization on a host table: Density, Entropy and the flag go up, Entropy and the flag come back; the groups stay on the host.
+// No tree is built.
+int mpg_heiii_reionization(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_heiii_step *step, const double *density,
+                           double *entropy, uint8_t *heiii_ionized, const double *group_mass, const double *group_cm,
+                           const uint64_t *group_minid, int64_t ngroups, mpg_heiii_result *result)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && step, "null argument");
+    MPG_CHECK(ngroups >= 0, "heiii_reionization: negative group number");
+    MPG_CHECK(pv->n == 0 || (density && entropy && heiii_ionized), "heiii_reionization: the arrays density, entropy and heiii_ionized are required");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    const size_t n = (size_t)pv->n;
+    eng->he_density.reserve(n + 1);
+    eng->he_entropy.reserve(n + 1);
+    eng->he_flag.reserve(n + 1);
+    if(n > 0) {
+        MPG_HIP(hipMemcpyAsync(eng->he_density.p, density, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        MPG_HIP(hipMemcpyAsync(eng->he_entropy.p, entropy, n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        MPG_HIP(hipMemcpyAsync(eng->he_flag.p, heiii_ionized, n, hipMemcpyHostToDevice, eng->stream));
+    }
+    heiii_call(eng, step, eng->he_density.p, eng->he_entropy.p, eng->he_flag.p, heiii_host_groups(group_mass, group_cm, group_minid, ngroups), result);
+    if(n > 0) {
+        MPG_HIP(hipMemcpyAsync(entropy, eng->he_entropy.p, n * sizeof(double), hipMemcpyDeviceToHost, eng->stream));
+        MPG_HIP(hipMemcpyAsync(heiii_ionized, eng->he_flag.p, n, hipMemcpyDeviceToHost, eng->stream));
+    }
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}

@@ -636,3 +636,27 @@ int mpg_resident_sph_blackhole(mpg_engine *eng, const mpg_particle_view *pv, con
     MPG_HIP(hipStreamSynchronize(eng->stream));
     API_END
 }
+
+// do_heiii_reionization on a resident gas run: Density and Entropy are the resident columns, so the heat is where the next cooling call
+// and the integrator read it; the flag travels in and out, the groups stay on the host.  The run's tree is neither read nor changed.
+int mpg_resident_sph_heiii_reionization(mpg_engine *eng, const mpg_particle_view *pv, const mpg_heiii_step *step, uint8_t *heiii_ionized,
+                                        const double *group_mass, const double *group_cm, const uint64_t *group_minid, int64_t ngroups,
+                                        mpg_heiii_result *result)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && step, "null argument");
+    MPG_CHECK(ngroups >= 0, "heiii_reionization: negative group number");
+    resident_sph_check(eng, pv);
+    const size_t n = (size_t)pv->n;
+    const mpg_sph_arrays &r = eng->res_sph_dev;
+    MPG_CHECK(r.density && r.entropy, "resident heiii_reionization: the gas arrays have no Density / Entropy");
+    MPG_CHECK(heiii_ionized || n == 0, "heiii_reionization: the array heiii_ionized is required");
+    eng->he_flag.reserve(n + 1);
+    if(n > 0)
+        MPG_HIP(hipMemcpyAsync(eng->he_flag.p, heiii_ionized, n, hipMemcpyHostToDevice, eng->stream));
+    heiii_call(eng, step, r.density, (double *)r.entropy, eng->he_flag.p, heiii_host_groups(group_mass, group_cm, group_minid, ngroups), result);
+    if(n > 0)
+        MPG_HIP(hipMemcpyAsync(heiii_ionized, eng->he_flag.p, n, hipMemcpyDeviceToHost, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    API_END
+}

@@ -194,6 +194,26 @@ RECOMB_CEN92, RECOMB_VERNER96, RECOMB_BADNELL06 = 0, 1, 2      # enum RecombType
 COOLING_KWH92, COOLING_ENZO2NYX, COOLING_SHERWOOD = 0, 1, 2    # enum CoolingType, cooling_rates.h:16-20
 
 
+class HeiiiParams(C.Structure):
+    """mpg_heiii_params: the members of struct qso_lightup_params (cooling_qso_lightup.c:53-71) that turn_on_quasars reads"""
+    _fields_ = [(k, C.c_double) for k in ("qso_candidate_min_mass", "qso_candidate_max_mass", "mean_bubble", "var_bubble", "heIIIreion_finish_frac")]
+
+
+class HeiiiStep(C.Structure):
+    """mpg_heiii_step"""
+    _fields_ = [("atime", C.c_double), ("desired_ion_frac", C.c_double), ("qso_inst_heating", C.c_double), ("uu_in_cgs", C.c_double),
+                ("n_gas_tot", C.c_int64), ("non_overlapping_bubble_number", C.c_int64), ("TotNgroups", C.c_int64)]
+
+
+class HeiiiResult(C.Structure):
+    """mpg_heiii_result"""
+    _fields_ = [("n_ionized_before", C.c_int64), ("flash_ionized", C.c_int64), ("iterations", C.c_int64), ("tot_n_ionized", C.c_int64),
+                ("initionfrac", C.c_double), ("curionfrac", C.c_double), ("stop_reason", C.c_int)]
+
+
+HEIII_NOTHING_TO_DO, HEIII_NO_CANDIDATES, HEIII_REACHED, HEIII_EXHAUSTED, HEIII_INSUFFICIENT = range(5)   # enum MPG_HEIII_*
+
+
 class CoolingArraysC(C.Structure):
     """mpg_cooling_arrays"""
     _fields_ = [(k, C.c_void_p) for k in COOLING_ARRAY_FIELDS]
@@ -1373,6 +1393,89 @@ class Engine:
         c = (C.c_double * 3)()
         self._ck(self.lib.mpg_winds_get_times(self.h, c))
         return dict(weight_ms=c[0], feedback_ms=c[1], apply_ms=c[2])
+
+    # ------------------------------------------------------------------ helium reionisation by quasar bubbles (cooling_qso_lightup.c)
+    # `step` is a HeiiiStep or a dict of its members; `groups` maps "mass", "cm" ([ngroups][3]) and "minid" (uint64; on the device as int64
+    # of the same bits) to device tensors (dev form) / contiguous numpy arrays (host forms), as dev_fof_groups fills them.  Every call returns
+    # the HeiiiResult as a dict.  The random table is the one of set_random_table.
+    def set_heiii_params(self, par):
+        if not isinstance(par, HeiiiParams):
+            par = HeiiiParams(**par)
+        self._ck(self.lib.mpg_set_heiii_params(self.h, C.byref(par)))
+
+    def heiii_set_batch(self, batch):
+        """bubbles per scan (1 .. 64; 0: the default); the result does not depend on it"""
+        self._ck(self.lib.mpg_heiii_set_batch(self.h, C.c_int(batch)))
+
+    @staticmethod
+    def _heiii_step(step):
+        return step if isinstance(step, HeiiiStep) else HeiiiStep(**step)
+
+    @staticmethod
+    def _heiii_result(r):
+        return {k: getattr(r, k) for k, _ in HeiiiResult._fields_}
+
+    def dev_heiii_ionization_fraction(self, heiii_ionized, n_gas_tot):
+        """(rows of type 0 with the flag, that number / n_gas_tot) on the bound particles; heiii_ionized: uint8 device tensor"""
+        c, f = C.c_int64(0), C.c_double(0.0)
+        self._ck(self.lib.mpg_dev_heiii_ionization_fraction(self.h, _ptr(heiii_ionized), C.c_int64(n_gas_tot), C.byref(c), C.byref(f)))
+        return c.value, f.value
+
+    def dev_heiii_reionization(self, step, density, entropy, heiii_ionized, groups):
+        """on the bound particles: density, entropy (float64) and heiii_ionized (uint8) are device tensors, entropy and the flag in / out"""
+        r = HeiiiResult()
+        m = groups.get("mass")
+        ng = 0 if m is None else m.shape[0]
+        self._ck(self.lib.mpg_dev_heiii_reionization(self.h, C.byref(self._heiii_step(step)), _ptr(density), _ptr(entropy), _ptr(heiii_ionized),
+                                                     _ptr(m), _ptr(groups.get("cm")), _ptr(groups.get("minid")), C.c_int64(ng), C.byref(r)))
+        return self._heiii_result(r)
+
+    @staticmethod
+    def _heiii_host(groups, **cols):
+        """pointers of the contiguous host columns (float64; uint8 for the flag) and of the host group columns"""
+        want = dict(density="float64", entropy="float64", heiii_ionized="uint8", mass="float64", cm="float64", minid="uint64")
+        out = {}
+        for k, t in list(cols.items()) + [(k, groups.get(k)) for k in ("mass", "cm", "minid")]:
+            if t is not None and (t.dtype != np.dtype(want[k]) or not t.flags["C_CONTIGUOUS"]):
+                raise EngineError("heiii host array %s must be contiguous %s" % (k, want[k]))
+            out[k] = None if t is None else t.ctypes.data_as(C.c_void_p)
+        m = groups.get("mass")
+        return out, 0 if m is None else len(m)
+
+    def heiii_reionization(self, P, BoxSize, step, density, entropy, heiii_ionized, groups):
+        """host form: P supplies Pos / Type / flags; numpy arrays; entropy and heiii_ionized come back"""
+        v = self._view(P)
+        p, ng = self._heiii_host(groups, density=density, entropy=entropy, heiii_ionized=heiii_ionized)
+        r = HeiiiResult()
+        self._ck(self.lib.mpg_heiii_reionization(self.h, C.byref(v), C.c_double(BoxSize), C.byref(self._heiii_step(step)), p["density"], p["entropy"],
+                                                 p["heiii_ionized"], p["mass"], p["cm"], p["minid"], C.c_int64(ng), C.byref(r)))
+        return self._heiii_result(r)
+
+    def resident_sph_heiii_reionization(self, P, step, heiii_ionized, groups):
+        """on a resident gas run: Density and Entropy are resident; the flag (numpy uint8) travels in and out"""
+        v = self._view(P)
+        p, ng = self._heiii_host(groups, heiii_ionized=heiii_ionized)
+        r = HeiiiResult()
+        self._ck(self.lib.mpg_resident_sph_heiii_reionization(self.h, C.byref(v), C.byref(self._heiii_step(step)), p["heiii_ionized"], p["mass"], p["cm"],
+                                                              p["minid"], C.c_int64(ng), C.byref(r)))
+        return self._heiii_result(r)
+
+    def heiii_export(self):
+        """the iterations of the last call: dict of arrays position, group, radius, count, curionfrac"""
+        n = C.c_int64(0)
+        self._ck(self.lib.mpg_heiii_export(self.h, C.c_int64(0), None, None, None, None, None, C.byref(n)))
+        m = max(n.value, 1)
+        d = dict(position=np.zeros(m, np.int64), group=np.zeros(m, np.int64), radius=np.zeros(m), count=np.zeros(m, np.int64), curionfrac=np.zeros(m))
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.mpg_heiii_export(self.h, C.c_int64(m), p(d["position"]), p(d["group"]), p(d["radius"]), p(d["count"]), p(d["curionfrac"]),
+                                           C.byref(n)))
+        return {k: a[:n.value] for k, a in d.items()}
+
+    def heiii_times(self):
+        """device time of the last call in ms, summed over its batches: the scans, the copies of the counts, the apply passes"""
+        c = (C.c_double * 3)()
+        self._ck(self.lib.mpg_heiii_get_times(self.h, c))
+        return dict(scan_ms=c[0], copy_ms=c[1], apply_ms=c[2])
 
     # ------------------------------------------------------------------ black-hole dynamical friction and the potential minimum (bhdynfric.c)
     # `arrays` maps the field names of mpg_bh_dynfric_arrays to device tensors (dev form) / contiguous numpy arrays (host forms) of the

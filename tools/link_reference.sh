@@ -13,7 +13,7 @@
 #   2. copy shim/*.c, shim/*.h and include/mpgadget_hip.h into <copy>/libgadget/;
 #   3. patch <copy>/libgadget/Makefile: drop gravpm.o gravshort-tree.o gravshort-pair.o gravity.o from GADGET_OBJS and add the shim
 #      objects; rename the five tree constructors in forcetree.o, the eight integrator entry points in timestep.o / drift.o and
-#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o, metal_return in metal_return.o, blackhole in blackhole.o and winds_and_feedback in winds.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
+#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o, metal_return in metal_return.o, blackhole in blackhole.o, winds_and_feedback in winds.o and do_heiii_reionization in cooling_qso_lightup.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
 #   4. add the two parameter hooks (set_densitypar, set_hydro_params), the accessors of mpg_shim.h and the
 #      mpg_shim_particles_changed() calls listed in INTEGRATION.md ("Where P[] is reordered") with sed;
 #   5. build the library of this repository, then `make` in the copy with LIBS += -L<repo>/mp-gadget_amd -lmpgadget_hip -lmpi.
@@ -22,13 +22,13 @@ REF=${1:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 WORK=${2:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 CHECK=${3:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c blackhole-hip.c winds-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
+SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c blackhole-hip.c winds-hip.c heiii-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
 SHIM_H="mpg_shim.h mpg_shim_epoch.h mpg_mpi_comm.h"
 REF_FILES="libgadget/Makefile libgadget/gravpm.c libgadget/gravshort-tree.c libgadget/gravshort-pair.c libgadget/gravity.c libgadget/forcetree.c
            libgadget/density.c libgadget/hydra.c libgadget/timestep.c libgadget/drift.c libgadget/timebinmgr.c libgadget/run.c libgadget/domain.c
            libgadget/exchange.c libgadget/fof.c libgadget/slotsmanager.c libgadget/veldisp.c libgadget/sfr_eff.c libgadget/cooling.c libgadget/cooling_rates.c
            libgadget/cooling_uvfluc.c libgadget/metal_return.c libgadget/blackhole.c libgadget/bhdynfric.c
-           libgadget/winds.c gadget/Makefile Makefile.rules Options.mk.example"
+           libgadget/winds.c libgadget/cooling_qso_lightup.c gadget/Makefile Makefile.rules Options.mk.example"
 
 echo "== 0. inputs"
 for f in $REF_FILES; do test -f "$REF/$f" || { echo "missing in the reference checkout: $f"; exit 1; }; done
@@ -69,7 +69,7 @@ echo "== 3. libgadget/Makefile"
 MK="$T/libgadget/Makefile"
 sed -i -e 's/\bgravshort-tree\.o gravshort-pair\.o hydra\.o/hydra.o/' -e 's/\bgravpm\.o powerspectrum\.o/powerspectrum.o/' \
        -e 's/\bpetapm\.o gravity\.o/petapm.o/' "$MK"
-sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o blackhole-hip.o winds-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
+sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o blackhole-hip.o winds-hip.o heiii-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
 cat >> "$MK" <<MKEOF
 
 # ---- MP-Gadget on libmpgadget_hip (tools/link_reference.sh)
@@ -82,6 +82,7 @@ CFLAGS += -DMPGADGET_HIP -I$ROOT/include
 .objs/metal_return.o: CFLAGS += -Dmetal_return=cpu_metal_return
 .objs/blackhole.o: CFLAGS += -Dblackhole=cpu_blackhole
 .objs/winds.o: CFLAGS += -Dwinds_and_feedback=cpu_winds_and_feedback
+.objs/cooling_qso_lightup.o: CFLAGS += -Ddo_heiii_reionization=cpu_do_heiii_reionization
 MKEOF
 
 echo "== 4. hooks in the reference sources (INTEGRATION.md lists them; each is one line)"
@@ -186,6 +187,13 @@ append(T + "/libgadget/winds.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_wind_
            "WindEfficiency", "WindSigma0", "WindSpeedFactor", "MinWindVelocity", "WindThermalFactor", "WindFreeTravelLength", "WindSpeed",
            "MaxWindFreeTravelTime", "WindFreeTravelDensThresh"))
        + "}")
+# the helium reionisation (heiii-hip.c): the file-static parameters, qso_inst_heating and the history table of cooling_qso_lightup.c
+append(T + "/libgadget/cooling_qso_lightup.c", "#include <mpgadget_hip.h>\n"
+       "void mpg_shim_heiii_params(mpg_heiii_params *p, double *inst_heating, double *heIIIreion_start, double *table_end)\n{\n"
+       + "".join("    p->%s = QSOLightupParams.%s;\n" % (k, k) for k in (
+           "qso_candidate_min_mass", "qso_candidate_max_mass", "mean_bubble", "var_bubble", "heIIIreion_finish_frac"))
+       + "    *inst_heating = qso_inst_heating;\n    *heIIIreion_start = QSOLightupParams.heIIIreion_start;\n    *table_end = He_zz[Nreionhist - 1];\n}\n"
+       "double mpg_shim_heiii_desired(double atime)\n{\n    return gsl_interp_eval(HeIII_intp, He_zz, XHeIII, atime, NULL);\n}")
 append(T + "/libgadget/sfr_eff.c", "void mpg_shim_sfr_blackhole(int *StarformationOn, int *BHFeedbackUseTcool, double *PhysDensThresh, double *OverDensThresh)\n"
        "{\n    *StarformationOn = sfr_params.StarformationOn;\n    *BHFeedbackUseTcool = sfr_params.BHFeedbackUseTcool;\n"
        "    *PhysDensThresh = sfr_params.PhysDensThresh;\n    *OverDensThresh = sfr_params.OverDensThresh;\n}")
@@ -200,8 +208,8 @@ PYEOF
 
 if [ "$CHECK" = "--check" ]; then
     # the patched reference files and the renamed objects still parse (nothing is compiled to an object, linked or run); cooling_rates.c,
-    # which only gains one accessor line, and metal_return.c, which gains two functions, call GSL and cannot be parsed with the typedef-only
-    # stand-ins
+    # which only gains one accessor line, metal_return.c, which gains two functions, and cooling_qso_lightup.c, which gains two accessors,
+    # call GSL and cannot be parsed with the typedef-only stand-ins
     for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c sfr_eff.c cooling.c cooling_uvfluc.c blackhole.c bhdynfric.c winds.c; do
         extra=""
         case $f in
