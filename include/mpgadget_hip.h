@@ -876,6 +876,112 @@ int mpg_heiii_set_batch(mpg_engine *eng, int batch);
  * the counts, [2] the apply passes.  The host's replay between [1] and [2], the fraction count and the flash are in none. */
 int mpg_heiii_get_times(mpg_engine *eng, double ms[3]);
 
+/* ---- star formation on the effective equation of state: cooling_and_starformation, libgadget/sfr_eff.c:186-394 (run.c:663-664) --------
+ * Everything in cooling_and_starformation that changes neither the number of rows nor a row's type: the loop of :224-272, the subgrid winds
+ * of :280-286 and the sums of :343-350, for ONE rank with StarformationOn.  For every listed row that passes the filter of :229:
+ *   winds_evolve (winds.c:374-391) when a `delaytime` column is given (mpg_set_wind_params is then required; NULL: DelayTime == 0);
+ *   the class: sfreff_on_eeqos (:534-566), or quicklyastarformation (:706-725) when QuickLymanAlphaProbability > 0;
+ *   a row that does not form stars: cooling_direct through the cooling kernel of mpg_dev_cooling on the compacted list of these rows;
+ *   a row on the effective equation of state: starformation (:731-800) without the spawning - get_sfr_eeqos (:804-841, one GetCoolingTime),
+ *       get_starformation_rate_full (:843-862) with the H2 (:1041-1077) and self-gravity (:1079-1112) factors, Sfr, Ne, both Metallicity
+ *       increments, cooling_relaxed (:666-701, with the BHFeedbackUseTcool 1 / 3 branch, its second GetCoolingTime and the clearing of
+ *       BHHeated), find_star_mass (:1002-1023), the draw table[(ID + 1) % size] < prob with w = table[ID % size], and the rule
+ *       Mass >= 1.1 mass_of_star that tells a spawned star from a converted particle.  With QuickLymanAlphaProbability > 0 a star-forming
+ *       row is converted as it is (:247-251): none of its columns changes.
+ * RESULTS besides the columns, all in the order of the active list (what gadget_compact_thread_arrays gives under the static schedule):
+ *   the new-star list: parent row, mass_of_star, spawn (1) or convert (0).  The kernel writes neither Mass, Generation, Type nor ID:
+ *       slots_split_particle, slots_convert, make_particle_star and the rest of :288-393 stay the caller's;
+ *   the MaybeWind list (:264-268), when a `stellarmass` column is given: the star-forming rows without a new star, StellarMass by particle;
+ *   sum_sm, localsfr, sum_dtime, sum_sf_part: summed in a fixed order, so two calls give the same bits.
+ * With WindOn and WIND_SUBGRID in the WindModel the call ends with winds_subgrid on the MaybeWind list (:280-286), as mpg_dev_winds_subgrid.
+ * A list entry outside the table is ignored and a time bin beyond 46 is read as 46, as in mpg_dev_cooling.  A row whose network hits its
+ * iteration limit keeps all its columns but DelayTime (winds_evolve has run before the row's class is known, as in the reference; for a
+ * star-forming row it can only have written 0), forms no star, enters no list and no sum but sum_sf_part, and makes the call return non-zero
+ * after every other row is done.  The lists on the device stay valid until the next call (mpg_sfr_dev_lists). */
+typedef struct mpg_sfr_params {
+    /* the members of struct SFRParams (sfr_eff.c:36-90) the loop reads, AFTER init_cooling_and_star_formation (the threshold is the caller's) */
+    int StarformationCriterion; /* enum StarformationCriterion, sfr_eff.h:16-23 */
+    int BoostSFDenseGas;
+    double BoostSFOverDenseFactor;
+    double FactorSN, FactorEVP, MaxSfrTimescale;
+    int Generations;
+    int BHFeedbackUseTcool;     /* 0, 1 or 3; 2 is refused (it needs get_egyeff in the classification) */
+    double QuickLymanAlphaProbability, QuickLymanAlphaTempThresh;
+    double EgySpecSN, EgySpecCold, PhysDensThresh, OverDensThresh;
+    double UnitSfr_in_solar_per_year, avg_baryon_mass, tau_fmol_unit, GravInternal;
+    int WindOn;
+    /* what is refused when it is set, so that a caller keeps its CPU path from the start */
+    int UVFluctuationOn; /* a UV-fluctuation table is loaded (UVF.enabled) */
+    int ExcursionSetReion; /* built with EXCUR_REION */
+    int NTask;           /* ranks of the run; 0 is read as 1 */
+} mpg_sfr_params;
+/* arrays in particle order, n entries (x 3 where noted); slot members are indexed by PARTICLE */
+typedef struct mpg_sfr_columns {
+    /* read */
+    const uint64_t *id;           /* P.ID */
+    const uint8_t *generation;    /* P.Generation; NULL = 0 */
+    const double *density;        /* SPHP.Density */
+    const double *hsml;           /* P.Hsml (SFR_CRITERION_MOLECULAR_H2) */
+    const double *divvel;         /* SPHP.DivVel (SFR_CRITERION_SELFGRAVITY) */
+    const double *curlvel;        /* SPHP.CurlVel (SFR_CRITERION_SELFGRAVITY) */
+    const double *gradrho_mag;    /* GradRho_mag (SFR_CRITERION_MOLECULAR_H2) */
+    const uint8_t *tb_hydro;      /* P.TimeBinHydro; NULL = 0 */
+    const uint8_t *heiii_ionized; /* P.HeIIIionized (cooling_direct); NULL = 0 */
+    const double *vdisp;          /* SPHP.VDisp (winds_subgrid) */
+    /* in / out */
+    double *entropy;              /* SPHP.Entropy */
+    double *ne;                   /* SPHP.Ne */
+    double *sfr;                  /* SPHP.Sfr */
+    double *metallicity;          /* SPHP.Metallicity */
+    double *delaytime;            /* SPHP.DelayTime; NULL = 0 everywhere, no winds_evolve */
+    uint8_t *bhheated;            /* P.BHHeated; NULL = 0 */
+    double *vel;                  /* [n][3] P.Vel (winds_subgrid) */
+    /* out */
+    double *stellarmass;          /* StellarMass of the rows of the MaybeWind list; NULL: no such list */
+} mpg_sfr_columns;
+typedef struct mpg_sfr_result {
+    int64_t treated;      /* listed rows that passed the filter */
+    int64_t cooled;       /* ... that went through cooling_direct */
+    int64_t sum_sf_part;  /* ... that were star-forming */
+    int64_t newstars, converted, spawned;
+    int64_t maybewind;
+    int64_t errors;       /* rows that hit an iteration limit: cooled and star-forming */
+    double sum_sm, localsfr, sum_dtime;
+} mpg_sfr_result;
+/* an error that names the setting for BHFeedbackUseTcool == 2, a UV-fluctuation table, EXCUR_REION and several ranks.  A fifth refusal
+ * belongs to one form: mpg_resident_sph_cooling_and_starformation with WindOn and WIND_SUBGRID (below). */
+int mpg_set_sfr_params(mpg_engine *eng, const mpg_sfr_params *par);
+/* on the bound particles (types from the bound table, garbage as type 7, Mass the bound column); d_active NULL = all particles.  Required:
+ * id, density, entropy, ne, sfr, metallicity and what the criterion reads; with WindOn and WIND_SUBGRID also vdisp, vel, delaytime and
+ * stellarmass.  The random table is that of mpg_set_random_table, the cooling parameters those of mpg_set_cooling_params. */
+int mpg_dev_cooling_and_starformation(mpg_engine *eng, const mpg_sfr_columns *A, const mpg_sph_times *T, const mpg_cooling_step *step,
+                                      const int *d_active, int64_t nactive);
+/* host form: `pv` supplies Mass / Type / flags, `A` holds HOST arrays in particle order (the shim gathers P and SphP into them) */
+int mpg_cooling_and_starformation(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_sfr_columns *A, const mpg_sph_times *T,
+                                  const mpg_cooling_step *step, const int *ActiveParticle, int64_t NumActiveParticle);
+/* on a resident gas run (mpg_resident_sph_begin): Density, Entropy and TimeBinHydro are the resident columns, and so are Hsml, DivVel and
+ * CurlVel, which the density loop of the stretch left there and whose host copies are stale (these six members of `A` are not read); every
+ * other member of `A` is a HOST array that travels.  REFUSED here: WindOn with WIND_SUBGRID, whose kicks would have to
+ * reach the resident Vel.  A caller with subgrid winds sets WindOn = 0 for this form, gives a `stellarmass` column, and runs winds_subgrid on
+ * the exported MaybeWind list after the stretch has ended (shim/cooling-hip.c does). */
+int mpg_resident_sph_cooling_and_starformation(mpg_engine *eng, const mpg_particle_view *pv, const mpg_sfr_columns *A, const mpg_sph_times *T,
+                                               const mpg_cooling_step *step, const int *ActiveParticle, int64_t NumActiveParticle);
+/* counts, sums and errors of the last call */
+int mpg_sfr_get_result(mpg_engine *eng, mpg_sfr_result *result);
+/* the two lists of the last call into host arrays (any may be NULL): the first `capacity` new stars (parent row, mass_of_star, 1 = spawn /
+ * 0 = convert), *nnew their number; the first `wcapacity` rows of the MaybeWind list, *nmaybewind its length */
+int mpg_sfr_export(mpg_engine *eng, int64_t capacity, int32_t *parent, double *mass_of_star, uint8_t *spawn, int64_t *nnew, int64_t wcapacity,
+                   int32_t *maybewind, int64_t *nmaybewind);
+/* ... and where they are on the device until the next call (any may be NULL; lengths in mpg_sfr_get_result) */
+int mpg_sfr_dev_lists(mpg_engine *eng, const int **d_parent, const double **d_mass_of_star, const uint8_t **d_spawn, const int **d_maybewind);
+/* per particle of the last call (host arrays of n entries, either may be NULL): the class (0 not treated, 1 cooled, 2 star-forming) and
+ * the network evaluations of a star-forming row (-1 for every other row; those of the cooled rows: mpg_cooling_export) */
+int mpg_sfr_export_rows(mpg_engine *eng, int64_t n, uint8_t *rowclass, int32_t *evaluations);
+/* statistics of the last call: [0] list entries, [1] rows treated, [2] cooled, [3] star-forming, [4] network evaluations of the
+ * star-forming rows summed, [5] star-forming rows that hit a limit, [6] new stars, [7] rows of the MaybeWind list.  After the call
+ * mpg_cooling_get_stats / mpg_cooling_export describe the cooled rows as after mpg_dev_cooling. */
+int mpg_sfr_get_stats(mpg_engine *eng, int64_t stats[8]);
+
 /* ---- introspection (tests, bench roofline accounting) ----------------------------------------- */
 typedef struct mpg_tree_stats {
     int64_t NumParticles; /* particles in the tree */

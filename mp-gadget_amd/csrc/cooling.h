@@ -319,6 +319,22 @@ MPG_HD double get_lambdanet(const Setup &S, double rho, double u, double redshif
     return LambdaNet;
 }
 
+// GetCoolingTime, cooling.c:143-163: code units in and out, rho the proper density; one get_heatingcooling_rate WITHOUT the
+// long-mean-free-path term; 0 for net heating
+MPG_HD double get_cooling_time(const Setup &S, double redshift, double u_old, double rho, double *ne_guess, double Z, Counters &C)
+{
+    if(!S.CoolingOn)
+        return 0;
+    rho *= S.density_in_phys_cgs / PROTONMASS;
+    u_old *= S.uu_in_cgs;
+    const double LambdaNet = get_heatingcooling_rate(S, rho, u_old, 1 - HYDROGEN_MASSFRAC, redshift, Z, ne_guess, C);
+    if(LambdaNet >= 0)
+        return 0;
+    double coolingtime = u_old / (-LambdaNet);
+    coolingtime /= S.tt_in_s;
+    return coolingtime;
+}
+
 // DoCooling, cooling.c:57-138.  Code units in and out; rho is the proper density.
 MPG_HD double do_cooling(const Setup &S, double redshift, double u_old, double rho, double dt, double *ne_guess, double Z, double MinEgySpec,
                          int isHeIIIionized, Counters &C)

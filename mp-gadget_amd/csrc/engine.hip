@@ -2191,6 +2191,135 @@ int mpg_winds_get_times(mpg_engine *eng, double ms[3])
     API_END
 }
 
+/* ------------------------------ star formation (sfr_eff.c:186-394) ------------------------------ */
+
+int mpg_set_sfr_params(mpg_engine *eng, const mpg_sfr_params *par)
+{
+    API_BEGIN
+    MPG_CHECK(eng && par, "null argument");
+    eng->sfr.set_params(*par);
+    API_END
+}
+
+int mpg_dev_cooling_and_starformation(mpg_engine *eng, const mpg_sfr_columns *A, const mpg_sph_times *T, const mpg_cooling_step *step,
+                                      const int *d_active, int64_t nactive)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A && T && step, "null argument");
+    MPG_CHECK(nactive >= 0, "cooling_and_starformation: negative list length");
+    MPG_CHECK(eng->sfr.have_params, "cooling_and_starformation: no parameters (mpg_set_sfr_params first)");
+    MPG_CHECK(eng->bh.rndsize > 0, "cooling_and_starformation: no random table (mpg_set_random_table first)");
+    MPG_CHECK(eng->d_mass || eng->n == 0, "cooling_and_starformation: no particles bound");
+    const mpg_sfr_params &P = eng->sfr.par;
+    MPG_CHECK(!(P.WindOn || A->delaytime) || eng->have_windpar, "cooling_and_starformation: no wind parameters (mpg_set_wind_params first)");
+    const bool subgrid = P.WindOn && (eng->windpar.WindModel & WIND_SUBGRID) != 0; // winds_are_subgrid, sfr_eff.c:205, 280
+    if(eng->n > 0) {
+        MPG_CHECK(A->id && A->density && A->entropy && A->ne && A->sfr && A->metallicity,
+                  "cooling_and_starformation: the columns id, density, entropy, ne, sfr and metallicity are required");
+        if(!(P.QuickLymanAlphaProbability > 0)) {
+            MPG_CHECK(!mpg::sfr::has(P.StarformationCriterion, mpg::sfr::CRIT_MOLECULAR_H2) || (A->hsml && A->gradrho_mag),
+                      "cooling_and_starformation: SFR_CRITERION_MOLECULAR_H2 needs the columns hsml and gradrho_mag");
+            MPG_CHECK(!mpg::sfr::has(P.StarformationCriterion, mpg::sfr::CRIT_SELFGRAVITY) || (A->divvel && A->curlvel),
+                      "cooling_and_starformation: SFR_CRITERION_SELFGRAVITY needs the columns divvel and curlvel");
+        }
+        MPG_CHECK(!subgrid || (A->vdisp && A->vel && A->delaytime && A->stellarmass),
+                  "cooling_and_starformation: WIND_SUBGRID needs the columns vdisp, vel, delaytime and stellarmass");
+    }
+    MPG_HIP(hipSetDevice(eng->device));
+    const SfrView v{eng->d_type, eng->d_mass, eng->n, *A};
+    const int64_t bad = eng->sfr.run(eng->cooling, v, A->delaytime ? &eng->windpar : nullptr, eng->bh.rnd.p, (uint64_t)eng->bh.rndsize, *T, *step, d_active,
+                                     nactive, eng->stream);
+    if(subgrid) { // sfr_eff.c:280-286
+        mpg_wind_arrays W{};
+        W.id = A->id;
+        W.vdisp = A->vdisp;
+        W.density = A->density;
+        W.vel = A->vel;
+        W.entropy = A->entropy;
+        W.delaytime = A->delaytime;
+        WindView wv;
+        WindScalars S;
+        winds_setup(eng, &W, T->atime, "cooling_and_starformation", wv, S);
+        eng->winds.reset();
+        if(eng->sfr.last.maybewind > 0)
+            eng->winds.subgrid(wv, S, eng->sfr.maybewind.p, eng->sfr.last.maybewind, A->stellarmass, eng->stream);
+    }
+    // the reference's endrun(1 / 10): every other row of the call has been treated
+    MPG_CHECK(bad == 0, "cooling_and_starformation: " + std::to_string(bad) + " row(s) hit an iteration limit of DoCooling or of the ionisation network, or reached "
+                                                                             "an electron abundance that is not finite; they keep their columns and form no star");
+    API_END
+}
+
+int mpg_sfr_get_result(mpg_engine *eng, mpg_sfr_result *result)
+{
+    API_BEGIN
+    MPG_CHECK(eng && result, "null argument");
+    *result = eng->sfr.last;
+    API_END
+}
+
+int mpg_sfr_export(mpg_engine *eng, int64_t capacity, int32_t *parent, double *mass_of_star, uint8_t *spawn, int64_t *nnew, int64_t wcapacity,
+                   int32_t *maybewind, int64_t *nmaybewind)
+{
+    API_BEGIN
+    MPG_CHECK(eng && capacity >= 0 && wcapacity >= 0, "mpg_sfr_export: null engine or negative capacity");
+    const SfrEngine &E = eng->sfr;
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    const size_t m = (size_t)(capacity < E.last.newstars ? capacity : E.last.newstars), mw = (size_t)(wcapacity < E.last.maybewind ? wcapacity : E.last.maybewind);
+    if(m > 0 && parent)
+        MPG_HIP(hipMemcpy(parent, E.ns_parent.p, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(m > 0 && mass_of_star)
+        MPG_HIP(hipMemcpy(mass_of_star, E.ns_mass.p, m * sizeof(double), hipMemcpyDeviceToHost));
+    if(m > 0 && spawn)
+        MPG_HIP(hipMemcpy(spawn, E.ns_spawn.p, m, hipMemcpyDeviceToHost));
+    if(mw > 0 && maybewind)
+        MPG_HIP(hipMemcpy(maybewind, E.maybewind.p, mw * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if(nnew)
+        *nnew = E.last.newstars;
+    if(nmaybewind)
+        *nmaybewind = E.last.maybewind;
+    API_END
+}
+
+int mpg_sfr_dev_lists(mpg_engine *eng, const int **d_parent, const double **d_mass_of_star, const uint8_t **d_spawn, const int **d_maybewind)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    if(d_parent)
+        *d_parent = eng->sfr.ns_parent.p;
+    if(d_mass_of_star)
+        *d_mass_of_star = eng->sfr.ns_mass.p;
+    if(d_spawn)
+        *d_spawn = eng->sfr.ns_spawn.p;
+    if(d_maybewind)
+        *d_maybewind = eng->sfr.maybewind.p;
+    API_END
+}
+
+int mpg_sfr_export_rows(mpg_engine *eng, int64_t n, uint8_t *rowclass, int32_t *evaluations)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    MPG_CHECK(n == eng->sfr.n_rows, "mpg_sfr_export_rows: n is not the particle number of the last call");
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    if(n > 0 && rowclass)
+        MPG_HIP(hipMemcpy(rowclass, eng->sfr.rowclass.p, (size_t)n, hipMemcpyDeviceToHost));
+    if(n > 0 && evaluations)
+        MPG_HIP(hipMemcpy(evaluations, eng->sfr.sfevals.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    API_END
+}
+
+int mpg_sfr_get_stats(mpg_engine *eng, int64_t stats[8])
+{
+    API_BEGIN
+    MPG_CHECK(eng && stats, "null argument");
+    for(int k = 0; k < SFR_NSTATS; k++)
+        stats[k] = eng->sfr.last_stats[k];
+    API_END
+}
+
 /* ------------------------------ helium reionisation by quasar bubbles (cooling_qso_lightup.c) ------------------------------ */
 
 int mpg_set_heiii_params(mpg_engine *eng, const mpg_heiii_params *par)

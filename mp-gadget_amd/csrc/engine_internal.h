@@ -7,6 +7,7 @@
 #include "sph.h"
 #include "veldisp.h"
 #include "cooling.h"
+#include "sfr.h"
 #include "metals.h"
 #include "winds.h"
 #include "heiii.h"
@@ -190,6 +191,9 @@ struct mpg_engine {
     HeiiiEngine heiii;
     DevBuf<double> he_density, he_entropy;
     DevBuf<uint8_t> he_flag;
+    // star formation (sfr.hip): parameters, the lists and counters of the last call; the staging of its host forms (fields of mpg_sfr_columns)
+    SfrEngine sfr;
+    DevBuf<char> sf_stage[std::size(SFR_FIELDS)];
     void prefetch_join()
     {
         if(prefetch_thread.joinable())

@@ -918,6 +918,28 @@ int mpg_cooling(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, co
     API_END
 }
 
+// cooling_and_starformation without the spawning for the listed particles of a host table (sfr_eff.c:224-286).  The columns are copied
+// back even when a row hit an iteration limit: that row's entries come back as they went up, all others are final.
+int mpg_cooling_and_starformation(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_sfr_columns *A, const mpg_sph_times *T,
+                                  const mpg_cooling_step *step, const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A && T && step, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    mpg_sfr_columns d{};
+    if(pv->n > 0)
+        stage_fields(SFR_FIELDS, *A, d, eng->sf_stage, pv->n, 0, "cooling_and_starformation", eng->stream);
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    const int rc = mpg_dev_cooling_and_starformation(eng, &d, T, step, d_act, NumActiveParticle);
+    const std::string err = rc ? mpg_last_error() : "";
+    if(pv->n > 0)
+        unstage_fields(SFR_FIELDS, *A, d, pv->n, 0, eng->stream);
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    MPG_CHECK(rc == 0, err);
+    API_END
+}
+
 // metal_return for the listed particles of a host table: Mass is the records' column (staged with the table, written back into it), the
 // other arrays go through stage_fields / unstage_fields (host_table.h)
 int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_metal_arrays *A, const int *ActiveParticle,

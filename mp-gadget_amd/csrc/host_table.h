@@ -471,6 +471,31 @@ constexpr ArrayField WD_FIELDS[] = {
 };
 static_assert(describes_every_member<mpg_wind_arrays>(WD_FIELDS), "WD_FIELDS follows mpg_wind_arrays");
 
+// cooling_and_starformation.  Density, Entropy, TimeBinHydro, Hsml, DivVel and CurlVel are resident columns on a resident gas run (the host
+// copies are stale inside a stretch); everything else travels.
+// (ARR_OPTIONAL where a criterion or the wind model decides: the call checks what it reads itself.)
+constexpr ArrayField SFR_FIELDS[] = {
+    MPG_ARRAY_FIELD(mpg_sfr_columns, id, 1, ARR_IN),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, generation, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, density, 1, ARR_IN | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, hsml, 1, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, divvel, 1, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, curlvel, 1, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, gradrho_mag, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, tb_hydro, 1, ARR_IN | ARR_OPTIONAL | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, heiii_ionized, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, vdisp, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, entropy, 1, ARR_IN | ARR_OUT | ARR_RES_ALIAS),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, ne, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, sfr, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, metallicity, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, delaytime, 1, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, bhheated, 1, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, vel, 3, ARR_IN | ARR_OUT | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_sfr_columns, stellarmass, 1, ARR_OUT | ARR_OPTIONAL),
+};
+static_assert(describes_every_member<mpg_sfr_columns>(SFR_FIELDS), "SFR_FIELDS follows mpg_sfr_columns");
+
 // Room for n particles of field F in its staging buffer and, when the host array `h` is given, its n entries on the way up (queued on
 // st): the device pointer.  (512 bytes of slack: 64 spare elements of the widest type, and never an empty allocation.)
 inline void *stage_field(const ArrayField &F, mpg::DevBuf<char> &buf, const void *h, int64_t n, hipStream_t st)

@@ -523,6 +523,37 @@ int mpg_resident_sph_cooling(mpg_engine *eng, const mpg_particle_view *pv, const
     API_END
 }
 
+// cooling_and_starformation without the spawning on a resident gas run: Density, Entropy, TimeBinHydro, Hsml, DivVel and CurlVel are the
+// resident columns, so
+// the new entropies are where the next density / hydro loop and the integrator read them; every other column travels (host_table.h).
+// The caller ends the stretch only when the new-star list is not empty.
+int mpg_resident_sph_cooling_and_starformation(mpg_engine *eng, const mpg_particle_view *pv, const mpg_sfr_columns *A, const mpg_sph_times *T,
+                                               const mpg_cooling_step *step, const int *ActiveParticle, int64_t NumActiveParticle)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && A && T && step, "null argument");
+    resident_sph_check(eng, pv);
+    const mpg_sph_arrays &r = eng->res_sph_dev;
+    MPG_CHECK(r.density && r.entropy, "resident cooling_and_starformation: the gas arrays have no Density / Entropy");
+    MPG_CHECK(!(eng->sfr.have_params && eng->sfr.par.WindOn && eng->have_windpar && (eng->windpar.WindModel & WIND_SUBGRID)),
+              "resident cooling_and_starformation: WindOn with WIND_SUBGRID is not carried on a resident gas run (the kicks change the resident Vel)");
+    mpg_sfr_columns d{};
+    stage_fields(SFR_FIELDS, *A, d, eng->sf_stage, pv->n, ARR_RES_ALIAS, "cooling_and_starformation", eng->stream);
+    d.density = r.density;
+    d.entropy = (double *)r.entropy;
+    d.tb_hydro = r.tb_hydro;
+    d.hsml = r.hsml; // (of the density loop of this stretch: the criteria read them)
+    d.divvel = r.divvel;
+    d.curlvel = r.curlvel;
+    const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
+    const int rc = mpg_dev_cooling_and_starformation(eng, &d, T, step, d_act, NumActiveParticle);
+    const std::string err = rc ? mpg_last_error() : "";
+    unstage_fields(SFR_FIELDS, *A, d, pv->n, ARR_RES_ALIAS, eng->stream);
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    MPG_CHECK(rc == 0, err);
+    API_END
+}
+
 // metal_return on a resident gas run, on the run's current tree (the one hydro_force has just used): Mass, Hsml and Density are resident
 // columns; the new masses also go into the records, which mpg_resident_end does not fetch.  The STARS' Hsml belongs to this call alone (no
 // SPH loop reads or writes it): when A->hsml is given, its rows of type 4 replace the resident column's before the call - the caller's

@@ -9,6 +9,32 @@ namespace mpg {
 constexpr int WIND_SUBGRID = 1, WIND_DECOUPLE_SPH = 2, WIND_USE_HALO = 4, WIND_FIXED_EFFICIENCY = 8, WIND_ISOTROPIC = 512; // enum WindModel, winds.h:13-20
 constexpr int WD_NSTATS = 6; // mpg_winds_get_stats
 
+#ifndef MPG_HD
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define MPG_HD __host__ __device__ inline
+#else
+#define MPG_HD inline
+#endif
+#endif
+// winds_evolve, winds.c:374-391, in two parts, for k_wind_evolve and for the star-formation loop (sfr.hip).  Is the particle still in the
+// wind once the density rule of :378-380 has been applied: only then is its time step read ...
+MPG_HD bool wind_still_delayed(const mpg_wind_params &P, double delaytime, double density, double a3inv)
+{
+    return delaytime > 0 && !(density * a3inv < P.WindFreeTravelDensThresh);
+}
+// ... and its new DelayTime (dtime = dloga / hubble of its hydro bin, read by a particle that is still delayed only)
+MPG_HD double wind_evolve_delay(const mpg_wind_params &P, double delaytime, double density, double a3inv, double dtime)
+{
+    if(delaytime > 0 && !wind_still_delayed(P, delaytime, density, a3inv))
+        return 0;
+    if(delaytime > 0) {
+        if(delaytime > P.MaxWindFreeTravelTime)
+            delaytime = P.MaxWindFreeTravelTime;
+        delaytime = delaytime - dtime > 0 ? delaytime - dtime : 0; // DMAX
+    }
+    return delaytime;
+}
+
 // device view of the caller's particle table and of mpg_wind_arrays (caller order, n entries each)
 struct WindView {
     const double *pos;

@@ -350,21 +350,17 @@ __global__ void __launch_bounds__(256) k_wind_evolve(const WindView A, const mpg
     if(!A.type || (A.type[i] & 7) != 0) // (no type column: all type 1, as everywhere)
         return;
     const double a3inv = 1 / (T.atime * T.atime * T.atime); // sfr_eff.c:211
-    const double before = A.a.delaytime[i];
-    double dt = before;
-    if(dt > 0 && A.a.density[i] * a3inv < P.WindFreeTravelDensThresh)
-        dt = 0;
-    if(dt > 0) {
-        if(dt > P.MaxWindFreeTravelTime)
-            dt = P.MaxWindFreeTravelTime;
+    const double before = A.a.delaytime[i], density = A.a.density[i];
+    double dtime = 0;
+    if(wind_still_delayed(P, before, density, a3inv)) {
         const int bin = A.a.tb_hydro[i];
         if(bin > 46) { // beyond TIMEBINS
             atomicAdd(ctr + CTR_BAD, 1u);
             return;
         }
-        const double dtime = T.dloga_bin[bin] / T.hubble;
-        dt = dt - dtime > 0 ? dt - dtime : 0; // DMAX
+        dtime = T.dloga_bin[bin] / T.hubble;
     }
+    const double dt = wind_evolve_delay(P, before, density, a3inv, dtime);
     if(before > 0)
         A.a.delaytime[i] = dt;
 }

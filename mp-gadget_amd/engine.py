@@ -194,6 +194,34 @@ RECOMB_CEN92, RECOMB_VERNER96, RECOMB_BADNELL06 = 0, 1, 2      # enum RecombType
 COOLING_KWH92, COOLING_ENZO2NYX, COOLING_SHERWOOD = 0, 1, 2    # enum CoolingType, cooling_rates.h:16-20
 
 
+SFR_COLUMN_FIELDS = ("id", "generation", "density", "hsml", "divvel", "curlvel", "gradrho_mag", "tb_hydro", "heiii_ionized", "vdisp", "entropy", "ne",
+                     "sfr", "metallicity", "delaytime", "bhheated", "vel", "stellarmass")
+SFR_COLUMN_DTYPES = dict(id="uint64", generation="uint8", tb_hydro="uint8", heiii_ionized="uint8", bhheated="uint8")
+# enum StarformationCriterion, sfr_eff.h:16-23
+SFR_CRITERION_DENSITY, SFR_CRITERION_MOLECULAR_H2, SFR_CRITERION_SELFGRAVITY, SFR_CRITERION_CONVERGENT_FLOW, SFR_CRITERION_CONTINUOUS_CUTOFF = 1, 3, 5, 13, 21
+
+
+class SfrColumnsC(C.Structure):
+    """mpg_sfr_columns"""
+    _fields_ = [(k, C.c_void_p) for k in SFR_COLUMN_FIELDS]
+
+
+class SfrParams(C.Structure):
+    """mpg_sfr_params: the members of struct SFRParams (sfr_eff.c:36-90) the loop reads, and the settings that are refused"""
+    _fields_ = [("StarformationCriterion", C.c_int), ("BoostSFDenseGas", C.c_int), ("BoostSFOverDenseFactor", C.c_double), ("FactorSN", C.c_double),
+                ("FactorEVP", C.c_double), ("MaxSfrTimescale", C.c_double), ("Generations", C.c_int), ("BHFeedbackUseTcool", C.c_int),
+                ("QuickLymanAlphaProbability", C.c_double), ("QuickLymanAlphaTempThresh", C.c_double), ("EgySpecSN", C.c_double),
+                ("EgySpecCold", C.c_double), ("PhysDensThresh", C.c_double), ("OverDensThresh", C.c_double), ("UnitSfr_in_solar_per_year", C.c_double),
+                ("avg_baryon_mass", C.c_double), ("tau_fmol_unit", C.c_double), ("GravInternal", C.c_double), ("WindOn", C.c_int),
+                ("UVFluctuationOn", C.c_int), ("ExcursionSetReion", C.c_int), ("NTask", C.c_int)]
+
+
+class SfrResult(C.Structure):
+    """mpg_sfr_result"""
+    _fields_ = [(k, C.c_int64) for k in ("treated", "cooled", "sum_sf_part", "newstars", "converted", "spawned", "maybewind", "errors")] + \
+               [(k, C.c_double) for k in ("sum_sm", "localsfr", "sum_dtime")]
+
+
 class HeiiiParams(C.Structure):
     """mpg_heiii_params: the members of struct qso_lightup_params (cooling_qso_lightup.c:53-71) that turn_on_quasars reads"""
     _fields_ = [(k, C.c_double) for k in ("qso_candidate_min_mass", "qso_candidate_max_mass", "mean_bubble", "var_bubble", "heIIIreion_finish_frac")]
@@ -1608,6 +1636,71 @@ class Engine:
         ev = np.zeros(n, np.int32)
         self._ck(self.lib.mpg_cooling_export(self.h, C.c_int64(n), ev.ctypes.data_as(C.c_void_p)))
         return ev
+
+    # ------------------------------------------------------------------ star formation (cooling_and_starformation, sfr_eff.c:186-394)
+    # `par` is a dict of the members of mpg_sfr_params (or an SfrParams); `columns` maps the field names of mpg_sfr_columns to device tensors
+    # (dev form) / contiguous numpy arrays (host forms) of the element types in SFR_COLUMN_DTYPES (float64 otherwise); `step` as for the
+    # cooling.  The random table is the one of set_random_table, the cooling and wind parameters those of their setters.
+    def set_sfr_params(self, par):
+        if not isinstance(par, SfrParams):
+            par = SfrParams(**par)
+        self._ck(self.lib.mpg_set_sfr_params(self.h, C.byref(par)))
+
+    def dev_cooling_and_starformation(self, columns, times, step, active=None, nactive=None):
+        """active: int32 device tensor of caller indices, or a raw device pointer (int) with `nactive` entries"""
+        a = _dev_arrays(SfrColumnsC, columns)
+        s = self.cooling_step(step)
+        nact = 0 if active is None else (int(nactive) if nactive is not None else active.shape[0])
+        self._ck(self.lib.mpg_dev_cooling_and_starformation(self.h, C.byref(a), C.byref(times), C.byref(s), _ptr(active), C.c_int64(nact)))
+
+    def cooling_and_starformation(self, P, BoxSize, columns, times, step, ActiveParticle=None):
+        v = self._view(P)
+        a = _host_arrays(SfrColumnsC, SFR_COLUMN_DTYPES, columns, "star formation", n=len(P))
+        s = self.cooling_step(step)
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_cooling_and_starformation(self.h, C.byref(v), C.c_double(BoxSize), C.byref(a), C.byref(times), C.byref(s), act,
+                                                        C.c_int64(nact)))
+
+    def resident_sph_cooling_and_starformation(self, P, columns, times, step, ActiveParticle=None):
+        """on a resident gas run: density, entropy, tb_hydro, hsml, divvel and curlvel are the resident columns (not read from `columns`), the
+        rest travels"""
+        v = self._view(P)
+        a = _host_arrays(SfrColumnsC, SFR_COLUMN_DTYPES, columns, "star formation", skip=("density", "entropy", "tb_hydro", "hsml", "divvel", "curlvel"), n=len(P))
+        s = self.cooling_step(step)
+        act, nact = _active(ActiveParticle)
+        self._ck(self.lib.mpg_resident_sph_cooling_and_starformation(self.h, C.byref(v), C.byref(a), C.byref(times), C.byref(s), act, C.c_int64(nact)))
+
+    def sfr_result(self):
+        r = SfrResult()
+        self._ck(self.lib.mpg_sfr_get_result(self.h, C.byref(r)))
+        return {k: getattr(r, k) for k, _ in SfrResult._fields_}
+
+    def sfr_export(self):
+        """the lists of the last call in the order of the active list: dict(parent, mass_of_star, spawn, maybewind)"""
+        r = self.sfr_result()
+        m, mw = r["newstars"], r["maybewind"]
+        parent, mass, spawn, wind = np.zeros(max(m, 1), np.int32), np.zeros(max(m, 1)), np.zeros(max(m, 1), np.uint8), np.zeros(max(mw, 1), np.int32)
+        nn, nw = C.c_int64(0), C.c_int64(0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.mpg_sfr_export(self.h, C.c_int64(m), p(parent), p(mass), p(spawn), C.byref(nn), C.c_int64(mw), p(wind), C.byref(nw)))
+        return dict(parent=parent[:m], mass_of_star=mass[:m], spawn=spawn[:m], maybewind=wind[:mw])
+
+    def sfr_dev_lists(self):
+        """raw device pointers of the lists of the last call (valid until the next): dict(parent, mass_of_star, spawn, maybewind)"""
+        ptr = [C.c_void_p() for _ in range(4)]
+        self._ck(self.lib.mpg_sfr_dev_lists(self.h, *[C.byref(x) for x in ptr]))
+        return dict(zip(("parent", "mass_of_star", "spawn", "maybewind"), (x.value for x in ptr)))
+
+    def sfr_export_rows(self, n):
+        """per particle of the last call: (class: 0 not treated, 1 cooled, 2 star-forming; network evaluations of a star-forming row, else -1)"""
+        cls, ev = np.zeros(n, np.uint8), np.zeros(n, np.int32)
+        self._ck(self.lib.mpg_sfr_export_rows(self.h, C.c_int64(n), cls.ctypes.data_as(C.c_void_p), ev.ctypes.data_as(C.c_void_p)))
+        return cls, ev
+
+    def sfr_stats(self):
+        c = (C.c_int64 * 8)()
+        self._ck(self.lib.mpg_sfr_get_stats(self.h, c))
+        return dict(listed=c[0], treated=c[1], cooled=c[2], starforming=c[3], evaluations=c[4], errors=c[5], newstars=c[6], maybewind=c[7])
 
     # ------------------------------------------------------------------ introspection
     def tree_stats(self):

@@ -9,7 +9,12 @@
  *     ... density, hydro_force, gravpm_force, force_tree_full, grav_short_tree, find_hydro_timesteps, apply_half_kick,
  *         apply_PM_half_kick of this step, drift_all_particles at the top of the next ...      (all on the device copies)
  *     mpg_shim_resident_end();                                   <- one fetch, before the next domain_maintain, a snapshot, FOF, or any
- *                                                                   host module that reads P[] / SphP[] (cooling, star formation)
+ *                                                                   host module that reads P[] / SphP[]
+ *   cooling_and_starformation needs no bracket: cooling-hip.c runs it on the resident columns and calls mpg_shim_resident_end() itself, in
+ *   the middle of the reference's function, in a step that has made a new star (or, with subgrid winds, a wind candidate).  That is why the
+ *   two host blocks of a stretch come from malloc and not from the reference's stack allocator, whose myfree accepts the LAST block only
+ *   (utils/memory.c: "Mismatched Free"): at that point the reference's and the shim's own mymalloc blocks lie above anything taken at
+ *   mpg_shim_resident_begin.  mpg_shim_resident_end itself allocates nothing from that allocator.
  *
  * - and compiles timestep.c and drift.c with the entry points below renamed (one line each in libgadget/Makefile, as for forcetree.o):
  *     timestep.o: CFLAGS += -Dapply_half_kick=cpu_apply_half_kick -Dapply_PM_half_kick=cpu_apply_PM_half_kick -Dfind_hydro_timesteps=cpu_find_hydro_timesteps
@@ -23,7 +28,7 @@
  *   - without SplitGravityTimestepsOn (run.c:553-565, 754-759): find_timesteps + apply_half_kick;
  *   - with it (the default, run.c:497-499, 536-540, 766-775): apply_hydro_half_kick, hierarchical_gravity_accelerations and
  *     hierarchical_gravity_and_timesteps, the level loop on the resident table (mpg_resident_hierarchical_*).  The StoredGravAccel of the step
- *     lives on the device between the two halves; if the stretch ends in between (cooling / star formation, FOF, a snapshot), the engine
+ *     lives on the device between the two halves; if the stretch ends in between (a step that makes a star, FOF, a snapshot), the engine
  *     writes it back into the caller's array and takes it up again in the second half.
  * Outside a resident stretch the definitions here call those cpu_ originals, so a run that never calls mpg_shim_resident_begin behaves as
  * before.  Inside one, the factors come from the reference's own get_exact_*_factor / dloga_from_dti (host arithmetic on the integer
@@ -37,6 +42,7 @@
 #include <mpi.h>
 #include <math.h>
 #include <string.h>
+#include <stdlib.h>
 #include "timestep.h"
 #include "drift.h"
 #include "timefac.h"
@@ -94,8 +100,11 @@ void mpg_shim_resident_begin(double BoxSize)
     mpg_particle_view v = view();
     ck(mpg_resident_begin(mpg_shim_engine(), &v, BoxSize));
     /* the slot fields, gathered once: what sph-hip.c gathers per call */
-    R.block = (double *)mymalloc("mpg_resident_sph", (size_t)n * 31 * sizeof(double));
-    R.tb = (uint8_t *)mymalloc("mpg_resident_tb", (size_t)n * 2);
+    /* (malloc, not mymalloc: mpg_shim_resident_end may run in the middle of a step, see the head of this file) */
+    R.block = (double *)malloc(((size_t)n * 31 + 1) * sizeof(double));
+    R.tb = (uint8_t *)malloc((size_t)n * 2 + 1);
+    if(!R.block || !R.tb)
+        endrun(5, "mpg_shim_resident_begin: no memory for the SPH columns of %ld particles\n", (long)n);
     double *q = R.block;
 #define COL(w) (q += (size_t)n * (w), q - (size_t)n * (w))
     memset(&R.A, 0, sizeof(R.A));
@@ -175,8 +184,10 @@ void mpg_shim_resident_end(void)
         for(k = 0; k < 3; k++)
             SPHP(i).HydroAccel[k] = R.A.hydroacc_out[3 * i + k];
     }
-    myfree(R.tb);
-    myfree(R.block);
+    free(R.tb);
+    free(R.block);
+    R.tb = NULL;
+    R.block = NULL;
     R.on = 0;
     mpg_shim_particles_changed(); /* (the host table is current again and may now be reordered) */
 }

@@ -112,7 +112,7 @@ void winds_and_feedback(int *NewStars, const int64_t NumNewStars, const double T
     if(winds_are_subgrid() || NumNewStars <= 0) /* winds.c:302-306 */
         return;
     if(mpg_shim_resident())
-        endrun(5, "winds_and_feedback(): inside a resident stretch (cooling-hip.c ends it before a star-forming step)\n");
+        endrun(5, "winds_and_feedback(): inside a resident stretch (cooling-hip.c ends it in a step that has made a star)\n");
     hand_over_parameters(rnd);
     mpg_wind_arrays A;
     uint64_t *id;

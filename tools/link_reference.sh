@@ -166,6 +166,21 @@ replace_once(T + "/libgadget/sfr_eff.c", "            else\n                cool
 replace_once(T + "/libgadget/sfr_eff.c", '    walltime_measure("/Cooling/Cooling");',
              '    { extern void mpg_shim_cooling_flush(double, double, const struct UVBG *); mpg_shim_cooling_flush(Time, hubble, &GlobalUVBG); }\n'
              '    walltime_measure("/Cooling/Cooling");')
+# ... and the loop of a star-forming run: a hook in front of it hands it to the device (cooling-hip.c: mpg_shim_sfr_loop), the reference's own
+# code behind it (winds_subgrid, the spawning of sfr_eff.c:288-393) runs on the lists the hook returns; an accessor for sfr_params
+replace_once(T + "/libgadget/sfr_eff.c", "    #pragma omp parallel reduction(+:localsfr) reduction(+: sum_sm) reduction(+:sum_dtime) reduction(+:sum_sf_part)",
+             "    { extern int mpg_shim_sfr_loop(ActiveParticles *, double, double, const struct UVBG *, MyFloat *, RandTable *, gadget_thread_arrays *,\n"
+             "                                   gadget_thread_arrays *, gadget_thread_arrays *, MyFloat *, double *, double *, double *, int64_t *);\n"
+             "    if(!mpg_shim_sfr_loop(act, Time, hubble, &GlobalUVBG, GradRho, rnd, &NewStarThread, &NewParentThread, &MaybeWindThread, StellarMass,\n"
+             "                          &sum_sm, &localsfr, &sum_dtime, &sum_sf_part)) {\n"
+             "    #pragma omp parallel reduction(+:localsfr) reduction(+: sum_sm) reduction(+:sum_dtime) reduction(+:sum_sf_part)")
+replace_once(T + "/libgadget/sfr_eff.c", '    report_memory_usage("SFR");', '    } }\n    report_memory_usage("SFR");')
+append(T + "/libgadget/sfr_eff.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_sfr_params(mpg_sfr_params *p)\n{\n    p->StarformationCriterion = (int)sfr_params.StarformationCriterion;\n"
+       + "".join("    p->%s = sfr_params.%s;\n" % (k, k) for k in (
+           "BoostSFDenseGas", "BoostSFOverDenseFactor", "FactorSN", "FactorEVP", "MaxSfrTimescale", "Generations", "BHFeedbackUseTcool",
+           "QuickLymanAlphaProbability", "QuickLymanAlphaTempThresh", "EgySpecSN", "EgySpecCold", "PhysDensThresh", "OverDensThresh",
+           "UnitSfr_in_solar_per_year", "avg_baryon_mass", "tau_fmol_unit", "WindOn"))
+       + "}")
 # the metal return (metals-hip.c): metal_yield is static and MetalParams file-static; a forwarding function and an accessor behind them
 append(T + "/libgadget/metal_return.c", "double mpg_shim_metal_yield(double dtmyrstart, double dtmyrend, double stellarmetal, struct MetalReturnPriv *priv, MyFloat *MetalYields, int tid, double masslow, double masshigh)\n"
        "{\n    return metal_yield(dtmyrstart, dtmyrend, stellarmetal, priv->hub, &priv->interp, MetalYields, priv->imf_norm, priv->gsl_work[tid], masslow, masshigh);\n}\n"
