@@ -1,4 +1,4 @@
-// engine_internal.h -- the engine object behind the C-ABI handle (include/mpgadget_hip.h), shared by engine.hip, host_forms.hip, resident.hip and dist.hip
+// engine_internal.h -- the engine object behind the C-ABI handle (include/mpgadget_hip.h), shared by engine.hip, integrator.hip, host_forms.hip, resident.hip and dist.hip
 #pragma once
 #include "../../include/mpgadget_hip.h"
 #include "grav_walk.h"
@@ -240,6 +240,23 @@ struct PlaneReduce {
     void (*max_host)(void *ctx, int64_t *v, int64_t count);
 };
 void planes_run(mpg_engine *eng, const mpg_plane_params *par, const uint8_t *d_flags, double *d_planes, int64_t *npart, const PlaneReduce *red);
+
+// the error word of a kernel, read back (synchronises the engine's stream)
+inline unsigned read_flag(mpg_engine *eng, unsigned *d)
+{
+    unsigned e = 0;
+    MPG_HIP(hipMemcpyAsync(&e, d, sizeof(e), hipMemcpyDeviceToHost, eng->stream));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    return e;
+}
+// ... and its round trip: the word zeroed, launch(word), read back; a kernel that raised it fails the call with `message`
+template <class Launch> inline void flagged_launch(mpg_engine *eng, const char *message, Launch &&launch)
+{
+    eng->ts_flag.reserve(4);
+    MPG_HIP(hipMemsetAsync(eng->ts_flag.p, 0, sizeof(unsigned), eng->stream));
+    launch(eng->ts_flag.p);
+    MPG_CHECK(read_flag(eng, eng->ts_flag.p) == 0, message);
+}
 
 #define API_BEGIN try {
 #define API_END_NORETURN             \

@@ -13,23 +13,27 @@ struct HierTimeline {
     int64_t ti0;
     double MinSizeTimestep;
 };
+// the scalars of one step that the step-assignment kernels share: the scale factor and Hubble rate, ErrTolIntAccuracy, the softening
+// (FORCE_SOFTENING), CourantFac, fac3 = pow(atime, 3 (1 - GAMMA) / 2), the timeline, the longest step allowed and the current time.  A
+// kernel reads the members its criteria need; the others may be left 0.
+struct StepScalars {
+    double atime, hubble, errtol, soft, courant, fac3;
+    HierTimeline T;
+    int64_t dti_max, Ti_Current;
+};
 void launch_timestep_hydro(int64_t n, const uint8_t *type, const double *hsml, const double *dthsml, const double *maxsig, const uint8_t *bh_mintimebin,
                            const double *dloga_for_bin, double atime, double hubble, double courant, double fac3, double *dloga, uint8_t *titype,
                            hipStream_t st);
 void launch_find_hydro_timesteps(const int *list, int64_t nlist, const uint8_t *type, const uint8_t *flags, const double *hsml, const double *dthsml,
                                  const double *maxsig, const uint8_t *bh_mintimebin, const double *dloga_for_bin, const uint8_t *tb_grav,
-                                 uint8_t *tb_hydro, double atime, double hubble, double courant, double fac3, const HierTimeline &T, int64_t dti_max,
-                                 int64_t Ti_Current, unsigned long long *out, hipStream_t st);
+                                 uint8_t *tb_hydro, const StepScalars &S, unsigned long long *out, hipStream_t st);
 void launch_find_timesteps(const int *list, int64_t nlist, const uint8_t *type, const uint8_t *flags, const double *gacc, const double *gpm,
                            const double *hsml, const double *dthsml, const double *maxsig, const uint8_t *bh_mintimebin, const double *dloga_for_bin,
-                           uint8_t *tb_grav, uint8_t *tb_hydro, double atime, double hubble, double errtol, double soft, double courant, double fac3,
-                           const HierTimeline &T, int64_t dti_max, int64_t Ti_Current, unsigned long long *out, hipStream_t st);
-void launch_assign_gravity_bins(const int *list, int64_t nlist, const double *gacc, const double *gpm, const uint8_t *flags, double atime,
-                                double hubble, double errtol, double soft, const HierTimeline &T, int64_t dti_max, int largest_active, uint8_t *tb,
-                                unsigned long long *counts, unsigned long long *bad, hipStream_t st);
-void launch_level_gravity_bins(const int *list, int64_t nlist, const double *gacc, const double *gpm, const uint8_t *flags, double atime, double hubble,
-                               double errtol, double soft, const HierTimeline &T, int64_t dti_max, int ti, uint8_t *tb, unsigned long long *bad,
-                               hipStream_t st);
+                           uint8_t *tb_grav, uint8_t *tb_hydro, const StepScalars &S, unsigned long long *out, hipStream_t st);
+void launch_assign_gravity_bins(const int *list, int64_t nlist, const double *gacc, const double *gpm, const uint8_t *flags, const StepScalars &S,
+                                int largest_active, uint8_t *tb, unsigned long long *counts, unsigned long long *bad, hipStream_t st);
+void launch_level_gravity_bins(const int *list, int64_t nlist, const double *gacc, const double *gpm, const uint8_t *flags, const StepScalars &S, int ti,
+                               uint8_t *tb, unsigned long long *bad, hipStream_t st);
 void launch_push_down_bins(const int *list, int64_t nlist, int push_down_bin, uint8_t *tb, hipStream_t st);
 void launch_kick_list(const int *list, int64_t nlist, double *vel, const double *acc, const uint8_t *flags, double gravkick, hipStream_t st);
 void launch_sublist_flags(const int *list, int64_t nlist, const uint8_t *tb, const uint8_t *flags, int maxtimebin, int64_t Ti_Current, int *value,
@@ -47,8 +51,7 @@ void launch_bh_subgrid_kick(int64_t n, const int *active, int64_t nactive, doubl
                             const double *dfaccel, const double *dragaccel, const mpg_kick_factors &K, unsigned *err, hipStream_t st);
 void launch_find_dynfric_timesteps(const int *list, int64_t nlist, const uint8_t *type, const uint8_t *flags, const double *vel, const double *df_vel,
                                    const double *hsml, const double *dthsml, const uint8_t *tb_grav, const uint8_t *tb_hydro, uint8_t *tb_dynfric,
-                                   double atime, double hubble, double errtol, double courant, const HierTimeline &T, int64_t dti_max,
-                                   int64_t Ti_Current, unsigned long long *out, hipStream_t st);
+                                   const StepScalars &S, unsigned long long *out, hipStream_t st);
 void launch_reposition_blackholes(int64_t n, double *pos, double *vel, const uint8_t *type, const uint8_t *flags, int *jump, const double *minpotpos,
                                   const double *minpotvel, double box, unsigned *err, hipStream_t st);
 void launch_timestep_gravity(int64_t n, const double *gacc, const double *gpm, double atime, double hubble, double errtol, double soft,

@@ -8,12 +8,16 @@
 //   k_hydro_half_kick  apply_hydro_half_kick + do_hydro_kick (gas part), no gravity kick        timestep.c:930-968, 1004-1036
 //   k_assign_gravity_bins, k_level_gravity_bins, k_push_down_bins, k_kick_list, k_sublist_flags
 //                    the per-particle loops of the hierarchical gravity level loop             timestep.c:239-599, 1435-1478
+//   k_find_hydro_timesteps, k_find_timesteps    the particle loops of the step assignment      timestep.c:629-698, 765-823
+//   k_timestep_gravity, k_timestep_hydro        the two criteria alone, as dloga per particle  timestep.c:1039-1118
 // The per-bin factors (get_exact_drift/gravkick/hydrokick_factor, dloga_from_dti) are computed by the caller with the
 // reference's own functions and passed in (mpg_kick_factors), as for the SPH loops.
 //   k_bh_subgrid_kick         the DFAccel / DragAccel kicks of type 5 in do_hydro_kick               timestep.c:1007-1013
 //   k_find_dynfric_timesteps  get_timestep_dynfric_dloga and the dynamic-friction bin                timestep.c:676-691, 1119-1145
 //   k_reposition_blackholes   the jump to the potential minimum in real_drift_particle               drift.c:31-53
 // are kernels of their own, called beside the loops above (k_half_kick and k_drift themselves leave type 5 to them).
+// The five step-assignment kernels take the step's scalars as one StepScalars (timestep.h) and share the conversion of a step to a bin
+// (round_down_power_of_two_dev, timestep_bin_dev, timebin_from_dti_dev).  The host side that drives all of this is integrator.hip.
 // Pure HBM streaming: per particle 73 B read + 32 B written (drift), 48 + 24 B (PM kick), up to 98 + 32 B (half kick), about 90 + 32 B
 // per gas particle (hydro half kick).
 // Floating-point contraction is off in this file: the reference's loops are compiled without FMA, and these results are
@@ -224,9 +228,9 @@ __device__ __forceinline__ int64_t convert_timestep_to_ti_dev(double dloga, cons
 
 // get_timestep_gravity_dloga, timestep.c:1045-1074
 __device__ __forceinline__ double gravity_dloga_dev(const int64_t i, const double *__restrict__ gacc, const double *__restrict__ gpm,
-                                                    const double atime, const double hubble, const double errtol, const double soft)
+                                                    const StepScalars &S)
 {
-    const double a2inv = 1 / (atime * atime);
+    const double a2inv = 1 / (S.atime * S.atime);
     double ax = a2inv * gacc[3 * i + 0];
     double ay = a2inv * gacc[3 * i + 1];
     double az = a2inv * gacc[3 * i + 2];
@@ -237,8 +241,8 @@ __device__ __forceinline__ double gravity_dloga_dev(const int64_t i, const doubl
     if(ac2 == 0)
         ac2 = 1.0e-60;
     const double ac = sqrt(ac2);
-    const double dt = sqrt(2 * errtol * atime * (soft / 2.8) / ac);
-    return dt * hubble;
+    const double dt = sqrt(2 * S.errtol * S.atime * (S.soft / 2.8) / ac);
+    return dt * S.hubble;
 }
 
 // get_timestep_hydro_dloga, timestep.c:1076-1118: the Courant criterion from the signal velocity and the Gadget-4 criterion on the change
@@ -294,47 +298,84 @@ __device__ __forceinline__ bool timebin_active_dev(const int bin, const int64_t 
     return bin <= 0 || Ti_Current <= 0 || (Ti_Current % dti) == 0; // ("bin 0 is always active and at time 0 all bins are active")
 }
 
+// round_down_power_of_two, timebinmgr.c:449-462 (dti >= 0 here)
+__device__ __forceinline__ int64_t round_down_power_of_two_dev(const int64_t dti)
+{
+    int64_t ti_min = (int64_t)1 << MPG_TIMEBINS;
+    while(ti_min > dti)
+        ti_min >>= 1;
+    return ti_min;
+}
+
+// get_timestep_bin, timestep.c:1301-1315 (dti a power of two, or 0)
+__device__ __forceinline__ int timestep_bin_dev(const int64_t dti) { return dti > 1 ? 63 - __clzll((unsigned long long)dti) : 0; }
+
+// get_timebin_from_dti, timestep.c:166-182: round_down_power_of_two, get_timestep_bin, and a longer step only onto an active bin
+__device__ __forceinline__ int timebin_from_dti_dev(const int64_t dti, const int binold, const int64_t Ti_Current)
+{
+    int bin = timestep_bin_dev(round_down_power_of_two_dev(dti));
+    if(bin > binold)
+        while(!timebin_active_dev(bin, Ti_Current) && bin > binold && bin > 1)
+            bin--;
+    return bin;
+}
+
+// print_bad_timebin's test (timestep.c:168-170)
+__device__ __forceinline__ bool bad_dti_dev(const int64_t dti) { return dti <= 1 || dti > ((int64_t)1 << MPG_TIMEBINS); }
+
+// The block's share of the counters of k_find_hydro_timesteps and k_find_timesteps, in shared memory: cnt[0..4] particles by criterion
+// (TI_ACCEL, TI_COURANT, TI_ACCRETE, TI_NEIGH, TI_HSML), cnt[5] badstepsizecount (bin < 1), cnt[6] print_bad_timebin cases, the smallest
+// and the largest bin.  block_counts_zero opens the kernel, block_counts_flush closes it: out[0..6] += cnt, out[7] by atomicMin
+// (initialised to TIMEBINS by the caller) and, with_max, out[8] by atomicMax (initialised to 0); a block without a particle adds nothing.
+struct BlockCounts {
+    unsigned cnt[8], minbin, maxbin;
+};
+__device__ __forceinline__ void block_counts_zero(BlockCounts &s)
+{
+    if(threadIdx.x < 8)
+        s.cnt[threadIdx.x] = 0;
+    if(threadIdx.x == 0) {
+        s.minbin = MPG_TIMEBINS + 1;
+        s.maxbin = 0;
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ void block_counts_flush(const BlockCounts &s, unsigned long long *__restrict__ out, const bool with_max)
+{
+    __syncthreads();
+    if(threadIdx.x < 7 && s.cnt[threadIdx.x])
+        atomicAdd(&out[threadIdx.x], (unsigned long long)s.cnt[threadIdx.x]);
+    if(threadIdx.x == 0 && s.minbin <= MPG_TIMEBINS) {
+        atomicMin(&out[7], (unsigned long long)s.minbin);
+        if(with_max)
+            atomicMax(&out[8], (unsigned long long)s.maxbin);
+    }
+}
+
 // The particle loop of find_hydro_timesteps (timestep.c:629-698) without the dynamic-friction bins of the black holes: the new hydro bin
-// of every active gas / black-hole particle.  out[0..4]: particles by criterion (TI_ACCEL, TI_COURANT, TI_ACCRETE, TI_NEIGH, TI_HSML),
-// out[5]: badstepsizecount (bin_hydro < 1), out[6]: print_bad_timebin cases (dti <= 1 or > TIMEBASE), out[7]: the smallest bin, by
-// atomicMin - initialised to TIMEBINS by the caller.
+// of every active gas / black-hole particle.  out: BlockCounts without the largest bin.
 __global__ void __launch_bounds__(256) k_find_hydro_timesteps(const int *__restrict__ list, int64_t nlist, const uint8_t *__restrict__ type,
                                                               const uint8_t *__restrict__ flags, const double *__restrict__ hsml,
                                                               const double *__restrict__ dthsml, const double *__restrict__ maxsig,
                                                               const uint8_t *__restrict__ bh_mintimebin, const double *__restrict__ dloga_for_bin,
-                                                              const uint8_t *__restrict__ tb_grav, uint8_t *__restrict__ tb_hydro, double atime,
-                                                              double hubble, double courant, double fac3, HierTimeline T, int64_t dti_max,
-                                                              int64_t Ti_Current, unsigned long long *__restrict__ out)
+                                                              const uint8_t *__restrict__ tb_grav, uint8_t *__restrict__ tb_hydro, const StepScalars S,
+                                                              unsigned long long *__restrict__ out)
 {
-    __shared__ unsigned s_cnt[8];
-    __shared__ unsigned s_min;
-    if(threadIdx.x < 8)
-        s_cnt[threadIdx.x] = 0;
-    if(threadIdx.x == 0)
-        s_min = MPG_TIMEBINS + 1;
-    __syncthreads();
+    __shared__ BlockCounts s;
+    block_counts_zero(s);
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(k < nlist) {
         const int64_t i = list ? list[k] : k;
         const int ty = type ? (type[i] & 7) : 1;
         if(!(flags && (flags[i] & 3)) && (ty == 0 || ty == 5)) {
             int titype;
-            const double dloga = hydro_dloga_dev(i, type, hsml, dthsml, maxsig, bh_mintimebin, dloga_for_bin, atime, hubble, courant, fac3, titype);
-            int64_t dti = convert_timestep_to_ti_dev(dloga, dti_max, T);
-            if(dti <= 1 || dti > ((int64_t)1 << MPG_TIMEBINS))
-                atomicAdd(&s_cnt[6], 1u);
-            // get_timebin_from_dti, timestep.c:166-182: round_down_power_of_two, get_timestep_bin, and a longer step only onto an active bin
-            int64_t ti_min = (int64_t)1 << MPG_TIMEBINS;
-            while(ti_min > dti)
-                ti_min >>= 1;
-            dti = ti_min;
-            int bin = 0;
-            if(dti > 1)
-                bin = 63 - __clzll((unsigned long long)dti);
+            const double dloga =
+                hydro_dloga_dev(i, type, hsml, dthsml, maxsig, bh_mintimebin, dloga_for_bin, S.atime, S.hubble, S.courant, S.fac3, titype);
+            const int64_t dti = convert_timestep_to_ti_dev(dloga, S.dti_max, S.T);
+            if(bad_dti_dev(dti))
+                atomicAdd(&s.cnt[6], 1u);
             const int binold = tb_hydro[i];
-            if(bin > binold)
-                while(!timebin_active_dev(bin, Ti_Current) && bin > binold && bin > 1)
-                    bin--;
+            int bin = timebin_from_dti_dev(dti, binold, S.Ti_Current);
             // the hydro step never exceeds the gravity step (timestep.c:651-655)
             const int bg = tb_grav ? tb_grav[i] : MPG_TIMEBINS;
             if(bin > bg) {
@@ -342,98 +383,62 @@ __global__ void __launch_bounds__(256) k_find_hydro_timesteps(const int *__restr
                 titype = 0;
             }
             if(bin < 1)
-                atomicAdd(&s_cnt[5], 1u);
-            atomicAdd(&s_cnt[titype], 1u);
-            if(timebin_active_dev(binold, Ti_Current) && timebin_active_dev(bin, Ti_Current))
+                atomicAdd(&s.cnt[5], 1u);
+            atomicAdd(&s.cnt[titype], 1u);
+            if(timebin_active_dev(binold, S.Ti_Current) && timebin_active_dev(bin, S.Ti_Current))
                 tb_hydro[i] = (uint8_t)bin;
-            atomicMin(&s_min, (unsigned)bin);
+            atomicMin(&s.minbin, (unsigned)bin);
         }
     }
-    __syncthreads();
-    if(threadIdx.x < 7 && s_cnt[threadIdx.x])
-        atomicAdd(&out[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
-    if(threadIdx.x == 0 && s_min <= MPG_TIMEBINS)
-        atomicMin(&out[7], (unsigned long long)s_min);
-}
-
-// get_timebin_from_dti, timestep.c:166-182: round_down_power_of_two, get_timestep_bin, and a longer step only onto an active bin
-__device__ __forceinline__ int timebin_from_dti_dev(int64_t dti, const int binold, const int64_t Ti_Current)
-{
-    int64_t ti_min = (int64_t)1 << MPG_TIMEBINS;
-    while(ti_min > dti)
-        ti_min >>= 1;
-    dti = ti_min;
-    int bin = 0;
-    if(dti > 1)
-        bin = 63 - __clzll((unsigned long long)dti);
-    if(bin > binold)
-        while(!timebin_active_dev(bin, Ti_Current) && bin > binold && bin > 1)
-            bin--;
-    return bin;
+    block_counts_flush(s, out, false);
 }
 
 // The particle loop of find_timesteps (timestep.c:765-823; the step assignment of a run WITHOUT SplitGravityTimestepsOn, run.c:756): per
 // active particle the gravity step from FullTreeGravAccel + GravPM, for gas / black holes the hydro step where it is shorter, both bins set
 // to the new bin when old and new bin are active.  Not carried: ForceEqualTimesteps (the caller refuses it).
-// out[0..4]: particles by criterion, out[5]: badstepsizecount (bin < 1), out[6]: print_bad_timebin cases, out[7]: smallest bin (atomicMin,
-// initialised to TIMEBINS), out[8]: largest bin (atomicMax, initialised to 0).
+// out: BlockCounts with the largest bin.
 __global__ void __launch_bounds__(256) k_find_timesteps(const int *__restrict__ list, int64_t nlist, const uint8_t *__restrict__ type,
                                                         const uint8_t *__restrict__ flags, const double *__restrict__ gacc, const double *__restrict__ gpm,
                                                         const double *__restrict__ hsml, const double *__restrict__ dthsml,
                                                         const double *__restrict__ maxsig, const uint8_t *__restrict__ bh_mintimebin,
                                                         const double *__restrict__ dloga_for_bin, uint8_t *__restrict__ tb_grav,
-                                                        uint8_t *__restrict__ tb_hydro, double atime, double hubble, double errtol, double soft,
-                                                        double courant, double fac3, HierTimeline T, int64_t dti_max, int64_t Ti_Current,
-                                                        unsigned long long *__restrict__ out)
+                                                        uint8_t *__restrict__ tb_hydro, const StepScalars S, unsigned long long *__restrict__ out)
 {
-    __shared__ unsigned s_cnt[8];
-    __shared__ unsigned s_min, s_max;
-    if(threadIdx.x < 8)
-        s_cnt[threadIdx.x] = 0;
-    if(threadIdx.x == 0) {
-        s_min = MPG_TIMEBINS + 1;
-        s_max = 0;
-    }
-    __syncthreads();
+    __shared__ BlockCounts s;
+    block_counts_zero(s);
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(k < nlist) {
         const int64_t i = list ? list[k] : k;
         if(!(flags && (flags[i] & 3))) {
             const int ty = type ? (type[i] & 7) : 1;
             int titype = 0;
-            const double dloga_gravity = gravity_dloga_dev(i, gacc, gpm, atime, hubble, errtol, soft);
-            int64_t dti = convert_timestep_to_ti_dev(dloga_gravity, dti_max, T);
+            int64_t dti = convert_timestep_to_ti_dev(gravity_dloga_dev(i, gacc, gpm, S), S.dti_max, S.T);
             if(ty == 0 || ty == 5) { // the hydro step: "always shorter"
                 int th;
-                const double dloga_hydro = hydro_dloga_dev(i, type, hsml, dthsml, maxsig, bh_mintimebin, dloga_for_bin, atime, hubble, courant, fac3, th);
-                const int64_t dti_hydro = convert_timestep_to_ti_dev(dloga_hydro, dti_max, T);
+                const double dloga_hydro =
+                    hydro_dloga_dev(i, type, hsml, dthsml, maxsig, bh_mintimebin, dloga_for_bin, S.atime, S.hubble, S.courant, S.fac3, th);
+                const int64_t dti_hydro = convert_timestep_to_ti_dev(dloga_hydro, S.dti_max, S.T);
                 if(dti_hydro < dti) {
                     dti = dti_hydro;
                     titype = th;
                 }
             }
-            if(dti <= 1 || dti > ((int64_t)1 << MPG_TIMEBINS))
-                atomicAdd(&s_cnt[6], 1u);
-            atomicAdd(&s_cnt[titype], 1u);
+            if(bad_dti_dev(dti))
+                atomicAdd(&s.cnt[6], 1u);
+            atomicAdd(&s.cnt[titype], 1u);
             const int binold = tb_hydro[i];
-            const int bin = timebin_from_dti_dev(dti, binold, Ti_Current);
+            const int bin = timebin_from_dti_dev(dti, binold, S.Ti_Current);
             if(bin < 1)
-                atomicAdd(&s_cnt[5], 1u);
-            if(timebin_active_dev(binold, Ti_Current) && timebin_active_dev(bin, Ti_Current)) {
+                atomicAdd(&s.cnt[5], 1u);
+            if(timebin_active_dev(binold, S.Ti_Current) && timebin_active_dev(bin, S.Ti_Current)) {
                 tb_hydro[i] = (uint8_t)bin;
                 tb_grav[i] = (uint8_t)bin;
             }
-            atomicMin(&s_min, (unsigned)bin);
-            atomicMax(&s_max, (unsigned)bin);
+            atomicMin(&s.minbin, (unsigned)bin);
+            atomicMax(&s.maxbin, (unsigned)bin);
         }
     }
-    __syncthreads();
-    if(threadIdx.x < 7 && s_cnt[threadIdx.x])
-        atomicAdd(&out[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
-    if(threadIdx.x == 0 && s_min <= MPG_TIMEBINS) {
-        atomicMin(&out[7], (unsigned long long)s_min);
-        atomicMax(&out[8], (unsigned long long)s_max);
-    }
+    block_counts_flush(s, out, true);
 }
 
 // The kicks of do_hydro_kick for black holes (timestep.c:1007-1013): Vel += DFAccel * Fgravkick, then Vel += DragAccel * Fgravkick - two
@@ -472,9 +477,8 @@ __global__ void __launch_bounds__(256) k_find_dynfric_timesteps(const int *__res
                                                                 const uint8_t *__restrict__ flags, const double *__restrict__ vel,
                                                                 const double *__restrict__ df_vel, const double *__restrict__ hsml,
                                                                 const double *__restrict__ dthsml, const uint8_t *__restrict__ tb_grav,
-                                                                const uint8_t *__restrict__ tb_hydro, uint8_t *__restrict__ tb_dynfric, double atime,
-                                                                double hubble, double errtol, double courant, HierTimeline T, int64_t dti_max,
-                                                                int64_t Ti_Current, unsigned long long *__restrict__ out)
+                                                                const uint8_t *__restrict__ tb_hydro, uint8_t *__restrict__ tb_dynfric,
+                                                                const StepScalars S, unsigned long long *__restrict__ out)
 {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(k >= nlist)
@@ -492,13 +496,13 @@ __global__ void __launch_bounds__(256) k_find_dynfric_timesteps(const int *__res
     if(bhvel2 > bhvel)
         bhvel = bhvel2;
     bhvel = sqrt(bhvel);
-    double dt = 2 * errtol * atime * atime * hsml[i] / (bhvel + 1e-20);
-    const double dt_hsml = courant * atime * atime * fabs(hsml[i] / ((dthsml ? dthsml[i] : 0.0) + 1e-20));
+    double dt = 2 * S.errtol * S.atime * S.atime * hsml[i] / (bhvel + 1e-20);
+    const double dt_hsml = S.courant * S.atime * S.atime * fabs(hsml[i] / ((dthsml ? dthsml[i] : 0.0) + 1e-20));
     if(dt_hsml < dt)
         dt = dt_hsml;
-    const double dloga = dt * hubble;
-    const int64_t dti = convert_timestep_to_ti_dev(dloga, dti_max, T);
-    int bin = timebin_from_dti_dev(dti, tb_dynfric[i], Ti_Current);
+    const double dloga = dt * S.hubble;
+    const int64_t dti = convert_timestep_to_ti_dev(dloga, S.dti_max, S.T);
+    int bin = timebin_from_dti_dev(dti, tb_dynfric[i], S.Ti_Current);
     const int bg = tb_grav ? tb_grav[i] : MPG_TIMEBINS, bh = tb_hydro[i];
     if(bin > bg)
         bin = bg;
@@ -549,10 +553,10 @@ __global__ void __launch_bounds__(256) k_reposition_blackholes(int64_t n, double
 }
 
 // The first loop of hierarchical_gravity_and_timesteps (timestep.c:345-370): new gravity bin of every particle of the list from
-// the stored acceleration; counts[bin] += 1; bad += 1 for dti <= 1 or > TIMEBASE (print_bad_timebin).
+// the stored acceleration; counts[bin] += 1; bad += 1 for dti <= 1 or > TIMEBASE (print_bad_timebin), tested here AFTER the rounding
+// (the find_* kernels test before it); the bin is clamped to largest_active and bin activity is not looked at.
 __global__ void __launch_bounds__(256) k_assign_gravity_bins(const int *__restrict__ list, int64_t nlist, const double *__restrict__ gacc,
-                                                             const double *__restrict__ gpm, const uint8_t *__restrict__ flags, double atime,
-                                                             double hubble, double errtol, double soft, HierTimeline T, int64_t dti_max,
+                                                             const double *__restrict__ gpm, const uint8_t *__restrict__ flags, const StepScalars S,
                                                              int largest_active, uint8_t *__restrict__ tb,
                                                              unsigned long long *__restrict__ counts, unsigned long long *__restrict__ bad)
 {
@@ -564,19 +568,10 @@ __global__ void __launch_bounds__(256) k_assign_gravity_bins(const int *__restri
     if(k < nlist) {
         const int64_t pa = list ? list[k] : k;
         if(!(flags && (flags[pa] & 3))) {
-            const double dloga = gravity_dloga_dev(pa, gacc, gpm, atime, hubble, errtol, soft);
-            int64_t dti = convert_timestep_to_ti_dev(dloga, dti_max, T);
-            // round_down_power_of_two, timebinmgr.c:449-462 (dti >= 0 here)
-            int64_t ti_min = (int64_t)1 << MPG_TIMEBINS;
-            while(ti_min > dti)
-                ti_min >>= 1;
-            dti = ti_min;
-            if(dti <= 1 || dti > ((int64_t)1 << MPG_TIMEBINS))
+            const int64_t dti = round_down_power_of_two_dev(convert_timestep_to_ti_dev(gravity_dloga_dev(pa, gacc, gpm, S), S.dti_max, S.T));
+            if(bad_dti_dev(dti))
                 atomicAdd(&s_cnt[MPG_TIMEBINS + 1], 1u);
-            // get_timestep_bin, timestep.c:1301-1315
-            int bin = 0;
-            if(dti > 1)
-                bin = 63 - __clzll((unsigned long long)dti);
+            int bin = timestep_bin_dev(dti);
             if(bin > largest_active)
                 bin = largest_active;
             atomicAdd(&s_cnt[bin], 1u);
@@ -596,9 +591,8 @@ __global__ void __launch_bounds__(256) k_assign_gravity_bins(const int *__restri
 // The loop of the lower levels (timestep.c:461-477): a particle whose step from the acceleration AT THIS LEVEL is shorter than
 // the level's goes one bin down; bad += 1 if that happens at ti == 1.
 __global__ void __launch_bounds__(256) k_level_gravity_bins(const int *__restrict__ list, int64_t nlist, const double *__restrict__ gacc,
-                                                            const double *__restrict__ gpm, const uint8_t *__restrict__ flags, double atime,
-                                                            double hubble, double errtol, double soft, HierTimeline T, int64_t dti_max, int ti,
-                                                            uint8_t *__restrict__ tb, unsigned long long *__restrict__ bad)
+                                                            const double *__restrict__ gpm, const uint8_t *__restrict__ flags, const StepScalars S,
+                                                            int ti, uint8_t *__restrict__ tb, unsigned long long *__restrict__ bad)
 {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if(k >= nlist)
@@ -606,8 +600,7 @@ __global__ void __launch_bounds__(256) k_level_gravity_bins(const int *__restric
     const int64_t pa = list ? list[k] : k;
     if(flags && (flags[pa] & 3))
         return;
-    const double dloga = gravity_dloga_dev(pa, gacc, gpm, atime, hubble, errtol, soft);
-    const int64_t dti = convert_timestep_to_ti_dev(dloga, dti_max, T);
+    const int64_t dti = convert_timestep_to_ti_dev(gravity_dloga_dev(pa, gacc, gpm, S), S.dti_max, S.T);
     const int64_t dti_bin = ti > 0 ? ((int64_t)1 << ti) : 0; // dti_from_timebin
     if(dti < dti_bin) {
         tb[pa] = (uint8_t)(ti - 1);
@@ -669,12 +662,11 @@ void launch_bh_subgrid_kick(int64_t n, const int *active, int64_t nactive, doubl
 
 void launch_find_dynfric_timesteps(const int *list, int64_t nlist, const uint8_t *type, const uint8_t *flags, const double *vel, const double *df_vel,
                                    const double *hsml, const double *dthsml, const uint8_t *tb_grav, const uint8_t *tb_hydro, uint8_t *tb_dynfric,
-                                   double atime, double hubble, double errtol, double courant, const HierTimeline &T, int64_t dti_max,
-                                   int64_t Ti_Current, unsigned long long *out, hipStream_t st)
+                                   const StepScalars &S, unsigned long long *out, hipStream_t st)
 {
     if(nlist > 0)
         hipLaunchKernelGGL(k_find_dynfric_timesteps, dim3(nblk(nlist)), dim3(256), 0, st, list, nlist, type, flags, vel, df_vel, hsml, dthsml, tb_grav,
-                           tb_hydro, tb_dynfric, atime, hubble, errtol, courant, T, dti_max, Ti_Current, out);
+                           tb_hydro, tb_dynfric, S, out);
     MPG_HIP(hipGetLastError());
 }
 
@@ -707,43 +699,37 @@ void launch_timestep_hydro(int64_t n, const uint8_t *type, const double *hsml, c
 
 void launch_find_hydro_timesteps(const int *list, int64_t nlist, const uint8_t *type, const uint8_t *flags, const double *hsml, const double *dthsml,
                                  const double *maxsig, const uint8_t *bh_mintimebin, const double *dloga_for_bin, const uint8_t *tb_grav,
-                                 uint8_t *tb_hydro, double atime, double hubble, double courant, double fac3, const HierTimeline &T, int64_t dti_max,
-                                 int64_t Ti_Current, unsigned long long *out, hipStream_t st)
+                                 uint8_t *tb_hydro, const StepScalars &S, unsigned long long *out, hipStream_t st)
 {
     if(nlist > 0)
         hipLaunchKernelGGL(k_find_hydro_timesteps, dim3(nblk(nlist)), dim3(256), 0, st, list, nlist, type, flags, hsml, dthsml, maxsig, bh_mintimebin,
-                           dloga_for_bin, tb_grav, tb_hydro, atime, hubble, courant, fac3, T, dti_max, Ti_Current, out);
+                           dloga_for_bin, tb_grav, tb_hydro, S, out);
     MPG_HIP(hipGetLastError());
 }
 
 void launch_find_timesteps(const int *list, int64_t nlist, const uint8_t *type, const uint8_t *flags, const double *gacc, const double *gpm,
                            const double *hsml, const double *dthsml, const double *maxsig, const uint8_t *bh_mintimebin, const double *dloga_for_bin,
-                           uint8_t *tb_grav, uint8_t *tb_hydro, double atime, double hubble, double errtol, double soft, double courant, double fac3,
-                           const HierTimeline &T, int64_t dti_max, int64_t Ti_Current, unsigned long long *out, hipStream_t st)
+                           uint8_t *tb_grav, uint8_t *tb_hydro, const StepScalars &S, unsigned long long *out, hipStream_t st)
 {
     if(nlist > 0)
         hipLaunchKernelGGL(k_find_timesteps, dim3(nblk(nlist)), dim3(256), 0, st, list, nlist, type, flags, gacc, gpm, hsml, dthsml, maxsig, bh_mintimebin,
-                           dloga_for_bin, tb_grav, tb_hydro, atime, hubble, errtol, soft, courant, fac3, T, dti_max, Ti_Current, out);
+                           dloga_for_bin, tb_grav, tb_hydro, S, out);
     MPG_HIP(hipGetLastError());
 }
 
-void launch_assign_gravity_bins(const int *list, int64_t nlist, const double *gacc, const double *gpm, const uint8_t *flags, double atime,
-                                double hubble, double errtol, double soft, const HierTimeline &T, int64_t dti_max, int largest_active, uint8_t *tb,
-                                unsigned long long *counts, unsigned long long *bad, hipStream_t st)
+void launch_assign_gravity_bins(const int *list, int64_t nlist, const double *gacc, const double *gpm, const uint8_t *flags, const StepScalars &S,
+                                int largest_active, uint8_t *tb, unsigned long long *counts, unsigned long long *bad, hipStream_t st)
 {
     if(nlist > 0)
-        hipLaunchKernelGGL(k_assign_gravity_bins, dim3(nblk(nlist)), dim3(256), 0, st, list, nlist, gacc, gpm, flags, atime, hubble, errtol, soft, T,
-                           dti_max, largest_active, tb, counts, bad);
+        hipLaunchKernelGGL(k_assign_gravity_bins, dim3(nblk(nlist)), dim3(256), 0, st, list, nlist, gacc, gpm, flags, S, largest_active, tb, counts, bad);
     MPG_HIP(hipGetLastError());
 }
 
-void launch_level_gravity_bins(const int *list, int64_t nlist, const double *gacc, const double *gpm, const uint8_t *flags, double atime, double hubble,
-                               double errtol, double soft, const HierTimeline &T, int64_t dti_max, int ti, uint8_t *tb, unsigned long long *bad,
-                               hipStream_t st)
+void launch_level_gravity_bins(const int *list, int64_t nlist, const double *gacc, const double *gpm, const uint8_t *flags, const StepScalars &S, int ti,
+                               uint8_t *tb, unsigned long long *bad, hipStream_t st)
 {
     if(nlist > 0)
-        hipLaunchKernelGGL(k_level_gravity_bins, dim3(nblk(nlist)), dim3(256), 0, st, list, nlist, gacc, gpm, flags, atime, hubble, errtol, soft, T,
-                           dti_max, ti, tb, bad);
+        hipLaunchKernelGGL(k_level_gravity_bins, dim3(nblk(nlist)), dim3(256), 0, st, list, nlist, gacc, gpm, flags, S, ti, tb, bad);
     MPG_HIP(hipGetLastError());
 }
 

@@ -288,6 +288,97 @@ def test_find_timesteps_bins(pkg, engine, orc):
     assert {0, 1, 3, 4} <= seen          # gravity, Courant, the black holes' neighbour limiter and the smoothing-length criterion all decided bins
 
 
+@pytest.mark.parametrize("nlist", [1, 255, 256, 257])
+def test_step_assignment_at_the_block_edge(pkg, engine, orc, nlist):
+    """the three step-assignment kernels on active lists that end one short of, at and one past the first block of 256 threads (and on a list
+    of one), drawn from 300 particles with the mix of case 1 of test_hydro_timestep_criterion_and_bins: the block's shared counters are
+    zeroed and flushed by a block that is partly (or barely) filled, and the bin comes from the shared conversion in the last lanes.  Bins,
+    result dicts and mintimebin / maxtimebin of dev_find_hydro_timesteps and dev_find_timesteps EQUAL the restatement
+    (oracle/hiergrav_oracle.py); dev_find_dynfric_timesteps as in test_gpu_dynfric.py: bins and figures EQUAL tests/dynfric_restated.py, no
+    step within 1e-9 of a bin boundary.  (No list of length 0: a null list means every particle in this interface.)"""
+    import torch
+    from oracle import hiergrav_oracle as H
+    import dynfric_restated as R
+    from test_gpu_hiergrav import to_struct, from_struct
+    rng = np.random.RandomState(11)
+    n = 300
+    typ = rng.choice([0, 0, 0, 1, 1, 4, 5], n).astype(np.uint8)
+    flags = ((rng.random_sample(n) < 0.03) * rng.randint(1, 4, n)).astype(np.uint8)
+    hsml = 10 ** rng.uniform(-1.5, 1.0, n)
+    dthsml = rng.standard_normal(n) * 10 ** rng.uniform(-3, 1, n)
+    dthsml[rng.random_sample(n) < 0.1] = 0.0
+    maxsig = 10 ** rng.uniform(0.5, 3.5, n)
+    bhmin = rng.randint(0, 12, n).astype(np.uint8)
+    gacc = rng.standard_normal((n, 3)) * 10 ** rng.uniform(-2, 4, (n, 1))
+    gpm = rng.standard_normal((n, 3)) * 1e-1
+    vel = rng.standard_normal((n, 3)) * 10 ** rng.uniform(-2, 2, (n, 1))
+    df_vel = rng.standard_normal((n, 3)) * (typ == 5)[:, None]
+    tbg = rng.randint(30, 42, n).astype(np.uint8)
+    tbh = np.minimum(rng.randint(28, 42, n), tbg).astype(np.uint8)
+    tbd = rng.randint(26, 40, n).astype(np.uint8)
+    atime, hubble, courant, errtol = 0.37, 0.21, 0.15, 0.025
+    sync = np.log(np.array([0.1, 0.25, 0.5, 1.0]))
+    tl = H.Timeline(sync)
+    Ti_cur = (1 << H.TIMEBINS) + (5 << 33)
+    live = (flags & 3) == 0
+
+    def active_list(must):                      # nlist distinct particles with `must` among them (a list of one still has a particle to count)
+        rest = rng.choice(np.setdiff1d(np.arange(n), [must]), nlist - 1, replace=False)
+        return np.sort(np.append(rest, must)).astype(np.int32)
+
+    act = active_list(np.nonzero(live & (typ == 0))[0][0])
+    act_bh = active_list(np.nonzero(live & (typ == 5))[0][0])
+    engine.set_gravshort_treepar()
+    engine.gravshort_set_softenings(0.5)
+    soft = 2.8 * 0.5 / 30.
+    engine.dev_bind_particles(torch.zeros(n, 3, dtype=torch.float64, device="cuda") + 0.5, torch.ones(n, dtype=torch.float32, device="cuda"), 1.0)
+    d = {k: dev(torch, v) for k, v in dict(type=typ, flags=flags, hsml=hsml, dthsml=dthsml, maxsignalvel=maxsig, bh_mintimebin=bhmin).items()}
+    # ---- find_hydro_timesteps: the times of that test's case 1
+    times = dict(mintimebin=30, maxtimebin=41, mingravtimebin=31, Ti_Current=Ti_cur, PM_length=1 << 41, PM_start=Ti_cur - (1 << 41), PM_kick=0,
+                 Ti_kick=[0] * (H.TIMEBINS + 1))
+    S = dict(type=typ, flags=flags, hsml=hsml, dthsml=dthsml, maxsignalvel=maxsig, tb_grav=tbg, tb_hydro=tbh.copy(), bh_mintimebin=bhmin)
+    t_o = dict(times, Ti_kick=list(times["Ti_kick"]))
+    ro = H.find_hydro_timesteps(S, act, t_o, tl, 1e-7, courant, atime, hubble)
+    d_tbh = dev(torch, tbh)
+    ts = to_struct(pkg, times)
+    rg = engine.dev_find_hydro_timesteps(dict(d, tb_grav=dev(torch, tbg), tb_hydro=d_tbh), dev(torch, act), ts, sync, 1e-7, courant, atime, hubble)
+    engine.synchronize()
+    t_g = dict(times)
+    from_struct(ts, t_g)
+    assert np.array_equal(d_tbh.cpu().numpy(), S["tb_hydro"])
+    assert rg == ro and sum(rg["ntitype"]) >= 1, (rg, ro)
+    assert t_g["mintimebin"] == t_o["mintimebin"] and t_g["maxtimebin"] == t_o["maxtimebin"]
+    # ---- find_timesteps, inside a PM step (the times of case 1 of test_find_timesteps_bins)
+    times = dict(times, PM_start=Ti_cur - (5 << 33), PM_kick=Ti_cur - (5 << 33))
+    S = dict(type=typ, flags=flags, gacc=gacc, gravpm=gpm, hsml=hsml, dthsml=dthsml, maxsignalvel=maxsig, tb_grav=tbg.copy(), tb_hydro=tbh.copy(),
+             bh_mintimebin=bhmin)
+    t_o = dict(times, Ti_kick=list(times["Ti_kick"]))
+    ro = H.find_timesteps(orc, S, act, t_o, tl, errtol, 1e-7, courant, atime, hubble, soft, dti_max_pm=1 << 43)
+    d_tbg, d_tbh = dev(torch, tbg), dev(torch, tbh)
+    ts = to_struct(pkg, times)
+    rg = engine.dev_find_timesteps(dict(d, tb_grav=d_tbg, tb_hydro=d_tbh), dev(torch, gacc), dev(torch, gpm), dev(torch, act), ts, sync, errtol, 1e-7,
+                                   courant, atime, hubble, dti_max_pm=1 << 43)
+    engine.synchronize()
+    t_g = dict(times)
+    from_struct(ts, t_g)
+    assert np.array_equal(d_tbh.cpu().numpy(), S["tb_hydro"]) and np.array_equal(d_tbg.cpu().numpy(), S["tb_grav"])
+    assert rg == ro and sum(rg["ntitype"]) >= 1, (rg, ro)
+    for k in ("mintimebin", "maxtimebin", "PM_length", "PM_start"):
+        assert t_g[k] == t_o[k], (k, t_g[k], t_o[k])
+    # ---- find_dynfric_timesteps
+    times = dict(times, PM_start=Ti_cur - (1 << 41), PM_kick=0)
+    S = dict(type=typ, flags=flags, vel=vel, df_vel=df_vel, hsml=hsml, dthsml=dthsml, tb_grav=tbg, tb_hydro=tbh, tb_dynfric=tbd.copy())
+    dd = {k: dev(torch, v) for k, v in S.items()}
+    res, margin = R.find_dynfric_timesteps(S, act_bh, times, tl, errtol, 1e-7, courant, atime, hubble)
+    assert margin > 1e-9, margin
+    got = engine.dev_find_dynfric_timesteps(dd, dev(torch, act_bh), to_struct(pkg, times), sync, errtol, 1e-7, courant, atime, hubble)
+    engine.synchronize()
+    assert np.array_equal(dd["tb_dynfric"].cpu().numpy(), S["tb_dynfric"])
+    assert got == res and res["nbh"] >= 1, (got, res)
+    ch = S["tb_dynfric"] != tbd
+    assert not ch[typ != 5].any() and (S["tb_dynfric"] <= tbg)[ch].all() and (S["tb_dynfric"] >= tbh)[ch].all()
+
+
 # ---- a resident gas run (round 5): gravity + density + hydro + time bins + kicks + drift, three steps, one upload and one final fetch
 def _gas_run_setup(pkg, n=12):
     G = 43.0071
