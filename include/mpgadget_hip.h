@@ -364,8 +364,10 @@ int mpg_veldisp_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iter
  * cooling_and_starformation takes the `else cooling_direct` branch, sfr_eff.c:270-271) and passes the step's UV background
  * (get_global_UVBG, cooling_rates.c:365-397), get_long_mean_free_path_heating(redshift) (cooling_qso_lightup.c:258) and per hydro bin
  * lastred = 1 / exp(loga_from_ti(Ti_Current - dti_from_timebin(bin))) - 1 (sfr_eff.c:483-484).
- * Not carried: the UV-fluctuation table (get_local_UVBG_from_global with UVF.enabled), EXCUR_REION's local_J21, cooling_relaxed, star
- * formation and winds; several ranks each call this form on their own gas (the loop is per particle).
+ * With a UV-fluctuation table loaded (mpg_set_uvf_table below) every row takes the background of get_local_UVBG_from_global at its own
+ * position, and the HIReionTemp test reads the row's own zreion.
+ * Not carried: EXCUR_REION's local_J21, cooling_relaxed, star formation and winds (mpg_dev_cooling_and_starformation has the last three);
+ * several ranks each call this form on their own gas (the loop is per particle).
  * Every loop is bounded: the two limits of 1000 are the reference's (cooling.c:32, cooling_rates.c:768); the two bracketing loops, which the
  * reference leaves unbounded, stop after 8192 steps.  A particle that hits a limit, or whose electron abundance is not finite, keeps its
  * Entropy / Ne / Sfr, counts in stats[5], and makes the call return non-zero after all other particles are done (the reference: endrun). */
@@ -451,6 +453,32 @@ int mpg_dev_cooling_state(mpg_engine *eng, int64_t n, const double *d_rho, const
 int mpg_cooling_get_stats(mpg_engine *eng, int64_t stats[6]);
 /* the evaluations of the network of every particle in the last mpg_dev_cooling (host array of n entries; -1: not treated) */
 int mpg_cooling_export(mpg_engine *eng, int64_t n, int32_t *evaluations);
+
+/* ---- patchy reionisation: the UV-fluctuation table, libgadget/cooling_uvfluc.c:115-197 ------------------------------------------
+ * UVFluctuationFile's Zreion_Table gives the reionisation redshift as a function of position.  With a table loaded, mpg_dev_cooling,
+ * mpg_cooling and mpg_resident_sph_cooling (and the three forms of cooling_and_starformation) first evaluate it at the position of every
+ * listed gas row (the bound positions; on a resident run the resident Pos) minus the offset below, into an engine-owned column
+ * (mpg_uvf_export), and then give every row the background of get_local_UVBG_from_global: zreion < redshift: every rate of struct UVBG 0
+ * and self_shield_dens the global one; otherwise the step's background; uvbg.zreion the local value in both cases, which is what the
+ * HIReionTemp test reads.  The read is interp_eval_periodic (utils/interp.c:134-170) with interp_init_dim(0, BoxSize): trilinear, the
+ * cells BoxSize / (Nside - 1) wide and wrapped after Nside of them, so the table's period is BoxSize Nside / (Nside - 1) as in the
+ * reference.  A row whose position is not finite, or 2^31 cells or more from the origin (the reference: undefined), gets zreion = NaN
+ * without a read of the table, keeps Entropy / Ne / Sfr, counts in stats[5] and makes the call return non-zero after all other rows are
+ * done.  Without a table every call is bit for bit what it is without this section.  The excursion set (EXCUR_REION, local_J21) is a
+ * different model and is not carried. */
+/* init_uvf_table (cooling_uvfluc.c:115-167) without the file: Zreion_Table[Nside][Nside][Nside], C order, from HOST memory; table == NULL
+ * removes it.  Refused: Nside < 2, BoxSize <= 0, a non-finite entry, Table[0] outside [0.01, 100] (:164). */
+int mpg_set_uvf_table(mpg_engine *eng, int64_t Nside, const double *table, double BoxSize);
+/* PartManager->CurrentParticleOffset for the calls that follow; {0,0,0} until set */
+int mpg_set_uvf_offset(mpg_engine *eng, const double offset[3]);
+/* zreion of n arbitrary points on the device ([n][3] in, [n] out): interp_eval_periodic(&UVF.interp, pos - offset, UVF.Table).  What
+ * get_neutral_fraction_sfreff (sfr_eff.c:580, 613) and stats.c:271 need before mpg_dev_cooling_state, which keeps taking one background:
+ * the caller splits its points by zreion < redshift.  A point that cannot be evaluated (above) gets NaN, and the call returns non-zero
+ * after all other points are done. */
+int mpg_dev_uvf_zreion(mpg_engine *eng, int64_t n, const double *d_pos, double *d_zreion);
+/* the zreion of every particle in the last cooling or cooling_and_starformation call with a table (host array of n entries; NaN: the row
+ * was not evaluated, or could not be) */
+int mpg_uvf_export(mpg_engine *eng, int64_t n, double *zreion);
 
 /* ---- return of stellar mass and metals to the gas: metal_return, libgadget/metal_return.c (run.c:613) ----------------------------
  * For every active star (Type == 4, not garbage) with massgenerated >= 1e-3 (Mass + TotalMassReturned) (metals_haswork, :714-724):
@@ -910,8 +938,10 @@ typedef struct mpg_sfr_params {
     double EgySpecSN, EgySpecCold, PhysDensThresh, OverDensThresh;
     double UnitSfr_in_solar_per_year, avg_baryon_mass, tau_fmol_unit, GravInternal;
     int WindOn;
+    /* UVF.enabled: must agree with the engine's table (mpg_set_uvf_table): refused when set without one, and every
+     * cooling_and_starformation call is refused while the two disagree */
+    int UVFluctuationOn;
     /* what is refused when it is set, so that a caller keeps its CPU path from the start */
-    int UVFluctuationOn; /* a UV-fluctuation table is loaded (UVF.enabled) */
     int ExcursionSetReion; /* built with EXCUR_REION */
     int NTask;           /* ranks of the run; 0 is read as 1 */
 } mpg_sfr_params;
@@ -948,8 +978,10 @@ typedef struct mpg_sfr_result {
     int64_t errors;       /* rows that hit an iteration limit: cooled and star-forming */
     double sum_sm, localsfr, sum_dtime;
 } mpg_sfr_result;
-/* an error that names the setting for BHFeedbackUseTcool == 2, a UV-fluctuation table, EXCUR_REION and several ranks.  A fifth refusal
- * belongs to one form: mpg_resident_sph_cooling_and_starformation with WindOn and WIND_SUBGRID (below). */
+/* an error that names the setting for BHFeedbackUseTcool == 2, UVFluctuationOn without a table on this engine (mpg_set_uvf_table comes
+ * first), EXCUR_REION and several ranks.  A fifth refusal belongs to one form: mpg_resident_sph_cooling_and_starformation with WindOn and
+ * WIND_SUBGRID (below).  With a table, starformation takes the row's own background (sfr_eff.c:745) in both GetCoolingTime calls, and the
+ * cooled rows theirs as in mpg_dev_cooling; a star-forming row whose position cannot be evaluated is an error row. */
 int mpg_set_sfr_params(mpg_engine *eng, const mpg_sfr_params *par);
 /* on the bound particles (types from the bound table, garbage as type 7, Mass the bound column); d_active NULL = all particles.  Required:
  * id, density, entropy, ne, sfr, metallicity and what the criterion reads; with WindOn and WIND_SUBGRID also vdisp, vel, delaytime and

@@ -32,6 +32,74 @@ struct Setup {
     double mmin[3], mmax[3], mstep[3];
 };
 
+// the UV-fluctuation table as a kernel reads it: Zreion_Table[Nside][Nside][Nside] in C order, interp_init_dim(d, 0, BoxSize) on every axis
+// (cooling_uvfluc.c:158-162), PartManager->CurrentParticleOffset
+struct UvfView {
+    const double *table;
+    long long nside;
+    double step; // BoxSize / (Nside - 1), utils/interp.c:53
+    double off[3];
+};
+
+// interp_eval_periodic (utils/interp.c:134-170) at pos - off: the cell and the fraction per axis, the eight corners wrapped into
+// [0, Nside), the sum in the reference's corner order (bit d of the corner number selects axis d).  The table wraps after Nside cells of
+// width BoxSize / (Nside - 1), as the reference's does.  The wrap is an integer modulo where the reference loops; the two agree for every
+// finite cell below 2^31 in magnitude.  A coordinate that is not finite or lies beyond that range (the reference: undefined) gives NaN
+// without reading the table.
+MPG_HD double uvf_zreion(const UvfView &U, const double *pos)
+{
+    long long xi[3];
+    double f[3];
+    for(int d = 0; d < 3; d++) {
+        const double xd = (pos[d] - U.off[d]) / U.step;
+        if(!(fabs(xd) < 2147483648.0)) // (false for NaN too)
+            return NAN;
+        const double fl = floor(xd);
+        xi[d] = (long long)fl;
+        f[d] = xd - fl;
+    }
+    const long long stride[3] = {U.nside * U.nside, U.nside, 1};
+    double ret = 0;
+    for(int i = 0; i < 8; i++) {
+        double filter = 1.0;
+        long long l = 0;
+        for(int d = 0; d < 3; d++) {
+            const int foffset = (i & (1 << d)) ? 1 : 0;
+            long long c = (xi[d] + foffset) % U.nside;
+            if(c < 0)
+                c += U.nside;
+            filter *= foffset ? f[d] : (1 - f[d]);
+            l += stride[d] * c;
+        }
+        ret += U.table[l] * filter;
+    }
+    return ret;
+}
+
+// get_local_UVBG_from_global (cooling_uvfluc.c:174-197) with the table's value at the particle: before its own reionisation every rate
+// is zero and self_shield_dens the global one, afterwards the global background; uvbg.zreion is the local value either way.  Only the
+// members of uvbg differ between the lanes of a wave; everything else of the copy stays what the kernel was given.
+MPG_HD Setup dark_setup(const Setup &S, bool dark)
+{
+    Setup L = S;
+    if(dark) {
+        L.uvbg.J_UV = 0;
+        L.uvbg.gJH0 = 0;
+        L.uvbg.gJHep = 0;
+        L.uvbg.gJHe0 = 0;
+        L.uvbg.epsH0 = 0;
+        L.uvbg.epsHep = 0;
+        L.uvbg.epsHe0 = 0;
+    }
+    return L;
+}
+MPG_HD Setup local_setup(const Setup &S, double zreion)
+{
+    Setup L = dark_setup(S, zreion < S.redshift);
+    L.uvbg.zreion = zreion;
+    return L;
+}
+
 struct Counters {
     int evals = 0;      // ne_internal evaluations
     int bisections = 0; // steps of DoCooling's bisection
@@ -409,7 +477,8 @@ MPG_HD double do_cooling(const Setup &S, double redshift, double u_old, double r
 // entropy_to_u, sfr_eff.c:138-142
 MPG_HD double entropy_to_u(double density, double a3inv) { return exp(GAMMA_MINUS1 * log(density * a3inv)) / GAMMA_MINUS1; }
 
-// cooling_direct, sfr_eff.c:463-514, for one particle; the UV background is the step's (no fluctuation table, no excursion set).
+// cooling_direct, sfr_eff.c:463-514, for one particle; the UV background is S's: the step's, or with a fluctuation table the particle's own
+// (local_setup); no excursion set.
 // Returns the new entropy; *ne holds SphP.Ne in and out; *reion tells whether the HIReionTemp branch was taken.
 MPG_HD double cooling_direct(const Setup &S, double density, double entropy, double *ne, double Z, int heiii, double dtime, double a3inv,
                              double lastred, Counters &C, int *reion)
@@ -465,11 +534,24 @@ struct CoolingEngine {
     int lds_tables = 0; // 1: the six network tables in LDS (MPG_COOLING_LDS), 0: in global memory
     int num_cus = 0;
     int form = 0;       // 0: one particle per lane to completion, 1: per-lane state machine with a wave-aggregated queue (MPG_COOLING_FORM)
+    // the UV-fluctuation table (init_uvf_table, cooling_uvfluc.c:115-167) and the zreion column of the last call (NaN: row not evaluated)
+    bool have_uvf = false;
+    DevBuf<double> uvf_table, uvf_z;
+    DevBuf<unsigned> uvf_bad;
+    int64_t uvf_nside = 0, n_uvf = 0;
+    double uvf_box = 0, uvf_off[3] = {0, 0, 0};
 
     void set_params(const mpg_cooling_params &p, hipStream_t st);
     void set_metal_table(int nz, const double *zbins, int nnh, const double *nhbins, int nt, const double *tbins, const double *rate, hipStream_t st);
+    void set_uvf_table(int64_t nside, const double *table, double BoxSize, hipStream_t st);
+    cool::UvfView uvf_view() const;
+    // zreion of n arbitrary points; returns the number of points whose coordinates are not finite or out of range (their zreion is NaN)
+    int64_t uvf_points(int64_t n, const double *d_pos, double *d_zreion, hipStream_t st);
+    // ... and of the listed gas rows of the bound table into uvf_z (every other row: NaN)
+    void uvf_rows(const double *d_pos, const uint8_t *type, const float *mass, const int *d_active, int64_t nactive, int64_t n, hipStream_t st);
     cool::Setup setup(const mpg_cooling_step &step, double redshift) const;
-    // cooling_direct on the listed particles; returns the number of particles that hit an iteration limit
+    // cooling_direct on the listed particles; returns the number of particles that hit an iteration limit.  With a table loaded every row
+    // takes its background from uvf_z, which the caller has filled (uvf_rows); a row whose zreion is NaN counts among the errors.
     int64_t run(const mpg_cooling_arrays &A, const uint8_t *type, const float *mass, const mpg_sph_times &T, const mpg_cooling_step &step,
                 const int *d_active, int64_t nactive, int64_t n, hipStream_t st);
     int64_t state(int64_t n, const double *rho, const double *u, double *ne, double *lambdanet, double *temp, double *nh0,

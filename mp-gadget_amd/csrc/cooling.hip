@@ -45,9 +45,12 @@ struct CoolTimes {
     double a3inv;
 };
 
-__global__ __launch_bounds__(COOL_BLOCK) void k_cooling(Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass,
-                                                        const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
-                                                        int use_lds)
+// UVF: every row takes its background from its own zreion (zr, by particle; get_local_UVBG_from_global).  A row whose zreion is NaN has
+// none: it is an error row.  Without a table the kernels (k_cooling, k_cooling_queue) are what they were.
+template <bool UVF>
+__device__ __forceinline__ void cooling_rows(Setup S, const CoolTimes &T, const mpg_cooling_arrays &A, const uint8_t *type, const float *mass,
+                                             const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats, const double *zr,
+                                             int use_lds)
 {
     S.net = stage_net_tables(S.net, use_lds != 0);
     unsigned long long mine[ST_N] = {0, 0, 0, 0, 0, 0};
@@ -59,13 +62,27 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling(Setup S, CoolTimes T, mp
         if(p < 0 || p >= n || (type ? type[p] : (uint8_t)1) != 0 || !(mass[p] > 0))
             p = -1;
     }
-    if(p >= 0) {
+    double zreion = 0;
+    if constexpr(UVF)
+        if(p >= 0)
+            zreion = zr[p];
+    if(UVF && p >= 0 && zreion != zreion) {
+        evals[p] = 0;
+        mine[ST_TREATED] = 1;
+        mine[ST_ERRORS] = 1;
+    }
+    else if(p >= 0) {
         const int bin = A.tb_hydro ? (A.tb_hydro[p] < 47 ? A.tb_hydro[p] : 46) : 0;
         double ne = A.ne[p];
         Counters C;
         int reion = 0;
-        const double ent = cooling_direct(S, A.density[p], A.entropy[p], &ne, A.metallicity ? A.metallicity[p] : 0.0,
-                                          A.heiii_ionized ? (int)A.heiii_ionized[p] : 0, T.dtime[bin], T.a3inv, T.lastred[bin], C, &reion);
+        double ent;
+        if constexpr(UVF)
+            ent = cooling_direct(local_setup(S, zreion), A.density[p], A.entropy[p], &ne, A.metallicity ? A.metallicity[p] : 0.0,
+                                 A.heiii_ionized ? (int)A.heiii_ionized[p] : 0, T.dtime[bin], T.a3inv, T.lastred[bin], C, &reion);
+        else
+            ent = cooling_direct(S, A.density[p], A.entropy[p], &ne, A.metallicity ? A.metallicity[p] : 0.0,
+                                 A.heiii_ionized ? (int)A.heiii_ionized[p] : 0, T.dtime[bin], T.a3inv, T.lastred[bin], C, &reion);
         if(!C.error) {
             A.ne[p] = ne;
             A.entropy[p] = ent;
@@ -82,6 +99,19 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling(Setup S, CoolTimes T, mp
     add_block_stats(stats, mine);
 }
 
+__global__ __launch_bounds__(COOL_BLOCK) void k_cooling(Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass,
+                                                        const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
+                                                        int use_lds)
+{
+    cooling_rows<false>(S, T, A, type, mass, active, nlist, n, evals, stats, nullptr, use_lds);
+}
+__global__ __launch_bounds__(COOL_BLOCK) void k_cooling_uvf(Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass,
+                                                            const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
+                                                            const double *zr, int use_lds)
+{
+    cooling_rows<true>(S, T, A, type, mass, active, nlist, n, evals, stats, zr, use_lds);
+}
+
 // ---- the second form: a per-lane state machine whose unit step is ONE evaluation of the network -----------------------------------------
 // The evaluations per particle differ by a factor of 17 and more (21 .. several hundred), so in k_cooling a wave runs as long as its
 // slowest particle.  Here a lane that has finished its particle takes the next entry of the list from a counter the wave advances once for
@@ -91,6 +121,7 @@ enum Phase { PH_INIT = 0, PH_UP, PH_DOWN, PH_BISECT };
 struct Lane {
     int64_t p = -1; // the particle in work, -1: none
     int phase, heiii, fp_i, sub, guard, iter;
+    int dark = 0; // with a UV-fluctuation table: the particle is not yet reionised (its zreion < redshift)
     double rho, u_old, MinEgySpec, dt, Z, enttou; // DoCooling's arguments in cgs
     double u_lower, u_upper, u;                   // the bracket, and the energy the network is being solved at
     double ne_guess, ne0, ne1;
@@ -183,13 +214,65 @@ __device__ inline bool lane_advance(Lane &L, double LambdaNet)
     }
 }
 
-__global__ __launch_bounds__(COOL_BLOCK) void k_cooling_queue(Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass,
-                                                              const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
-                                                              unsigned long long *queue, int use_lds)
+// one trip of k_cooling_queue's loop for a lane that holds a particle: one evaluation of the network (scipy_optimize_fixed_point,
+// cooling_rates.c:784-805) under the background of S, and what follows from it
+__device__ __forceinline__ void one_evaluation(const Setup &S, Lane &L, unsigned long long *mine, const mpg_cooling_arrays &A, int *evals)
+{
+    const double helium = 1 - HYDROGEN_MASSFRAC;
+    const double nh = L.rho * (1 - helium);
+    double logt1;
+    bool converged = false;
+    if(L.sub == 0) {
+        L.ne1 = ne_internal(S, nh, L.u, L.ne0 * nh, helium, &logt1, L.C) / nh;
+        if(fabs(L.ne1 - L.ne0) < 1e-6) {
+            L.ne0 = L.ne1;
+            converged = true;
+        }
+        else
+            L.sub = 1;
+    }
+    else {
+        const double ne2 = ne_internal(S, nh, L.u, L.ne1 * nh, helium, &logt1, L.C) / nh;
+        const double d = L.ne0 + ne2 - 2.0 * L.ne1;
+        double pp = ne2;
+        if(d > 1e-15 || d < -1e-15)
+            pp = L.ne0 - (L.ne1 - L.ne0) * (L.ne1 - L.ne0) / d;
+        L.ne0 = pp;
+        if(L.ne0 < 0)
+            L.ne0 = 0;
+        L.sub = 0;
+        if(++L.fp_i == S.net_maxiter)
+            L.C.error = 1;
+    }
+    bool done = L.C.error != 0;
+    if(converged) {
+        double LambdaNet = heatingcooling_at_equilibrium(S, L.rho, L.u, helium, S.redshift, L.Z, L.ne0 * nh, logt1, &L.ne_guess);
+        if(!L.heiii)
+            LambdaNet += S.lmfp_heating / (S.units_rho_crit_baryon * pow(1 + S.redshift, 3.0));
+        done = lane_advance(L, LambdaNet);
+    }
+    if(done) {
+        if(!L.C.error) {
+            A.ne[L.p] = L.ne_guess;
+            A.entropy[L.p] = (L.u / S.uu_in_cgs) / L.enttou;
+            A.sfr[L.p] = 0;
+        }
+        evals[L.p] = L.C.evals;
+        mine[ST_EVALS] += L.C.evals;
+        mine[ST_BISECT] += L.C.bisections;
+        mine[ST_FLOOR] += L.C.error ? 0 : L.C.floor;
+        mine[ST_ERRORS] += L.C.error;
+        L.p = -1;
+    }
+}
+
+template <bool UVF>
+__device__ __forceinline__ void cooling_queue(Setup S, const CoolTimes &T, const mpg_cooling_arrays &A, const uint8_t *type, const float *mass,
+                                              const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
+                                              unsigned long long *queue, const double *zr, int use_lds)
 {
     S.net = stage_net_tables(S.net, use_lds != 0);
     unsigned long long mine[ST_N] = {0, 0, 0, 0, 0, 0};
-    const double helium = 1 - HYDROGEN_MASSFRAC;
     const int lane = __lane_id();
     Lane L;
     bool more = true; // the list may still hold entries
@@ -211,6 +294,17 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_queue(Setup S, CoolTimes
                     int64_t p = active ? (int64_t)active[t] : t;
                     if(p < 0 || p >= n || (type ? type[p] : (uint8_t)1) != 0 || !(mass[p] > 0))
                         p = -1;
+                    double zreion = S.uvbg.zreion;
+                    if constexpr(UVF)
+                        if(p >= 0) {
+                            zreion = zr[p];
+                            if(zreion != zreion) {
+                                evals[p] = 0;
+                                mine[ST_TREATED]++;
+                                mine[ST_ERRORS]++;
+                                p = -1;
+                            }
+                        }
                     if(p >= 0) {
                         // cooling_direct up to the call of DoCooling (sfr_eff.c:463-506) and DoCooling's head (cooling.c:59-75)
                         const int bin = A.tb_hydro ? (A.tb_hydro[p] < 47 ? A.tb_hydro[p] : 46) : 0;
@@ -219,7 +313,7 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_queue(Setup S, CoolTimes
                         L.enttou = entropy_to_u(density, T.a3inv);
                         const double uold = A.entropy[p] * L.enttou;
                         mine[ST_TREATED]++;
-                        if(S.HIReionTemp > 0 && S.uvbg.zreion >= S.redshift && S.uvbg.zreion < T.lastred[bin]) {
+                        if(S.HIReionTemp > 0 && zreion >= S.redshift && zreion < T.lastred[bin]) {
                             const double meanweight = 4 / (8 - 6 * (1 - HYDROGEN_MASSFRAC));
                             double unew = S.temp_to_u / meanweight * S.HIReionTemp;
                             if(uold > unew)
@@ -237,6 +331,7 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_queue(Setup S, CoolTimes
                         else {
                             const double meanweight = 4.0 / (1 + 3 * HYDROGEN_MASSFRAC);
                             L.p = p;
+                            L.dark = UVF && zreion < S.redshift;
                             L.ne_guess = A.ne[p];
                             L.Z = A.metallicity ? A.metallicity[p] : 0.0;
                             L.heiii = A.heiii_ionized ? (int)A.heiii_ionized[p] : 0;
@@ -260,54 +355,28 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_queue(Setup S, CoolTimes
             break;
         if(L.p >= 0) { // (an if, not a continue: all lanes of the wave meet again at the ballot above)
             // ---- one evaluation of the network (scipy_optimize_fixed_point, cooling_rates.c:784-805)
-            const double nh = L.rho * (1 - helium);
-            double logt1;
-            bool converged = false;
-            if(L.sub == 0) {
-                L.ne1 = ne_internal(S, nh, L.u, L.ne0 * nh, helium, &logt1, L.C) / nh;
-                if(fabs(L.ne1 - L.ne0) < 1e-6) {
-                    L.ne0 = L.ne1;
-                    converged = true;
-                }
-                else
-                    L.sub = 1;
-            }
-            else {
-                const double ne2 = ne_internal(S, nh, L.u, L.ne1 * nh, helium, &logt1, L.C) / nh;
-                const double d = L.ne0 + ne2 - 2.0 * L.ne1;
-                double pp = ne2;
-                if(d > 1e-15 || d < -1e-15)
-                    pp = L.ne0 - (L.ne1 - L.ne0) * (L.ne1 - L.ne0) / d;
-                L.ne0 = pp;
-                if(L.ne0 < 0)
-                    L.ne0 = 0;
-                L.sub = 0;
-                if(++L.fp_i == S.net_maxiter)
-                    L.C.error = 1;
-            }
-            bool done = L.C.error != 0;
-            if(converged) {
-                double LambdaNet = heatingcooling_at_equilibrium(S, L.rho, L.u, helium, S.redshift, L.Z, L.ne0 * nh, logt1, &L.ne_guess);
-                if(!L.heiii)
-                    LambdaNet += S.lmfp_heating / (S.units_rho_crit_baryon * pow(1 + S.redshift, 3.0));
-                done = lane_advance(L, LambdaNet);
-            }
-            if(done) {
-                if(!L.C.error) {
-                    A.ne[L.p] = L.ne_guess;
-                    A.entropy[L.p] = (L.u / S.uu_in_cgs) / L.enttou;
-                    A.sfr[L.p] = 0;
-                }
-                evals[L.p] = L.C.evals;
-                mine[ST_EVALS] += L.C.evals;
-                mine[ST_BISECT] += L.C.bisections;
-                mine[ST_FLOOR] += L.C.error ? 0 : L.C.floor;
-                mine[ST_ERRORS] += L.C.error;
-                L.p = -1;
-            }
+            if constexpr(UVF)
+                one_evaluation(dark_setup(S, L.dark != 0), L, mine, A, evals);
+            else
+                one_evaluation(S, L, mine, A, evals);
         }
     }
     add_block_stats(stats, mine);
+}
+
+__global__ __launch_bounds__(COOL_BLOCK) void k_cooling_queue(Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass,
+                                                              const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
+                                                              unsigned long long *queue, int use_lds)
+{
+    cooling_queue<false>(S, T, A, type, mass, active, nlist, n, evals, stats, queue, nullptr, use_lds);
+}
+// ... with a UV-fluctuation table.  The six rates of the lane's background are vector registers during an evaluation; left to itself the
+// compiler ends two registers above what lets two waves share a SIMD as they do without a table, so it is told to stay within that.
+__global__ __launch_bounds__(COOL_BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void k_cooling_queue_uvf(
+    Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass, const int *active, int64_t nlist, int64_t n, int *evals,
+    unsigned long long *stats, unsigned long long *queue, const double *zr, int use_lds)
+{
+    cooling_queue<true>(S, T, A, type, mass, active, nlist, n, evals, stats, queue, zr, use_lds);
 }
 
 __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_state(Setup S, double helium, int64_t n, const double *rho, const double *u, double *ne,
@@ -335,6 +404,30 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_state(Setup S, double he
         mine[ST_ERRORS] = C.error;
     }
     add_block_stats(stats, mine);
+}
+
+// the reionisation redshift of the UV-fluctuation table (cool::uvf_zreion), one lane per entry.  rows == 0: at the points pos[t], into
+// out[t]; a point that gives NaN counts in *bad.  rows != 0: at the listed gas rows of the table of n particles (the filter of k_cooling),
+// into out[p]; the cooling kernels count the NaN rows.
+constexpr int UVF_BLOCK = 256;
+__global__ __launch_bounds__(UVF_BLOCK) void k_uvf_zreion(const UvfView U, const double *__restrict__ pos, const uint8_t *__restrict__ type,
+                                                          const float *__restrict__ mass, const int *__restrict__ active, const int64_t nlist,
+                                                          const int64_t n, double *__restrict__ out, unsigned *__restrict__ bad, const int rows)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(t >= nlist)
+        return;
+    int64_t p = t;
+    if(rows) {
+        p = active ? (int64_t)active[t] : t;
+        if(p < 0 || p >= n || (type ? type[p] : (uint8_t)1) != 0 || !(mass[p] > 0))
+            return;
+    }
+    const double x[3] = {pos[3 * p], pos[3 * p + 1], pos[3 * p + 2]};
+    const double z = uvf_zreion(U, x);
+    out[p] = z;
+    if(!rows && z != z)
+        atomicAdd(bad, 1u);
 }
 
 void upload(DevBuf<double> &buf, const double *h, size_t count, hipStream_t st)
@@ -385,6 +478,70 @@ void CoolingEngine::set_metal_table(int nz, const double *zbins, int nnh, const 
     mmin[0] = zbins[0], mmin[1] = nhbins[0], mmin[2] = tbins[0];
     mmax[0] = zbins[nz - 1], mmax[1] = nhbins[nnh - 1], mmax[2] = tbins[nt - 1];
     have_metal = true;
+}
+
+void CoolingEngine::set_uvf_table(int64_t nside, const double *table, double BoxSize, hipStream_t st)
+{
+    if(!table) {
+        have_uvf = false;
+        uvf_table.release();
+        return;
+    }
+    // (a cube of 2^20 cells a side is far beyond any memory; the bound keeps Nside^3 inside 64 bits)
+    MPG_CHECK(nside >= 2 && nside <= (1 << 20), "mpg_set_uvf_table: Nside outside 2 .. 2^20 (an axis needs two points)");
+    MPG_CHECK(BoxSize > 0 && BoxSize - BoxSize == 0, "mpg_set_uvf_table: BoxSize must be positive and finite");
+    const size_t count = (size_t)nside * nside * nside;
+    for(size_t i = 0; i < count; i++)
+        MPG_CHECK(table[i] - table[i] == 0, "mpg_set_uvf_table: table holds an entry that is not finite (entry " + std::to_string(i) + ")");
+    // cooling_uvfluc.c:164
+    MPG_CHECK(table[0] >= 0.01 && table[0] <= 100.0, "mpg_set_uvf_table: table[0] outside [0.01, 100] (UV Fluctuation out of range)");
+    have_uvf = false;
+    upload(uvf_table, table, count, st);
+    uvf_nside = nside;
+    uvf_box = BoxSize;
+    have_uvf = true;
+}
+
+UvfView CoolingEngine::uvf_view() const
+{
+    UvfView U;
+    U.table = uvf_table.p;
+    U.nside = uvf_nside;
+    U.step = (uvf_box - 0) / (uvf_nside - 1); // interp_init_dim(d, 0, BoxSize), utils/interp.c:53
+    for(int d = 0; d < 3; d++)
+        U.off[d] = uvf_off[d];
+    return U;
+}
+
+int64_t CoolingEngine::uvf_points(int64_t n, const double *d_pos, double *d_zreion, hipStream_t st)
+{
+    MPG_CHECK(have_uvf, "mpg_dev_uvf_zreion: no table (mpg_set_uvf_table first)");
+    if(n <= 0)
+        return 0;
+    uvf_bad.reserve(4);
+    MPG_HIP(hipMemsetAsync(uvf_bad.p, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(k_uvf_zreion, dim3(nblk(n, UVF_BLOCK)), dim3(UVF_BLOCK), 0, st, uvf_view(), d_pos, (const uint8_t *)nullptr, (const float *)nullptr,
+                       (const int *)nullptr, n, n, d_zreion, uvf_bad.p, 0);
+    MPG_HIP(hipGetLastError());
+    unsigned bad = 0;
+    MPG_HIP(hipMemcpyAsync(&bad, uvf_bad.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipStreamSynchronize(st));
+    return bad;
+}
+
+void CoolingEngine::uvf_rows(const double *d_pos, const uint8_t *type, const float *mass, const int *d_active, int64_t nactive, int64_t n, hipStream_t st)
+{
+    MPG_CHECK(have_uvf, "cooling: no UV-fluctuation table");
+    const int64_t nlist = d_active ? nactive : n;
+    uvf_z.reserve((size_t)n + 1);
+    n_uvf = n;
+    if(n > 0)
+        MPG_HIP(hipMemsetAsync(uvf_z.p, 0xff, (size_t)n * sizeof(double), st)); // (all bits set: a NaN)
+    if(nlist > 0 && n > 0) {
+        hipLaunchKernelGGL(k_uvf_zreion, dim3(nblk(nlist, UVF_BLOCK)), dim3(UVF_BLOCK), 0, st, uvf_view(), d_pos, type, mass, d_active, nlist, n, uvf_z.p,
+                           (unsigned *)nullptr, 1);
+        MPG_HIP(hipGetLastError());
+    }
 }
 
 Setup CoolingEngine::setup(const mpg_cooling_step &step, double redshift) const
@@ -455,12 +612,22 @@ int64_t CoolingEngine::run(const mpg_cooling_arrays &A, const uint8_t *type, con
         CT.a3inv = 1. / (T.atime * T.atime * T.atime); // sfr_eff.c:195
         const size_t lds = lds_tables ? (size_t)NRECOMBTAB * NNET * sizeof(double) : 0;
         const unsigned blocks = (unsigned)((nlist + COOL_BLOCK - 1) / COOL_BLOCK);
+        MPG_CHECK(!have_uvf || n_uvf == n, "cooling: the zreion column was not filled for this table");
+        const double *zr = have_uvf ? uvf_z.p : nullptr;
         if(form == 1) {
             // resident waves that pull from the list: no more blocks than keep every CU busy
             const unsigned cap = (unsigned)num_cus * 8u;
-            hipLaunchKernelGGL(k_cooling_queue, dim3(blocks < cap ? blocks : cap), dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n,
-                               d_evals.p, d_stats.p, d_stats.p + ST_N, lds_tables);
+            const dim3 grid(blocks < cap ? blocks : cap);
+            if(have_uvf)
+                hipLaunchKernelGGL(k_cooling_queue_uvf, grid, dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p,
+                                   d_stats.p + ST_N, zr, lds_tables);
+            else
+                hipLaunchKernelGGL(k_cooling_queue, grid, dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p,
+                                   d_stats.p + ST_N, lds_tables);
         }
+        else if(have_uvf)
+            hipLaunchKernelGGL(k_cooling_uvf, dim3(blocks), dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p, zr,
+                               lds_tables);
         else
             hipLaunchKernelGGL(k_cooling, dim3(blocks), dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p,
                                lds_tables);

@@ -1251,10 +1251,61 @@ int mpg_dev_cooling(mpg_engine *eng, const mpg_cooling_arrays *A, const mpg_sph_
     MPG_CHECK(eng->n == 0 || (A->density && A->entropy && A->ne && A->sfr), "cooling: the arrays density, entropy, ne and sfr are required");
     MPG_CHECK(eng->d_mass || eng->n == 0, "cooling: no particles bound");
     MPG_HIP(hipSetDevice(eng->device));
+    if(eng->cooling.have_uvf) // the zreion of every listed gas row from the bound positions (get_local_UVBG_from_global)
+        eng->cooling.uvf_rows(eng->d_pos, eng->d_type, eng->d_mass, d_active, nactive, eng->n, eng->stream);
     const int64_t bad = eng->cooling.run(*A, eng->d_type, eng->d_mass, *T, *step, d_active, nactive, eng->n, eng->stream);
     // the reference's endrun(1 / 10): every other particle of the call has been treated
     MPG_CHECK(bad == 0, "cooling: " + std::to_string(bad) + " particle(s) hit an iteration limit of DoCooling or of the ionisation network, or reached an "
-                                                           "electron abundance that is not finite; they keep their Entropy and Ne");
+                                                           "electron abundance that is not finite" +
+                            (eng->cooling.have_uvf ? ", or have a position at which the UV-fluctuation table cannot be read (not finite)" : "") +
+                            "; they keep their Entropy and Ne");
+    API_END
+}
+
+/* ------------------------------ the UV-fluctuation table (cooling_uvfluc.c:115-197) ------------------------------ */
+
+int mpg_set_uvf_table(mpg_engine *eng, int64_t Nside, const double *table, double BoxSize)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream)); // (a kernel in flight may still read the table this call replaces)
+    eng->cooling.set_uvf_table(Nside, table, BoxSize, eng->stream);
+    API_END
+}
+
+int mpg_set_uvf_offset(mpg_engine *eng, const double offset[3])
+{
+    API_BEGIN
+    MPG_CHECK(eng && offset, "null argument");
+    MPG_CHECK(offset[0] - offset[0] == 0 && offset[1] - offset[1] == 0 && offset[2] - offset[2] == 0, "mpg_set_uvf_offset: offset is not finite");
+    for(int d = 0; d < 3; d++)
+        eng->cooling.uvf_off[d] = offset[d];
+    API_END
+}
+
+int mpg_dev_uvf_zreion(mpg_engine *eng, int64_t n, const double *d_pos, double *d_zreion)
+{
+    API_BEGIN
+    MPG_CHECK(eng && n >= 0, "null argument");
+    MPG_CHECK(n == 0 || (d_pos && d_zreion), "mpg_dev_uvf_zreion: pos and zreion are required");
+    MPG_HIP(hipSetDevice(eng->device));
+    const int64_t bad = eng->cooling.uvf_points(n, d_pos, d_zreion, eng->stream);
+    // (the reference: undefined behaviour) every other point of the call has its value
+    MPG_CHECK(bad == 0, "mpg_dev_uvf_zreion: " + std::to_string(bad) + " point(s) have a coordinate that is not finite or lies 2^31 cells or more "
+                                                                      "from the table's origin; their zreion is NaN");
+    API_END
+}
+
+int mpg_uvf_export(mpg_engine *eng, int64_t n, double *zreion)
+{
+    API_BEGIN
+    MPG_CHECK(eng && zreion, "null argument");
+    MPG_CHECK(n == eng->cooling.n_uvf, "mpg_uvf_export: n is not the particle number of the last cooling call with a UV-fluctuation table");
+    MPG_HIP(hipSetDevice(eng->device));
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    if(n > 0)
+        MPG_HIP(hipMemcpy(zreion, eng->cooling.uvf_z.p, n * sizeof(double), hipMemcpyDeviceToHost));
     API_END
 }
 
@@ -1629,7 +1680,7 @@ int mpg_set_sfr_params(mpg_engine *eng, const mpg_sfr_params *par)
 {
     API_BEGIN
     MPG_CHECK(eng && par, "null argument");
-    eng->sfr.set_params(*par);
+    eng->sfr.set_params(*par, eng->cooling.have_uvf);
     API_END
 }
 
@@ -1643,6 +1694,10 @@ int mpg_dev_cooling_and_starformation(mpg_engine *eng, const mpg_sfr_columns *A,
     MPG_CHECK(eng->bh.rndsize > 0, "cooling_and_starformation: no random table (mpg_set_random_table first)");
     MPG_CHECK(eng->d_mass || eng->n == 0, "cooling_and_starformation: no particles bound");
     const mpg_sfr_params &P = eng->sfr.par;
+    // starformation and cooling_direct take the background get_local_UVBG gives: the setting and the table go together
+    MPG_CHECK((P.UVFluctuationOn != 0) == eng->cooling.have_uvf,
+              P.UVFluctuationOn ? "cooling_and_starformation: UVFluctuationOn is set but the engine holds no UV-fluctuation table (mpg_set_uvf_table)"
+                                : "cooling_and_starformation: the engine holds a UV-fluctuation table but UVFluctuationOn is 0 (mpg_set_sfr_params)");
     MPG_CHECK(!(P.WindOn || A->delaytime) || eng->have_windpar, "cooling_and_starformation: no wind parameters (mpg_set_wind_params first)");
     const bool subgrid = P.WindOn && (eng->windpar.WindModel & WIND_SUBGRID) != 0; // winds_are_subgrid, sfr_eff.c:205, 280
     if(eng->n > 0) {
@@ -1658,7 +1713,7 @@ int mpg_dev_cooling_and_starformation(mpg_engine *eng, const mpg_sfr_columns *A,
                   "cooling_and_starformation: WIND_SUBGRID needs the columns vdisp, vel, delaytime and stellarmass");
     }
     MPG_HIP(hipSetDevice(eng->device));
-    const SfrView v{eng->d_type, eng->d_mass, eng->n, *A};
+    const SfrView v{eng->d_type, eng->d_mass, eng->n, *A, eng->d_pos};
     const int64_t bad = eng->sfr.run(eng->cooling, v, A->delaytime ? &eng->windpar : nullptr, eng->bh.rnd.p, (uint64_t)eng->bh.rndsize, *T, *step, d_active,
                                      nactive, eng->stream);
     if(subgrid) { // sfr_eff.c:280-286
@@ -1678,7 +1733,9 @@ int mpg_dev_cooling_and_starformation(mpg_engine *eng, const mpg_sfr_columns *A,
     }
     // the reference's endrun(1 / 10): every other row of the call has been treated
     MPG_CHECK(bad == 0, "cooling_and_starformation: " + std::to_string(bad) + " row(s) hit an iteration limit of DoCooling or of the ionisation network, or reached "
-                                                                             "an electron abundance that is not finite; they keep their columns and form no star");
+                                                                             "an electron abundance that is not finite" +
+                            (eng->cooling.have_uvf ? ", or have a position at which the UV-fluctuation table cannot be read (not finite)" : "") +
+                            "; they keep their columns and form no star");
     API_END
 }
 

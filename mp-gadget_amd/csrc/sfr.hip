@@ -173,11 +173,13 @@ __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_push(const uint8_t *__restric
         sflist[blockoff[2 * blockIdx.x + 1] + rb] = p;
 }
 
-// starformation (sfr_eff.c:731-800) for every row of the star-forming list: one lane per row, 2 .. 3 solves of the network
+// starformation (sfr_eff.c:731-800) for every row of the star-forming list: one lane per row, 2 .. 3 solves of the network.  UVF: under the
+// row's own background (sfr_eff.c:745; zr by particle, cool::local_setup); a row whose zreion is NaN is an error row.
+template <bool UVF>
 __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_eeqos(const Setup S, const SfrTimes T, const SfrScalars P, const SfrView A, const int *__restrict__ sflist,
                                                          const int64_t nsf, uint8_t *__restrict__ outcome, double *__restrict__ sfmass,
                                                          int *__restrict__ sfevals, unsigned *__restrict__ blockcnt, double *__restrict__ partial,
-                                                         unsigned long long *__restrict__ ctr)
+                                                         unsigned long long *__restrict__ ctr, const double *__restrict__ zr)
 {
     __shared__ unsigned wc[2][SFR_WAVES];
     __shared__ double ws[3][SFR_WAVES];
@@ -214,7 +216,19 @@ __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_eeqos(const Setup S, const Sf
             r.tb_hydro = bin;
             const unsigned long long id = a.id[p];
             Counters C;
-            const RowResult o = starformation(S, P.p, r, T.dloga[bin], T.hubble, T.atime, T.a3inv, P.rnd[id % P.rndsize], P.rnd[(id + 1ull) % P.rndsize], C);
+            RowResult o;
+            if constexpr(UVF) {
+                const double zreion = zr[p];
+                if(zreion != zreion) {
+                    o = RowResult{};
+                    o.outcome = OUT_ERROR;
+                }
+                else
+                    o = starformation(local_setup(S, zreion), P.p, r, T.dloga[bin], T.hubble, T.atime, T.a3inv, P.rnd[id % P.rndsize],
+                                      P.rnd[(id + 1ull) % P.rndsize], C);
+            }
+            else
+                o = starformation(S, P.p, r, T.dloga[bin], T.hubble, T.atime, T.a3inv, P.rnd[id % P.rndsize], P.rnd[(id + 1ull) % P.rndsize], C);
             out = o.outcome;
             evals = (unsigned)C.evals;
             sfevals[p] = C.evals;
@@ -289,12 +303,12 @@ __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_lists(const uint8_t *__restri
 
 } // namespace
 
-void SfrEngine::set_params(const mpg_sfr_params &p)
+void SfrEngine::set_params(const mpg_sfr_params &p, bool have_uvf_table)
 {
     // what the engine does not carry is refused when it is set, so that a caller keeps its CPU path from the start
     MPG_CHECK(p.BHFeedbackUseTcool != 2, "star formation: BHFeedbackUseTcool == 2 is not carried (get_egyeff in sfreff_on_eeqos)");
     MPG_CHECK(p.BHFeedbackUseTcool >= 0 && p.BHFeedbackUseTcool <= 3, "star formation: BHFeedbackUseTcool mode not supported");
-    MPG_CHECK(!p.UVFluctuationOn, "star formation: UVFluctuationOn (a UV-fluctuation table) is not carried (get_local_UVBG)");
+    MPG_CHECK(!p.UVFluctuationOn || have_uvf_table, "star formation: UVFluctuationOn without a UV-fluctuation table on this engine (mpg_set_uvf_table first)");
     MPG_CHECK(!p.ExcursionSetReion, "star formation: ExcursionSetReion (EXCUR_REION) is not carried (local_J21, zreion)");
     MPG_CHECK(p.NTask <= 1, "star formation: NTask > 1 is not carried; several ranks keep the CPU function");
     MPG_CHECK(p.Generations >= 1 && p.Generations <= 14, "star formation: Generations outside 1 .. 14");
@@ -338,6 +352,9 @@ int64_t SfrEngine::run(CoolingEngine &cooling, const SfrView &A, const mpg_wind_
     P.rnd = rnd;
     P.rndsize = rndsize;
     unsigned tot[2] = {0, 0};
+    // the zreion of every listed gas row, cooled or star-forming, before either kernel reads it
+    if(cooling.have_uvf)
+        cooling.uvf_rows(A.pos, A.type, A.mass, d_active, nactive, n, st);
     if(nlist > 0) {
         hipLaunchKernelGGL(k_sfr_classify, dim3(nb), dim3(SFR_BLOCK), 0, st, cooling.par.temp_to_u, ST, P, A, d_active, nlist, cls.p, rowclass.p, blockcnt.p);
         hipLaunchKernelGGL(k_sfr_scan, dim3(1), dim3(SFR_BLOCK), 0, st, blockcnt.p, (int64_t)nb, totals.p, (const double *)nullptr, (double *)nullptr);
@@ -374,7 +391,8 @@ int64_t SfrEngine::run(CoolingEngine &cooling, const SfrView &A, const mpg_wind_
         ctr.reserve(SC_N);
         MPG_HIP(hipMemsetAsync(ctr.p, 0, SC_N * sizeof(unsigned long long), st));
         const Setup S = cooling.setup(step, 1 / T.atime - 1); // sfr_eff.c:211
-        hipLaunchKernelGGL(k_sfr_eeqos, dim3(nb2), dim3(SFR_BLOCK), 0, st, S, ST, P, A, sflist.p, nsf, outcome.p, sfmass.p, sfevals.p, blockcnt.p, partial.p, ctr.p);
+        hipLaunchKernelGGL(cooling.have_uvf ? k_sfr_eeqos<true> : k_sfr_eeqos<false>, dim3(nb2), dim3(SFR_BLOCK), 0, st, S, ST, P, A, sflist.p, nsf, outcome.p,
+                           sfmass.p, sfevals.p, blockcnt.p, partial.p, ctr.p, cooling.have_uvf ? (const double *)cooling.uvf_z.p : (const double *)nullptr);
         hipLaunchKernelGGL(k_sfr_scan, dim3(1), dim3(SFR_BLOCK), 0, st, blockcnt.p, (int64_t)nb2, totals.p, (const double *)partial.p, sums.p);
         hipLaunchKernelGGL(k_sfr_lists, dim3(nb2), dim3(SFR_BLOCK), 0, st, outcome.p, sflist.p, sfmass.p, nsf, blockcnt.p, ns_parent.p, ns_mass.p, ns_spawn.p,
                            A.a.stellarmass ? maybewind.p : (int *)nullptr);

@@ -1637,6 +1637,32 @@ class Engine:
         self._ck(self.lib.mpg_cooling_export(self.h, C.c_int64(n), ev.ctypes.data_as(C.c_void_p)))
         return ev
 
+    # ------------------------------------------------------------------ patchy reionisation (the UV-fluctuation table, cooling_uvfluc.c:115-197)
+    def set_uvf_table(self, table=None, BoxSize=0.0):
+        """init_uvf_table without the file: Zreion_Table[Nside][Nside][Nside] (C order); no arguments removes the table"""
+        if table is None:
+            self._ck(self.lib.mpg_set_uvf_table(self.h, C.c_int64(0), None, C.c_double(0.0)))
+            return
+        t = np.ascontiguousarray(table, np.float64)
+        if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[1] != t.shape[2]:
+            raise EngineError("UV-fluctuation table: table must have the shape (Nside, Nside, Nside)")
+        self._ck(self.lib.mpg_set_uvf_table(self.h, C.c_int64(t.shape[0]), t.ctypes.data_as(C.c_void_p), C.c_double(BoxSize)))
+
+    def set_uvf_offset(self, offset):
+        """PartManager->CurrentParticleOffset for the calls that follow"""
+        o = (C.c_double * 3)(*[float(x) for x in offset])
+        self._ck(self.lib.mpg_set_uvf_offset(self.h, o))
+
+    def dev_uvf_zreion(self, pos, out):
+        """zreion at n arbitrary points: device tensors float64 [n][3] in, [n] out"""
+        self._ck(self.lib.mpg_dev_uvf_zreion(self.h, C.c_int64(pos.shape[0]), _ptr(pos), _ptr(out)))
+
+    def uvf_export(self, n):
+        """zreion of every particle in the last cooling call with a table (NaN: not evaluated)"""
+        z = np.zeros(n, np.float64)
+        self._ck(self.lib.mpg_uvf_export(self.h, C.c_int64(n), z.ctypes.data_as(C.c_void_p)))
+        return z
+
     # ------------------------------------------------------------------ star formation (cooling_and_starformation, sfr_eff.c:186-394)
     # `par` is a dict of the members of mpg_sfr_params (or an SfrParams); `columns` maps the field names of mpg_sfr_columns to device tensors
     # (dev form) / contiguous numpy arrays (host forms) of the element types in SFR_COLUMN_DTYPES (float64 otherwise); `step` as for the

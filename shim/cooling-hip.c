@@ -21,8 +21,9 @@
  *     cooling_direct(...)` of sfr_eff.c:270-271 first offers the particle to mpg_shim_cooling_queue(), and mpg_shim_cooling_flush() runs the
  *     queued list on the device before walltime_measure("/Cooling/Cooling").  Deferring is equivalent: starformation(p_i) reads and writes
  *     particle p_i only.
- * With several ranks, a UV-fluctuation table (init_uvf_table) or the excursion-set reionisation in use, the reference's code runs
- * unchanged: the queue refuses every particle.
+ * A UV-fluctuation table (init_uvf_table) is loaded onto the device once, with PartManager->BoxSize, and every device call is preceded by
+ * mpg_set_uvf_offset(PartManager->CurrentParticleOffset): the engine then gives every row the background of get_local_UVBG_from_global.
+ * With several ranks or the excursion-set reionisation in use, the reference's code runs unchanged: the queue refuses every particle.
  * The parameters are file-static in the reference; tools/link_reference.sh appends one accessor each to cooling_rates.c, cooling.c,
  * cooling_uvfluc.c and sfr_eff.c (listed in INTEGRATION.md).
  * Compiled inside the reference tree (see gravity-hip.c). */
@@ -53,7 +54,8 @@ void cpu_cooling_and_starformation(ActiveParticles *act, double Time, double dlo
 /* the accessors appended to the reference files (tools/link_reference.sh, step 4) */
 struct cooling_params mpg_shim_cooling_params(void);                       /* cooling_rates.c: CoolingParams */
 struct cooling_units mpg_shim_cooling_units(void);                         /* cooling.c: coolunits */
-int mpg_shim_uvf_in_use(void);                                             /* cooling_uvfluc.c: UVF.enabled || uvf_params.ExcursionSetReionOn */
+int mpg_shim_uvf_table(int64_t *nside, double **table);                    /* cooling_uvfluc.c: UVF.Nside, UVF.Table; returns UVF.enabled */
+int mpg_shim_excursion_set_on(void);                                       /* cooling_uvfluc.c: uvf_params.ExcursionSetReionOn */
 int mpg_shim_metal_table(int *n, double **bins, double **rate);            /* cooling_uvfluc.c: MetalCool; returns !CoolingNoMetal */
 void mpg_shim_sfr_cooling(int *StarformationOn, double *MinGasTemp, double *temp_to_u, double *HIReionTemp); /* sfr_eff.c: sfr_params */
 void mpg_shim_sfr_params(mpg_sfr_params *p);                               /* sfr_eff.c: sfr_params after init_cooling_and_star_formation */
@@ -104,13 +106,26 @@ static void set_params(void)
         ck(mpg_set_metal_cooling_table(mpg_shim_engine(), n[0], bins[0], n[1], bins[1], n[2], bins[2], rate));
     else
         ck(mpg_set_metal_cooling_table(mpg_shim_engine(), 0, NULL, 0, NULL, 0, NULL, NULL));
+    /* init_uvf_table (cooling_uvfluc.c:158-162): the table spans the box */
+    int64_t nside;
+    double *table;
+    if(mpg_shim_uvf_table(&nside, &table))
+        ck(mpg_set_uvf_table(mpg_shim_engine(), nside, table, PartManager->BoxSize));
+    else
+        ck(mpg_set_uvf_table(mpg_shim_engine(), 0, NULL, 0));
     params_set = 1;
 }
 
-/* the device form serves one rank with the global UV background */
+/* the device form serves one rank, with the global UV background or that of a UV-fluctuation table; not the excursion set */
 static int device_cooling_usable(void)
 {
-    return mpg_shim_ntask() == 1 && !mpg_shim_uvf_in_use();
+    return mpg_shim_ntask() == 1 && !mpg_shim_excursion_set_on();
+}
+
+/* PartManager->CurrentParticleOffset (cooling_uvfluc.c:185-188) for the device call that follows */
+static void set_uvf_offset(void)
+{
+    ck(mpg_set_uvf_offset(mpg_shim_engine(), PartManager->CurrentParticleOffset));
 }
 
 /* the bin tables and the UV background of a step */
@@ -169,6 +184,7 @@ static void cool_on_device(const int *list, int64_t nlist, double Time, double h
         tb[i] = P[i].TimeBinHydro;
     }
     mpg_particle_view v = mpg_shim_view();
+    set_uvf_offset();
     if(resident)
         ck(mpg_resident_sph_cooling(mpg_shim_engine(), &v, &t, &step, list, nlist, ne, metallicity, heiii));
     else {
@@ -234,7 +250,7 @@ int mpg_shim_sfr_loop(ActiveParticles *act, double Time, double hubble, const st
     set_params();
     mpg_sfr_params sp;
     memset(&sp, 0, sizeof(sp));
-    mpg_shim_sfr_params(&sp);
+    mpg_shim_sfr_params(&sp); /* (UVFluctuationOn from UVF.enabled: set_params above has loaded that table) */
     sp.GravInternal = sfr_grav;
     sp.NTask = 1;
     const int resident = mpg_shim_resident();
@@ -328,6 +344,7 @@ int mpg_shim_sfr_loop(ActiveParticles *act, double Time, double hubble, const st
     A.vel = vel;
     A.stellarmass = stellarmass;
     mpg_particle_view v = mpg_shim_view();
+    set_uvf_offset();
     if(resident)
         ck(mpg_resident_sph_cooling_and_starformation(mpg_shim_engine(), &v, &A, &t, &step, list, nlist));
     else {
@@ -411,7 +428,7 @@ void cooling_and_starformation(ActiveParticles *act, double Time, double dloga, 
     int sfon;
     double a, b, c;
     mpg_shim_sfr_cooling(&sfon, &a, &b, &c);
-    if(!device_cooling_usable()) { /* several ranks, a UV-fluctuation table, the excursion set: the reference's own code */
+    if(!device_cooling_usable()) { /* several ranks, the excursion set: the reference's own code */
         if(mpg_shim_resident())
             endrun(5, "cooling_and_starformation(): the reference's loop inside a resident stretch (mpg_shim_resident_end first)\n");
         cpu_cooling_and_starformation(act, Time, dloga, tree, GravAccel, ddecomp, CP, GradRho, rnd, FdSfr);

@@ -149,6 +149,8 @@ append(T + "/libgadget/timebinmgr.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_
 append(T + "/libgadget/cooling_rates.c", "struct cooling_params mpg_shim_cooling_params(void) { return CoolingParams; }")
 append(T + "/libgadget/cooling.c", "struct cooling_units mpg_shim_cooling_units(void) { return coolunits; }")
 append(T + "/libgadget/cooling_uvfluc.c", "int mpg_shim_uvf_in_use(void) { return UVF.enabled || uvf_params.ExcursionSetReionOn; }\n"
+       "int mpg_shim_uvf_table(int64_t *nside, double **table) { *nside = UVF.enabled ? UVF.Nside : 0; *table = UVF.enabled ? UVF.Table : NULL; return UVF.enabled; }\n"
+       "int mpg_shim_excursion_set_on(void) { return uvf_params.ExcursionSetReionOn; }\n"
        "int mpg_shim_metal_table(int *n, double **bins, double **rate)\n{\n    if(MetalCool.CoolingNoMetal)\n        return 0;\n"
        "    n[0] = MetalCool.NRedshift_bins; n[1] = MetalCool.NHydrogenNumberDensity_bins; n[2] = MetalCool.NTemperature_bins;\n"
        "    bins[0] = MetalCool.Redshift_bins; bins[1] = MetalCool.HydrogenNumberDensity_bins; bins[2] = MetalCool.Temperature_bins;\n"
@@ -180,6 +182,7 @@ append(T + "/libgadget/sfr_eff.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_sfr
            "BoostSFDenseGas", "BoostSFOverDenseFactor", "FactorSN", "FactorEVP", "MaxSfrTimescale", "Generations", "BHFeedbackUseTcool",
            "QuickLymanAlphaProbability", "QuickLymanAlphaTempThresh", "EgySpecSN", "EgySpecCold", "PhysDensThresh", "OverDensThresh",
            "UnitSfr_in_solar_per_year", "avg_baryon_mass", "tau_fmol_unit", "WindOn"))
+       + "    { extern int mpg_shim_uvf_table(int64_t *, double **); int64_t nside; double *table; p->UVFluctuationOn = mpg_shim_uvf_table(&nside, &table); }\n"
        + "}")
 # the metal return (metals-hip.c): metal_yield is static and MetalParams file-static; a forwarding function and an accessor behind them
 append(T + "/libgadget/metal_return.c", "double mpg_shim_metal_yield(double dtmyrstart, double dtmyrend, double stellarmetal, struct MetalReturnPriv *priv, MyFloat *MetalYields, int tid, double masslow, double masshigh)\n"
