@@ -37,7 +37,10 @@ __device__ __forceinline__ void pair_force(const Src4 s, const double dx, const 
     double fac = s.m * rinv * rinv * rinv;
     double facpot = -s.m * rinv;
     if(r2 < gp.h * gp.h) { // Gadget-2 softening spline with the reference's truncated constants
-        const double u = r / gp.h;
+        // The reference takes its branch on u = sqrt(r2) / h, both correctly rounded, and with the truncated constants the two branches
+        // differ by 6e-13 where they meet.  r2 * rsqrt(r2) may sit one unit beside sqrt(r2) - a pair at r = h / 2 to the bit then took
+        // the inner branch - so r gets one Heron step here, where it decides something (rare branch; 0 stays 0).
+        const double u = fma(fma(-r, r, r2), 0.5 * rinv, r) / gp.h;
         double wpk;
         if(u < 0.5) {
             fac = s.m * gp.h3inv * (10.666666666667 + u * u * (32.0 * u - 38.4));

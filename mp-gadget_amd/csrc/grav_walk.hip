@@ -84,7 +84,10 @@ __global__ void __launch_bounds__(256, 6) k_grav_walk(const TreeView tv, const G
     const int64_t npart = tv.npart;
     int no = valid ? 0 : -1;
     int ps = 0, pc = 0;
-    double spx = px, spy = py, spz = pz; // target shifted to the periodic image of the pending range (FASTWRAP)
+    // shift (a whole number of boxes, exact) of the pending range's periodic image (FASTWRAP).  It is taken off the fp64 difference
+    // source - target, as NEAREST() does it: subtracting a target moved by a box instead rounds the target to the last place of Box, which is
+    // 1e-13 of a separation of 1e-3 across a face (a clump on a corner: 3e-14 of its absolute sum, seen against the tree-free sums)
+    double shx = 0, shy = 0, shz = 0;
     double ax = 0, ay = 0, az = 0, pot = 0;
     unsigned n_pp = 0, n_vis = 0, n_used = 0;
 
@@ -106,6 +109,7 @@ __global__ void __launch_bounds__(256, 6) k_grav_walk(const TreeView tv, const G
                 // periodic image of this node relative to the target: k = rint((c - p)/Box) per axis
                 const double kx = rint((g.cx - px) * gp.invbox), ky = rint((g.cy - py) * gp.invbox), kz = rint((g.cz - pz) * gp.invbox);
                 double qx = fma(kx, gp.box, px), qy = fma(ky, gp.box, py), qz = fma(kz, gp.box, pz);
+                double ux = kx * gp.box, uy = ky * gp.box, uz = kz * gp.box;
                 const double cdx = fabs(g.cx - qx), cdy = fabs(g.cy - qy), cdz = fabs(g.cz - qz);
                 double dx = mom.x - qx, dy = mom.y - qy, dz = mom.z - qz;
                 if(!FASTWRAP || g.len * 4.0 > gp.box) {
@@ -115,6 +119,9 @@ __global__ void __launch_bounds__(256, 6) k_grav_walk(const TreeView tv, const G
                     qx = fma(jx, gp.box, px);
                     qy = fma(jy, gp.box, py);
                     qz = fma(jz, gp.box, pz);
+                    ux = jx * gp.box;
+                    uy = jy * gp.box;
+                    uz = jz * gp.box;
                     dx = fma(-jx, gp.box, mom.x - px);
                     dy = fma(-jy, gp.box, mom.y - py);
                     dz = fma(-jz, gp.box, mom.z - pz);
@@ -136,9 +143,9 @@ __global__ void __launch_bounds__(256, 6) k_grav_walk(const TreeView tv, const G
                         // node used unopened: its moments are a 1-element source range
                         ps = (int)(npart + no);
                         pc = 1;
-                        spx = qx;
-                        spy = qy;
-                        spz = qz;
+                        shx = ux;
+                        shy = uy;
+                        shz = uz;
                         no = lk.sibling;
                         if(COUNT)
                             n_used++;
@@ -146,9 +153,9 @@ __global__ void __launch_bounds__(256, 6) k_grav_walk(const TreeView tv, const G
                     else if(lk.pcount > 0) {
                         ps = lk.pstart;
                         pc = lk.pcount;
-                        spx = qx;
-                        spy = qy;
-                        spz = qz;
+                        shx = ux;
+                        shy = uy;
+                        shz = uz;
                         no = lk.sibling;
                         if(COUNT)
                             n_pp += lk.pcount;
@@ -170,9 +177,9 @@ __global__ void __launch_bounds__(256, 6) k_grav_walk(const TreeView tv, const G
                 const Src4 sc = tv.src[ps + k];
                 double dx, dy, dz;
                 if(FASTWRAP) {
-                    dx = sc.x - spx;
-                    dy = sc.y - spy;
-                    dz = sc.z - spz;
+                    dx = (sc.x - px) - shx;
+                    dy = (sc.y - py) - shy;
+                    dz = (sc.z - pz) - shz;
                 }
                 else {
                     dx = nearest_img(sc.x - px, gp.box, gp.invbox);

@@ -32,12 +32,15 @@ namespace mpg {
 
 constexpr int STK = 160; // pending child ranges per group (LIFO): <= 7 per tree level + 8, 21 levels
 
-__device__ __forceinline__ void image_shift(const int code, const GravParams &gp, const double px, const double py, const double pz,
-                                            double &spx, double &spy, double &spz)
+// separation of a source from the target on the periodic image `code` of its range: the image's shift (whole boxes, exact) taken off the fp64
+// difference source - target, as NEAREST() does it.  (Subtracting a target moved by a box rounds the target to the last place of Box:
+// 1e-13 of a separation of 1e-3 across a face, 3e-14 of the absolute sum of a clump on a corner, seen against the tree-free sums.)
+__device__ __forceinline__ void image_diff(const int code, const GravParams &gp, const Src4 &s, const double px, const double py, const double pz,
+                                           double &dx, double &dy, double &dz)
 {
-    spx = fma((double)((code & 3) - 1), gp.box, px);
-    spy = fma((double)(((code >> 2) & 3) - 1), gp.box, py);
-    spz = fma((double)(((code >> 4) & 3) - 1), gp.box, pz);
+    dx = fma(-(double)((code & 3) - 1), gp.box, s.x - px);
+    dy = fma(-(double)(((code >> 2) & 3) - 1), gp.box, s.y - py);
+    dz = fma(-(double)(((code >> 4) & 3) - 1), gp.box, s.z - pz);
 }
 
 // counters (COUNT builds): [0] pair interactions [1] nodes visited [2] nodes used unopened
@@ -286,15 +289,8 @@ __global__ void __launch_bounds__(256, 3) k_grav_walk_coop(const TreeView tv, co
                     }
                     double dxa = 0, dya = 0, dza = 0, dxb = 0, dyb = 0, dzb = 0;
                     if(FASTWRAP) {
-                        double spx, spy, spz;
-                        image_shift(ea.y >> 4, gp, px, py, pz, spx, spy, spz);
-                        dxa = sa.x - spx;
-                        dya = sa.y - spy;
-                        dza = sa.z - spz;
-                        image_shift(eb.y >> 4, gp, px, py, pz, spx, spy, spz);
-                        dxb = sb.x - spx;
-                        dyb = sb.y - spy;
-                        dzb = sb.z - spz;
+                        image_diff(ea.y >> 4, gp, sa, px, py, pz, dxa, dya, dza);
+                        image_diff(eb.y >> 4, gp, sb, px, py, pz, dxb, dyb, dzb);
                     }
                     else {
                         dxa = sa.x - px;
@@ -335,11 +331,7 @@ __global__ void __launch_bounds__(256, 3) k_grav_walk_coop(const TreeView tv, co
                     const Src4 sc = tv.momB[it.x];
                     double dx, dy, dz;
                     if(FASTWRAP) {
-                        double spx, spy, spz;
-                        image_shift(it.y >> 4, gp, px, py, pz, spx, spy, spz);
-                        dx = sc.x - spx;
-                        dy = sc.y - spy;
-                        dz = sc.z - spz;
+                        image_diff(it.y >> 4, gp, sc, px, py, pz, dx, dy, dz);
                     }
                     else {
                         dx = sc.x - px;

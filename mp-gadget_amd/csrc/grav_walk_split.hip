@@ -73,9 +73,15 @@ __device__ __forceinline__ double rcp_nr(double x)
     return fma(fma(-x, y, 1.0), y, y);
 }
 
-__device__ __forceinline__ void softened_pair(const double r, const double m, const double hinv, const double h3inv, double &fac, double &facpot)
+// The branch is the reference's: it tests u = sqrt(r2) / h, both correctly rounded, and with the truncated constants the two branches
+// differ by 6e-13 where they meet.  r = r2 * rsqrt(r2) and r * (1 / h) may each sit a unit beside that - a pair at r = h / 2 to the bit
+// took the inner branch - so here, where u decides something, r gets one Heron step (rinv: its reciprocal) and the quotient one correction.
+__device__ __forceinline__ void softened_pair(const double r0, const double r2, const double rinv, const double m, const double h, const double hinv,
+                                              const double h3inv, double &fac, double &facpot)
 {
-    const double u = r * hinv;
+    const double r = fma(fma(-r0, r0, r2), 0.5 * rinv, r0);
+    const double q = r * hinv;
+    const double u = fma(fma(-q, h, r), hinv, q);
     double wpk;
     if(u < 0.5) {
         fac = m * h3inv * (MPG_K(10.666666666667) + u * u * (MPG_K(32.0) * u - MPG_K(38.4)));
@@ -123,9 +129,11 @@ __device__ __forceinline__ void pair_soft(const GravParams &gp, PairTmp &t)
         t.facpot = t.m * gp.hinv * -2.8;
     }
     else {
-        if(!(t.rinv < 1e150))
+        if(!(t.rinv < 1e150)) {
             t.r = 0.0;
-        softened_pair(t.r, t.m, gp.hinv, gp.h3inv, t.fac, t.facpot);
+            t.rinv = 0.0; // (r stays 0 through softened_pair's Heron step)
+        }
+        softened_pair(t.r, t.r2, t.rinv, t.m, gp.h, gp.hinv, gp.h3inv, t.fac, t.facpot);
     }
 }
 

@@ -296,7 +296,17 @@ __global__ void __launch_bounds__(256) k_leaf_moments(int64_t nnodes, int64_t np
         }
     }
     Src4 o;
-    if(m > 0) {
+    if(lk.pcount == 1 && m > 0) {
+        // The centre of mass of one particle is its position TO THE BIT, not (m x) / m, which may sit one unit in the last place beside it.
+        // The two-kernel walk lists an opened leaf of one particle by this record (k_walk_lists8, m_single): seen from that particle
+        // itself the separation must be exactly zero, or the spline's 32 m / (3 h^3) at r = 0 turns the last bit of a coordinate into
+        // a self-acceleration (1e-10 of the particle's acceleration at a softening of a tenth of the mean separation).
+        const Src4 p = src[lk.pstart];
+        o.x = p.x;
+        o.y = p.y;
+        o.z = p.z;
+    }
+    else if(m > 0) {
         o.x = sx / m;
         o.y = sy / m;
         o.z = sz / m;
