@@ -1,4 +1,5 @@
-// engine_internal.h -- the engine object behind the C-ABI handle (include/mpgadget_hip.h), shared by engine.hip, integrator.hip, host_forms.hip, resident.hip and dist.hip
+// engine_internal.h -- the engine object behind the C-ABI handle (include/mpgadget_hip.h), shared by engine.hip, physics.hip, integrator.hip,
+// host_forms.hip, resident.hip and dist.hip
 #pragma once
 #include "../../include/mpgadget_hip.h"
 #include "grav_walk.h"
@@ -213,7 +214,7 @@ extern "C" void wait_for_leaf_blocks(mpg_engine *eng, hipStream_t st);          
 // the host arrays of the SPH forms staged, `dev` filled with their device copies; the planes of a staged or resident table
 void stage_particles(mpg_engine *eng, const mpg_particle_view *P, double BoxSize);
 void stage_sph(mpg_engine *eng, const mpg_sph_arrays *host, mpg_sph_arrays *dev, int64_t n);
-// engine.hip, also used by host_forms.hip and resident.hip: the black-hole call on device arrays; when the call has a target, build == 1 builds
+// physics.hip, also used by host_forms.hip and resident.hip: the black-hole call on device arrays; when the call has a target, build == 1 builds
 // the tree of gas and black holes with hmax (from A->hsml) if the current tree is not one, build == 2 builds it in any case
 // ... and its queue pass alone: the number of targets the call would have (the host forms stage their arrays only when there is one)
 extern "C" int64_t blackhole_targets(mpg_engine *eng, const int *d_active, int64_t nactive);
@@ -223,7 +224,7 @@ extern "C" void blackhole_call(mpg_engine *eng, const mpg_blackhole_arrays *A, c
 // mask when it has a target
 extern "C" int64_t dynfric_listed(mpg_engine *eng, const int *d_active, int64_t nactive);
 extern "C" void dynfric_call(mpg_engine *eng, const mpg_bh_dynfric_arrays *A, const mpg_sph_times *T, const int *d_active, int64_t nactive);
-// ... and the helium reionisation call on device particle columns with the groups wherever `groups` finds them (engine.hip)
+// ... and the helium reionisation call on device particle columns with the groups wherever `groups` finds them (physics.hip)
 extern "C" void heiii_call(mpg_engine *eng, const mpg_heiii_step *step, const double *d_density, double *d_entropy, uint8_t *d_flag, const HeiiiGroups &groups,
                 mpg_heiii_result *result);
 // ... the groups from HOST columns (host_forms.hip)

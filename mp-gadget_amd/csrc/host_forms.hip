@@ -1,5 +1,5 @@
 // host_forms.hip -- the host-pointer ("drop-in") entry points: the caller's particle table (mpg_particle_view) and host arrays are
-// packed, uploaded, run through the mpg_dev_* calls of engine.hip and the results written back, on top of host_table.h.  The calls on a
+// packed, uploaded, run through the mpg_dev_* calls of engine.hip, physics.hip and integrator.hip and the results written back, on top of host_table.h.  The calls on a
 // device-resident table are resident.hip's.
 #include "engine_internal.h"
 #include <atomic>

@@ -706,9 +706,10 @@ def _full_size_properties(pkg, orc, ic, n):
     old = torch.full((N,), 1e-7, dtype=torch.float64, device="cuda")
     eng.dev_gravpm_force(gpm, None)
     eng.dev_force_tree_build()
+    eng.synchronize()        # (the engine's stream is not torch's: GravPM is final before torch reads it ...)
     if ic != "s_grid":       # a realistic OldAcc for the relative criterion (with 1e-7 every node of the dense clump would be opened)
         old = torch.clamp(gpm.norm(dim=1) / G, min=1e-7).contiguous()
-    eng.synchronize()
+    torch.cuda.synchronize() # (... and OldAcc, like the zeroed outputs, is final before the walk reads it)
     clk.mark("pm+tree")
     eng.dev_grav_short_tree(acc, oldacc=old)
     eng.synchronize()
