@@ -1547,7 +1547,7 @@ int mpg_dev_pm_slab_readout(mpg_engine *eng, const double *ghost_recv, const int
  * collectives the path needs as callbacks over its own communicator (run.c: MPI_Allreduce / MPI_Alltoall / MPI_Alltoallv;
  * the Python host side: torch.distributed = RCCL over xGMI), and every rank calls the mpg_dist_* functions collectively, as it
  * calls gravpm_force / force_tree_full / grav_short_tree today.  All choreography (what is sent where, in which order) is in
- * the library (csrc/dist.hip); a callback only moves bytes.
+ * the library (csrc/dist.hip and the csrc/dist_*.hip beside it); a callback only moves bytes.
  *
  * Particles live on the rank that owns their Peano-Hilbert TopLeaf (domain_decompose_full).  Per force step:
  *   PM     every particle's {Pos, Mass} goes to the rank(s) owning the x-planes its CIC cloud touches (32 B per particle: an

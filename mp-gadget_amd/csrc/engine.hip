@@ -332,7 +332,7 @@ int mpg_dev_pm_slab_readout(mpg_engine *eng, const double *ghost_recv, const int
     API_END
 }
 
-// tree of the bound particles + moments on the given stream (csrc/dist.hip: beside the PM step, from a second host thread)
+// tree of the bound particles + moments on the given stream (csrc/dist_gravity.hip: beside the PM step, from a second host thread)
 // What the default walk kernels read beside the depth-first tree - the level-ordered copy and the leaves' particles in blocks of 8 - made
 // with the tree, on the tree's stream (beside the PM force when one is queued), not at the start of the walk (rounds 1-5: 0.5 ms of every
 // walk at 256^3).  Not when the phases are being timed (the tree's phases are its own) or another kernel was selected.
@@ -471,6 +471,14 @@ int mpg_dev_force_update_hmax(mpg_engine *eng, const double *d_hsml)
     eng->sph.hsml_view = v;
     eng->sph.hmax_pending = true;
     eng->sph.calc_hmax(eng->tree, eng->stream);
+    API_END
+}
+
+int mpg_dev_force_tree_set_min_leaf_level(mpg_engine *eng, int level)
+{
+    API_BEGIN
+    MPG_CHECK(eng && level >= 0 && level <= 8, "mpg_dev_force_tree_set_min_leaf_level: level must be in [0, 8]");
+    eng->tree.force_internal_above = level;
     API_END
 }
 

@@ -1,5 +1,5 @@
 // engine_internal.h -- the engine object behind the C-ABI handle (include/mpgadget_hip.h), shared by engine.hip, physics.hip, integrator.hip,
-// host_forms.hip, resident.hip and dist.hip
+// host_forms.hip, resident.hip and the multi-rank layer (dist_internal.h, dist*.hip)
 #pragma once
 #include "../../include/mpgadget_hip.h"
 #include "grav_walk.h"
@@ -231,7 +231,7 @@ extern "C" void heiii_call(mpg_engine *eng, const mpg_heiii_step *step, const do
 HeiiiGroups heiii_host_groups(const double *mass, const double *cm, const uint64_t *minid, int64_t ngroups);
 void host_planes(mpg_engine *eng, const mpg_particle_view *P, const mpg_plane_params *par, double *planes, int64_t *npart);
 
-// potential planes (planes.hip).  red: the sums over the ranks of the several-GPU form (dist.hip), or null; sum_device returns with the
+// potential planes (planes.hip).  red: the sums over the ranks of the several-GPU form (dist_gravity.hip), or null; sum_device returns with the
 // device array summed and usable on the engine's stream
 struct PlaneReduce {
     void *ctx;

@@ -1,7 +1,7 @@
 // host_table.h -- the marshalling layer of the host-pointer ("drop-in") forms: everything that reads or writes the caller's records
 // (mpg_particle_view) and host arrays: mpg_sph_arrays through SPH_FIELDS, whose staging has rules of its own (host_forms.hip), and the
 // structs of the velocity dispersion, cooling, metal return, black holes, dynamical friction and winds through one ArrayField table each
-// and stage_fields / unstage_fields.  Used by host_forms.hip, resident.hip and dist.hip; no engine state lives here.
+// and stage_fields / unstage_fields.  Used by host_forms.hip, resident.hip and dist_host.hip; no engine state lives here.
 #pragma once
 #include "../../include/mpgadget_hip.h"
 #include "mpg_common.h"

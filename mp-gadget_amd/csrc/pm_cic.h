@@ -1,6 +1,6 @@
 // pm_cic.h -- the real-space rules of the particle mesh, each written once (device-inline): the base cell and CIC residual of a
 // position, its fold into the mesh, the slab that owns it, the corner order with its weight and mesh index, and the 4-point
-// difference stencil of the one-pass read-out.  pm.hip deposits and reads out by them, dist.hip routes particles by them: a rank
+// difference stencil of the one-pass read-out.  pm.hip deposits and reads out by them, dist_gravity.hip routes particles by them: a rank
 // receives a particle because of the same base cell that the slab kernels then find.
 // Every order of operations here is deliberate (parity with the reference is bit-sensitive): see DESIGN.md 3.3.
 #pragma once

@@ -3,7 +3,7 @@
 // The reference's force path is collective over MPI_COMM_WORLD: the export / import of tree-walk queries (treewalk.c:586-655:
 // MPI_Alltoall of counts, then MPI_Isend / MPI_Irecv per peer) and the PM mesh exchanges (petapm.c:751, 815, 869: MPI_Alltoallv).  On a
 // node of MI355X those exchanges belong on RCCL over xGMI, device memory to device memory, as stream-ordered work: this file implements
-// the three collectives csrc/dist.hip asks its caller for
+// the three collectives the multi-rank layer (csrc/dist.hip) asks its caller for
 //     alltoallv  = ncclGroupStart + one ncclSend / ncclRecv per peer with data + ncclGroupEnd  (xGMI is point to point: every pair of
 //                  GPUs has its own link, so the grouped sends of one exchange run on all links at once)
 //     allreduce  = ncclAllReduce in place
