@@ -1030,6 +1030,16 @@ int mpg_tree_export(mpg_engine *eng, int32_t *level, double *center, double *len
                     int32_t *sibling, int32_t *pstart, int32_t *pcount);
 /* Tree-order permutation: order[k] = caller index of the k-th particle in tree order (n entries). */
 int mpg_tree_export_order(mpg_engine *eng, int32_t *order);
+/* Diagnostic read-out of what the build derives from the node table for the kernels that walk it (each array may be NULL; M = numnodes).
+ * The level-ordered copy is made if it does not exist yet; the search geometry of the SPH loops and the leaf blocks of the two-kernel
+ * gravity walk are copied only where a loop or a walk has made them for the current tree, and never created here:
+ *   dfs_of_bfs[M]      pre-order number of the i-th node in level order (a stable sort by level)
+ *   linkB[M][4]        firstchild (a leaf: the merge counts of its sibling leaves, pair | quad << 4 | all << 8), nchild, pstart, pcount
+ *   geoB[M][4], momB[M][4]   (centre, len) and (cofm, mass) in level order;  hmaxB[M]: present[0]
+ *   geoS[M][4]         cube around each node's particles: present[1];  hsmaxS[M] largest smoothing length of its SPH sources: present[2]
+ *   srcL[(M+1)*8][4]   the leaves' particles in blocks of 8 (x, y, z, mass) by level-order node number: present[3] */
+int mpg_tree_export_derived(mpg_engine *eng, int32_t *dfs_of_bfs, int32_t *linkB, double *geoB, double *momB, double *hmaxB, double *geoS,
+                            double *hsmaxS, double *srcL, int32_t present[4]);
 /* Walk counters of the last grav_short_tree: [0] particle-particle interactions (= the reference's Ninteractions,
  * treewalk.c:904-912), [1] nodes visited, [2] nodes used unopened, [3] targets, [4..7] phase statistics of the
  * cooperative kernel: phase-A group steps, nodes consumed by them (of 8 tested each), phase-B lane-steps issued, of which active; [8],[9] wave clock cycles spent in phase A / phase B (summed over waves). */

@@ -1129,6 +1129,41 @@ int mpg_tree_export_order(mpg_engine *eng, int32_t *order)
     API_END
 }
 
+int mpg_tree_export_derived(mpg_engine *eng, int32_t *dfs_of_bfs, int32_t *linkB, double *geoB, double *momB, double *hmaxB, double *geoS,
+                            double *hsmaxS, double *srcL, int32_t present[4])
+{
+    API_BEGIN
+    MPG_CHECK(eng && present, "null argument");
+    MPG_CHECK(eng->tree_allocated, "no tree");
+    MPG_HIP(hipSetDevice(eng->device));
+    TreeBuilder &t = eng->tree;
+    t.ensure_level_order(eng->stream);
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    if(eng->pad_pending) // (leaf blocks being written on the tree's own stream)
+        MPG_HIP(hipEventSynchronize(eng->ev_pad_done));
+    const TreeView v = t.view();
+    const size_t M = (size_t)t.nnodes;
+    const auto out = [&](void *dst, const void *src, size_t bytes) {
+        if(dst && src)
+            MPG_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    };
+    static_assert(sizeof(NodeLinkB) == 4 * sizeof(int32_t) && sizeof(NodeGeo) == 4 * sizeof(double) && sizeof(Src4) == 4 * sizeof(double),
+                  "the read-out copies the records as they are");
+    out(dfs_of_bfs, t.nid_b.p, M * sizeof(uint32_t));
+    out(linkB, v.linkB, M * sizeof(NodeLinkB));
+    out(geoB, v.geoB, M * sizeof(NodeGeo));
+    out(momB, v.momB, M * sizeof(Src4));
+    out(hmaxB, v.hmaxB, M * sizeof(double));
+    out(geoS, v.geoS, M * sizeof(NodeGeo));
+    out(hsmaxS, v.hsmaxS, M * sizeof(double));
+    out(srcL, v.srcL, (M + 1) * 8 * sizeof(Src4));
+    present[0] = v.hmaxB != nullptr;
+    present[1] = v.geoS != nullptr;
+    present[2] = v.hsmaxS != nullptr;
+    present[3] = v.srcL != nullptr;
+    API_END
+}
+
 int mpg_walk_get_counters(mpg_engine *eng, int64_t counters[10])
 {
     API_BEGIN

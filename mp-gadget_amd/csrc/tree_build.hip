@@ -727,9 +727,10 @@ void TreeBuilder::build(int64_t n, const double *d_pos, const float *d_mass, con
     // --- sort (stable: particles with equal keys stay in caller order), leaf levels, node numbering.
     // A tree whose leaves all lie at level <= 10 is fully determined by the top 30 bits of the keys: those bits are sorted first (4 radix
     // passes instead of 8) and the leaf levels found are the check - a level-10 cell with more than 8 particles shows up as a leaf level
-    // > 10, and the sort is then done again on all bits (a clustered set: 4 passes lost).  Within a leaf of a shallow tree the particles
-    // are in caller order instead of key order: the node set and every decision are the same, sums differ by rounding.  The attempt is
-    // made for EVERY tree, whatever the builder built before: the particle order is a function of the particle set alone.
+    // > 10, and the sort is then done again on all bits (a clustered set: 4 passes lost).  Particles of a leaf of a shallow tree that agree
+    // in their first ten digits are in caller order instead of key order: the node set and every decision are the same, sums differ by
+    // rounding.  The attempt is made for EVERY tree, whatever the builder built before: the particle order is a function of the particle set
+    // alone.
     static const bool full_sort_only = getenv("MPG_TREE_FULL_SORT") != nullptr;
     bool short_sort = !full_sort_only;
     constexpr int SHORT_LEVELS = 10;

@@ -1748,6 +1748,25 @@ class Engine:
         d["order"] = order
         return d
 
+    def tree_export_derived(self):
+        """what the build derives from the node table (mpg_tree_export_derived): the level order and its copies; parts that no loop or walk
+        has made for the current tree are None"""
+        n = self.tree_stats().numnodes
+        d = dict(dfs_of_bfs=np.zeros(n, np.int32), linkB=np.zeros((n, 4), np.int32), geoB=np.zeros((n, 4)), momB=np.zeros((n, 4)),
+                 hmaxB=np.zeros(n), geoS=np.zeros((n, 4)), hsmaxS=np.zeros(n), srcL=np.zeros((n + 1, 8, 4)))
+        present = (C.c_int32 * 4)()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._ck(self.lib.mpg_tree_export_derived(self.h, *[p(d[k]) for k in ("dfs_of_bfs", "linkB", "geoB", "momB", "hmaxB", "geoS", "hsmaxS", "srcL")],
+                                                  present))
+        for k, have in zip(("hmaxB", "geoS", "hsmaxS", "srcL"), present):
+            if not have:
+                d[k] = None
+        return d
+
+    def dev_force_tree_set_min_leaf_level(self, level):
+        """domain-decomposed runs: cells above `level` are never leaves (0: the reference's tree)"""
+        self._ck(self.lib.mpg_dev_force_tree_set_min_leaf_level(self.h, int(level)))
+
     def walk_counters(self):
         c = (C.c_int64 * 10)()
         self._ck(self.lib.mpg_walk_get_counters(self.h, c))

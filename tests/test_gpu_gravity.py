@@ -48,8 +48,8 @@ def assert_accel_parity(a_hip, a_ref, errtol=0.002):
 # ------------------------------------------------------------------------------- tree
 @pytest.mark.parametrize("kind", ["grid", "clust", "tiny9", "tiny8", "one"])
 def test_tree_topology_and_moments(pkg, engine, orc, kind):
-    """Same node SET as forcetree.c produces (cell is internal iff > 8 particles), same geometry, moments to 1e-13,
-    every particle in exactly one leaf (test_forcetree.c:119-171)."""
+    """Same node SET as forcetree.c produces (cell is internal iff > 8 particles), same geometry, moments within the derived count of
+    roundings of tests/tree_restated.py (and to 1e-13 of the oracle's), every particle in exactly one leaf (test_forcetree.c:119-171)."""
     if kind == "grid":
         pos, mass, box = pkg.ics.s_grid(20)
     elif kind == "clust":
@@ -75,6 +75,14 @@ def test_tree_topology_and_moments(pkg, engine, orc, kind):
     assert np.array_equal(d["center"][live][io], t["center"][ih])        # bit-identical geometry
     assert np.array_equal(d["len"][live][io], t["len"][ih])
     assert np.allclose(d["mass"][live][io], t["mass"][ih], rtol=1e-14, atol=0)
+    # moments: the derived bound of tests/tree_restated.py (a count of roundings per node; ~100 x 2^-53 at these roots, where 1e-13 * box
+    # allowed ~900), against long-double sums over each node's own particles - for the GPU tree and for the oracle's
+    import tree_restated as TR
+    T = TR.restate(pos, mass, box)
+    ph = TR.match_by_cell(t["level"], t["center"], T)
+    TR.gate_moments(T, t["mass"][ph], t["cofm"][ph], kind + " GPU", exact_single=True)
+    po = TR.match_by_cell(d["level"][live], d["center"][live], T)
+    TR.gate_moments(T, d["mass"][live][po], d["cofm"][live][po], kind + " oracle")
     assert np.abs(d["cofm"][live][io] - t["cofm"][ih]).max() <= 1e-13 * box
     # leaves: occupancy and ownership
     nocc = np.where(d["childtype"][live] == 0, d["noccupied"][live], 0)[io]
