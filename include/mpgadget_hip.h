@@ -1365,7 +1365,9 @@ int mpg_dev_order_by_type_and_key(mpg_engine *eng, int64_t n, const unsigned cha
 /* ---- friends-of-friends groups (libgadget/fof.c) on the bound particles: primary linking of the
  * FOFPrimaryLinkTypes at the comoving linking length, secondary particles attached to the nearest primary one, groups of at
  * least FOFHaloMinLength members numbered by (Length descending, MinID).  A group is labelled by its smallest particle ID.
- * Not carried: the sub-grid group properties (Sfr, metals, black-hole masses, MaxDens / seed index) and groups that span ranks. */
+ * The sub-grid half of struct Group (Sfr, metal masses, MassHeIonized, black-hole masses, MaxDens / seed_index) and fof_seed are
+ * the calls mpg_dev_fof_subgrid / mpg_dev_fof_seed below, on ONE rank: groups that span ranks (mpg_dist_dev_fof_fof) keep the
+ * table they have, without the sub-grid members and without seeding.  Not carried: fof_set_escapefraction (EXCUR_REION). */
 typedef struct mpg_fof_params {     /* struct FOFParams, fof.c:37-48, as far as this path reads it */
     int FOFPrimaryLinkTypes;        /* bit mask of particle types, default 2 (dark matter) */
     int FOFSecondaryLinkTypes;      /* default 1 + 16 + 32 (gas, stars, black holes); disjoint from the primary types */
@@ -1387,6 +1389,82 @@ int mpg_dev_fof_fof(mpg_engine *eng, const mpg_fof_params *par, const uint64_t *
                     const unsigned char *d_flags, int64_t *d_grnr, int64_t *ngroups);
 /* the group table of the last mpg_dev_fof_fof, in MinID order (the order of fof.Group) */
 int mpg_dev_fof_groups(mpg_engine *eng, const mpg_fof_groups *out);
+
+/* ---- the sub-grid half of add_particle_to_group (fof.c:647-676) and fof_seed (fof.c:1345-1449, blackhole.c:1039-1111) on the groups
+ * of the last mpg_dev_fof_fof.  Membership, Mass and Type are those of that call and of the bound particles; garbage and swallowed
+ * rows enter the sums exactly where the FOF call made them members of a group (as in the reference, which does not test them again).
+ * Columns are device arrays in particle order, slot members (SphP / StarP / BHP) indexed by PARTICLE; entries of rows of other types
+ * are not read.  Any column may be NULL: its terms are 0, and without `density` no group gets a seed.
+ *   gas          Sfr += Sfr, GasMetalMass += Metallicity Mass, GasMetalElemMass[j] += Metals[j] Mass, MassHeIonized += Mass HeIIIionized
+ *   stars        StellarMetalMass += Metallicity Mass, StellarMetalElemMass[j] += Metals[j] Mass
+ *   black holes  BH_Mass += BHP.Mass, BH_Mdot += BHP.Mdot
+ * Every sum is fp64 with exact terms widened from the columns' types.  The reference keeps GasMetalElemMass, StellarMetalElemMass and
+ * MassHeIonized in float accumulators (fof.h:47-54); the engine returns the fp64 sums.
+ * MaxDens / seed_index: the largest Density > 0 among the gas rows of the group that are not decoupled (WindDecouple && DelayTime > 0,
+ * winds.c:114-120), and the row that has it.  THE ONE DEFINED DIFFERENCE: among rows of EQUAL largest density the reference keeps the
+ * one its qsort puts first (unspecified); the engine keeps the one of smaller particle index, whatever the order of arrival (a 64-bit
+ * atomic maximum of the density's bits, then a 64-bit atomic minimum of the index among the rows that equal it).  A group
+ * without such a row has MaxDens = 0 and seed_index = -1. */
+typedef struct mpg_fof_subgrid_columns {
+    const double *sfr;            /* SphP.Sfr */
+    const double *metallicity;    /* SphP.Metallicity of gas rows, StarP.Metallicity of star rows: one column */
+    const float *metals;          /* [n][9] SphP.Metals / StarP.Metals */
+    const uint8_t *heiii_ionized; /* P.HeIIIionized */
+    const double *bh_mass;        /* BHP.Mass */
+    const double *bh_mdot;        /* BHP.Mdot */
+    const double *density;        /* SphP.Density */
+    const double *delaytime;      /* SphP.DelayTime */
+    int WindDecouple;             /* HAS(wind_params.WindModel, WIND_DECOUPLE_SPH) */
+} mpg_fof_subgrid_columns;
+typedef struct mpg_fof_subgrid_groups { /* device arrays of ngroups entries in MinID order (as mpg_fof_groups); NULL = not wanted */
+    double *Sfr, *GasMetalMass, *StellarMetalMass;
+    double *GasMetalElemMass, *StellarMetalElemMass; /* [g][9] */
+    double *MassHeIonized, *BH_Mass, *BH_Mdot, *MaxDens;
+    int64_t *seed_index;                             /* particle index, -1: none */
+} mpg_fof_subgrid_groups;
+/* ERRORS (returned): no mpg_dev_fof_fof since the particles were last bound; the bound count differs from the FOF's.  `out` may be NULL:
+ * the sums are then only kept for mpg_dev_fof_seed. */
+int mpg_dev_fof_subgrid(mpg_engine *eng, const mpg_fof_subgrid_columns *A, const mpg_fof_subgrid_groups *out);
+
+typedef struct mpg_fof_seed_params {
+    double MinFoFMassForNewSeed, MinMStarForNewSeed;                        /* fof_params, fof.c:37-48 */
+    double SeedBlackHoleMass, MaxSeedBlackHoleMass, SeedBlackHoleMassIndex; /* blackhole_params, blackhole.c:28-54 */
+    double SeedBHDynMass;
+} mpg_fof_seed_params;
+/* the columns blackhole_make_one (blackhole.c:1056-1111) reads and writes, in particle order; slots_convert is type = 5 here.  A NULL
+ * output column is skipped.  Pos is the bound one. */
+typedef struct mpg_bh_seed_columns {
+    /* read */
+    const uint64_t *id;             /* P.ID: the power-law seed mass draws table[(ID + 23) % size], the sum wrapping as unsigned 64-bit */
+    const uint8_t *tb_hydro;        /* P.TimeBinHydro */
+    /* in / out */
+    uint8_t *type;                  /* P.Type: must be 0 for every seed (endrun 7772), becomes 5; NULL: the bound column is checked */
+    float *mass;                    /* P.Mass: becomes SeedBHDynMass when that is > 0; NULL: the bound column is read */
+    /* out */
+    double *bh_mass, *mseed;        /* BHP.Mass, BHP.Mseed */
+    double *mdot;                   /* BHP.Mdot = 0 */
+    double *formationtime;          /* BHP.FormationTime = atime */
+    uint64_t *swallowid;            /* BHP.SwallowID = (uint64) -1 */
+    double *bh_density;             /* BHP.Density = 0 */
+    uint8_t *tb_dynfric;            /* BHP.TimeBinDynFric = P.TimeBinHydro */
+    double *minpotpos;              /* [n][3] BHP.MinPotPos = P.Pos */
+    double *dfaccel, *df_surroundingvel, *dragaccel; /* [n][3] = 0 */
+    double *df_surroundingrmsvel, *df_surroundingdensity; /* = 0 */
+    int32_t *jumptominpot;          /* = 0 */
+    int32_t *countprogs;            /* = 1 */
+    double *mtrack;                 /* BHP.Mtrack = the old P.Mass when SeedBHDynMass > 0, else -1 */
+    double *kineticfdbkenergy, *vdisp; /* = 0 */
+} mpg_bh_seed_columns;
+/* fof_seed on the groups of the last mpg_dev_fof_subgrid: a group is marked when Mass >= MinFoFMassForNewSeed && MassType[4] >=
+ * MinMStarForNewSeed && LenType[5] == 0 && seed_index >= 0 (fof.c:1356-1365); the marked groups, in group (MinID) order, give the list
+ * d_seed_group[k] / d_seed_particle[k] (device arrays of `cap` entries, either may be NULL), *nseeds its length.  With `cols` every
+ * listed particle becomes a black hole (blackhole_make_one); cols == NULL: the list only.  *nwarn (may be NULL) counts the rows for
+ * which the reference prints its mass warning (blackhole.c:1105).
+ * ERRORS (returned): no mpg_dev_fof_subgrid since the last mpg_dev_fof_fof; MaxSeedBlackHoleMass > 0 with `cols` and without a random
+ * table (mpg_set_random_table) or without cols->id; a listed row that is no gas (endrun 7772): found before anything is written; cap smaller
+ * than the list: *nseeds is set, no list is written and nothing is converted, the caller repeats with room. */
+int mpg_dev_fof_seed(mpg_engine *eng, const mpg_fof_seed_params *par, double atime, const mpg_bh_seed_columns *cols, int64_t cap,
+                     int64_t *d_seed_particle, int64_t *d_seed_group, int64_t *nseeds, int64_t *nwarn);
 
 /* ---- snapshot / IC wire format: the "bigfile" blocks petaio.c reads and writes (libgadget/petaio.c:986-1120;
  * format: depends/bigfile/src/bigfile.c).  `file` is the snapshot directory (PART_000, an MP-GenIC output), `block` a column such

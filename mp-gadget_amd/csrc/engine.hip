@@ -228,6 +228,7 @@ int mpg_dev_bind_particles(mpg_engine *eng, int64_t n, const double *d_pos, cons
     MPG_CHECK(BoxSize > 0, "mpg_dev_bind_particles: BoxSize must be positive");
     eng->host_join(); // (a prefetch or a write-back of the host-pointer calls still uses the binding and the stream)
     eng->n = n;
+    eng->fof.cat_n = -1; // (a group catalogue belongs to the particles it was made of: mpg_dev_fof_subgrid asks for a new one)
     eng->d_pos = d_pos;
     eng->d_mass = d_mass;
     eng->d_type = d_type;
@@ -876,6 +877,88 @@ int mpg_dev_fof_groups(mpg_engine *eng, const mpg_fof_groups *out)
     t.Imom = out->Imom;
     t.FirstPos = out->FirstPos;
     eng->fof.export_groups(t, eng->stream);
+    API_END
+}
+
+// the sub-grid half of struct Group on the groups of the last mpg_dev_fof_fof (fof.c:647-676)
+int mpg_dev_fof_subgrid(mpg_engine *eng, const mpg_fof_subgrid_columns *A, const mpg_fof_subgrid_groups *out)
+{
+    API_BEGIN
+    MPG_CHECK(eng && A, "fof_subgrid: null argument");
+    MPG_CHECK(eng->fof.cat_n >= 0, "fof_subgrid: no mpg_dev_fof_fof since the particles were bound");
+    MPG_CHECK(eng->fof.cat_n == eng->n, "fof_subgrid: the bound particle count differs from that of the last mpg_dev_fof_fof");
+    MPG_HIP(hipSetDevice(eng->device));
+    const FofSubgridIn in{A->sfr, A->metallicity, A->metals, A->heiii_ionized, A->bh_mass, A->bh_mdot, A->density, A->delaytime, A->WindDecouple};
+    FofSubgridTable t{};
+    if(out)
+        t = FofSubgridTable{out->Sfr, out->GasMetalMass, out->StellarMetalMass, out->GasMetalElemMass, out->StellarMetalElemMass, out->MassHeIonized,
+                            out->BH_Mass, out->BH_Mdot, out->MaxDens, (long long *)out->seed_index};
+    eng->fof.subgrid(eng->n, eng->d_mass, eng->d_type, in, t, eng->stream);
+    API_END
+}
+
+// fof_seed (fof.c:1345-1449) with blackhole_make_one (blackhole.c:1056-1111) on the caller's columns
+int mpg_dev_fof_seed(mpg_engine *eng, const mpg_fof_seed_params *par, double atime, const mpg_bh_seed_columns *cols, int64_t cap,
+                     int64_t *d_seed_particle, int64_t *d_seed_group, int64_t *nseeds, int64_t *nwarn)
+{
+    API_BEGIN
+    MPG_CHECK(eng && par && nseeds && cap >= 0, "fof_seed: bad argument");
+    *nseeds = 0;
+    MPG_CHECK(eng->fof.cat_n >= 0 && eng->fof.cat_n == eng->n && eng->fof.sub_done,
+              "fof_seed: no mpg_dev_fof_subgrid since the last mpg_dev_fof_fof on the bound particles");
+    const bool powerlaw = par->MaxSeedBlackHoleMass > 0;
+    if(cols && powerlaw) {
+        MPG_CHECK(eng->bh.rndsize > 0, "fof_seed: MaxSeedBlackHoleMass > 0 needs the random table (mpg_set_random_table first)");
+        MPG_CHECK(cols->id, "fof_seed: MaxSeedBlackHoleMass > 0 needs the id column");
+    }
+    MPG_HIP(hipSetDevice(eng->device));
+    FofSeedPar p{};
+    p.MinFoFMass = par->MinFoFMassForNewSeed;
+    p.MinMStar = par->MinMStarForNewSeed;
+    p.SeedMass = par->SeedBlackHoleMass;
+    p.MaxSeedMass = par->MaxSeedBlackHoleMass;
+    p.SeedDynMass = par->SeedBHDynMass;
+    if(powerlaw) { // the constants of bh_powerlaw_seed_mass (blackhole.c:1044-1051), once per call
+        const double x1 = 1 + par->SeedBlackHoleMassIndex;
+        p.pl_p0 = pow(par->SeedBlackHoleMass, x1);
+        p.pl_norm = pow(par->MaxSeedBlackHoleMass, x1) - p.pl_p0;
+        p.pl_inv = 1. / x1;
+    }
+    p.atime = atime;
+    p.rnd = eng->bh.rnd.p;
+    p.rndsize = (uint64_t)eng->bh.rndsize;
+    FofSeedCols c{};
+    if(cols) {
+        c.id = (const unsigned long long *)cols->id;
+        c.tb_hydro = cols->tb_hydro;
+        c.pos = eng->d_pos;
+        c.type_in = cols->type ? cols->type : eng->d_type;
+        c.mass_in = cols->mass ? cols->mass : eng->d_mass;
+        c.type = cols->type;
+        c.mass = cols->mass;
+        c.bh_mass = cols->bh_mass;
+        c.mseed = cols->mseed;
+        c.mdot = cols->mdot;
+        c.formationtime = cols->formationtime;
+        c.swallowid = (unsigned long long *)cols->swallowid;
+        c.bh_density = cols->bh_density;
+        c.tb_dynfric = cols->tb_dynfric;
+        c.minpotpos = cols->minpotpos;
+        c.dfaccel = cols->dfaccel;
+        c.df_surroundingvel = cols->df_surroundingvel;
+        c.dragaccel = cols->dragaccel;
+        c.df_surroundingrmsvel = cols->df_surroundingrmsvel;
+        c.df_surroundingdensity = cols->df_surroundingdensity;
+        c.jumptominpot = cols->jumptominpot;
+        c.countprogs = cols->countprogs;
+        c.mtrack = cols->mtrack;
+        c.kineticfdbkenergy = cols->kineticfdbkenergy;
+        c.vdisp = cols->vdisp;
+    }
+    bool notgas = false;
+    *nseeds = eng->fof.seed(p, cols ? &c : nullptr, cap, (long long *)d_seed_particle, (long long *)d_seed_group, nwarn, &notgas, eng->stream);
+    MPG_CHECK(!notgas, "fof_seed: a seed row is no gas particle (only gas turns into black holes, blackhole.c:1057); nothing was converted");
+    MPG_CHECK(*nseeds <= cap, "fof_seed: the seed list needs more room than cap (*nseeds is set; nothing was converted)");
     API_END
 }
 

@@ -18,8 +18,11 @@
 //   k_fof_secondary the same neighbour search around each secondary particle, keeping the nearest primary
 //   catalogue       radix sort of (label, particle), run lengths = group lengths, the groups long enough are selected in label
 //                   order, ranked by a stable sort on length, and their properties are summed with wave-aggregated atomics
-// Not carried: the sub-grid group properties (star formation rate, metals, black-hole masses, MaxDens / seeding), ghosts of
-// other ranks (a group is complete on one GPU).
+//   sub-grid sums   k_fof_subgrid: the other half of add_particle_to_group (fof.c:647-676: Sfr, metal masses, MassHeIonized, BH_Mass,
+//                   BH_Mdot) summed by segments of a wave; MaxDens / seed_index in two order-independent passes (k_fof_seed_index)
+//   fof_seed        fof.c:1345-1449: k_fof_seed_mark, the marked groups compacted in group order, k_blackhole_make_one
+//                   (blackhole.c:1039-1111) on the caller's columns
+// Not carried: ghosts of other ranks (a group is complete on one GPU; dist_fof.hip adds the parts up, without the sub-grid sums).
 #include "fof.h"
 #include "ngb_walk.h"
 #include "timestep.h"
@@ -395,12 +398,257 @@ __global__ void __launch_bounds__(256) k_fof_export(int64_t ng, const unsigned l
             out.Imom[9 * g + c] = a[16 + c];
 }
 
+// ---- the sub-grid half of add_particle_to_group (fof.c:647-676) ----
+// the group (index in MinID order) of particle i from P[].GrNr, or -1
+__device__ __forceinline__ int group_of(const long long *__restrict__ p_grnr, const int *__restrict__ rank_order, int64_t i)
+{
+    const long long r = p_grnr[i];
+    return r > 0 ? rank_order[r - 1] : -1;
+}
+
+// a gas row that may become a seed (fof.c:670, winds.c:114-120): the bits of its density, 0 otherwise.  Positive doubles order as their bits.
+__device__ __forceinline__ unsigned long long seed_bits(const FofSubgridIn &c, int64_t i)
+{
+    const double d = c.density[i];
+    if(!(d > 0) || (c.WindDecouple && c.delaytime && c.delaytime[i] > 0))
+        return 0ull;
+    return (unsigned long long)__double_as_longlong(d);
+}
+
+// Rows in label order: the rows of a group are consecutive, so the lanes of a wave fall into segments of equal group index (with
+// FOFHaloMinLength small a wave holds many, and rows of no kept group between them).  Every quantity is summed over each segment with six
+// masked __shfl_down steps - step s adds the lane 2^s further on when it lies in the same segment, which, segments being contiguous,
+// leaves the segment's total in its head lane - and the head lane issues ONE atomic per non-zero quantity.  No LDS, no barrier: a
+// block-wide LDS form would hold 256 x 24 doubles (48 KiB) or take the quantities in passes, for sums that cross waves only where a group
+// does.  Gas, star and black-hole quantities are skipped by waves that hold no such row (a wave-uniform test).
+__global__ void __launch_bounds__(256) k_fof_subgrid(int64_t n, const int *__restrict__ sidx, const long long *__restrict__ p_grnr,
+                                                     const int *__restrict__ rank_order, const float *__restrict__ mass,
+                                                     const uint8_t *__restrict__ type, const FofSubgridIn c, double *__restrict__ sum,
+                                                     unsigned long long *__restrict__ maxbits)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int g = -1, t = -1;
+    int64_t i = 0;
+    if(k < n) {
+        i = sidx[k];
+        g = group_of(p_grnr, rank_order, i);
+        if(g >= 0)
+            t = type ? type[i] : 1;
+    }
+    const bool gas = t == 0, star = t == 4, bh = t == 5;
+    const bool any_gas = __builtin_amdgcn_ballot_w64(gas) != 0, any_star = __builtin_amdgcn_ballot_w64(star) != 0,
+               any_bh = __builtin_amdgcn_ballot_w64(bh) != 0;
+    if(!(any_gas || any_star || any_bh))
+        return;
+    // the segment of this lane: its head, and for every step whether the lane 2^s further on belongs to it
+    const int gprev = __shfl_up(g, 1);
+    const bool head = g >= 0 && (lane == 0 || gprev != g);
+    unsigned same = 0;
+    for(int s = 0; s < 6; s++) {
+        const int go = __shfl_down(g, 1 << s);
+        if(lane + (1 << s) < 64 && go == g)
+            same |= 1u << s;
+    }
+    auto emit = [&](int q, double x) {
+        for(int s = 0; s < 6; s++) {
+            const double y = __shfl_down(x, 1 << s);
+            if(same & (1u << s))
+                x += y;
+        }
+        if(head && x != 0.0)
+            unsafeAtomicAdd(&sum[(size_t)g * FOF_NSUB + q], x);
+    };
+    double m = 0, zm = 0, em[9];
+    for(int j = 0; j < 9; j++)
+        em[j] = 0;
+    if(gas || star) { // the 36-byte rows of Metals are read for these rows only
+        m = (double)mass[i];
+        zm = c.metallicity ? c.metallicity[i] * m : 0.0;
+        if(c.metals)
+            for(int j = 0; j < 9; j++)
+                em[j] = (double)c.metals[9 * i + j] * m; // exact: two widened floats
+    }
+    if(any_gas) {
+        emit(0, gas && c.sfr ? c.sfr[i] : 0.0);
+        emit(1, gas ? zm : 0.0);
+        for(int j = 0; j < 9; j++)
+            emit(2 + j, gas ? em[j] : 0.0);
+        emit(11, gas && c.heiii && c.heiii[i] ? m : 0.0);
+        if(c.density) { // MaxDens, first pass: the largest bits of the segment, one atomic maximum per segment
+            unsigned long long b = gas ? seed_bits(c, i) : 0ull;
+            for(int s = 0; s < 6; s++) {
+                const unsigned long long o = __shfl_down(b, 1 << s);
+                if((same & (1u << s)) && o > b)
+                    b = o;
+            }
+            if(head && b)
+                atomicMax(&maxbits[g], b);
+        }
+    }
+    if(any_star) {
+        emit(12, star ? zm : 0.0);
+        for(int j = 0; j < 9; j++)
+            emit(13 + j, star ? em[j] : 0.0);
+    }
+    if(any_bh) {
+        emit(22, bh && c.bh_mass ? c.bh_mass[i] : 0.0);
+        emit(23, bh && c.bh_mdot ? c.bh_mdot[i] : 0.0);
+    }
+}
+
+// seed_index, second pass (particle order): among the rows that hold their group's MaxDens, the smallest particle index
+__global__ void __launch_bounds__(256) k_fof_seed_index(int64_t n, const long long *__restrict__ p_grnr, const int *__restrict__ rank_order,
+                                                        const uint8_t *__restrict__ type, const FofSubgridIn c,
+                                                        const unsigned long long *__restrict__ maxbits, unsigned long long *__restrict__ seed)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n || !type || type[i] != 0)
+        return;
+    const int g = group_of(p_grnr, rank_order, i);
+    if(g < 0)
+        return;
+    const unsigned long long b = seed_bits(c, i);
+    if(b && b == maxbits[g])
+        atomicMin(&seed[g], (unsigned long long)i);
+}
+
+__global__ void __launch_bounds__(256) k_fof_subgrid_export(int64_t ng, const double *__restrict__ sum, const unsigned long long *__restrict__ maxbits,
+                                                            long long *__restrict__ seed, FofSubgridTable out)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(g >= ng)
+        return;
+    const double *a = sum + (size_t)g * FOF_NSUB;
+    if(maxbits[g] == 0)
+        seed[g] = -1; // (held ~0 for the atomic minimum)
+    if(out.Sfr)
+        out.Sfr[g] = a[0];
+    if(out.GasMetalMass)
+        out.GasMetalMass[g] = a[1];
+    if(out.MassHeIonized)
+        out.MassHeIonized[g] = a[11];
+    if(out.StellarMetalMass)
+        out.StellarMetalMass[g] = a[12];
+    for(int j = 0; j < 9; j++) {
+        if(out.GasMetalElemMass)
+            out.GasMetalElemMass[9 * g + j] = a[2 + j];
+        if(out.StellarMetalElemMass)
+            out.StellarMetalElemMass[9 * g + j] = a[13 + j];
+    }
+    if(out.BH_Mass)
+        out.BH_Mass[g] = a[22];
+    if(out.BH_Mdot)
+        out.BH_Mdot[g] = a[23];
+    if(out.MaxDens)
+        out.MaxDens[g] = __longlong_as_double((long long)maxbits[g]);
+    if(out.seed_index)
+        out.seed_index[g] = seed[g];
+}
+
+// fof_seed's marks, fof.c:1356-1365
+__global__ void __launch_bounds__(256) k_fof_seed_mark(int64_t ng, const double *__restrict__ acc, const int *__restrict__ lentype,
+                                                       const long long *__restrict__ seed, double minmass, double minmstar, uint8_t *__restrict__ keep)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(g < ng)
+        keep[g] = (acc[(size_t)g * NQ] >= minmass && acc[(size_t)g * NQ + 1 + 4] >= minmstar && lentype[6 * g + 5] == 0 && seed[g] >= 0) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(256) k_fof_seed_list(int64_t ns, const long long *__restrict__ seed_g, const long long *__restrict__ seed,
+                                                       long long *__restrict__ d_group, long long *__restrict__ d_particle)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(s >= ns)
+        return;
+    if(d_group)
+        d_group[s] = seed_g[s];
+    if(d_particle)
+        d_particle[s] = seed[seed_g[s]];
+}
+
+// blackhole_make_one's test (blackhole.c:1057), before anything is written
+__global__ void __launch_bounds__(256) k_fof_seed_check(int64_t ns, const long long *__restrict__ seed_g, const long long *__restrict__ seed,
+                                                        const uint8_t *__restrict__ type, unsigned *__restrict__ err)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(s < ns && (!type || type[seed[seed_g[s]]] != 0))
+        atomicOr(err, 1u);
+}
+
+// blackhole_make_one, blackhole.c:1056-1111, one lane per seed; bh_powerlaw_seed_mass, :1039-1053
+__global__ void __launch_bounds__(256) k_blackhole_make_one(int64_t ns, const long long *__restrict__ seed_g, const long long *__restrict__ seed,
+                                                            const FofSeedPar p, const FofSeedCols c, unsigned long long *__restrict__ nwarn)
+{
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(s >= ns)
+        return;
+    const int64_t i = seed[seed_g[s]];
+    if(c.type)
+        c.type[i] = 5; // slots_convert: slot members are columns indexed by particle
+    double bhm = p.SeedMass;
+    if(p.MaxSeedMass > 0) {
+        const double w = p.rnd[(c.id[i] + 23ull) % p.rndsize]; // get_random_number(ID + 23): the sum wraps as unsigned 64-bit
+        bhm = pow(w * p.pl_norm + p.pl_p0, p.pl_inv);
+    }
+    if(c.bh_mass)
+        c.bh_mass[i] = bhm;
+    if(c.mseed)
+        c.mseed[i] = bhm;
+    if(c.mdot)
+        c.mdot[i] = 0;
+    if(c.formationtime)
+        c.formationtime[i] = p.atime;
+    if(c.swallowid)
+        c.swallowid[i] = ~0ull;
+    if(c.bh_density)
+        c.bh_density[i] = 0;
+    if(c.tb_dynfric && c.tb_hydro)
+        c.tb_dynfric[i] = c.tb_hydro[i];
+    for(int d = 0; d < 3; d++) {
+        if(c.minpotpos)
+            c.minpotpos[3 * i + d] = c.pos[3 * i + d];
+        if(c.dfaccel)
+            c.dfaccel[3 * i + d] = 0;
+        if(c.df_surroundingvel)
+            c.df_surroundingvel[3 * i + d] = 0;
+        if(c.dragaccel)
+            c.dragaccel[3 * i + d] = 0;
+    }
+    if(c.df_surroundingrmsvel)
+        c.df_surroundingrmsvel[i] = 0;
+    if(c.df_surroundingdensity)
+        c.df_surroundingdensity[i] = 0;
+    if(c.jumptominpot)
+        c.jumptominpot[i] = 0;
+    if(c.countprogs)
+        c.countprogs[i] = 1;
+    float pm = c.mass_in[i];
+    double mtrack = -1; // (this column is not used then)
+    if(p.SeedDynMass > 0) {
+        mtrack = (double)pm;
+        pm = (float)p.SeedDynMass; // P.Mass is a float
+        if(c.mass)
+            c.mass[i] = pm;
+    }
+    if(c.mtrack)
+        c.mtrack[i] = mtrack;
+    if((double)pm < bhm || (double)pm < mtrack) // the reference's warning, :1105
+        atomicAdd(nwarn, 1ull);
+    if(c.kineticfdbkenergy)
+        c.kineticfdbkenergy[i] = 0;
+    if(c.vdisp)
+        c.vdisp[i] = 0;
+}
+
 } // namespace
 
 int64_t FofEngine::run(TreeBuilder &tree, const FofInput &in, hipStream_t st)
 {
     compute_labels(tree, in, st);
-    return catalogue(in, in.n, nullptr, 0, true, st);
+    const int64_t ng = catalogue(in, in.n, nullptr, 0, true, st);
+    cat_n = in.n; // (the catalogue of one rank's whole groups: what subgrid() and seed() work on)
+    return ng;
 }
 
 // primary linking + secondary attachment: label[i] = the smallest ID of the particles linked with i (its own ID if none)
@@ -409,6 +657,8 @@ void FofEngine::compute_labels(TreeBuilder &tree, const FofInput &in, hipStream_
     const int64_t n = in.n;
     const int64_t np = tree.npart;
     ngroups = 0;
+    cat_n = -1;
+    sub_done = false;
     err.reserve(4);
     MPG_HIP(hipMemsetAsync(err.p, 0, sizeof(unsigned), st));
     label.reserve((size_t)n + 1);
@@ -541,6 +791,83 @@ void FofEngine::export_groups(const FofTable &out, hipStream_t st)
         hipLaunchKernelGGL(k_fof_export, dim3(nblk(ngroups)), dim3(256), 0, st, ngroups, (const unsigned long long *)g_minid.p, g_len.p, g_grnr.p,
                            g_lentype.p, g_acc.p, g_first.p, out);
     MPG_HIP(hipGetLastError());
+}
+
+void FofEngine::subgrid(int64_t n, const float *mass, const uint8_t *type, const FofSubgridIn &in, const FofSubgridTable &out, hipStream_t st)
+{
+    sub_done = false;
+    const int64_t ng = ngroups;
+    if(ng > 0 && n > 0) {
+        s_sum.reserve((size_t)ng * FOF_NSUB);
+        s_maxbits.reserve((size_t)ng);
+        s_seed.reserve((size_t)ng);
+        MPG_HIP(hipMemsetAsync(s_sum.p, 0, (size_t)ng * FOF_NSUB * sizeof(double), st));
+        MPG_HIP(hipMemsetAsync(s_maxbits.p, 0, (size_t)ng * sizeof(unsigned long long), st));
+        MPG_HIP(hipMemsetAsync(s_seed.p, 0xff, (size_t)ng * sizeof(long long), st));
+        // (ord_b of the catalogue: the group of every number, fof.c:1127-1134)
+        hipLaunchKernelGGL(k_fof_subgrid, dim3(nblk(n)), dim3(256), 0, st, n, (const int *)sidx.p, (const long long *)p_grnr.p, (const int *)ord_b.p, mass,
+                           type, in, s_sum.p, s_maxbits.p);
+        if(in.density)
+            hipLaunchKernelGGL(k_fof_seed_index, dim3(nblk(n)), dim3(256), 0, st, n, (const long long *)p_grnr.p, (const int *)ord_b.p, type, in,
+                               (const unsigned long long *)s_maxbits.p, (unsigned long long *)s_seed.p);
+        hipLaunchKernelGGL(k_fof_subgrid_export, dim3(nblk(ng)), dim3(256), 0, st, ng, (const double *)s_sum.p, (const unsigned long long *)s_maxbits.p,
+                           s_seed.p, out);
+    }
+    MPG_HIP(hipGetLastError());
+    sub_done = true;
+}
+
+int64_t FofEngine::seed(const FofSeedPar &par, const FofSeedCols *cols, int64_t cap, long long *d_particle, long long *d_group, int64_t *nwarn,
+                        bool *notgas, hipStream_t st)
+{
+    *notgas = false;
+    if(nwarn)
+        *nwarn = 0;
+    const int64_t ng = ngroups;
+    if(ng == 0)
+        return 0;
+    keep.reserve((size_t)ng + 1);
+    seed_g.reserve((size_t)ng + 1);
+    cnt.reserve(8);
+    err.reserve(4);
+    hipLaunchKernelGGL(k_fof_seed_mark, dim3(nblk(ng)), dim3(256), 0, st, ng, (const double *)g_acc.p, (const int *)g_lentype.p, (const long long *)s_seed.p,
+                       par.MinFoFMass, par.MinMStar, keep.p);
+    size_t b = 0;
+    rocprim::counting_iterator<long long> groups(0);
+    MPG_HIP(rocprim::select(nullptr, b, groups, keep.p, seed_g.p, cnt.p + 3, (size_t)ng, st));
+    tmp.reserve(b + 16);
+    MPG_HIP(rocprim::select((void *)tmp.p, b, groups, keep.p, seed_g.p, cnt.p + 3, (size_t)ng, st));
+    unsigned long long ns = 0;
+    MPG_HIP(hipMemcpyAsync(&ns, cnt.p + 3, sizeof(ns), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipStreamSynchronize(st));
+    if(ns == 0 || (int64_t)ns > cap)
+        return (int64_t)ns;
+    if(cols) {
+        MPG_HIP(hipMemsetAsync(err.p, 0, sizeof(unsigned), st));
+        hipLaunchKernelGGL(k_fof_seed_check, dim3(nblk((int64_t)ns)), dim3(256), 0, st, (int64_t)ns, (const long long *)seed_g.p, (const long long *)s_seed.p,
+                           cols->type_in, err.p);
+        unsigned e = 0;
+        MPG_HIP(hipMemcpyAsync(&e, err.p, sizeof(e), hipMemcpyDeviceToHost, st));
+        MPG_HIP(hipStreamSynchronize(st));
+        if(e) {
+            *notgas = true;
+            return (int64_t)ns;
+        }
+    }
+    hipLaunchKernelGGL(k_fof_seed_list, dim3(nblk((int64_t)ns)), dim3(256), 0, st, (int64_t)ns, (const long long *)seed_g.p, (const long long *)s_seed.p,
+                       d_group, d_particle);
+    if(cols) {
+        MPG_HIP(hipMemsetAsync(cnt.p + 4, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(k_blackhole_make_one, dim3(nblk((int64_t)ns)), dim3(256), 0, st, (int64_t)ns, (const long long *)seed_g.p,
+                           (const long long *)s_seed.p, par, *cols, cnt.p + 4);
+        unsigned long long w = 0;
+        MPG_HIP(hipMemcpyAsync(&w, cnt.p + 4, sizeof(w), hipMemcpyDeviceToHost, st));
+        MPG_HIP(hipStreamSynchronize(st));
+        if(nwarn)
+            *nwarn = (int64_t)w;
+    }
+    MPG_HIP(hipGetLastError());
+    return (int64_t)ns;
 }
 
 } // namespace mpg

@@ -151,6 +151,7 @@ static void stage_particles_body(mpg_engine *eng, const mpg_particle_view *P, do
         MPG_HIP(hipEventRecord(eng->ev_acc_up, eng->copy_stream));
     }
     eng->n = n;
+    eng->fof.cat_n = -1; // (a group catalogue belongs to the particles it was made of)
     eng->d_pos = eng->s_pos.p;
     eng->d_mass = eng->s_mass.p;
     eng->d_type = eng->s_type.p;

@@ -416,6 +416,38 @@ class FofGroupsC(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("MinID", "Length", "GrNr", "LenType", "Mass", "MassType", "CM", "Vel", "Jmom", "Imom", "FirstPos")]
 
 
+FOF_SUBGRID_COLUMNS = ("sfr", "metallicity", "metals", "heiii_ionized", "bh_mass", "bh_mdot", "density", "delaytime")
+FOF_SUBGRID_DTYPES = dict(metals="float32", heiii_ionized="uint8")
+FOF_SUBGRID_GROUPS = ("Sfr", "GasMetalMass", "StellarMetalMass", "GasMetalElemMass", "StellarMetalElemMass", "MassHeIonized", "BH_Mass", "BH_Mdot",
+                      "MaxDens", "seed_index")
+BH_SEED_COLUMNS = ("id", "tb_hydro", "type", "mass", "bh_mass", "mseed", "mdot", "formationtime", "swallowid", "bh_density", "tb_dynfric",
+                   "minpotpos", "dfaccel", "df_surroundingvel", "dragaccel", "df_surroundingrmsvel", "df_surroundingdensity", "jumptominpot",
+                   "countprogs", "mtrack", "kineticfdbkenergy", "vdisp")
+BH_SEED_DTYPES = dict(id="uint64", swallowid="uint64", tb_hydro="uint8", type="uint8", tb_dynfric="uint8", mass="float32", jumptominpot="int32",
+                      countprogs="int32")
+
+
+class FofSubgridColumnsC(C.Structure):
+    """mpg_fof_subgrid_columns"""
+    _fields_ = [(k, C.c_void_p) for k in FOF_SUBGRID_COLUMNS] + [("WindDecouple", C.c_int)]
+
+
+class FofSubgridGroupsC(C.Structure):
+    """mpg_fof_subgrid_groups"""
+    _fields_ = [(k, C.c_void_p) for k in FOF_SUBGRID_GROUPS]
+
+
+class FofSeedParams(C.Structure):
+    """mpg_fof_seed_params"""
+    _fields_ = [(k, C.c_double) for k in ("MinFoFMassForNewSeed", "MinMStarForNewSeed", "SeedBlackHoleMass", "MaxSeedBlackHoleMass",
+                                          "SeedBlackHoleMassIndex", "SeedBHDynMass")]
+
+
+class BhSeedColumnsC(C.Structure):
+    """mpg_bh_seed_columns"""
+    _fields_ = [(k, C.c_void_p) for k in BH_SEED_COLUMNS]
+
+
 GRAVKICK_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_int64, C.c_int64)
 # mpg_nu_response_fn (include/mpgadget_hip.h): (ctx, nonzero, kk, delta_cdm, Nmodes, logknu, delta_nu_ratio, nu_prefac, MtotbyMcdm) -> int
 NU_RESPONSE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64),
@@ -1055,6 +1087,45 @@ class Engine:
         out = FofGroupsC(*[g[k].data_ptr() for k in ("MinID", "Length", "GrNr", "LenType", "Mass", "MassType", "CM", "Vel", "Jmom", "Imom", "FirstPos")])
         self._ck(self.lib.mpg_dev_fof_groups(self.h, C.byref(out)))
         return g
+
+    def dev_fof_subgrid(self, ngroups, WindDecouple=0, device="cuda", **columns):
+        """mpg_dev_fof_subgrid on the groups of the last dev_fof_fof: the sub-grid half of struct Group as a dict of device tensors
+        (MinID order, fp64 sums, seed_index int64).  columns: device tensors in particle order named as in FOF_SUBGRID_COLUMNS
+        (float64; metals float32 [n][9], heiii_ionized uint8); a column left out or None contributes nothing."""
+        import torch
+        bad = set(columns) - set(FOF_SUBGRID_COLUMNS)
+        if bad:
+            raise EngineError("dev_fof_subgrid: unknown column(s) %s" % sorted(bad))
+        A = FofSubgridColumnsC(*[_ptr(columns.get(k)) for k in FOF_SUBGRID_COLUMNS], int(WindDecouple))
+        mk = lambda shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=device)
+        g = {k: mk((ngroups, 9)) if k.endswith("ElemMass") else mk(ngroups) for k in FOF_SUBGRID_GROUPS[:-1]}
+        g["seed_index"] = mk(ngroups, torch.int64)
+        out = FofSubgridGroupsC(*[g[k].data_ptr() for k in FOF_SUBGRID_GROUPS])
+        self._ck(self.lib.mpg_dev_fof_subgrid(self.h, C.byref(A), C.byref(out)))
+        return g
+
+    def dev_fof_seed(self, params, atime, columns=None, cap=None, device="cuda"):
+        """mpg_dev_fof_seed on the groups of the last dev_fof_subgrid.  params: FofSeedParams; columns: dict of device tensors named as in
+        BH_SEED_COLUMNS (element types BH_SEED_DTYPES, float64 otherwise), updated in place, or None for the list alone.  Returns
+        (seed_particle, seed_group, nwarn): int64 device tensors of the list's length.  cap: the room offered (default: as much as the
+        list needs); when it is too small an EngineError carrying .nseeds is raised and nothing is converted."""
+        import torch
+        A = None if columns is None else _dev_arrays(BhSeedColumnsC, columns)
+        ns, nw = C.c_int64(0), C.c_int64(0)
+        if cap is None:       # the length first: the list alone into no room
+            rc = self.lib.mpg_dev_fof_seed(self.h, C.byref(params), C.c_double(atime), None, C.c_int64(0), None, None, C.byref(ns), None)
+            if rc and ns.value == 0:
+                self._ck(rc)
+            cap = ns.value
+        part = torch.zeros(cap, dtype=torch.int64, device=device)
+        grp = torch.zeros(cap, dtype=torch.int64, device=device)
+        rc = self.lib.mpg_dev_fof_seed(self.h, C.byref(params), C.c_double(atime), None if A is None else C.byref(A), C.c_int64(cap), _ptr(part),
+                                       _ptr(grp), C.byref(ns), C.byref(nw))
+        if rc:
+            e = EngineError(self.lib.mpg_last_error().decode())
+            e.nseeds = ns.value
+            raise e
+        return part[:ns.value], grp[:ns.value], nw.value
 
     # hierarchical gravity (timestep.c:239-599)
     @staticmethod
