@@ -366,7 +366,9 @@ int mpg_veldisp_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iter
  * lastred = 1 / exp(loga_from_ti(Ti_Current - dti_from_timebin(bin))) - 1 (sfr_eff.c:483-484).
  * With a UV-fluctuation table loaded (mpg_set_uvf_table below) every row takes the background of get_local_UVBG_from_global at its own
  * position, and the HIReionTemp test reads the row's own zreion.
- * Not carried: EXCUR_REION's local_J21, cooling_relaxed, star formation and winds (mpg_dev_cooling_and_starformation has the last three);
+ * Not carried: the READ of EXCUR_REION's local_J21 / zreion (get_local_UVBG_from_J21; the two columns are made by mpg_dev_calculate_uvbg
+ * below and read by the caller's own cooling loop), cooling_relaxed, star formation and winds (mpg_dev_cooling_and_starformation has the
+ * last three);
  * several ranks each call this form on their own gas (the loop is per particle).
  * Every loop is bounded: the two limits of 1000 are the reference's (cooling.c:32, cooling_rates.c:768); the two bracketing loops, which the
  * reference leaves unbounded, stop after 8192 steps.  A particle that hits a limit, or whose electron abundance is not finite, keeps its
@@ -464,8 +466,8 @@ int mpg_cooling_export(mpg_engine *eng, int64_t n, int32_t *evaluations);
  * cells BoxSize / (Nside - 1) wide and wrapped after Nside of them, so the table's period is BoxSize Nside / (Nside - 1) as in the
  * reference.  A row whose position is not finite, or 2^31 cells or more from the origin (the reference: undefined), gets zreion = NaN
  * without a read of the table, keeps Entropy / Ne / Sfr, counts in stats[5] and makes the call return non-zero after all other rows are
- * done.  Without a table every call is bit for bit what it is without this section.  The excursion set (EXCUR_REION, local_J21) is a
- * different model and is not carried. */
+ * done.  Without a table every call is bit for bit what it is without this section.  The excursion set (EXCUR_REION) is a
+ * different model: its producer is mpg_dev_calculate_uvbg below; its consumer in this loop, get_local_UVBG_from_J21, is not carried. */
 /* init_uvf_table (cooling_uvfluc.c:115-167) without the file: Zreion_Table[Nside][Nside][Nside], C order, from HOST memory; table == NULL
  * removes it.  Refused: Nside < 2, BoxSize <= 0, a non-finite entry, Table[0] outside [0.01, 100] (:164). */
 int mpg_set_uvf_table(mpg_engine *eng, int64_t Nside, const double *table, double BoxSize);
@@ -1367,7 +1369,8 @@ int mpg_dev_order_by_type_and_key(mpg_engine *eng, int64_t n, const unsigned cha
  * least FOFHaloMinLength members numbered by (Length descending, MinID).  A group is labelled by its smallest particle ID.
  * The sub-grid half of struct Group (Sfr, metal masses, MassHeIonized, black-hole masses, MaxDens / seed_index) and fof_seed are
  * the calls mpg_dev_fof_subgrid / mpg_dev_fof_seed below, on ONE rank: groups that span ranks (mpg_dist_dev_fof_fof) keep the
- * table they have, without the sub-grid members and without seeding.  Not carried: fof_set_escapefraction (EXCUR_REION). */
+ * table they have, without the sub-grid members and without seeding.  fof_set_escapefraction (EXCUR_REION) is
+ * mpg_dev_fof_set_escapefraction below, on one rank as well. */
 typedef struct mpg_fof_params {     /* struct FOFParams, fof.c:37-48, as far as this path reads it */
     int FOFPrimaryLinkTypes;        /* bit mask of particle types, default 2 (dark matter) */
     int FOFSecondaryLinkTypes;      /* default 1 + 16 + 32 (gas, stars, black holes); disjoint from the primary types */
@@ -1465,6 +1468,67 @@ typedef struct mpg_bh_seed_columns {
  * than the list: *nseeds is set, no list is written and nothing is converted, the caller repeats with room. */
 int mpg_dev_fof_seed(mpg_engine *eng, const mpg_fof_seed_params *par, double atime, const mpg_bh_seed_columns *cols, int64_t cap,
                      int64_t *d_seed_particle, int64_t *d_seed_group, int64_t *nseeds, int64_t *nwarn);
+
+/* fof_set_escapefraction (fof.c:832-870, EXCUR_REION) on the groups of the last mpg_dev_fof_fof: d_escfrac[n] (device, particle order)
+ * receives Group.Mass for every gas or star row that is a member of a group and 0 for every other gas or star row; rows of other types
+ * are left untouched.  The value is the Mass column of mpg_dev_fof_groups bit for bit.  mpg_dev_calculate_uvbg converts it.
+ * ERRORS (returned): those of mpg_dev_fof_subgrid. */
+int mpg_dev_fof_set_escapefraction(mpg_engine *eng, double *d_escfrac);
+
+/* ---- excursion-set reionisation (EXCUR_REION; libgadget/uvbg.c:471-594 through petapm_reion, petapm.c:381-577) on the bound particles
+ * of ONE rank: the producer of SphP.local_J21 / SphP.zreion.  The consumer (get_local_UVBG_from_J21 in cooling and star formation) is
+ * not carried: mpg_set_sfr_params keeps refusing ExcursionSetReion, and the caller's own cooling loop reads the two columns.
+ *   1. init_particle_uvbg: local_J21 = 0 for gas; escfrac (the halo mass of mpg_dev_fof_set_escapefraction) becomes
+ *      min(1, EscapeFractionNorm (M UnitMass_in_g / SOLAR_MASS / 1e10 / HubbleParam)^EscapeFractionScaling) for stars with escfrac != 0
+ *      and, only with ReionUseParticleSFR, for such gas (the reference's `continue`, uvbg.c:483)
+ *   2. three CIC deposits on a UVBGdim^3 mesh: Mass of every row; Mass fesc of stars; Sfr fesc of gas (with ReionUseParticleSFR)
+ *   3. forward transforms, divided by UVBGdim^3
+ *   4. the radii R = min(ReionRBubbleMax, Box), R / ReionDeltaRFactor, ... down to the last, unfiltered step at R = Box / UVBGdim
+ *      (petapm_reion_c2r): per radius one filter pass over the modes, one batched inverse transform, one pass over the cells
+ *      (reion_loop_pm) on the float grids J21 / xHI, which stay on the device
+ *   5. the volume- and mass-weighted neutral fractions of the last step, summed in a fixed order (equal input, equal numbers)
+ *   6. readout_J21: a gas row takes the largest J21 of its 8 CIC corners when that exceeds its local_J21; zreion becomes 1 / Time - 1
+ *      where it was -1 and the row took a value
+ * DEFINED DIFFERENCES: rows of type 7 (the engine's garbage / swallowed convention) are not deposited, the reference deposits
+ * such stale rows; the real-space top hat W(kR) is evaluated in fp64 where the reference calls sinf / cosf / powf on the double kR; the
+ * transforms are divided by UVBGdim^3 as a double, the reference's int overflows above 1290, which is refused here. */
+typedef struct mpg_uvbg_params {
+    int ReionFilterType;              /* 0 real-space top hat, 1 k-space top hat, 2 Gaussian (uvbg.c:215-248) */
+    int RtoMFilterType;               /* 0 top hat, 1 Gaussian (uvbg.c:155-173) */
+    double ReionRBubbleMax, ReionRBubbleMin, ReionDeltaRFactor;
+    double ReionNionPhotPerBary, AlphaUV, EscapeFractionNorm, EscapeFractionScaling;
+    int ReionUseParticleSFR;
+    double ReionSFRTimescale;
+    int UVBGdim;
+    double Time, Omega0, OmegaBaryon, RhoCrit, HubbleParam; /* the step: atime and CP's members */
+    double hubble;                    /* hubble_function(CP, Time) */
+    double UnitLength_in_cm, UnitMass_in_g, UnitTime_in_s;
+    int NTask;                        /* several ranks are refused */
+} mpg_uvbg_params;
+typedef struct mpg_uvbg_columns {     /* device (mpg_dev_*) or host (mpg_calculate_uvbg) arrays in particle order; rows of other types are not touched */
+    double *sfr;                      /* in: SphP.Sfr; required with ReionUseParticleSFR, else may be NULL */
+    double *escfrac;                  /* in / out: SphP / StarP.EscapeFraction, one column: the halo mass comes back converted */
+    double *local_J21;                /* out: SphP.local_J21 */
+    double *zreion;                   /* in / out: SphP.zreion */
+} mpg_uvbg_columns;
+typedef struct mpg_uvbg_result {
+    double volume_weighted_global_xHI, mass_weighted_global_xHI;
+    int64_t nradii;                   /* filter steps taken, the last (unfiltered) one included */
+    int64_t radii_cap;                /* in: room in radii (0: none wanted) */
+    double *radii;                    /* out, host: the first min(nradii, radii_cap) radii */
+} mpg_uvbg_result;
+/* ERRORS (returned, each names the setting): unknown ReionFilterType / RtoMFilterType; ReionDeltaRFactor <= 1; ReionRBubbleMax or
+ * ReionRBubbleMin not positive; UVBGdim < 4 or > 1290; ReionUseParticleSFR without an sfr column; NTask > 1; a negative escape fraction
+ * (found at the end of the call: the columns are then as the reference's endrun would leave them, converted up to that row). */
+int mpg_dev_calculate_uvbg(mpg_engine *eng, const mpg_uvbg_params *par, const mpg_uvbg_columns *cols, mpg_uvbg_result *result);
+/* the grids of the last mpg_dev_calculate_uvbg, x slowest: d_J21 / d_xHI float[dim^3] (UVBGgrids, what save_uvbg_grids writes),
+ * d_deposit double[3][dim^3] = the mass, star and SFR grids as deposited (the third is zero without ReionUseParticleSFR).  Device
+ * arrays; any may be NULL.  `dim` must be the UVBGdim of that call. */
+int mpg_dev_uvbg_grids(mpg_engine *eng, int dim, float *d_J21, float *d_xHI, double *d_deposit);
+/* calculate_uvbg for a host table: Pos / Mass / Type from the records (garbage and swallowed black holes are type 7), the columns host
+ * arrays of pv->n entries */
+int mpg_calculate_uvbg(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_uvbg_params *par, const mpg_uvbg_columns *cols,
+                       mpg_uvbg_result *result);
 
 /* ---- snapshot / IC wire format: the "bigfile" blocks petaio.c reads and writes (libgadget/petaio.c:986-1120;
  * format: depends/bigfile/src/bigfile.c).  `file` is the snapshot directory (PART_000, an MP-GenIC output), `block` a column such

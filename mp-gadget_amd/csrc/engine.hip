@@ -897,6 +897,18 @@ int mpg_dev_fof_subgrid(mpg_engine *eng, const mpg_fof_subgrid_columns *A, const
     API_END
 }
 
+// fof_set_escapefraction (fof.c:832-870) on the groups of the last mpg_dev_fof_fof
+int mpg_dev_fof_set_escapefraction(mpg_engine *eng, double *d_escfrac)
+{
+    API_BEGIN
+    MPG_CHECK(eng && (d_escfrac || eng->n == 0), "fof_set_escapefraction: null argument");
+    MPG_CHECK(eng->fof.cat_n >= 0, "fof_set_escapefraction: no mpg_dev_fof_fof since the particles were bound");
+    MPG_CHECK(eng->fof.cat_n == eng->n, "fof_set_escapefraction: the bound particle count differs from that of the last mpg_dev_fof_fof");
+    MPG_HIP(hipSetDevice(eng->device));
+    eng->fof.set_escapefraction(eng->n, eng->d_type, d_escfrac, eng->stream);
+    API_END
+}
+
 // fof_seed (fof.c:1345-1449) with blackhole_make_one (blackhole.c:1056-1111) on the caller's columns
 int mpg_dev_fof_seed(mpg_engine *eng, const mpg_fof_seed_params *par, double atime, const mpg_bh_seed_columns *cols, int64_t cap,
                      int64_t *d_seed_particle, int64_t *d_seed_group, int64_t *nseeds, int64_t *nwarn)

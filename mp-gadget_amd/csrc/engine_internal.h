@@ -19,6 +19,7 @@
 #include "planes.h"
 #include "domain.h"
 #include "fof.h"
+#include "uvbg.h"
 #include "snapshot_io.h"
 #include "tree_build.h"
 #include "host_table.h"
@@ -195,6 +196,9 @@ struct mpg_engine {
     // star formation (sfr.hip): parameters, the lists and counters of the last call; the staging of its host forms (fields of mpg_sfr_columns)
     SfrEngine sfr;
     DevBuf<char> sf_stage[std::size(SFR_FIELDS)];
+    // excursion-set reionisation (uvbg.hip): meshes, plans and the float grids of the last call; the staging of its host form
+    UvbgEngine uvbg;
+    DevBuf<char> uv_stage[std::size(UVBG_FIELDS)];
     void prefetch_join()
     {
         if(prefetch_thread.joinable())

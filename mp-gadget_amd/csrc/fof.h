@@ -84,6 +84,8 @@ struct FofEngine {
     // *notgas: a listed row is no gas (blackhole.c:1057); nothing was converted then.
     int64_t seed(const FofSeedPar &par, const FofSeedCols *cols, int64_t cap, long long *d_particle, long long *d_group, int64_t *nwarn, bool *notgas,
                  hipStream_t st);
+    // fof_set_escapefraction (fof.c:832-870): escfrac[i] = the Mass of row i's group for gas and stars (0 outside every group); other rows untouched
+    void set_escapefraction(int64_t n, const uint8_t *type, double *escfrac, hipStream_t st);
     DevBuf<int> parent, root_of, val, list, sidx, ord_a, ord_b, g_grnr, g_lentype;
     DevBuf<unsigned long long> minid, label, slabel, run_label, g_minid, cnt;
     DevBuf<unsigned> run_count, run_start, g_len, g_start, lenkey_a, lenkey_b, err;

@@ -817,6 +817,29 @@ void FofEngine::subgrid(int64_t n, const float *mass, const uint8_t *type, const
     sub_done = true;
 }
 
+// fof_set_escapefraction (fof.c:832-870): the halo mass of every gas and star row, 0 for those in no group; Group.Mass is a[0] of g_acc, what
+// k_fof_export writes
+__global__ void __launch_bounds__(256) k_fof_escapefraction(int64_t n, const long long *__restrict__ p_grnr, const int *__restrict__ rank_order,
+                                                            const uint8_t *__restrict__ type, const double *__restrict__ acc, double *__restrict__ escfrac)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n)
+        return;
+    const int t = type ? type[i] : 1;
+    if(t != 0 && t != 4)
+        return;
+    const int g = group_of(p_grnr, rank_order, i);
+    escfrac[i] = g >= 0 ? acc[(size_t)g * NQ] : 0.;
+}
+
+void FofEngine::set_escapefraction(int64_t n, const uint8_t *type, double *escfrac, hipStream_t st)
+{
+    if(n > 0)
+        hipLaunchKernelGGL(k_fof_escapefraction, dim3(nblk(n)), dim3(256), 0, st, n, (const long long *)p_grnr.p, (const int *)ord_b.p, type,
+                           (const double *)g_acc.p, escfrac);
+    MPG_HIP(hipGetLastError());
+}
+
 int64_t FofEngine::seed(const FofSeedPar &par, const FofSeedCols *cols, int64_t cap, long long *d_particle, long long *d_group, int64_t *nwarn,
                         bool *notgas, hipStream_t st)
 {

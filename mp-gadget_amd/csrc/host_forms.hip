@@ -941,6 +941,26 @@ int mpg_cooling_and_starformation(mpg_engine *eng, const mpg_particle_view *pv, 
     API_END
 }
 
+// calculate_uvbg for a host table (uvbg.c:506-593): the four columns go through stage_fields / unstage_fields (host_table.h)
+int mpg_calculate_uvbg(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_uvbg_params *par, const mpg_uvbg_columns *A,
+                       mpg_uvbg_result *result)
+{
+    API_BEGIN
+    MPG_CHECK(eng && pv && par && A && result, "calculate_uvbg: null argument");
+    MPG_HIP(hipSetDevice(eng->device));
+    stage_particles(eng, pv, BoxSize);
+    mpg_uvbg_columns d{};
+    if(pv->n > 0)
+        stage_fields(UVBG_FIELDS, *A, d, eng->uv_stage, pv->n, 0, "calculate_uvbg", eng->stream);
+    const int rc = mpg_dev_calculate_uvbg(eng, par, &d, result);
+    const std::string err = rc ? mpg_last_error() : "";
+    if(pv->n > 0)
+        unstage_fields(UVBG_FIELDS, *A, d, pv->n, 0, eng->stream);
+    MPG_HIP(hipStreamSynchronize(eng->stream));
+    MPG_CHECK(rc == 0, err);
+    API_END
+}
+
 // metal_return for the listed particles of a host table: Mass is the records' column (staged with the table, written back into it), the
 // other arrays go through stage_fields / unstage_fields (host_table.h)
 int mpg_metal_return(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_metal_arrays *A, const int *ActiveParticle,

@@ -496,6 +496,16 @@ constexpr ArrayField SFR_FIELDS[] = {
 };
 static_assert(describes_every_member<mpg_sfr_columns>(SFR_FIELDS), "SFR_FIELDS follows mpg_sfr_columns");
 
+// calculate_uvbg: the halo mass goes up in escfrac and comes back converted; zreion is in / out; sfr is read with ReionUseParticleSFR (the call
+// checks it)
+constexpr ArrayField UVBG_FIELDS[] = {
+    MPG_ARRAY_FIELD(mpg_uvbg_columns, sfr, 1, ARR_IN | ARR_OPTIONAL),
+    MPG_ARRAY_FIELD(mpg_uvbg_columns, escfrac, 1, ARR_IN | ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_uvbg_columns, local_J21, 1, ARR_OUT),
+    MPG_ARRAY_FIELD(mpg_uvbg_columns, zreion, 1, ARR_IN | ARR_OUT),
+};
+static_assert(describes_every_member<mpg_uvbg_columns>(UVBG_FIELDS), "UVBG_FIELDS follows mpg_uvbg_columns");
+
 // Room for n particles of field F in its staging buffer and, when the host array `h` is given, its n entries on the way up (queued on
 // st): the device pointer.  (512 bytes of slack: 64 spare elements of the widest type, and never an empty allocation.)
 inline void *stage_field(const ArrayField &F, mpg::DevBuf<char> &buf, const void *h, int64_t n, hipStream_t st)

@@ -437,6 +437,31 @@ class FofSubgridGroupsC(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in FOF_SUBGRID_GROUPS]
 
 
+UVBG_COLUMN_FIELDS = ("sfr", "escfrac", "local_J21", "zreion")
+UVBG_COLUMN_DTYPES = {}
+
+
+class UvbgColumnsC(C.Structure):
+    """mpg_uvbg_columns"""
+    _fields_ = [(k, C.c_void_p) for k in UVBG_COLUMN_FIELDS]
+
+
+class UvbgParams(C.Structure):
+    """mpg_uvbg_params: the members of struct UVBGParams (uvbg.c:32-56) the loop reads, the step's cosmology and units"""
+    _fields_ = [("ReionFilterType", C.c_int), ("RtoMFilterType", C.c_int), ("ReionRBubbleMax", C.c_double), ("ReionRBubbleMin", C.c_double),
+                ("ReionDeltaRFactor", C.c_double), ("ReionNionPhotPerBary", C.c_double), ("AlphaUV", C.c_double), ("EscapeFractionNorm", C.c_double),
+                ("EscapeFractionScaling", C.c_double), ("ReionUseParticleSFR", C.c_int), ("ReionSFRTimescale", C.c_double), ("UVBGdim", C.c_int),
+                ("Time", C.c_double), ("Omega0", C.c_double), ("OmegaBaryon", C.c_double), ("RhoCrit", C.c_double), ("HubbleParam", C.c_double),
+                ("hubble", C.c_double), ("UnitLength_in_cm", C.c_double), ("UnitMass_in_g", C.c_double), ("UnitTime_in_s", C.c_double),
+                ("NTask", C.c_int)]
+
+
+class UvbgResult(C.Structure):
+    """mpg_uvbg_result"""
+    _fields_ = [("volume_weighted_global_xHI", C.c_double), ("mass_weighted_global_xHI", C.c_double), ("nradii", C.c_int64),
+                ("radii_cap", C.c_int64), ("radii", C.POINTER(C.c_double))]
+
+
 class FofSeedParams(C.Structure):
     """mpg_fof_seed_params"""
     _fields_ = [(k, C.c_double) for k in ("MinFoFMassForNewSeed", "MinMStarForNewSeed", "SeedBlackHoleMass", "MaxSeedBlackHoleMass",
@@ -1126,6 +1151,46 @@ class Engine:
             e.nseeds = ns.value
             raise e
         return part[:ns.value], grp[:ns.value], nw.value
+
+    def dev_fof_set_escapefraction(self, escfrac):
+        """mpg_dev_fof_set_escapefraction on the groups of the last dev_fof_fof: escfrac (float64 [n] device tensor, particle order) takes the
+        halo mass of every gas and star row (0 outside every group); rows of other types keep what they hold."""
+        self._ck(self.lib.mpg_dev_fof_set_escapefraction(self.h, _ptr(escfrac)))
+
+    # ------------------------------------------------------------------ excursion-set reionisation (calculate_uvbg, uvbg.c:506-593)
+    # `par` is a dict of the members of mpg_uvbg_params (or a UvbgParams); `columns` maps the names of UVBG_COLUMN_FIELDS to float64 device
+    # tensors (dev form) / contiguous numpy arrays of len(P) (host form), updated in place.  Returns dict(volume_weighted_global_xHI,
+    # mass_weighted_global_xHI, radii): radii is the numpy array of the filter radii, the last (unfiltered) step included.
+    @staticmethod
+    def _uvbg_call(call, par):
+        if not isinstance(par, UvbgParams):
+            par = UvbgParams(**par)
+        radii = np.zeros(16384, np.float64)       # (MAX_R_ITERATIONS + 1 steps at the most)
+        res = UvbgResult(0.0, 0.0, 0, len(radii), radii.ctypes.data_as(C.POINTER(C.c_double)))
+        call(C.byref(par), C.byref(res))
+        return dict(volume_weighted_global_xHI=res.volume_weighted_global_xHI, mass_weighted_global_xHI=res.mass_weighted_global_xHI,
+                    radii=radii[:res.nradii].copy())
+
+    def dev_calculate_uvbg(self, par, columns):
+        a = _dev_arrays(UvbgColumnsC, columns)
+        return self._uvbg_call(lambda p, r: self._ck(self.lib.mpg_dev_calculate_uvbg(self.h, p, C.byref(a), r)), par)
+
+    def calculate_uvbg(self, P, BoxSize, par, columns):
+        v = self._view(P)
+        a = _host_arrays(UvbgColumnsC, UVBG_COLUMN_DTYPES, columns, "calculate_uvbg", n=len(P))
+        return self._uvbg_call(lambda p, r: self._ck(self.lib.mpg_calculate_uvbg(self.h, C.byref(v), C.c_double(BoxSize), p, C.byref(a), r)), par)
+
+    def dev_uvbg_grids(self, dim, deposits=False, device="cuda"):
+        """The grids of the last dev_calculate_uvbg as device tensors [dim, dim, dim], x slowest: dict(J21, xHI) float32 and, with
+        `deposits`, mass / star / sfr float64 as deposited (what save_uvbg_grids writes are the first two)."""
+        import torch
+        g = dict(J21=torch.empty((dim,) * 3, dtype=torch.float32, device=device), xHI=torch.empty((dim,) * 3, dtype=torch.float32, device=device))
+        dep = torch.empty((3,) + (dim,) * 3, dtype=torch.float64, device=device) if deposits else None
+        self._ck(self.lib.mpg_dev_uvbg_grids(self.h, C.c_int(dim), _ptr(g["J21"]), _ptr(g["xHI"]), _ptr(dep)))
+        self.synchronize()
+        if deposits:
+            g.update(mass=dep[0], star=dep[1], sfr=dep[2])
+        return g
 
     # hierarchical gravity (timestep.c:239-599)
     @staticmethod

@@ -35,8 +35,9 @@ RENAMES = {
     "blackhole.c": ["blackhole"],
     "winds.c": ["winds_and_feedback"],
     "cooling_qso_lightup.c": ["do_heiii_reionization"],
+    "uvbg.c": ["calculate_uvbg"],
 }
-SHIM_C = ["gravity-hip.c", "sph-hip.c", "forcetree-hip.c", "timestep-hip.c", "veldisp-hip.c", "cooling-hip.c", "metals-hip.c", "blackhole-hip.c", "winds-hip.c", "heiii-hip.c", "mpg_mpi_comm.c", "mpg_rccl_mpi.c"]
+SHIM_C = ["gravity-hip.c", "sph-hip.c", "forcetree-hip.c", "timestep-hip.c", "veldisp-hip.c", "cooling-hip.c", "metals-hip.c", "blackhole-hip.c", "winds-hip.c", "heiii-hip.c", "uvbg-hip.c", "mpg_mpi_comm.c", "mpg_rccl_mpi.c"]
 EXTERNAL = [("pfft", r"^pfft_"), ("fftw", r"^fftw_"), ("gsl", r"^gsl_"), ("mpi", r"^P?MPI_"), ("openmp", r"^(GOMP_|omp_)"),
             ("hdf5", r"^H5")]
 

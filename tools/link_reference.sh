@@ -13,7 +13,7 @@
 #   2. copy shim/*.c, shim/*.h and include/mpgadget_hip.h into <copy>/libgadget/;
 #   3. patch <copy>/libgadget/Makefile: drop gravpm.o gravshort-tree.o gravshort-pair.o gravity.o from GADGET_OBJS and add the shim
 #      objects; rename the five tree constructors in forcetree.o, the eight integrator entry points in timestep.o / drift.o and
-#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o, metal_return in metal_return.o, blackhole in blackhole.o, winds_and_feedback in winds.o and do_heiii_reionization in cooling_qso_lightup.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
+#      winds_find_vel_disp in veldisp.o, cooling_and_starformation in sfr_eff.o, metal_return in metal_return.o, blackhole in blackhole.o, winds_and_feedback in winds.o, do_heiii_reionization in cooling_qso_lightup.o and calculate_uvbg in uvbg.o (-Dname=cpu_name); guard the three SPH loops of density.c / hydra.c (-DMPGADGET_HIP);
 #   4. add the two parameter hooks (set_densitypar, set_hydro_params), the accessors of mpg_shim.h and the
 #      mpg_shim_particles_changed() calls listed in INTEGRATION.md ("Where P[] is reordered") with sed;
 #   5. build the library of this repository, then `make` in the copy with LIBS += -L<repo>/mp-gadget_amd -lmpgadget_hip -lmpi.
@@ -22,13 +22,13 @@ REF=${1:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 WORK=${2:?usage: link_reference.sh <reference checkout> <work dir> [--check]}
 CHECK=${3:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c blackhole-hip.c winds-hip.c heiii-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
+SHIM_C="gravity-hip.c sph-hip.c forcetree-hip.c timestep-hip.c veldisp-hip.c cooling-hip.c metals-hip.c blackhole-hip.c winds-hip.c heiii-hip.c uvbg-hip.c mpg_mpi_comm.c mpg_rccl_mpi.c"
 SHIM_H="mpg_shim.h mpg_shim_epoch.h mpg_mpi_comm.h"
 REF_FILES="libgadget/Makefile libgadget/gravpm.c libgadget/gravshort-tree.c libgadget/gravshort-pair.c libgadget/gravity.c libgadget/forcetree.c
            libgadget/density.c libgadget/hydra.c libgadget/timestep.c libgadget/drift.c libgadget/timebinmgr.c libgadget/run.c libgadget/domain.c
            libgadget/exchange.c libgadget/fof.c libgadget/slotsmanager.c libgadget/veldisp.c libgadget/sfr_eff.c libgadget/cooling.c libgadget/cooling_rates.c
            libgadget/cooling_uvfluc.c libgadget/metal_return.c libgadget/blackhole.c libgadget/bhdynfric.c
-           libgadget/winds.c libgadget/cooling_qso_lightup.c gadget/Makefile Makefile.rules Options.mk.example"
+           libgadget/winds.c libgadget/cooling_qso_lightup.c libgadget/uvbg.c gadget/Makefile Makefile.rules Options.mk.example"
 
 echo "== 0. inputs"
 for f in $REF_FILES; do test -f "$REF/$f" || { echo "missing in the reference checkout: $f"; exit 1; }; done
@@ -60,7 +60,9 @@ if [ "$CHECK" = "--check" ]; then
     printf 'typedef struct gsl_interp2d gsl_interp2d;\n' > "$STUB/shim/gsl/gsl_interp2d.h"
     printf 'typedef struct gsl_integration_workspace gsl_integration_workspace;\n' > "$STUB/shim/gsl/gsl_integration.h"
     for f in $SHIM_C; do
-        gcc -std=gnu11 -fopenmp -fsyntax-only -Wall -Wextra -Werror -I "$STUB" -I "$STUB/shim" -I "$MPIINC" -I "$T/libgadget" -I "$T" "$T/libgadget/$f" \
+        extra=""
+        case $f in uvbg-hip.c) extra="-DEXCUR_REION";; esac   # (its body exists only in such a build, as the reference's calculate_uvbg does)
+        gcc -std=gnu11 -fopenmp -fsyntax-only -Wall -Wextra -Werror $extra -I "$STUB" -I "$STUB/shim" -I "$MPIINC" -I "$T/libgadget" -I "$T" "$T/libgadget/$f" \
             || { echo "the shim file $f does not parse against this checkout"; exit 1; }
     done
 fi
@@ -69,7 +71,7 @@ echo "== 3. libgadget/Makefile"
 MK="$T/libgadget/Makefile"
 sed -i -e 's/\bgravshort-tree\.o gravshort-pair\.o hydra\.o/hydra.o/' -e 's/\bgravpm\.o powerspectrum\.o/powerspectrum.o/' \
        -e 's/\bpetapm\.o gravity\.o/petapm.o/' "$MK"
-sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o blackhole-hip.o winds-hip.o heiii-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
+sed -i -e 's/^\(GADGET_OBJS =  \\\)$/\1\n\t gravity-hip.o sph-hip.o forcetree-hip.o timestep-hip.o veldisp-hip.o cooling-hip.o metals-hip.o blackhole-hip.o winds-hip.o heiii-hip.o uvbg-hip.o mpg_mpi_comm.o mpg_rccl_mpi.o \\/' "$MK"
 cat >> "$MK" <<MKEOF
 
 # ---- MP-Gadget on libmpgadget_hip (tools/link_reference.sh)
@@ -83,6 +85,7 @@ CFLAGS += -DMPGADGET_HIP -I$ROOT/include
 .objs/blackhole.o: CFLAGS += -Dblackhole=cpu_blackhole
 .objs/winds.o: CFLAGS += -Dwinds_and_feedback=cpu_winds_and_feedback
 .objs/cooling_qso_lightup.o: CFLAGS += -Ddo_heiii_reionization=cpu_do_heiii_reionization
+.objs/uvbg.o: CFLAGS += -Dcalculate_uvbg=cpu_calculate_uvbg
 MKEOF
 
 echo "== 4. hooks in the reference sources (INTEGRATION.md lists them; each is one line)"
@@ -212,6 +215,12 @@ append(T + "/libgadget/cooling_qso_lightup.c", "#include <mpgadget_hip.h>\n"
            "qso_candidate_min_mass", "qso_candidate_max_mass", "mean_bubble", "var_bubble", "heIIIreion_finish_frac"))
        + "    *inst_heating = qso_inst_heating;\n    *heIIIreion_start = QSOLightupParams.heIIIreion_start;\n    *table_end = He_zz[Nreionhist - 1];\n}\n"
        "double mpg_shim_heiii_desired(double atime)\n{\n    return gsl_interp_eval(HeIII_intp, He_zz, XHeIII, atime, NULL);\n}")
+# the excursion-set reionisation (uvbg-hip.c): the file-static parameters of uvbg.c
+append(T + "/libgadget/uvbg.c", "#include <mpgadget_hip.h>\nvoid mpg_shim_uvbg_params(mpg_uvbg_params *p)\n{\n"
+       + "".join("    p->%s = uvbg_params.%s;\n" % (k, k) for k in (
+           "ReionFilterType", "RtoMFilterType", "ReionRBubbleMax", "ReionRBubbleMin", "ReionDeltaRFactor", "ReionNionPhotPerBary", "AlphaUV",
+           "EscapeFractionNorm", "EscapeFractionScaling", "ReionUseParticleSFR", "ReionSFRTimescale", "UVBGdim"))
+       + "}")
 append(T + "/libgadget/sfr_eff.c", "void mpg_shim_sfr_blackhole(int *StarformationOn, int *BHFeedbackUseTcool, double *PhysDensThresh, double *OverDensThresh)\n"
        "{\n    *StarformationOn = sfr_params.StarformationOn;\n    *BHFeedbackUseTcool = sfr_params.BHFeedbackUseTcool;\n"
        "    *PhysDensThresh = sfr_params.PhysDensThresh;\n    *OverDensThresh = sfr_params.OverDensThresh;\n}")
@@ -228,7 +237,7 @@ if [ "$CHECK" = "--check" ]; then
     # the patched reference files and the renamed objects still parse (nothing is compiled to an object, linked or run); cooling_rates.c,
     # which only gains one accessor line, metal_return.c, which gains two functions, and cooling_qso_lightup.c, which gains two accessors,
     # call GSL and cannot be parsed with the typedef-only stand-ins
-    for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c sfr_eff.c cooling.c cooling_uvfluc.c blackhole.c bhdynfric.c winds.c; do
+    for f in density.c hydra.c timestep.c timebinmgr.c domain.c exchange.c slotsmanager.c drift.c forcetree.c veldisp.c sfr_eff.c cooling.c cooling_uvfluc.c blackhole.c bhdynfric.c winds.c uvbg.c; do
         extra=""
         case $f in
             forcetree.c) extra="-Dforce_tree_full=cpu_force_tree_full -Dforce_tree_rebuild_mask=cpu_force_tree_rebuild_mask -Dforce_tree_active_moments=cpu_force_tree_active_moments -Dforce_tree_calc_moments=cpu_force_tree_calc_moments -Dforce_tree_free=cpu_force_tree_free";;
@@ -238,6 +247,7 @@ if [ "$CHECK" = "--check" ]; then
             sfr_eff.c) extra="-Dcooling_and_starformation=cpu_cooling_and_starformation";;
             blackhole.c) extra="-Dblackhole=cpu_blackhole";;
             winds.c) extra="-Dwinds_and_feedback=cpu_winds_and_feedback";;
+            uvbg.c) extra="-Dcalculate_uvbg=cpu_calculate_uvbg -DEXCUR_REION";;
         esac
         if ! gcc -std=gnu11 -fopenmp -fsyntax-only -DMPGADGET_HIP $extra -I "$STUB" -I "$MPIINC" -I "$ROOT/include" -I "$T/libgadget" -I "$T" -I "$REF/depends/bigfile/src" "$T/libgadget/$f" 2> "$STUB/err"; then
             if grep -q 'gsl/.*No such file' "$STUB/err"; then
