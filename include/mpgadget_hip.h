@@ -366,9 +366,9 @@ int mpg_veldisp_export(mpg_engine *eng, int64_t n, double *radius, int32_t *iter
  * lastred = 1 / exp(loga_from_ti(Ti_Current - dti_from_timebin(bin))) - 1 (sfr_eff.c:483-484).
  * With a UV-fluctuation table loaded (mpg_set_uvf_table below) every row takes the background of get_local_UVBG_from_global at its own
  * position, and the HIReionTemp test reads the row's own zreion.
- * Not carried: the READ of EXCUR_REION's local_J21 / zreion (get_local_UVBG_from_J21; the two columns are made by mpg_dev_calculate_uvbg
- * below and read by the caller's own cooling loop), cooling_relaxed, star formation and winds (mpg_dev_cooling_and_starformation has the
- * last three);
+ * With an excursion-set model loaded and its two columns bound (mpg_set_excursion_set below) every row takes the background of
+ * get_local_UVBG_from_J21 while redshift > ExcursionSetZStop.
+ * Not carried: cooling_relaxed, star formation and winds (mpg_dev_cooling_and_starformation has them);
  * several ranks each call this form on their own gas (the loop is per particle).
  * Every loop is bounded: the two limits of 1000 are the reference's (cooling.c:32, cooling_rates.c:768); the two bracketing loops, which the
  * reference leaves unbounded, stop after 8192 steps.  A particle that hits a limit, or whose electron abundance is not finite, keeps its
@@ -467,7 +467,7 @@ int mpg_cooling_export(mpg_engine *eng, int64_t n, int32_t *evaluations);
  * reference.  A row whose position is not finite, or 2^31 cells or more from the origin (the reference: undefined), gets zreion = NaN
  * without a read of the table, keeps Entropy / Ne / Sfr, counts in stats[5] and makes the call return non-zero after all other rows are
  * done.  Without a table every call is bit for bit what it is without this section.  The excursion set (EXCUR_REION) is a
- * different model: its producer is mpg_dev_calculate_uvbg below; its consumer in this loop, get_local_UVBG_from_J21, is not carried. */
+ * different model: its producer is mpg_dev_calculate_uvbg below, its consumer in this loop mpg_set_excursion_set. */
 /* init_uvf_table (cooling_uvfluc.c:115-167) without the file: Zreion_Table[Nside][Nside][Nside], C order, from HOST memory; table == NULL
  * removes it.  Refused: Nside < 2, BoxSize <= 0, a non-finite entry, Table[0] outside [0.01, 100] (:164). */
 int mpg_set_uvf_table(mpg_engine *eng, int64_t Nside, const double *table, double BoxSize);
@@ -481,6 +481,42 @@ int mpg_dev_uvf_zreion(mpg_engine *eng, int64_t n, const double *d_pos, double *
 /* the zreion of every particle in the last cooling or cooling_and_starformation call with a table (host array of n entries; NaN: the row
  * was not evaluated, or could not be) */
 int mpg_uvf_export(mpg_engine *eng, int64_t n, double *zreion);
+
+/* ---- the excursion set's J21 in cooling and star formation: get_local_UVBG_from_J21 / get_local_UVBG, cooling_uvfluc.c:199-246 --------
+ * The consumer of SphP.local_J21 / SphP.zreion, which mpg_dev_calculate_uvbg makes.  With a model loaded and redshift > ExcursionSetZStop,
+ * the three forms of cooling and of cooling_and_starformation give every listed gas row the background
+ *   J_UV = J21, zreion the row's, gJH0 = c.gJH0 J21, epsH0 = c.epsH0 J21 1.60218e-12, gJHe0 and epsHe0 likewise, gJHep = epsHep = 0,
+ *   self_shield_dens = get_self_shield_dens(redshift) of the row's gJH0 (cooling_rates.c:345-361; 1e10 where gJH0 == 0),
+ * and the HIReionTemp test (sfr_eff.c:488) reads the row's zreion.  At or below ExcursionSetZStop, with ExcursionSetReionOn == 0 and
+ * without a model every call is bit for bit what it is without this section: the global background, or the UV-fluctuation table's.
+ * A row whose J21 is NaN or negative, or whose zreion is NaN, keeps Entropy / Ne / Sfr, counts in stats[5] and makes the call return
+ * non-zero after all other rows are done.  Not carried: several ranks, BHFeedbackUseTcool == 2. */
+typedef struct mpg_excursion_set_params {
+    /* struct UVFparams, cooling_uvfluc.c:25-30 (AlphaUV is recorded and not read: the caller has evaluated the coefficients at it) */
+    int ExcursionSetReionOn;
+    double ExcursionSetZStop;
+    double AlphaUV;
+    /* get_J21_coeffs(AlphaUV) as the reference returns it (cooling_rates.c:419-430): after pow(10, .) * PhotoIonizeFactor, the eps in
+     * eV/s.  The two Hep members are carried for completeness and not read. */
+    double gJH0, gJHe0, gJHep, epsH0, epsHe0, epsHep;
+} mpg_excursion_set_params;
+/* par == NULL removes the model.  The engine reads no file: the caller interpolates J21CoeffFile.  Refused: a coefficient that is not
+ * finite or is negative, an ExcursionSetZStop that is not finite. */
+int mpg_set_excursion_set(mpg_engine *eng, const mpg_excursion_set_params *par);
+/* the two columns, doubles in particle order, for the calls that follow: the pointers mpg_dev_calculate_uvbg wrote local_J21 and zreion
+ * through, so producer and consumer chain on the device.  They are bound for the particle table bound at this moment; a call on a table
+ * of another size is refused.  NULL, NULL unbinds.  A call in the J21 mode with no columns bound is refused. */
+int mpg_dev_set_excursion_columns(mpg_engine *eng, const double *d_local_J21, const double *d_zreion);
+/* ... HOST arrays for the host forms (mpg_cooling, mpg_cooling_and_starformation): they travel with every such call, as DelayTime does */
+int mpg_set_excursion_columns(mpg_engine *eng, const double *local_J21, const double *zreion);
+/* ... HOST arrays of a resident gas run, uploaded now and in effect until the next call or the end of the stretch, as ne travels */
+int mpg_resident_sph_set_excursion_columns(mpg_engine *eng, const double *local_J21, const double *zreion);
+/* get_local_UVBG for n arbitrary points on the device: d_out[n] from d_J21[n] and d_zreion[n] at `redshift` with the background of
+ * `global` below ExcursionSetZStop or without a model (the UV-fluctuation table is not read here: mpg_dev_uvf_zreion has it).  What
+ * get_neutral_fraction_sfreff and stats.c:271 need before mpg_dev_cooling_state.  A point whose J21 is NaN or negative or whose zreion is
+ * NaN gets a struct of NaNs, and the call returns non-zero after all other points are done. */
+int mpg_dev_excursion_uvbg(mpg_engine *eng, int64_t n, const double *d_J21, const double *d_zreion, double redshift, const mpg_uvbg *global,
+                           mpg_uvbg *d_out);
 
 /* ---- return of stellar mass and metals to the gas: metal_return, libgadget/metal_return.c (run.c:613) ----------------------------
  * For every active star (Type == 4, not garbage) with massgenerated >= 1e-3 (Mass + TotalMassReturned) (metals_haswork, :714-724):
@@ -943,8 +979,9 @@ typedef struct mpg_sfr_params {
     /* UVF.enabled: must agree with the engine's table (mpg_set_uvf_table): refused when set without one, and every
      * cooling_and_starformation call is refused while the two disagree */
     int UVFluctuationOn;
+    /* built with EXCUR_REION: refused on an engine without an excursion-set model (mpg_set_excursion_set comes first) */
+    int ExcursionSetReion;
     /* what is refused when it is set, so that a caller keeps its CPU path from the start */
-    int ExcursionSetReion; /* built with EXCUR_REION */
     int NTask;           /* ranks of the run; 0 is read as 1 */
 } mpg_sfr_params;
 /* arrays in particle order, n entries (x 3 where noted); slot members are indexed by PARTICLE */
@@ -981,7 +1018,7 @@ typedef struct mpg_sfr_result {
     double sum_sm, localsfr, sum_dtime;
 } mpg_sfr_result;
 /* an error that names the setting for BHFeedbackUseTcool == 2, UVFluctuationOn without a table on this engine (mpg_set_uvf_table comes
- * first), EXCUR_REION and several ranks.  A fifth refusal belongs to one form: mpg_resident_sph_cooling_and_starformation with WindOn and
+ * first), EXCUR_REION without an excursion-set model on this engine (mpg_set_excursion_set comes first) and several ranks.  A fifth refusal belongs to one form: mpg_resident_sph_cooling_and_starformation with WindOn and
  * WIND_SUBGRID (below).  With a table, starformation takes the row's own background (sfr_eff.c:745) in both GetCoolingTime calls, and the
  * cooled rows theirs as in mpg_dev_cooling; a star-forming row whose position cannot be evaluated is an error row. */
 int mpg_set_sfr_params(mpg_engine *eng, const mpg_sfr_params *par);
@@ -1477,7 +1514,7 @@ int mpg_dev_fof_set_escapefraction(mpg_engine *eng, double *d_escfrac);
 
 /* ---- excursion-set reionisation (EXCUR_REION; libgadget/uvbg.c:471-594 through petapm_reion, petapm.c:381-577) on the bound particles
  * of ONE rank: the producer of SphP.local_J21 / SphP.zreion.  The consumer (get_local_UVBG_from_J21 in cooling and star formation) is
- * not carried: mpg_set_sfr_params keeps refusing ExcursionSetReion, and the caller's own cooling loop reads the two columns.
+ * mpg_set_excursion_set above: the two output columns of this call are what mpg_dev_set_excursion_columns binds.
  *   1. init_particle_uvbg: local_J21 = 0 for gas; escfrac (the halo mass of mpg_dev_fof_set_escapefraction) becomes
  *      min(1, EscapeFractionNorm (M UnitMass_in_g / SOLAR_MASS / 1e10 / HubbleParam)^EscapeFractionScaling) for stars with escfrac != 0
  *      and, only with ReionUseParticleSFR, for such gas (the reference's `continue`, uvbg.c:483)

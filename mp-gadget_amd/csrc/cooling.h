@@ -100,6 +100,43 @@ MPG_HD Setup local_setup(const Setup &S, double zreion)
     return L;
 }
 
+// the excursion set's model as a kernel reads it: get_J21_coeffs(AlphaUV) (the four members get_local_UVBG_from_J21 reads) and the two
+// factors of get_self_shield_dens at the call's redshift
+struct J21View {
+    double gJH0, gJHe0, epsH0, epsHe0;
+    SelfShieldFactors ss;
+};
+// a row of the two columns that has no background: J21 NaN or negative, zreion NaN
+MPG_HD bool j21_row_bad(double J21, double zreion) { return !(J21 >= 0) || zreion != zreion; }
+// get_local_UVBG_from_J21, cooling_uvfluc.c:199-231: the rates, each the reference's products in the reference's order ...
+MPG_HD void j21_rates(mpg_uvbg &u, const J21View &X, double J21)
+{
+    u.J_UV = J21;
+    u.gJH0 = X.gJH0 * J21;
+    u.epsH0 = X.epsH0 * J21 * 1.60218e-12;
+    u.gJHe0 = X.gJHe0 * J21;
+    u.epsHe0 = X.epsHe0 * J21 * 1.60218e-12;
+    u.gJHep = 0.;
+    u.epsHep = 0.;
+}
+// ... and the whole background of a row.  As in dark_setup only the members of uvbg differ between the lanes of a wave.
+MPG_HD Setup j21_setup(const Setup &S, const J21View &X, double J21, double zreion)
+{
+    Setup L = S;
+    j21_rates(L.uvbg, X, J21);
+    L.uvbg.zreion = zreion;
+    L.uvbg.self_shield_dens = self_shield_dens(X.ss, L.uvbg.gJH0);
+    return L;
+}
+// ... rebuilt from the two numbers a lane of the queue form keeps across its evaluations (zreion is read before the first of them only)
+MPG_HD Setup j21_lane_setup(const Setup &S, const J21View &X, double J21, double ssdens)
+{
+    Setup L = S;
+    j21_rates(L.uvbg, X, J21);
+    L.uvbg.self_shield_dens = ssdens;
+    return L;
+}
+
 struct Counters {
     int evals = 0;      // ne_internal evaluations
     int bisections = 0; // steps of DoCooling's bisection
@@ -478,7 +515,7 @@ MPG_HD double do_cooling(const Setup &S, double redshift, double u_old, double r
 MPG_HD double entropy_to_u(double density, double a3inv) { return exp(GAMMA_MINUS1 * log(density * a3inv)) / GAMMA_MINUS1; }
 
 // cooling_direct, sfr_eff.c:463-514, for one particle; the UV background is S's: the step's, or with a fluctuation table the particle's own
-// (local_setup); no excursion set.
+// (local_setup), or with the excursion set's columns the one of its J21 (j21_setup).
 // Returns the new entropy; *ne holds SphP.Ne in and out; *reion tells whether the HIReionTemp branch was taken.
 MPG_HD double cooling_direct(const Setup &S, double density, double entropy, double *ne, double Z, int heiii, double dtime, double a3inv,
                              double lastred, Counters &C, int *reion)
@@ -540,7 +577,26 @@ struct CoolingEngine {
     DevBuf<unsigned> uvf_bad;
     int64_t uvf_nside = 0, n_uvf = 0;
     double uvf_box = 0, uvf_off[3] = {0, 0, 0};
+    // the excursion set (set_uvf_params, cooling_uvfluc.c:33-45, with get_J21_coeffs(AlphaUV)) and SphP.local_J21 / SphP.zreion: the device
+    // columns in effect (mpg_dev_set_excursion_columns, or s_j21 / s_zre after mpg_resident_sph_set_excursion_columns) and the table size
+    // they were bound for; the host columns the host forms upload per call into s_j21_call / s_zre_call
+    bool have_exc = false;
+    mpg_excursion_set_params exc{};
+    const double *d_j21 = nullptr, *d_zre = nullptr;
+    int64_t n_exc = 0;
+    const double *h_j21 = nullptr, *h_zre = nullptr;
+    DevBuf<double> s_j21, s_zre, s_j21_call, s_zre_call;
+    DevBuf<unsigned> exc_bad;
 
+    void set_excursion_set(const mpg_excursion_set_params *p);
+    // get_local_UVBG's switch (cooling_uvfluc.c:238)
+    bool j21_mode(double redshift) const { return have_exc && exc.ExcursionSetReionOn && redshift > exc.ExcursionSetZStop; }
+    cool::J21View j21_view(double redshift) const;
+    // in the J21 mode: the columns are bound, and for a table of n particles; `who` names the call in the refusal
+    void check_excursion_columns(const char *who, double redshift, int64_t n) const;
+    // get_local_UVBG at n arbitrary points; returns the number of points without a background (J21 NaN or negative, zreion NaN)
+    int64_t excursion_points(int64_t n, const double *d_J21, const double *d_zreion, double redshift, const mpg_uvbg &global, mpg_uvbg *d_out,
+                             hipStream_t st);
     void set_params(const mpg_cooling_params &p, hipStream_t st);
     void set_metal_table(int nz, const double *zbins, int nnh, const double *nhbins, int nt, const double *tbins, const double *rate, hipStream_t st);
     void set_uvf_table(int64_t nside, const double *table, double BoxSize, hipStream_t st);

@@ -45,13 +45,17 @@ struct CoolTimes {
     double a3inv;
 };
 
-// UVF: every row takes its background from its own zreion (zr, by particle; get_local_UVBG_from_global).  A row whose zreion is NaN has
-// none: it is an error row.  Without a table the kernels (k_cooling, k_cooling_queue) are what they were.
-template <bool UVF>
+// where a row's background comes from (get_local_UVBG, cooling_uvfluc.c:236-246).
+// BG_UVF: from its own zreion (zr, by particle; get_local_UVBG_from_global).  A row whose zreion is NaN has none: it is an error row.
+// BG_J21: from its own J21 and zreion (j21 and zr, by particle; get_local_UVBG_from_J21, X the model).  A row whose J21 is NaN or negative
+// or whose zreion is NaN is an error row.  Without either the kernels (k_cooling, k_cooling_queue) are what they were.
+enum Background { BG_GLOBAL = 0, BG_UVF = 1, BG_J21 = 2 };
+template <int BG>
 __device__ __forceinline__ void cooling_rows(Setup S, const CoolTimes &T, const mpg_cooling_arrays &A, const uint8_t *type, const float *mass,
                                              const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats, const double *zr,
-                                             int use_lds)
+                                             int use_lds, const double *j21 = nullptr, const J21View *X = nullptr)
 {
+    constexpr bool UVF = BG == BG_UVF;
     S.net = stage_net_tables(S.net, use_lds != 0);
     unsigned long long mine[ST_N] = {0, 0, 0, 0, 0, 0};
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -62,11 +66,14 @@ __device__ __forceinline__ void cooling_rows(Setup S, const CoolTimes &T, const 
         if(p < 0 || p >= n || (type ? type[p] : (uint8_t)1) != 0 || !(mass[p] > 0))
             p = -1;
     }
-    double zreion = 0;
-    if constexpr(UVF)
+    double zreion = 0, J21 = 0;
+    if constexpr(BG != BG_GLOBAL)
         if(p >= 0)
             zreion = zr[p];
-    if(UVF && p >= 0 && zreion != zreion) {
+    if constexpr(BG == BG_J21)
+        if(p >= 0)
+            J21 = j21[p];
+    if((UVF && p >= 0 && zreion != zreion) || (BG == BG_J21 && p >= 0 && j21_row_bad(J21, zreion))) {
         evals[p] = 0;
         mine[ST_TREATED] = 1;
         mine[ST_ERRORS] = 1;
@@ -79,6 +86,9 @@ __device__ __forceinline__ void cooling_rows(Setup S, const CoolTimes &T, const 
         double ent;
         if constexpr(UVF)
             ent = cooling_direct(local_setup(S, zreion), A.density[p], A.entropy[p], &ne, A.metallicity ? A.metallicity[p] : 0.0,
+                                 A.heiii_ionized ? (int)A.heiii_ionized[p] : 0, T.dtime[bin], T.a3inv, T.lastred[bin], C, &reion);
+        else if constexpr(BG == BG_J21)
+            ent = cooling_direct(j21_setup(S, *X, J21, zreion), A.density[p], A.entropy[p], &ne, A.metallicity ? A.metallicity[p] : 0.0,
                                  A.heiii_ionized ? (int)A.heiii_ionized[p] : 0, T.dtime[bin], T.a3inv, T.lastred[bin], C, &reion);
         else
             ent = cooling_direct(S, A.density[p], A.entropy[p], &ne, A.metallicity ? A.metallicity[p] : 0.0,
@@ -103,13 +113,19 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling(Setup S, CoolTimes T, mp
                                                         const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
                                                         int use_lds)
 {
-    cooling_rows<false>(S, T, A, type, mass, active, nlist, n, evals, stats, nullptr, use_lds);
+    cooling_rows<BG_GLOBAL>(S, T, A, type, mass, active, nlist, n, evals, stats, nullptr, use_lds);
 }
 __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_uvf(Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass,
                                                             const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
                                                             const double *zr, int use_lds)
 {
-    cooling_rows<true>(S, T, A, type, mass, active, nlist, n, evals, stats, zr, use_lds);
+    cooling_rows<BG_UVF>(S, T, A, type, mass, active, nlist, n, evals, stats, zr, use_lds);
+}
+__global__ __launch_bounds__(COOL_BLOCK) void k_cooling_j21(Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass,
+                                                            const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
+                                                            const double *j21, const double *zr, J21View X, int use_lds)
+{
+    cooling_rows<BG_J21>(S, T, A, type, mass, active, nlist, n, evals, stats, zr, use_lds, j21, &X);
 }
 
 // ---- the second form: a per-lane state machine whose unit step is ONE evaluation of the network -----------------------------------------
@@ -266,11 +282,16 @@ __device__ __forceinline__ void one_evaluation(const Setup &S, Lane &L, unsigned
     }
 }
 
-template <bool UVF>
+template <int BG>
 __device__ __forceinline__ void cooling_queue(Setup S, const CoolTimes &T, const mpg_cooling_arrays &A, const uint8_t *type, const float *mass,
                                               const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
-                                              unsigned long long *queue, const double *zr, int use_lds)
+                                              unsigned long long *queue, const double *zr, int use_lds, const double *j21 = nullptr,
+                                              const J21View *X = nullptr)
 {
+    constexpr bool UVF = BG == BG_UVF;
+    // BG_J21: what a lane keeps of its particle's background across the evaluations: J21 and the self-shield density of its gJH0; the four
+    // rates are two or three products each and are made again in every evaluation
+    [[maybe_unused]] double lane_j21 = 0, lane_ssd = 0;
     S.net = stage_net_tables(S.net, use_lds != 0);
     unsigned long long mine[ST_N] = {0, 0, 0, 0, 0, 0};
     const int lane = __lane_id();
@@ -305,6 +326,17 @@ __device__ __forceinline__ void cooling_queue(Setup S, const CoolTimes &T, const
                                 p = -1;
                             }
                         }
+                    if constexpr(BG == BG_J21)
+                        if(p >= 0) {
+                            zreion = zr[p];
+                            lane_j21 = j21[p];
+                            if(j21_row_bad(lane_j21, zreion)) {
+                                evals[p] = 0;
+                                mine[ST_TREATED]++;
+                                mine[ST_ERRORS]++;
+                                p = -1;
+                            }
+                        }
                     if(p >= 0) {
                         // cooling_direct up to the call of DoCooling (sfr_eff.c:463-506) and DoCooling's head (cooling.c:59-75)
                         const int bin = A.tb_hydro ? (A.tb_hydro[p] < 47 ? A.tb_hydro[p] : 46) : 0;
@@ -332,6 +364,8 @@ __device__ __forceinline__ void cooling_queue(Setup S, const CoolTimes &T, const
                             const double meanweight = 4.0 / (1 + 3 * HYDROGEN_MASSFRAC);
                             L.p = p;
                             L.dark = UVF && zreion < S.redshift;
+                            if constexpr(BG == BG_J21)
+                                lane_ssd = self_shield_dens(X->ss, X->gJH0 * lane_j21);
                             L.ne_guess = A.ne[p];
                             L.Z = A.metallicity ? A.metallicity[p] : 0.0;
                             L.heiii = A.heiii_ionized ? (int)A.heiii_ionized[p] : 0;
@@ -357,6 +391,8 @@ __device__ __forceinline__ void cooling_queue(Setup S, const CoolTimes &T, const
             // ---- one evaluation of the network (scipy_optimize_fixed_point, cooling_rates.c:784-805)
             if constexpr(UVF)
                 one_evaluation(dark_setup(S, L.dark != 0), L, mine, A, evals);
+            else if constexpr(BG == BG_J21)
+                one_evaluation(j21_lane_setup(S, *X, lane_j21, lane_ssd), L, mine, A, evals);
             else
                 one_evaluation(S, L, mine, A, evals);
         }
@@ -368,7 +404,7 @@ __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_queue(Setup S, CoolTimes
                                                               const int *active, int64_t nlist, int64_t n, int *evals, unsigned long long *stats,
                                                               unsigned long long *queue, int use_lds)
 {
-    cooling_queue<false>(S, T, A, type, mass, active, nlist, n, evals, stats, queue, nullptr, use_lds);
+    cooling_queue<BG_GLOBAL>(S, T, A, type, mass, active, nlist, n, evals, stats, queue, nullptr, use_lds);
 }
 // ... with a UV-fluctuation table.  The six rates of the lane's background are vector registers during an evaluation; left to itself the
 // compiler ends two registers above what lets two waves share a SIMD as they do without a table, so it is told to stay within that.
@@ -376,7 +412,14 @@ __global__ __launch_bounds__(COOL_BLOCK) __attribute__((amdgpu_waves_per_eu(2)))
     Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass, const int *active, int64_t nlist, int64_t n, int *evals,
     unsigned long long *stats, unsigned long long *queue, const double *zr, int use_lds)
 {
-    cooling_queue<true>(S, T, A, type, mass, active, nlist, n, evals, stats, queue, zr, use_lds);
+    cooling_queue<BG_UVF>(S, T, A, type, mass, active, nlist, n, evals, stats, queue, zr, use_lds);
+}
+// ... with the excursion set's columns: two doubles per lane across the evaluations, the same limit
+__global__ __launch_bounds__(COOL_BLOCK) __attribute__((amdgpu_waves_per_eu(2))) void k_cooling_queue_j21(
+    Setup S, CoolTimes T, mpg_cooling_arrays A, const uint8_t *type, const float *mass, const int *active, int64_t nlist, int64_t n, int *evals,
+    unsigned long long *stats, unsigned long long *queue, const double *j21, const double *zr, J21View X, int use_lds)
+{
+    cooling_queue<BG_J21>(S, T, A, type, mass, active, nlist, n, evals, stats, queue, zr, use_lds, j21, &X);
 }
 
 __global__ __launch_bounds__(COOL_BLOCK) void k_cooling_state(Setup S, double helium, int64_t n, const double *rho, const double *u, double *ne,
@@ -428,6 +471,31 @@ __global__ __launch_bounds__(UVF_BLOCK) void k_uvf_zreion(const UvfView U, const
     out[p] = z;
     if(!rows && z != z)
         atomicAdd(bad, 1u);
+}
+
+// get_local_UVBG (cooling_uvfluc.c:236-246) at n arbitrary points, one lane per point.  j21mode == 0: the global background G for every
+// point.  Otherwise get_local_UVBG_from_J21; a point without a background (j21_row_bad) gets NaN in every member and counts in *bad.
+__global__ __launch_bounds__(UVF_BLOCK) void k_excursion_uvbg(const J21View X, const mpg_uvbg G, const int j21mode, const int64_t n,
+                                                              const double *__restrict__ j21, const double *__restrict__ zr,
+                                                              mpg_uvbg *__restrict__ out, unsigned *__restrict__ bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i >= n)
+        return;
+    mpg_uvbg u = G;
+    if(j21mode) {
+        const double J21 = j21[i], zreion = zr[i];
+        if(j21_row_bad(J21, zreion)) {
+            u.J_UV = u.gJH0 = u.gJHep = u.gJHe0 = u.epsH0 = u.epsHep = u.epsHe0 = u.self_shield_dens = u.zreion = NAN;
+            atomicAdd(bad, 1u);
+        }
+        else {
+            j21_rates(u, X, J21);
+            u.zreion = zreion;
+            u.self_shield_dens = self_shield_dens(X.ss, u.gJH0);
+        }
+    }
+    out[i] = u;
 }
 
 void upload(DevBuf<double> &buf, const double *h, size_t count, hipStream_t st)
@@ -544,6 +612,61 @@ void CoolingEngine::uvf_rows(const double *d_pos, const uint8_t *type, const flo
     }
 }
 
+void CoolingEngine::set_excursion_set(const mpg_excursion_set_params *p)
+{
+    if(!p) {
+        have_exc = false;
+        exc = mpg_excursion_set_params{};
+        return;
+    }
+    const double c[6] = {p->gJH0, p->gJHe0, p->gJHep, p->epsH0, p->epsHe0, p->epsHep};
+    const char *const name[6] = {"gJH0", "gJHe0", "gJHep", "epsH0", "epsHe0", "epsHep"};
+    for(int k = 0; k < 6; k++)
+        MPG_CHECK(c[k] - c[k] == 0 && c[k] >= 0, std::string("mpg_set_excursion_set: the coefficient ") + name[k] + " is not finite or is negative");
+    MPG_CHECK(p->ExcursionSetZStop - p->ExcursionSetZStop == 0, "mpg_set_excursion_set: ExcursionSetZStop is not finite");
+    exc = *p;
+    have_exc = true;
+}
+
+J21View CoolingEngine::j21_view(double redshift) const
+{
+    J21View X;
+    X.gJH0 = exc.gJH0;
+    X.gJHe0 = exc.gJHe0;
+    X.epsH0 = exc.epsH0;
+    X.epsHe0 = exc.epsHe0;
+    X.ss = self_shield_factors(redshift, par.fBar);
+    return X;
+}
+
+void CoolingEngine::check_excursion_columns(const char *who, double redshift, int64_t n) const
+{
+    if(!j21_mode(redshift))
+        return;
+    MPG_CHECK(d_j21 && d_zre, std::string(who) + ": the excursion set is on and redshift > ExcursionSetZStop, but no local_J21 / zreion columns are bound "
+                                                 "(mpg_dev_set_excursion_columns, mpg_set_excursion_columns or mpg_resident_sph_set_excursion_columns first)");
+    MPG_CHECK(n_exc == n, std::string(who) + ": the local_J21 / zreion columns were bound for a table of " + std::to_string(n_exc) +
+                              " particles, this call is on " + std::to_string(n));
+}
+
+int64_t CoolingEngine::excursion_points(int64_t n, const double *d_J21, const double *d_zreion, double redshift, const mpg_uvbg &global,
+                                        mpg_uvbg *d_out, hipStream_t st)
+{
+    if(n <= 0)
+        return 0;
+    const int jm = j21_mode(redshift);
+    MPG_CHECK(!jm || have_params, "mpg_dev_excursion_uvbg: mpg_set_cooling_params has not been called (fBar)");
+    exc_bad.reserve(4);
+    MPG_HIP(hipMemsetAsync(exc_bad.p, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(k_excursion_uvbg, dim3(nblk(n, UVF_BLOCK)), dim3(UVF_BLOCK), 0, st, jm ? j21_view(redshift) : J21View{}, global, jm, n, d_J21,
+                       d_zreion, d_out, exc_bad.p);
+    MPG_HIP(hipGetLastError());
+    unsigned bad = 0;
+    MPG_HIP(hipMemcpyAsync(&bad, exc_bad.p, sizeof(bad), hipMemcpyDeviceToHost, st));
+    MPG_HIP(hipStreamSynchronize(st));
+    return bad;
+}
+
 Setup CoolingEngine::setup(const mpg_cooling_step &step, double redshift) const
 {
     Setup S{};
@@ -596,6 +719,9 @@ int64_t CoolingEngine::run(const mpg_cooling_arrays &A, const uint8_t *type, con
 {
     MPG_CHECK(have_params, "cooling: mpg_set_cooling_params has not been called");
     const int64_t nlist = d_active ? nactive : n;
+    const double redshift = 1 / T.atime - 1; // sfr_eff.c:211
+    const bool jm = j21_mode(redshift);
+    check_excursion_columns("cooling", redshift, n);
     d_stats.reserve(ST_N + 1); // (the last entry is the list position of the queue form)
     d_evals.reserve((size_t)n + 1);
     n_evals = n;
@@ -603,7 +729,7 @@ int64_t CoolingEngine::run(const mpg_cooling_arrays &A, const uint8_t *type, con
     if(n > 0)
         MPG_HIP(hipMemsetAsync(d_evals.p, 0xff, (size_t)n * sizeof(int), st));
     if(nlist > 0) {
-        const Setup S = setup(step, 1 / T.atime - 1); // sfr_eff.c:211
+        const Setup S = setup(step, redshift);
         CoolTimes CT;
         for(int b = 0; b < 47; b++) {
             CT.dtime[b] = T.dloga_bin[b] / T.hubble;
@@ -612,20 +738,29 @@ int64_t CoolingEngine::run(const mpg_cooling_arrays &A, const uint8_t *type, con
         CT.a3inv = 1. / (T.atime * T.atime * T.atime); // sfr_eff.c:195
         const size_t lds = lds_tables ? (size_t)NRECOMBTAB * NNET * sizeof(double) : 0;
         const unsigned blocks = (unsigned)((nlist + COOL_BLOCK - 1) / COOL_BLOCK);
-        MPG_CHECK(!have_uvf || n_uvf == n, "cooling: the zreion column was not filled for this table");
-        const double *zr = have_uvf ? uvf_z.p : nullptr;
+        // get_local_UVBG: the excursion set's columns above ExcursionSetZStop, else the table's zreion, else the global background
+        const bool uvf = have_uvf && !jm;
+        MPG_CHECK(!uvf || n_uvf == n, "cooling: the zreion column was not filled for this table");
+        const double *zr = uvf ? uvf_z.p : nullptr;
+        const J21View X = jm ? j21_view(redshift) : J21View{};
         if(form == 1) {
             // resident waves that pull from the list: no more blocks than keep every CU busy
             const unsigned cap = (unsigned)num_cus * 8u;
             const dim3 grid(blocks < cap ? blocks : cap);
-            if(have_uvf)
+            if(jm)
+                hipLaunchKernelGGL(k_cooling_queue_j21, grid, dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p,
+                                   d_stats.p + ST_N, d_j21, d_zre, X, lds_tables);
+            else if(uvf)
                 hipLaunchKernelGGL(k_cooling_queue_uvf, grid, dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p,
                                    d_stats.p + ST_N, zr, lds_tables);
             else
                 hipLaunchKernelGGL(k_cooling_queue, grid, dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p,
                                    d_stats.p + ST_N, lds_tables);
         }
-        else if(have_uvf)
+        else if(jm)
+            hipLaunchKernelGGL(k_cooling_j21, dim3(blocks), dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p, d_j21,
+                               d_zre, X, lds_tables);
+        else if(uvf)
             hipLaunchKernelGGL(k_cooling_uvf, dim3(blocks), dim3(COOL_BLOCK), lds, st, S, CT, A, type, mass, d_active, nlist, n, d_evals.p, d_stats.p, zr,
                                lds_tables);
         else

@@ -252,5 +252,42 @@ MPG_HD double cool_fit(int k, double temp, int recomb, int cooling)
     }
 }
 
+// get_self_shield_dens, cooling_rates.c:345-361 (Rahmati 2012 eq. 13), in three pieces: the grey opacity of the Faucher-Giguere 2009
+// background at a redshift (GrayOpac, cooling_rates.c:75-76; clamped outside the table, gsl's linear interpolation inside), the two
+// factors that depend on the redshift and on fBar alone, and what is left per background
+constexpr int NGRAY = 6;
+MPG_HD double grey_opacity(double redshift)
+{
+    const double ydata[NGRAY] = {2.59e-18, 2.37e-18, 2.27e-18, 2.15e-18, 2.02e-18, 1.94e-18};
+    const double zz[NGRAY] = {0, 1, 2, 3, 4, 5};
+    if(redshift <= zz[0])
+        return ydata[0];
+    if(redshift >= zz[NGRAY - 1])
+        return ydata[NGRAY - 1];
+    int i = 0; // gsl_interp_bsearch: zz[i] <= redshift < zz[i + 1]
+    while(i < NGRAY - 2 && redshift >= zz[i + 1])
+        i++;
+    const double dx = zz[i + 1] - zz[i], dy = ydata[i + 1] - ydata[i]; // linear_eval, gsl interpolation/linear.c
+    return ydata[i] + (redshift - zz[i]) / dx * dy;
+}
+struct SelfShieldFactors {
+    double opac; // pow(greyopac / 2.49e-18, -2./3)
+    double fbar; // pow(fBar / 0.17, -1./3)
+};
+MPG_HD SelfShieldFactors self_shield_factors(double redshift, double fBar)
+{
+    SelfShieldFactors F;
+    F.opac = pow(grey_opacity(redshift) / 2.49e-18, -2. / 3);
+    F.fbar = pow(fBar / 0.17, -1. / 3);
+    return F;
+}
+MPG_HD double self_shield_dens(const SelfShieldFactors &F, double gJH0)
+{
+    if(gJH0 == 0) // before the background switches on there is no self-shielding
+        return 1e10;
+    const double G12 = gJH0 / 1e-12;
+    return 6.73e-3 * F.opac * pow(G12, 2. / 3) * F.fbar;
+}
+
 } // namespace cool
 } // namespace mpg

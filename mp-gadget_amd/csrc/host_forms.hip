@@ -897,6 +897,36 @@ int mpg_find_vel_disp(mpg_engine *eng, const mpg_particle_view *pv, double BoxSi
     API_END
 }
 
+// the host local_J21 / zreion columns of mpg_set_excursion_columns travel with a host-form call and are the columns in effect for it; the
+// device columns bound before come back into effect when the guard ends (as DelayTime does in mpg_hydro_force)
+struct ExcursionColumnsOfCall {
+    CoolingEngine &E;
+    const double *j21, *zre;
+    int64_t n_exc;
+    const bool swapped;
+    ExcursionColumnsOfCall(mpg_engine *eng, int64_t n) : E(eng->cooling), j21(E.d_j21), zre(E.d_zre), n_exc(E.n_exc), swapped(E.h_j21 && n > 0)
+    {
+        if(!swapped)
+            return;
+        // (buffers of their own: s_j21 / s_zre may hold the columns of mpg_resident_sph_set_excursion_columns)
+        E.s_j21_call.reserve((size_t)n + 1);
+        E.s_zre_call.reserve((size_t)n + 1);
+        MPG_HIP(hipMemcpyAsync(E.s_j21_call.p, E.h_j21, (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        MPG_HIP(hipMemcpyAsync(E.s_zre_call.p, E.h_zre, (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        E.d_j21 = E.s_j21_call.p;
+        E.d_zre = E.s_zre_call.p;
+        E.n_exc = n;
+    }
+    ~ExcursionColumnsOfCall()
+    {
+        if(swapped) {
+            E.d_j21 = j21;
+            E.d_zre = zre;
+            E.n_exc = n_exc;
+        }
+    }
+};
+
 // cooling_direct for the listed particles of a host table (sfr_eff.c:463-514).  The results are copied back even when a particle hit an
 // iteration limit: that particle's entries come back as they went up, all others are final.
 int mpg_cooling(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, const mpg_cooling_arrays *A, const mpg_sph_times *T,
@@ -910,7 +940,11 @@ int mpg_cooling(mpg_engine *eng, const mpg_particle_view *pv, double BoxSize, co
     mpg_cooling_arrays d{};
     stage_fields(COOL_FIELDS, *A, d, eng->cl_stage, pv->n, 0, "cooling", eng->stream);
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
-    const int rc = mpg_dev_cooling(eng, &d, T, step, d_act, NumActiveParticle);
+    int rc;
+    {
+        const ExcursionColumnsOfCall guard(eng, pv->n);
+        rc = mpg_dev_cooling(eng, &d, T, step, d_act, NumActiveParticle);
+    }
     const std::string err = rc ? mpg_last_error() : "";
     if(pv->n > 0)
         unstage_fields(COOL_FIELDS, *A, d, pv->n, 0, eng->stream);
@@ -932,7 +966,11 @@ int mpg_cooling_and_starformation(mpg_engine *eng, const mpg_particle_view *pv, 
     if(pv->n > 0)
         stage_fields(SFR_FIELDS, *A, d, eng->sf_stage, pv->n, 0, "cooling_and_starformation", eng->stream);
     const int *d_act = upload_active(eng->s_active, ActiveParticle, NumActiveParticle, eng->stream);
-    const int rc = mpg_dev_cooling_and_starformation(eng, &d, T, step, d_act, NumActiveParticle);
+    int rc;
+    {
+        const ExcursionColumnsOfCall guard(eng, pv->n);
+        rc = mpg_dev_cooling_and_starformation(eng, &d, T, step, d_act, NumActiveParticle);
+    }
     const std::string err = rc ? mpg_last_error() : "";
     if(pv->n > 0)
         unstage_fields(SFR_FIELDS, *A, d, pv->n, 0, eng->stream);

@@ -261,14 +261,62 @@ int mpg_dev_cooling(mpg_engine *eng, const mpg_cooling_arrays *A, const mpg_sph_
     MPG_CHECK(eng->n == 0 || (A->density && A->entropy && A->ne && A->sfr), "cooling: the arrays density, entropy, ne and sfr are required");
     MPG_CHECK(eng->d_mass || eng->n == 0, "cooling: no particles bound");
     MPG_HIP(hipSetDevice(eng->device));
-    if(eng->cooling.have_uvf) // the zreion of every listed gas row from the bound positions (get_local_UVBG_from_global)
+    const bool jm = eng->cooling.j21_mode(1 / T->atime - 1);
+    eng->cooling.check_excursion_columns("cooling", 1 / T->atime - 1, eng->n);
+    if(eng->cooling.have_uvf && !jm) // the zreion of every listed gas row from the bound positions (get_local_UVBG_from_global)
         eng->cooling.uvf_rows(eng->d_pos, eng->d_type, eng->d_mass, d_active, nactive, eng->n, eng->stream);
     const int64_t bad = eng->cooling.run(*A, eng->d_type, eng->d_mass, *T, *step, d_active, nactive, eng->n, eng->stream);
     // the reference's endrun(1 / 10): every other particle of the call has been treated
     MPG_CHECK(bad == 0, "cooling: " + std::to_string(bad) + " particle(s) hit an iteration limit of DoCooling or of the ionisation network, or reached an "
                                                            "electron abundance that is not finite" +
-                            (eng->cooling.have_uvf ? ", or have a position at which the UV-fluctuation table cannot be read (not finite)" : "") +
+                            (jm                      ? ", or have a local_J21 that is NaN or negative or a zreion that is NaN"
+                             : eng->cooling.have_uvf ? ", or have a position at which the UV-fluctuation table cannot be read (not finite)"
+                                                     : "") +
                             "; they keep their Entropy and Ne");
+    API_END
+}
+
+/* ------------------------------ the excursion set's J21 (cooling_uvfluc.c:199-246) ------------------------------ */
+
+int mpg_set_excursion_set(mpg_engine *eng, const mpg_excursion_set_params *par)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    eng->cooling.set_excursion_set(par);
+    API_END
+}
+
+int mpg_dev_set_excursion_columns(mpg_engine *eng, const double *d_local_J21, const double *d_zreion)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    MPG_CHECK((d_local_J21 == nullptr) == (d_zreion == nullptr), "mpg_dev_set_excursion_columns: local_J21 and zreion go together");
+    eng->cooling.d_j21 = d_local_J21;
+    eng->cooling.d_zre = d_zreion;
+    eng->cooling.n_exc = d_local_J21 ? eng->n : 0;
+    API_END
+}
+
+int mpg_set_excursion_columns(mpg_engine *eng, const double *local_J21, const double *zreion)
+{
+    API_BEGIN
+    MPG_CHECK(eng, "null argument");
+    MPG_CHECK((local_J21 == nullptr) == (zreion == nullptr), "mpg_set_excursion_columns: local_J21 and zreion go together");
+    eng->cooling.h_j21 = local_J21;
+    eng->cooling.h_zre = zreion;
+    API_END
+}
+
+int mpg_dev_excursion_uvbg(mpg_engine *eng, int64_t n, const double *d_J21, const double *d_zreion, double redshift, const mpg_uvbg *global,
+                           mpg_uvbg *d_out)
+{
+    API_BEGIN
+    MPG_CHECK(eng && global && n >= 0, "null argument");
+    MPG_CHECK(n == 0 || (d_J21 && d_zreion && d_out), "mpg_dev_excursion_uvbg: J21, zreion and out are required");
+    MPG_HIP(hipSetDevice(eng->device));
+    const int64_t bad = eng->cooling.excursion_points(n, d_J21, d_zreion, redshift, *global, d_out, eng->stream);
+    MPG_CHECK(bad == 0, "mpg_dev_excursion_uvbg: " + std::to_string(bad) + " point(s) have a J21 that is NaN or negative or a zreion that is NaN; "
+                                                                          "their background is NaN");
     API_END
 }
 
@@ -661,7 +709,7 @@ int mpg_set_sfr_params(mpg_engine *eng, const mpg_sfr_params *par)
 {
     API_BEGIN
     MPG_CHECK(eng && par, "null argument");
-    eng->sfr.set_params(*par, eng->cooling.have_uvf);
+    eng->sfr.set_params(*par, eng->cooling.have_uvf, eng->cooling.have_exc);
     API_END
 }
 
@@ -679,6 +727,10 @@ int mpg_dev_cooling_and_starformation(mpg_engine *eng, const mpg_sfr_columns *A,
     MPG_CHECK((P.UVFluctuationOn != 0) == eng->cooling.have_uvf,
               P.UVFluctuationOn ? "cooling_and_starformation: UVFluctuationOn is set but the engine holds no UV-fluctuation table (mpg_set_uvf_table)"
                                 : "cooling_and_starformation: the engine holds a UV-fluctuation table but UVFluctuationOn is 0 (mpg_set_sfr_params)");
+    MPG_CHECK(!P.ExcursionSetReion || eng->cooling.have_exc,
+              "cooling_and_starformation: ExcursionSetReion (EXCUR_REION) is set but the engine holds no excursion-set model (mpg_set_excursion_set)");
+    const bool jm = eng->cooling.j21_mode(1 / T->atime - 1);
+    eng->cooling.check_excursion_columns("cooling_and_starformation", 1 / T->atime - 1, eng->n);
     MPG_CHECK(!(P.WindOn || A->delaytime) || eng->have_windpar, "cooling_and_starformation: no wind parameters (mpg_set_wind_params first)");
     const bool subgrid = P.WindOn && (eng->windpar.WindModel & WIND_SUBGRID) != 0; // winds_are_subgrid, sfr_eff.c:205, 280
     if(eng->n > 0) {
@@ -715,7 +767,9 @@ int mpg_dev_cooling_and_starformation(mpg_engine *eng, const mpg_sfr_columns *A,
     // the reference's endrun(1 / 10): every other row of the call has been treated
     MPG_CHECK(bad == 0, "cooling_and_starformation: " + std::to_string(bad) + " row(s) hit an iteration limit of DoCooling or of the ionisation network, or reached "
                                                                              "an electron abundance that is not finite" +
-                            (eng->cooling.have_uvf ? ", or have a position at which the UV-fluctuation table cannot be read (not finite)" : "") +
+                            (jm                      ? ", or have a local_J21 that is NaN or negative or a zreion that is NaN"
+                             : eng->cooling.have_uvf ? ", or have a position at which the UV-fluctuation table cannot be read (not finite)"
+                                                     : "") +
                             "; they keep their columns and form no star");
     API_END
 }

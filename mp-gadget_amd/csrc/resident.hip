@@ -261,6 +261,39 @@ int mpg_resident_sph_end(mpg_engine *eng, const mpg_sph_arrays *A)
     eng->sph_resident = false;
     if(eng->d_delaytime == eng->s_delaytime.p) // the column of mpg_resident_sph_set_delaytime ends with the stretch
         eng->d_delaytime = nullptr;
+    if(eng->cooling.d_j21 && eng->cooling.d_j21 == eng->cooling.s_j21.p) { // ... and so do those of mpg_resident_sph_set_excursion_columns
+        eng->cooling.d_j21 = eng->cooling.d_zre = nullptr;
+        eng->cooling.n_exc = 0;
+    }
+    API_END
+}
+
+// SphP.local_J21 / SphP.zreion of a resident gas run for the cooling and star formation of the stretch: uploaded now, in effect until the
+// next call or the end of the stretch
+int mpg_resident_sph_set_excursion_columns(mpg_engine *eng, const double *local_J21, const double *zreion)
+{
+    API_BEGIN
+    MPG_CHECK(eng && eng->sph_resident, "mpg_resident_sph_set_excursion_columns: no resident gas arrays");
+    MPG_CHECK((local_J21 == nullptr) == (zreion == nullptr), "mpg_resident_sph_set_excursion_columns: local_J21 and zreion go together");
+    MPG_HIP(hipSetDevice(eng->device));
+    CoolingEngine &E = eng->cooling;
+    const int64_t n = eng->res_n;
+    if(!local_J21 || n <= 0) {
+        if(E.d_j21 && E.d_j21 == E.s_j21.p) {
+            E.d_j21 = E.d_zre = nullptr;
+            E.n_exc = 0;
+        }
+    }
+    else {
+        E.s_j21.reserve((size_t)n + 1);
+        E.s_zre.reserve((size_t)n + 1);
+        MPG_HIP(hipMemcpyAsync(E.s_j21.p, local_J21, (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        MPG_HIP(hipMemcpyAsync(E.s_zre.p, zreion, (size_t)n * sizeof(double), hipMemcpyHostToDevice, eng->stream));
+        MPG_HIP(hipStreamSynchronize(eng->stream));
+        E.d_j21 = E.s_j21.p;
+        E.d_zre = E.s_zre.p;
+        E.n_exc = n;
+    }
     API_END
 }
 

@@ -256,8 +256,9 @@ struct SfrEngine {
     int64_t n_rows = 0; // particles rowclass / sfevals were last written for
     mpg_sfr_result last{};
     int64_t last_stats[SFR_NSTATS] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // have_uvf_table: the engine holds a UV-fluctuation table, which UVFluctuationOn must agree with
-    void set_params(const mpg_sfr_params &p, bool have_uvf_table);
+    // have_uvf_table: the engine holds a UV-fluctuation table, which UVFluctuationOn must agree with; have_excursion_set: it holds an
+    // excursion-set model, without which ExcursionSetReion is refused
+    void set_params(const mpg_sfr_params &p, bool have_uvf_table, bool have_excursion_set);
     // the loop of cooling_and_starformation up to the spawning; returns the rows that hit an iteration limit (cooled and star-forming)
     int64_t run(CoolingEngine &cooling, const SfrView &A, const mpg_wind_params *wind, const double *rnd, uint64_t rndsize, const mpg_sph_times &T,
                 const mpg_cooling_step &step, const int *d_active, int64_t nactive, hipStream_t st);

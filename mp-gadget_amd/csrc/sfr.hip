@@ -174,12 +174,13 @@ __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_push(const uint8_t *__restric
 }
 
 // starformation (sfr_eff.c:731-800) for every row of the star-forming list: one lane per row, 2 .. 3 solves of the network.  UVF: under the
-// row's own background (sfr_eff.c:745; zr by particle, cool::local_setup); a row whose zreion is NaN is an error row.
-template <bool UVF>
-__global__ __launch_bounds__(SFR_BLOCK) void k_sfr_eeqos(const Setup S, const SfrTimes T, const SfrScalars P, const SfrView A, const int *__restrict__ sflist,
-                                                         const int64_t nsf, uint8_t *__restrict__ outcome, double *__restrict__ sfmass,
-                                                         int *__restrict__ sfevals, unsigned *__restrict__ blockcnt, double *__restrict__ partial,
-                                                         unsigned long long *__restrict__ ctr, const double *__restrict__ zr)
+// row's own background (sfr_eff.c:745; zr by particle, cool::local_setup); a row whose zreion is NaN is an error row.  J21: under the
+// background of the row's J21 and zreion (cool::j21_setup, X the model); a row that cool::j21_row_bad names is an error row.
+template <bool UVF, bool J21>
+__device__ __forceinline__ void sfr_eeqos_rows(const Setup &S, const SfrTimes &T, const SfrScalars &P, const SfrView &A, const int *__restrict__ sflist,
+                                               const int64_t nsf, uint8_t *__restrict__ outcome, double *__restrict__ sfmass, int *__restrict__ sfevals,
+                                               unsigned *__restrict__ blockcnt, double *__restrict__ partial, unsigned long long *__restrict__ ctr,
+                                               const double *__restrict__ zr, const double *__restrict__ j21 = nullptr, const J21View *X = nullptr)
 {
     __shared__ unsigned wc[2][SFR_WAVES];
     __shared__ double ws[3][SFR_WAVES];
@@ -225,6 +226,16 @@ __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_eeqos(const Setup S, const Sf
                 }
                 else
                     o = starformation(local_setup(S, zreion), P.p, r, T.dloga[bin], T.hubble, T.atime, T.a3inv, P.rnd[id % P.rndsize],
+                                      P.rnd[(id + 1ull) % P.rndsize], C);
+            }
+            else if constexpr(J21) {
+                const double zreion = zr[p], local_J21 = j21[p];
+                if(j21_row_bad(local_J21, zreion)) {
+                    o = RowResult{};
+                    o.outcome = OUT_ERROR;
+                }
+                else
+                    o = starformation(j21_setup(S, *X, local_J21, zreion), P.p, r, T.dloga[bin], T.hubble, T.atime, T.a3inv, P.rnd[id % P.rndsize],
                                       P.rnd[(id + 1ull) % P.rndsize], C);
             }
             else
@@ -280,6 +291,23 @@ __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_eeqos(const Setup S, const Sf
     }
 }
 
+template <bool UVF>
+__global__ __launch_bounds__(SFR_BLOCK) void k_sfr_eeqos(const Setup S, const SfrTimes T, const SfrScalars P, const SfrView A, const int *__restrict__ sflist,
+                                                         const int64_t nsf, uint8_t *__restrict__ outcome, double *__restrict__ sfmass,
+                                                         int *__restrict__ sfevals, unsigned *__restrict__ blockcnt, double *__restrict__ partial,
+                                                         unsigned long long *__restrict__ ctr, const double *__restrict__ zr)
+{
+    sfr_eeqos_rows<UVF, false>(S, T, P, A, sflist, nsf, outcome, sfmass, sfevals, blockcnt, partial, ctr, zr);
+}
+__global__ __launch_bounds__(SFR_BLOCK) void k_sfr_eeqos_j21(const Setup S, const SfrTimes T, const SfrScalars P, const SfrView A, const int *__restrict__ sflist,
+                                                             const int64_t nsf, uint8_t *__restrict__ outcome, double *__restrict__ sfmass,
+                                                             int *__restrict__ sfevals, unsigned *__restrict__ blockcnt, double *__restrict__ partial,
+                                                             unsigned long long *__restrict__ ctr, const double *__restrict__ j21,
+                                                             const double *__restrict__ zr, const J21View X)
+{
+    sfr_eeqos_rows<false, true>(S, T, P, A, sflist, nsf, outcome, sfmass, sfevals, blockcnt, partial, ctr, zr, j21, &X);
+}
+
 // the new-star list and the MaybeWind list from the outcomes, in list order
 __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_lists(const uint8_t *__restrict__ outcome, const int *__restrict__ sflist, const double *__restrict__ sfmass,
                                                          const int64_t nsf, const unsigned *__restrict__ blockoff, int *__restrict__ ns_parent,
@@ -303,13 +331,14 @@ __global__ __launch_bounds__(SFR_BLOCK) void k_sfr_lists(const uint8_t *__restri
 
 } // namespace
 
-void SfrEngine::set_params(const mpg_sfr_params &p, bool have_uvf_table)
+void SfrEngine::set_params(const mpg_sfr_params &p, bool have_uvf_table, bool have_excursion_set)
 {
     // what the engine does not carry is refused when it is set, so that a caller keeps its CPU path from the start
     MPG_CHECK(p.BHFeedbackUseTcool != 2, "star formation: BHFeedbackUseTcool == 2 is not carried (get_egyeff in sfreff_on_eeqos)");
     MPG_CHECK(p.BHFeedbackUseTcool >= 0 && p.BHFeedbackUseTcool <= 3, "star formation: BHFeedbackUseTcool mode not supported");
     MPG_CHECK(!p.UVFluctuationOn || have_uvf_table, "star formation: UVFluctuationOn without a UV-fluctuation table on this engine (mpg_set_uvf_table first)");
-    MPG_CHECK(!p.ExcursionSetReion, "star formation: ExcursionSetReion (EXCUR_REION) is not carried (local_J21, zreion)");
+    MPG_CHECK(!p.ExcursionSetReion || have_excursion_set,
+              "star formation: ExcursionSetReion (EXCUR_REION) without an excursion-set model on this engine (mpg_set_excursion_set first)");
     MPG_CHECK(p.NTask <= 1, "star formation: NTask > 1 is not carried; several ranks keep the CPU function");
     MPG_CHECK(p.Generations >= 1 && p.Generations <= 14, "star formation: Generations outside 1 .. 14");
     MPG_CHECK(p.PhysDensThresh > 0 && p.MaxSfrTimescale > 0, "star formation: PhysDensThresh and MaxSfrTimescale must be positive (after init_cooling_and_star_formation)");
@@ -352,8 +381,12 @@ int64_t SfrEngine::run(CoolingEngine &cooling, const SfrView &A, const mpg_wind_
     P.rnd = rnd;
     P.rndsize = rndsize;
     unsigned tot[2] = {0, 0};
+    const double redshift = 1 / T.atime - 1; // sfr_eff.c:211
+    const bool jm = cooling.j21_mode(redshift);
+    cooling.check_excursion_columns("cooling_and_starformation", redshift, n);
+    const bool uvf = cooling.have_uvf && !jm;
     // the zreion of every listed gas row, cooled or star-forming, before either kernel reads it
-    if(cooling.have_uvf)
+    if(uvf)
         cooling.uvf_rows(A.pos, A.type, A.mass, d_active, nactive, n, st);
     if(nlist > 0) {
         hipLaunchKernelGGL(k_sfr_classify, dim3(nb), dim3(SFR_BLOCK), 0, st, cooling.par.temp_to_u, ST, P, A, d_active, nlist, cls.p, rowclass.p, blockcnt.p);
@@ -390,9 +423,13 @@ int64_t SfrEngine::run(CoolingEngine &cooling, const SfrView &A, const mpg_wind_
         partial.reserve(3 * (size_t)nb2 + 3);
         ctr.reserve(SC_N);
         MPG_HIP(hipMemsetAsync(ctr.p, 0, SC_N * sizeof(unsigned long long), st));
-        const Setup S = cooling.setup(step, 1 / T.atime - 1); // sfr_eff.c:211
-        hipLaunchKernelGGL(cooling.have_uvf ? k_sfr_eeqos<true> : k_sfr_eeqos<false>, dim3(nb2), dim3(SFR_BLOCK), 0, st, S, ST, P, A, sflist.p, nsf, outcome.p,
-                           sfmass.p, sfevals.p, blockcnt.p, partial.p, ctr.p, cooling.have_uvf ? (const double *)cooling.uvf_z.p : (const double *)nullptr);
+        const Setup S = cooling.setup(step, redshift);
+        if(jm)
+            hipLaunchKernelGGL(k_sfr_eeqos_j21, dim3(nb2), dim3(SFR_BLOCK), 0, st, S, ST, P, A, sflist.p, nsf, outcome.p, sfmass.p, sfevals.p, blockcnt.p,
+                               partial.p, ctr.p, cooling.d_j21, cooling.d_zre, cooling.j21_view(redshift));
+        else
+            hipLaunchKernelGGL(uvf ? k_sfr_eeqos<true> : k_sfr_eeqos<false>, dim3(nb2), dim3(SFR_BLOCK), 0, st, S, ST, P, A, sflist.p, nsf, outcome.p,
+                               sfmass.p, sfevals.p, blockcnt.p, partial.p, ctr.p, uvf ? (const double *)cooling.uvf_z.p : (const double *)nullptr);
         hipLaunchKernelGGL(k_sfr_scan, dim3(1), dim3(SFR_BLOCK), 0, st, blockcnt.p, (int64_t)nb2, totals.p, (const double *)partial.p, sums.p);
         hipLaunchKernelGGL(k_sfr_lists, dim3(nb2), dim3(SFR_BLOCK), 0, st, outcome.p, sflist.p, sfmass.p, nsf, blockcnt.p, ns_parent.p, ns_mass.p, ns_spawn.p,
                            A.a.stellarmass ? maybewind.p : (int *)nullptr);

@@ -252,6 +252,12 @@ class Uvbg(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("J_UV", "gJH0", "gJHep", "gJHe0", "epsH0", "epsHep", "epsHe0", "self_shield_dens", "zreion")]
 
 
+class ExcursionSetParams(C.Structure):
+    """mpg_excursion_set_params: struct UVFparams (cooling_uvfluc.c:25-30) and get_J21_coeffs(AlphaUV)"""
+    _fields_ = [("ExcursionSetReionOn", C.c_int), ("ExcursionSetZStop", C.c_double), ("AlphaUV", C.c_double)] + \
+               [(k, C.c_double) for k in ("gJH0", "gJHe0", "gJHep", "epsH0", "epsHe0", "epsHep")]
+
+
 class CoolingParams(C.Structure):
     """mpg_cooling_params: struct cooling_params (cooling_rates.h:23-58), struct cooling_units (cooling.h:32-44), three members of sfr_params"""
     _fields_ = [("recomb", C.c_int), ("cooling", C.c_int), ("SelfShieldingOn", C.c_int), ("PhotoIonizationOn", C.c_int), ("fBar", C.c_double),
@@ -1798,6 +1804,47 @@ class Engine:
         z = np.zeros(n, np.float64)
         self._ck(self.lib.mpg_uvf_export(self.h, C.c_int64(n), z.ctypes.data_as(C.c_void_p)))
         return z
+
+    # ------------------------------------------------------------------ the excursion set's J21 (get_local_UVBG_from_J21, cooling_uvfluc.c:199-246)
+    def set_excursion_set(self, par=None):
+        """set_uvf_params with get_J21_coeffs(AlphaUV): a dict of the members of mpg_excursion_set_params (excursion.params makes one from a
+        J21CoeffFile), or an ExcursionSetParams; no argument removes the model"""
+        if par is None:
+            self._ck(self.lib.mpg_set_excursion_set(self.h, None))
+            return
+        if not isinstance(par, ExcursionSetParams):
+            par = ExcursionSetParams(**par)
+        self._ck(self.lib.mpg_set_excursion_set(self.h, C.byref(par)))
+
+    def dev_set_excursion_columns(self, local_J21=None, zreion=None):
+        """SphP.local_J21 / SphP.zreion for the calls that follow: float64 device tensors in particle order of the table bound now (the
+        two dev_calculate_uvbg wrote); no arguments unbinds"""
+        self._keep["excursion_columns"] = (local_J21, zreion)
+        self._ck(self.lib.mpg_dev_set_excursion_columns(self.h, _ptr(local_J21), _ptr(zreion)))
+
+    @staticmethod
+    def _excursion_host(local_J21, zreion):
+        for name, t in (("local_J21", local_J21), ("zreion", zreion)):
+            if t is not None and (t.dtype != np.float64 or not t.flags["C_CONTIGUOUS"]):
+                raise EngineError("%s must be contiguous float64" % name)
+        return [None if t is None else t.ctypes.data_as(C.c_void_p) for t in (local_J21, zreion)]
+
+    def set_excursion_columns(self, local_J21=None, zreion=None):
+        """... numpy float64 [n] for the host forms (cooling, cooling_and_starformation): they travel with every such call"""
+        p = self._excursion_host(local_J21, zreion)
+        self._keep["h_excursion_columns"] = (local_J21, zreion)
+        self._ck(self.lib.mpg_set_excursion_columns(self.h, p[0], p[1]))
+
+    def resident_sph_set_excursion_columns(self, local_J21=None, zreion=None):
+        """... numpy float64 [n] of a resident gas run: uploaded now, in effect until the next call or the end of the stretch"""
+        p = self._excursion_host(local_J21, zreion)
+        self._ck(self.lib.mpg_resident_sph_set_excursion_columns(self.h, p[0], p[1]))
+
+    def dev_excursion_uvbg(self, J21, zreion, redshift, out, uvbg=None):
+        """get_local_UVBG at n arbitrary points: float64 device tensors [n] in, `out` a float64 device tensor [n][9] (the members of
+        mpg_uvbg in the order of Uvbg); `uvbg` the global background (a dict, as in a cooling step) for redshift <= ExcursionSetZStop"""
+        g = Uvbg(**(uvbg or {}))
+        self._ck(self.lib.mpg_dev_excursion_uvbg(self.h, C.c_int64(J21.shape[0]), _ptr(J21), _ptr(zreion), C.c_double(redshift), C.byref(g), _ptr(out)))
 
     # ------------------------------------------------------------------ star formation (cooling_and_starformation, sfr_eff.c:186-394)
     # `par` is a dict of the members of mpg_sfr_params (or an SfrParams); `columns` maps the field names of mpg_sfr_columns to device tensors

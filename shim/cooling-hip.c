@@ -23,7 +23,9 @@
  *     particle p_i only.
  * A UV-fluctuation table (init_uvf_table) is loaded onto the device once, with PartManager->BoxSize, and every device call is preceded by
  * mpg_set_uvf_offset(PartManager->CurrentParticleOffset): the engine then gives every row the background of get_local_UVBG_from_global.
- * With several ranks or the excursion-set reionisation in use, the reference's code runs unchanged: the queue refuses every particle.
+ * With the excursion set in use (ExcursionSetReionOn, a build with EXCUR_REION) the model goes to the engine once with the coefficients of the
+ * reference's own get_J21_coeffs(AlphaUV), and every device call binds SphP.local_J21 / SphP.zreion gathered by particle.
+ * With several ranks the reference's code runs unchanged: the queue refuses every particle.
  * The parameters are file-static in the reference; tools/link_reference.sh appends one accessor each to cooling_rates.c, cooling.c,
  * cooling_uvfluc.c and sfr_eff.c (listed in INTEGRATION.md).
  * Compiled inside the reference tree (see gravity-hip.c). */
@@ -56,6 +58,7 @@ struct cooling_params mpg_shim_cooling_params(void);                       /* co
 struct cooling_units mpg_shim_cooling_units(void);                         /* cooling.c: coolunits */
 int mpg_shim_uvf_table(int64_t *nside, double **table);                    /* cooling_uvfluc.c: UVF.Nside, UVF.Table; returns UVF.enabled */
 int mpg_shim_excursion_set_on(void);                                       /* cooling_uvfluc.c: uvf_params.ExcursionSetReionOn */
+void mpg_shim_uvf_params(int *ExcursionSetReionOn, double *ExcursionSetZStop, double *AlphaUV); /* cooling_uvfluc.c: uvf_params */
 int mpg_shim_metal_table(int *n, double **bins, double **rate);            /* cooling_uvfluc.c: MetalCool; returns !CoolingNoMetal */
 void mpg_shim_sfr_cooling(int *StarformationOn, double *MinGasTemp, double *temp_to_u, double *HIReionTemp); /* sfr_eff.c: sfr_params */
 void mpg_shim_sfr_params(mpg_sfr_params *p);                               /* sfr_eff.c: sfr_params after init_cooling_and_star_formation */
@@ -113,13 +116,67 @@ static void set_params(void)
         ck(mpg_set_uvf_table(mpg_shim_engine(), nside, table, PartManager->BoxSize));
     else
         ck(mpg_set_uvf_table(mpg_shim_engine(), 0, NULL, 0));
+    /* set_uvf_params (cooling_uvfluc.c:33-45) with get_J21_coeffs(AlphaUV), which get_local_UVBG_from_J21 evaluates per particle */
+    if(mpg_shim_excursion_set_on()) {
+        mpg_excursion_set_params ep;
+        memset(&ep, 0, sizeof(ep));
+        mpg_shim_uvf_params(&ep.ExcursionSetReionOn, &ep.ExcursionSetZStop, &ep.AlphaUV);
+        const struct J21_coeffs c = get_J21_coeffs(ep.AlphaUV);
+        ep.gJH0 = c.gJH0;
+        ep.gJHe0 = c.gJHe0;
+        ep.gJHep = c.gJHep;
+        ep.epsH0 = c.epsH0;
+        ep.epsHe0 = c.epsHe0;
+        ep.epsHep = c.epsHep;
+        ck(mpg_set_excursion_set(mpg_shim_engine(), &ep));
+    }
+    else
+        ck(mpg_set_excursion_set(mpg_shim_engine(), NULL));
     params_set = 1;
 }
 
-/* the device form serves one rank, with the global UV background or that of a UV-fluctuation table; not the excursion set */
+/* SphP.local_J21 / SphP.zreion by particle for the device call that follows (sfr_eff.c:478-480, :741-743); the caller frees the block.
+ * Without the excursion set nothing is gathered and nothing is bound. */
+static double *bind_excursion_columns(int resident)
+{
+    double *cols = NULL;
+#ifdef EXCUR_REION
+    if(mpg_shim_excursion_set_on()) {
+        const int64_t n = PartManager->NumPart;
+        int64_t i;
+        cols = (double *)mymalloc("mpg_excursion", ((size_t)n * 2 + 1) * sizeof(double));
+        #pragma omp parallel for
+        for(i = 0; i < n; i++) {
+            const int gas = P[i].Type == 0 && !P[i].IsGarbage;
+            cols[i] = gas ? SPHP(i).local_J21 : 0;
+            cols[n + i] = gas ? SPHP(i).zreion : -1;
+        }
+        if(resident)
+            ck(mpg_resident_sph_set_excursion_columns(mpg_shim_engine(), cols, cols + n));
+        else
+            ck(mpg_set_excursion_columns(mpg_shim_engine(), cols, cols + n));
+    }
+#else
+    (void)resident;
+#endif
+    return cols;
+}
+
+static void unbind_excursion_columns(double *cols, int resident)
+{
+    if(!cols)
+        return;
+    if(resident)
+        ck(mpg_resident_sph_set_excursion_columns(mpg_shim_engine(), NULL, NULL));
+    else
+        ck(mpg_set_excursion_columns(mpg_shim_engine(), NULL, NULL));
+    myfree(cols);
+}
+
+/* the device form serves one rank, with the global UV background, that of a UV-fluctuation table or that of the excursion set's J21 */
 static int device_cooling_usable(void)
 {
-    return mpg_shim_ntask() == 1 && !mpg_shim_excursion_set_on();
+    return mpg_shim_ntask() == 1;
 }
 
 /* PartManager->CurrentParticleOffset (cooling_uvfluc.c:185-188) for the device call that follows */
@@ -185,6 +242,7 @@ static void cool_on_device(const int *list, int64_t nlist, double Time, double h
     }
     mpg_particle_view v = mpg_shim_view();
     set_uvf_offset();
+    double *excursion = bind_excursion_columns(resident);
     if(resident)
         ck(mpg_resident_sph_cooling(mpg_shim_engine(), &v, &t, &step, list, nlist, ne, metallicity, heiii));
     else {
@@ -193,6 +251,7 @@ static void cool_on_device(const int *list, int64_t nlist, double Time, double h
         mpg_cooling_arrays A = {density, entropy, ne, sfr, metallicity, heiii, tb};
         ck(mpg_cooling(mpg_shim_engine(), &v, PartManager->BoxSize, &A, &t, &step, list, nlist));
     }
+    unbind_excursion_columns(excursion, resident);
     /* sfr_eff.c:509-513 for the particles the loop treats (sfr_eff.c:229) */
     const int64_t count = list ? nlist : n;
     #pragma omp parallel for
@@ -253,6 +312,7 @@ int mpg_shim_sfr_loop(ActiveParticles *act, double Time, double hubble, const st
     mpg_shim_sfr_params(&sp); /* (UVFluctuationOn from UVF.enabled: set_params above has loaded that table) */
     sp.GravInternal = sfr_grav;
     sp.NTask = 1;
+    sp.ExcursionSetReion = mpg_shim_excursion_set_on(); /* (set_params above has passed the model) */
     const int resident = mpg_shim_resident();
     const int subgrid = sp.WindOn && winds_are_subgrid() && MaybeWind->sizes && StellarMass;
     if(resident && subgrid)
@@ -345,6 +405,7 @@ int mpg_shim_sfr_loop(ActiveParticles *act, double Time, double hubble, const st
     A.stellarmass = stellarmass;
     mpg_particle_view v = mpg_shim_view();
     set_uvf_offset();
+    double *excursion = bind_excursion_columns(resident);
     if(resident)
         ck(mpg_resident_sph_cooling_and_starformation(mpg_shim_engine(), &v, &A, &t, &step, list, nlist));
     else {
@@ -352,6 +413,7 @@ int mpg_shim_sfr_loop(ActiveParticles *act, double Time, double hubble, const st
         v = mpg_shim_view();
         ck(mpg_cooling_and_starformation(mpg_shim_engine(), &v, PartManager->BoxSize, &A, &t, &step, list, nlist));
     }
+    unbind_excursion_columns(excursion, resident);
     /* the columns of the rows the loop treats (sfr_eff.c:229) back into P / SphP */
     const int64_t count = list ? nlist : n;
     #pragma omp parallel for
@@ -428,7 +490,7 @@ void cooling_and_starformation(ActiveParticles *act, double Time, double dloga, 
     int sfon;
     double a, b, c;
     mpg_shim_sfr_cooling(&sfon, &a, &b, &c);
-    if(!device_cooling_usable()) { /* several ranks, the excursion set: the reference's own code */
+    if(!device_cooling_usable()) { /* several ranks: the reference's own code */
         if(mpg_shim_resident())
             endrun(5, "cooling_and_starformation(): the reference's loop inside a resident stretch (mpg_shim_resident_end first)\n");
         cpu_cooling_and_starformation(act, Time, dloga, tree, GravAccel, ddecomp, CP, GradRho, rnd, FdSfr);

@@ -154,6 +154,8 @@ append(T + "/libgadget/cooling.c", "struct cooling_units mpg_shim_cooling_units(
 append(T + "/libgadget/cooling_uvfluc.c", "int mpg_shim_uvf_in_use(void) { return UVF.enabled || uvf_params.ExcursionSetReionOn; }\n"
        "int mpg_shim_uvf_table(int64_t *nside, double **table) { *nside = UVF.enabled ? UVF.Nside : 0; *table = UVF.enabled ? UVF.Table : NULL; return UVF.enabled; }\n"
        "int mpg_shim_excursion_set_on(void) { return uvf_params.ExcursionSetReionOn; }\n"
+       "void mpg_shim_uvf_params(int *ExcursionSetReionOn, double *ExcursionSetZStop, double *AlphaUV)\n"
+       "{ *ExcursionSetReionOn = uvf_params.ExcursionSetReionOn; *ExcursionSetZStop = uvf_params.ExcursionSetZStop; *AlphaUV = uvf_params.AlphaUV; }\n"
        "int mpg_shim_metal_table(int *n, double **bins, double **rate)\n{\n    if(MetalCool.CoolingNoMetal)\n        return 0;\n"
        "    n[0] = MetalCool.NRedshift_bins; n[1] = MetalCool.NHydrogenNumberDensity_bins; n[2] = MetalCool.NTemperature_bins;\n"
        "    bins[0] = MetalCool.Redshift_bins; bins[1] = MetalCool.HydrogenNumberDensity_bins; bins[2] = MetalCool.Temperature_bins;\n"
