@@ -1512,6 +1512,63 @@ int mpg_dev_fof_seed(mpg_engine *eng, const mpg_fof_seed_params *par, double ati
  * ERRORS (returned): those of mpg_dev_fof_subgrid. */
 int mpg_dev_fof_set_escapefraction(mpg_engine *eng, double *d_escfrac);
 
+/* ---- the group catalogue on disk: fof_save_groups / fof_save_particles (fof.c:1157-1163, fofpetaio.c:38-159) on ONE rank, from device
+ * columns in particle order.  The file holds `Header` (twelve attributes, fofpetaio.c:448-459), the FOFGroups blocks in GrNr order
+ * (fofpetaio.c:538-568; the getters of :464-536) and, with SaveParticles, one block "<ptype>/<name>" per descriptor holding the selected
+ * rows of that type sorted by GrNr (register_io_blocks with WriteGroupID, petaio.c:986-1080).
+ *   selected:   GrNr >= 0, type < 6, flag bit 0 (IsGarbage) and bit 1 (Swallowed) clear (fofpetaio.c:33-36, petaio.c:117-154)
+ *   in_group:   GrNr >= 0 and type < 6, whatever the flags: NumPartInGroupTotal of the header (fofpetaio.c:432-436)
+ * THE ONE DEFINED DIFFERENCE: rows of equal (type, GrNr) keep ascending particle index; the reference's qsort_openmp with
+ * order_by_type_and_grnr (fofpetaio.c:202-218, :389) leaves their order unspecified.
+ * GrNr counts from 1 here as in fof.c:1127-1134: the FOFGroups blocks are scattered to row GrNr - 1, GroupID holds GrNr itself.
+ * The wraps of the position getters are the reference's two loops of repeated addition (the bits match), each bounded at 64 trips: a value
+ * that is not finite or lies further out fails the call with the block and the row named, and nothing of that block is written. */
+enum { MPG_DT_F8 = 0, MPG_DT_F4 = 1, MPG_DT_U1 = 2, MPG_DT_U4 = 3, MPG_DT_U8 = 4, MPG_DT_I4 = 5, MPG_DT_I8 = 6 };
+enum {
+    MPG_CONV_NONE = 0,     /* SIMPLE_GETTER: out = (block type) column */
+    MPG_CONV_POSITION = 1, /* GTPosition, petaio.c:744-753: f64 [3] - CurrentParticleOffset, wrapped into (0, BoxSize]; f8 */
+    MPG_CONV_VELOCITY = 2, /* GTVelocity, petaio.c:803-817: (float)(fac * Vel), fac = 1 / atime with UsePeculiarVelocity, else 1 */
+    MPG_CONV_GROUPID = 3   /* GTGroupID, petaio.c:887: the int64 GrNr column as u4; d_data NULL: the GrNr of the last mpg_dev_fof_fof */
+};
+typedef struct mpg_fof_catalogue_params {
+    double atime;
+    double CurrentParticleOffset[3];
+    int UsePeculiarVelocity, MetalReturnOn, SaveParticles;
+    int nfile;                 /* files per non-empty block; an empty block gets NFILE: 0 (petaio.c:673-676) */
+    double hubble;             /* hubble_function(CP, atime): RSDFactor = 1 / (atime hubble), / atime again without peculiar velocities */
+    double MassTable[6];
+    double OmegaLambda, Omega0, HubbleParam, CMBTemperature, OmegaBaryon;
+} mpg_fof_catalogue_params;    /* (BoxSize is that of the bound particles) */
+typedef struct mpg_catalogue_block {
+    const char *name;          /* the block is "<ptype>/<name>" */
+    int ptype;                 /* 0..5 */
+    const void *d_data;        /* device column [n][nmemb] in PARTICLE order, n the bound particles */
+    int src_dtype;             /* MPG_DT_F8, F4, U1, U8, I4 or I8: the column's element type */
+    int nmemb;
+    int dtype;                 /* MPG_DT_F8, F4, U1, U4, U8 or I4: the block's type in the file */
+    int conv;                  /* MPG_CONV_* */
+} mpg_catalogue_block;
+/* fof_select_func + petaio_build_selection + order_by_type_and_grnr: d_perm[n] (device; the first count[0] + ... + count[5] entries are
+ * the order, type by type, the rest are the rows not selected), count[6] the selected rows per type, in_group[6].  d_grnr NULL: the GrNr of
+ * the last mpg_dev_fof_fof (ERRORS: those of mpg_dev_fof_subgrid); else an int64 column of the bound particles, values below 2^32, and no
+ * FOF call is needed.  d_flags may be NULL. */
+int mpg_dev_fof_pig_order(mpg_engine *eng, const int64_t *d_grnr, const unsigned char *d_flags, int *d_perm, int64_t count[6], int64_t in_group[6]);
+/* the gather of one block, device to device: d_out[j][k] = getter(column[d_perm[j]][k]) for j < count; block->ptype and name only label
+ * errors.  ERRORS (returned, d_out untouched by a POSITION block): a d_perm[j] outside the bound particles; a POSITION value that is not
+ * finite or more than 64 boxes outside - the first such row j is named. */
+int mpg_dev_gather_block(mpg_engine *eng, const int *d_perm, int64_t count, const mpg_catalogue_block *block, const mpg_fof_catalogue_params *params,
+                         void *d_out);
+/* the whole of fof_save_particles on the groups of the last mpg_dev_fof_fof (and, for the sub-grid members of the FOFGroups blocks, of the
+ * last mpg_dev_fof_subgrid; zeros without one): Header, the FOFGroups blocks (the four metal blocks only with MetalReturnOn), and with
+ * SaveParticles the `nblocks` particle blocks, each of count[ptype] rows (a type without members gets blocks of size 0).  Every block is
+ * gathered into one device buffer, copied into one pinned host buffer and written from there.
+ * ERRORS (returned, the block named): those of mpg_dev_fof_subgrid and every fault of a descriptor are found before anything is written and
+ * create no file; a refused POSITION row ends the call at its block. */
+int mpg_dev_fof_save_groups(mpg_engine *eng, const char *path, const mpg_fof_catalogue_params *params, const mpg_catalogue_block *blocks, int nblocks,
+                            const unsigned char *d_flags);
+/* device times in ms of the last calls: the order (keys + sort); the sum of the gathers; the FOFGroups scatters */
+int mpg_fof_catalogue_get_times(mpg_engine *eng, double ms[3]);
+
 /* ---- excursion-set reionisation (EXCUR_REION; libgadget/uvbg.c:471-594 through petapm_reion, petapm.c:381-577) on the bound particles
  * of ONE rank: the producer of SphP.local_J21 / SphP.zreion.  The consumer (get_local_UVBG_from_J21 in cooling and star formation) is
  * mpg_set_excursion_set above: the two output columns of this call are what mpg_dev_set_excursion_columns binds.

@@ -12,4 +12,5 @@ from . import dist  # noqa: F401
 from . import planes  # noqa: F401
 from . import heiii  # noqa: F401
 from . import excursion  # noqa: F401
+from . import fof_catalogue  # noqa: F401
 from .engine import Engine, EngineError, PARTICLE_DTYPE, make_particles, SphTimes, KickFactors, DriftKickTimes  # noqa: F401

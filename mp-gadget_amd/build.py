@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libmpgadget_hip.so")
-SOURCES = ["tree_build.hip", "grav_walk.hip", "grav_walk_coop.hip", "grav_walk_split.hip", "grav_pair_walk.hip", "pm.hip", "planes.hip", "sph.hip", "veldisp.hip", "cooling.hip", "sfr.hip", "metals.hip", "blackhole.hip", "dynfric.hip", "winds.hip", "heiii.hip", "timestep.hip", "peano.hip", "domain.hip", "fof.hip", "uvbg.hip", "snapshot_io.hip", "engine.hip", "physics.hip", "integrator.hip", "host_forms.hip", "resident.hip", "dist.hip", "dist_gravity.hip", "dist_sph.hip", "dist_domain.hip", "dist_fof.hip", "dist_host.hip", "rccl_comm.hip"]
+SOURCES = ["tree_build.hip", "grav_walk.hip", "grav_walk_coop.hip", "grav_walk_split.hip", "grav_pair_walk.hip", "pm.hip", "planes.hip", "sph.hip", "veldisp.hip", "cooling.hip", "sfr.hip", "metals.hip", "blackhole.hip", "dynfric.hip", "winds.hip", "heiii.hip", "timestep.hip", "peano.hip", "domain.hip", "fof.hip", "fof_catalogue.hip", "uvbg.hip", "snapshot_io.hip", "engine.hip", "physics.hip", "integrator.hip", "host_forms.hip", "resident.hip", "dist.hip", "dist_gravity.hip", "dist_sph.hip", "dist_domain.hip", "dist_fof.hip", "dist_host.hip", "rccl_comm.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 # experiments (-D...): MPG_EXTRA_FLAGS="file.hip:-Dx -Dy" applies to one source, MPG_EXTRA_FLAGS="-Dx" to all; part of the

@@ -19,6 +19,7 @@
 #include "planes.h"
 #include "domain.h"
 #include "fof.h"
+#include "fof_catalogue.h"
 #include "uvbg.h"
 #include "snapshot_io.h"
 #include "tree_build.h"
@@ -96,6 +97,7 @@ struct mpg_engine {
     PeanoScratch peano;
     DomainScratch domain;
     FofEngine fof;
+    CatalogueEngine cat; // the group catalogue on disk (fof_catalogue.hip): the order, the staging pair, the times of the last call
     PlaneEngine planes;
     VdispEngine vdisp; // DM velocity dispersion (veldisp.c): the loop's state
     // ---- everything below is the host-pointer ("drop-in") layer's: host_forms.hip and resident.hip (the engine only destroys it) ----

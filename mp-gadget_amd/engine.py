@@ -443,6 +443,56 @@ class FofSubgridGroupsC(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in FOF_SUBGRID_GROUPS]
 
 
+# the group catalogue on disk (mpg_dev_fof_save_groups): the codes MPG_DT_* / MPG_CONV_* by position; torch has no unsigned 32- and 64-bit
+# types, so u4 / u8 travel in int32 / int64 tensors of the same bits
+CATALOGUE_DTYPES = ("f8", "f4", "u1", "u4", "u8", "i4", "i8")
+CATALOGUE_CONVS = ("NONE", "POSITION", "VELOCITY", "GROUPID")
+CATALOGUE_TORCH = dict(f8="float64", f4="float32", u1="uint8", u4="int32", u8="int64", i4="int32", i8="int64")
+CATALOGUE_SRC_OF_TORCH = dict(float64="f8", float32="f4", uint8="u1", int32="i4", int64="i8")
+
+
+class FofCatalogueParams(C.Structure):
+    """mpg_fof_catalogue_params"""
+    _fields_ = [("atime", C.c_double), ("CurrentParticleOffset", C.c_double * 3), ("UsePeculiarVelocity", C.c_int), ("MetalReturnOn", C.c_int),
+                ("SaveParticles", C.c_int), ("nfile", C.c_int), ("hubble", C.c_double), ("MassTable", C.c_double * 6), ("OmegaLambda", C.c_double),
+                ("Omega0", C.c_double), ("HubbleParam", C.c_double), ("CMBTemperature", C.c_double), ("OmegaBaryon", C.c_double)]
+
+
+class CatalogueBlockC(C.Structure):
+    """mpg_catalogue_block"""
+    _fields_ = [("name", C.c_char_p), ("ptype", C.c_int), ("d_data", C.c_void_p), ("src_dtype", C.c_int), ("nmemb", C.c_int), ("dtype", C.c_int),
+                ("conv", C.c_int)]
+
+
+def fof_catalogue_params(atime, hubble=1.0, CurrentParticleOffset=(0.0, 0.0, 0.0), UsePeculiarVelocity=1, MetalReturnOn=1, SaveParticles=1, nfile=1,
+                         MassTable=(0.0,) * 6, OmegaLambda=0.0, Omega0=0.0, HubbleParam=0.0, CMBTemperature=0.0, OmegaBaryon=0.0):
+    """mpg_fof_catalogue_params from keywords"""
+    return FofCatalogueParams(float(atime), (C.c_double * 3)(*[float(x) for x in CurrentParticleOffset]), int(UsePeculiarVelocity), int(MetalReturnOn),
+                              int(SaveParticles), int(nfile), float(hubble), (C.c_double * 6)(*[float(x) for x in MassTable]), float(OmegaLambda),
+                              float(Omega0), float(HubbleParam), float(CMBTemperature), float(OmegaBaryon))
+
+
+def catalogue_block(name, ptype, column, dtype, conv="NONE", src_dtype=None):
+    """mpg_catalogue_block of a device tensor [n] or [n, nmemb] (None only with GROUPID: the GrNr of the last dev_fof_fof).  src_dtype: the
+    column's element type when the tensor's own does not say it ("u8" for IDs kept in an int64 tensor); default: the tensor's, and "u8" for an
+    int64 tensor that goes into a u8 block."""
+    if dtype not in CATALOGUE_DTYPES or conv not in CATALOGUE_CONVS:
+        raise EngineError("catalogue block %d/%s: unknown dtype %r or conversion %r" % (ptype, name, dtype, conv))
+    if column is None:
+        src, nmemb = "i8", 1
+    else:
+        if not column.is_contiguous() or column.dim() not in (1, 2):
+            raise EngineError("catalogue block %d/%s: the column must be a contiguous [n] or [n, nmemb] tensor" % (ptype, name))
+        src = src_dtype or CATALOGUE_SRC_OF_TORCH.get(str(column.dtype).split(".")[-1])
+        if src is None or src not in CATALOGUE_DTYPES:
+            raise EngineError("catalogue block %d/%s: unsupported column type %s" % (ptype, name, column.dtype))
+        if src_dtype is None and src == "i8" and dtype == "u8":
+            src = "u8"
+        nmemb = 1 if column.dim() == 1 else int(column.shape[1])
+    return CatalogueBlockC(name.encode(), int(ptype), None if column is None else column.data_ptr(), CATALOGUE_DTYPES.index(src), nmemb,
+                           CATALOGUE_DTYPES.index(dtype), CATALOGUE_CONVS.index(conv))
+
+
 UVBG_COLUMN_FIELDS = ("sfr", "escfrac", "local_J21", "zreion")
 UVBG_COLUMN_DTYPES = {}
 
@@ -1162,6 +1212,46 @@ class Engine:
         """mpg_dev_fof_set_escapefraction on the groups of the last dev_fof_fof: escfrac (float64 [n] device tensor, particle order) takes the
         halo mass of every gas and star row (0 outside every group); rows of other types keep what they hold."""
         self._ck(self.lib.mpg_dev_fof_set_escapefraction(self.h, _ptr(escfrac)))
+
+    # the group catalogue on disk (fof_save_groups, fofpetaio.c); see mp-gadget_amd/fof_catalogue.py for the block tables and the writer on top
+    def dev_fof_pig_order(self, grnr=None, flags=None, n=None, device="cuda"):
+        """mpg_dev_fof_pig_order on the bound particles: (perm, count, in_group).  perm: int32 device tensor of the selected rows (GrNr >= 0,
+        type < 6, neither garbage nor swallowed) by (type, GrNr), equal keys in ascending index; count[6] its rows per type; in_group[6] the rows
+        with GrNr >= 0 per type whatever their flags.  grnr: int64 [n] device tensor, or None for the GrNr of the last dev_fof_fof."""
+        import torch
+        if n is None:
+            n = self._keep["bind"][0].shape[0] if grnr is None else grnr.shape[0]
+        perm = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
+        count, ing = (C.c_int64 * 6)(), (C.c_int64 * 6)()
+        self._ck(self.lib.mpg_dev_fof_pig_order(self.h, _ptr(grnr), _ptr(flags), _ptr(perm), count, ing))
+        count, ing = np.array(list(count), np.int64), np.array(list(ing), np.int64)
+        return perm[:int(count.sum())], count, ing
+
+    def dev_gather_block(self, perm, column, dtype, conv="NONE", params=None, src_dtype=None, out=None, name="block", ptype=0):
+        """mpg_dev_gather_block: out[j] = getter(column[perm[j]]) as a device tensor of the block's type ([count] or [count, nmemb]; u4 / u8 in
+        int32 / int64 tensors of the same bits).  perm: int32 device tensor; params: FofCatalogueParams (fof_catalogue_params), needed by
+        POSITION and VELOCITY; out: a tensor to fill instead of a new one."""
+        import torch
+        blk = catalogue_block(name, ptype, column, dtype, conv, src_dtype)
+        count = int(perm.shape[0])
+        if out is None:
+            shape = (count,) if blk.nmemb == 1 else (count, blk.nmemb)
+            out = torch.zeros(shape, dtype=getattr(torch, CATALOGUE_TORCH[dtype]), device=perm.device)
+        par = params if params is not None else fof_catalogue_params(1.0)
+        self._ck(self.lib.mpg_dev_gather_block(self.h, _ptr(perm), C.c_int64(count), C.byref(blk), C.byref(par), _ptr(out)))
+        return out
+
+    def dev_fof_save_groups(self, path, params, blocks=(), flags=None):
+        """mpg_dev_fof_save_groups: the catalogue of the last dev_fof_fof (and dev_fof_subgrid) at `path`.  params: FofCatalogueParams; blocks:
+        CatalogueBlockC descriptors (catalogue_block) of the particle blocks; flags: uint8 device tensor (bit 0 IsGarbage, bit 1 Swallowed)."""
+        arr = (CatalogueBlockC * max(len(blocks), 1))(*blocks)
+        self._ck(self.lib.mpg_dev_fof_save_groups(self.h, str(path).encode(), C.byref(params), arr, len(blocks), _ptr(flags)))
+
+    def fof_catalogue_times(self):
+        """device times in ms of the last calls: the order, the sum of the gathers, the FOFGroups blocks"""
+        c = (C.c_double * 3)()
+        self._ck(self.lib.mpg_fof_catalogue_get_times(self.h, c))
+        return dict(order_ms=c[0], gather_ms=c[1], group_ms=c[2])
 
     # ------------------------------------------------------------------ excursion-set reionisation (calculate_uvbg, uvbg.c:506-593)
     # `par` is a dict of the members of mpg_uvbg_params (or a UvbgParams); `columns` maps the names of UVBG_COLUMN_FIELDS to float64 device
